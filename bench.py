@@ -8,7 +8,8 @@ One "step" = one full pass of the hot path over one batch: the complete T-step s
 random-init weights), including the per-step posterior + categorical draw (device Philox RNG) and, for N > 1, the
 final RCCL all_gather of the predictions.  Inputs are resident in HBM when timing starts.  Prints ONE JSON line on
 rank 0.  With --gpus N > 1 and no launcher environment the script starts its own ranks
-(torch.distributed.run, one process per GPU, 127.0.0.1 rendezvous).
+(torch.distributed.run, one process per GPU, 127.0.0.1 rendezvous).  --dump-outputs DIR writes what the last timed step
+returned (dump_outputs): with the same arguments the inputs are identical from run to run, so two builds compare output for output.
 """
 import argparse
 import json
@@ -52,6 +53,38 @@ CONFIGS = {
                     H=512, W=1024, K=20, C_img=3, T=250, batch=4, bp=dict(LIDC_BP, base_channels=64), fce=None, algo_mb=6502.1, weights_mb=102.5,
                     epilogue_mb=167.8, gflop=625.5, attn_gflop=183.9, image="normal"),
 }
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6       # --dump-outputs: at most this much in all
+
+
+def dump_outputs(out_dir: str, arrays: dict, limit: int = DUMP_LIMIT_BYTES, seed: int = 0) -> dict:
+    """Write every array as <out_dir>/<name>.npy (float64 stays float64, anything else becomes float32).  When the whole set is over
+    `limit` bytes, each array keeps a fixed seeded sample of its leading (sample) dimension, or of its elements when one row alone is
+    over its share; the sorted indices kept go to <name>_index.npy (float64, into the leading dimension or the flattened array).
+    Returns {name: what was written} for the JSON line."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    host = {k: v.astype(np.float64 if v.dtype == np.float64 else np.float32, copy=False) for k, v in host.items()}
+    total = sum(v.nbytes for v in host.values())
+    info = {}
+    for name, a in host.items():
+        entry = {"shape": list(a.shape), "dtype": str(a.dtype)}
+        if total > limit:
+            share = limit * a.nbytes // total
+            rng = np.random.default_rng(seed)
+            if a.ndim > 1 and a[:1].nbytes + 8 <= share:
+                keep = np.sort(rng.choice(a.shape[0], share // (a[:1].nbytes + 8), replace=False))
+                a = a[keep]
+                entry["sample"] = f"{len(keep)} of {entry['shape'][0]} rows of the leading dimension (seed {seed})"
+            else:
+                keep = np.sort(rng.choice(a.size, share // (a.itemsize + 8), replace=False))
+                entry["sample"] = f"{len(keep)} of {a.size} elements of the flattened array (seed {seed})"
+                a = a.reshape(-1)[keep]
+            np.save(os.path.join(out_dir, name + "_index.npy"), keep.astype(np.float64))
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+        info[name] = entry
+    return info
 
 
 def cpu_model_name() -> str:
@@ -309,8 +342,12 @@ def main():
     ap.add_argument("--secondary", action="store_true", help="N > 1 only: run rank 0's untimed secondary pass (roofline taps, per-stage table) although the "
                                                              "other ranks wait in the final barrier meanwhile (default at N > 1: skipped; at N = 1 it always runs "
                                                              "unless --no-secondary)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last one returned as DIR/<name>.npy "
+                                                                      "(float32; at most 64 MB in all, a fixed seeded sample of a larger output)")
     ap.add_argument("--cpu-probe", type=int, default=0, help=argparse.SUPPRESS)      # child mode of cpu_baseline's all-cores probe
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.cpu_probe:
         _cpu_probe_child(args.cpu_probe, 1, args.config)
         return
@@ -370,6 +407,7 @@ def main():
         feat = torch.from_numpy(rng.standard_normal((n, 384, H // 8, W // 8)).astype(np.float32)).to(dev)
     x = torch.nn.functional.one_hot(torch.from_numpy(np.random.default_rng(42 + play_rank).integers(0, K, (n, H, W))), K)
     x = x.permute(0, 3, 1, 2).float().to(dev)
+    torch.manual_seed(0)                                          # (rng torch_cpu: the host noise is the same from run to run)
     t_arg = {} if not args.denoise_steps else {"t": torch.as_tensor(10000 + args.denoise_steps)}
     n_dsteps = args.denoise_steps or T
     gather_buf = [None]
@@ -431,6 +469,7 @@ def main():
                     for r, (v, b) in enumerate(zip(allr, blobs))]
         dt = max(float(v[0]) for v in allr)
     assert torch.isfinite(out).all()
+    dumped = dump_outputs(args.dump_outputs, {"diffusion_out": out}) if args.dump_outputs and rank == 0 else None
 
     res = None
     if rank == 0:
@@ -465,6 +504,8 @@ def main():
             res["out_sha256"] = digest
         if args.emulate_rank:
             res["config"]["emulated_rank"] = args.emulate_rank
+        if dumped is not None:
+            res["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         step_bytes = (cfg["algo_mb"] * n + cfg["weights_mb"]) * 1e6
         fr = step_bytes / (ms_dstep * 1e-3) / 1e9
         res["roofline_step"] = {"bound": "hbm", "achieved": fr, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": fr / HBM_PEAK_GBS,

@@ -483,6 +483,28 @@ def test_bench_self_launch_retries_once_without_its_own_ipc_override(monkeypatch
         assert e.value.code == 7 and envs == want, (preset, stderr, envs)
 
 
+def test_bench_dump_outputs_within_budget(tmp_path):
+    """--dump-outputs: a small output is written whole as float32; a larger one as the same seeded sample of its rows on every call,
+    with the row indices beside it, within the byte budget; a row over the budget falls back to a seeded sample of elements."""
+    import bench
+    small = torch.arange(24, dtype=torch.float16).reshape(2, 3, 4)
+    info = bench.dump_outputs(str(tmp_path / "s"), {"out": small})
+    got = np.load(tmp_path / "s" / "out.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small.float().numpy()) and "sample" not in info["out"]
+    assert not (tmp_path / "s" / "out_index.npy").exists()
+    big = torch.randn(10, 4, 8, 8)                                  # 10 rows of 1 KiB
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"out": big}, limit=4000)
+    rows = np.load(tmp_path / "a" / "out_index.npy")
+    assert rows.dtype == np.float64 and np.array_equal(rows, np.load(tmp_path / "b" / "out_index.npy"))
+    got = np.load(tmp_path / "a" / "out.npy")
+    assert 1 <= len(rows) and got.nbytes + rows.nbytes <= 4000 and np.array_equal(got, big.numpy()[rows.astype(np.int64)])
+    bench.dump_outputs(str(tmp_path / "e"), {"out": big}, limit=600)
+    idx = np.load(tmp_path / "e" / "out_index.npy").astype(np.int64)
+    got = np.load(tmp_path / "e" / "out.npy")
+    assert got.ndim == 1 and got.nbytes + idx.nbytes <= 600 and np.array_equal(got, big.numpy().reshape(-1)[idx])
+
+
 def test_execution_mode_is_measured_once_and_only_where_it_pays(monkeypatch):
     """substreams = 0 (host logic on a stub engine whose run() sleeps by mode): a sampling call of >= CALIBRATION_MIN_STEPS steps on a
     batch the static rule gives two streams times {2, 1 streams} x {graph, eager}, keeps the fastest, re-sets every engine's inputs
