@@ -34,24 +34,6 @@
 
 namespace ccdm {
 
-// Ablation / timeline switches (bits 8.. of `prec`, used by tools/bench_conv.py) exist only in a -DCCDM_ABLATION build
-// (CCDM_ABLATION=1 python -c "from ccdm_stochastic_segmentation_amd import hip; hip.build()"): as run-time tests they put
-// a branch around every store and every phase of the production kernel.
-//   1 no MFMA | 2 no commit | 4 no loads | 8 no stores | 16 phase timeline | 32 no weight-fragment staging (wrong results: what
-//   removing the global -> registers -> LDS round trip of the B chunk could buy) | 64 no halo (every halo request is pointed at the
-//   nearest CORE pixel of its tile — wrong results: what the tile's halo rows / columns cost in fetched bytes and time) |
-//   256 no barriers (wrong results)
-//   512 / 1024: pad the LDS request so that at most 2 / 1 blocks fit a CU (host side, always available)
-#ifdef CCDM_ABLATION
-#define CCDM_DBG(bit) ((dbg & (bit)) != 0)
-#else
-#define CCDM_DBG(bit) false
-#endif
-// phase timeline of one block (ablation bit 16 of prec; read back with ccdm_debug_read_timeline)
-__device__ unsigned long long g_timeline[1024];
-#define CCDM_STAMP(slot) do { if (CCDM_DBG(16) && blockIdx.x == gridDim.x / 2 && blockIdx.y == 0 && tid == 0 && tl < 1020) \
-        g_timeline[tl++] = ((unsigned long long)(slot) << 56) | (__builtin_amdgcn_s_memtime() & 0x00ffffffffffffffull); } while (0)
-
 // F32  : CK = 32 channels per chunk; LDS pixel = 33 floats (odd stride: conflict-free column reads).
 // F16X3: CK = 16 channels per chunk; LDS pixel = 16 hi halfs | 16 lo halfs | 16 B pad = 80 B = 20 dwords:
 //        the 16 pixels of a ds_read_b128 lane group land on 16 disjoint 4-bank slots (20*p mod 64).
@@ -160,10 +142,6 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
     const int step = a.step_ptr ? *a.step_ptr : 0;
     const int emb_row = (a.emb_row_of_sample ? a.emb_row_of_sample[n] : 0) + step;
     const bool has_gn = a.stats0 != nullptr;
-    const int dbg = a.prec >> 8;          // ablation switches for tools/bench_conv.py (CCDM_ABLATION builds only)
-    (void)dbg;
-    int tl = 0;
-    CCDM_STAMP(12);
 
     const int aWout = a.Wout, aCout = a.Cout, aHout = a.Hout, aWin = a.Win;
     const size_t in_px = (size_t)a.Hin * a.Win;
@@ -225,15 +203,12 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
     // requested with the next halo) were built, parity-tested and measured neutral to slower in rounds 1-2; they are gone.
     constexpr int DEPTH = 1;
     f32x4 reg[DEPTH][NITEM_R];
-#ifndef CCDM_BDMA
-#define CCDM_BDMA 1
-#endif
     // weight fragments by LDS-DMA instead of through registers — on the narrow-tile variants, where the B chunk (36-74 KB) outweighs the
     // halo tile: same-box A/B per stage 16x16 423 -> 402 us, 32x32 420 -> 414 us per denoise step; the wide-tile variants LOSE with it
     // (128x128 1358 -> 1378 us: the request sits behind barrier A instead of in front of it, and their chunk is only 18 KB)
     // (not the stride-2 variants: their commit is short — raw input — so the DMA's round trip sat exposed between the two barriers:
     //  Downsample 128x128 -> 64x64 61.2 -> 58.9 us, 64x64 -> 32x32 20.6 -> 19.8 us through registers, round 5)
-    constexpr bool BDMA = CCDM_BDMA && PREC != CCDM_PREC_F32 && TW < 32 && STRIDE == 1;
+    constexpr bool BDMA = PREC != CCDM_PREC_F32 && TW < 32 && STRIDE == 1;
     f32x4 regB[1][(NITEM_B > 0 && !BDMA) ? NITEM_B : 1];
     unsigned valid[DEPTH];         // generic walk: bit i = item i lies inside the image
     unsigned rowmask[DEPTH];       // row-structured: bit i = core row of pass i inside the image (wave-uniform)
@@ -301,7 +276,7 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
                 return;
             }
         }
-        const bool skseg = KS > 1 && (ch >= nchunk_main || CCDM_DBG(64));   // uniform: skip-segment chunk (1x1, no halo needed)
+        const bool skseg = KS > 1 && ch >= nchunk_main;   // uniform: skip-segment chunk (1x1, no halo needed)
         const int ylo = skseg ? min(oy0, Hc - 1) : 0, yhi = skseg ? min(oy0 + TH - 1, Hc - 1) : Hc - 1;
         const int xlo = skseg ? min(ox0, Wc - 1) : 0, xhi = skseg ? min(ox0 + TW - 1, Wc - 1) : Wc - 1;
         // Every load is issued unconditionally with its address clamped into the tensor; padding is zeroed at commit.
@@ -539,7 +514,7 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
                 if (item < (unsigned)(HP * QPP)) put(std::true_type{}, reg[d][i], ((valid[d] >> i) & 1u) != 0u, (int)(item / QPP));
             }
         }
-        if (PREC != CCDM_PREC_F32 && !BDMA && !CCDM_DBG(32)) {
+        if (PREC != CCDM_PREC_F32 && !BDMA) {
 #pragma unroll
             for (int i = 0; i < NITEM_B; ++i) {
                 const int j = (int)t_ + i * NT;
@@ -586,7 +561,6 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
     };
 
     f32x16 acc[MI][NI];
-    CCDM_STAMP(1);
     // (tile, chunk) walk of this block — tile = slice, slice + slices, ... — carried as scalar counters: the current
     // iteration's (chunk, ty, tx) and, one step ahead, the prefetch's (no divisions in the loop)
     const int adv_y = k.slices / k.tiles_x, adv_x = k.slices % k.tiles_x;
@@ -603,7 +577,6 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
     issue(std::integral_constant<int, 0>{}, pf_ch, pf_ty, pf_tx);
     advance(pf_ch, pf_ty, pf_tx);
     __builtin_amdgcn_sched_barrier(0);
-    CCDM_STAMP(13);
     // the small loads issued at the top are consumed here, behind the first halo request
 #pragma unroll
     for (int ni = 0; ni < NI; ++ni) {
@@ -616,7 +589,6 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
     // GroupNorm's (scale, shift) table for this sample, from the prefetched partials (the halo region of LDS is free until the
     // first commit, which sits behind the loop-top barrier)
     if (has_gn) gn_affine_block(a, n, emb_row, gpf, reinterpret_cast<f64x2*>(halo_b), ab);
-    CCDM_STAMP(14);
     // one iteration = one (tile, chunk); D_ = the register set it consumes (static: the loop below is unrolled by DEPTH)
     auto iterate = [&](auto D_) {
         if (chunk == 0) {
@@ -627,33 +599,26 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
 #pragma unroll
                     for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.0f;
         }
-        CCDM_STAMP(2);
-        if (!CCDM_DBG(4) && !CCDM_DBG(32)) issueB(D_, chunk);
-        if (!CCDM_DBG(256)) __syncthreads();          // previous MFMA phase has finished reading LDS (and ab[] is visible)
-        CCDM_STAMP(3);
+        issueB(D_, chunk);
+        __syncthreads();          // previous MFMA phase has finished reading LDS (and ab[] is visible)
         if constexpr (BDMA) {
             // (the halo registers were requested an iteration ago; naming them here makes the compiler place its wait for them in
             //  front of the DMA requests — with a DMA in flight it would otherwise wait for EVERYTHING at the commit's first use)
 #pragma unroll
             for (int i = 0; i < NITEM_R; ++i) asm volatile("" : "+v"(reg[0][i]));
-            if (!CCDM_DBG(4) && !CCDM_DBG(32)) issueB_dma(chunk);
+            issueB_dma(chunk);
         }
-        if (!CCDM_DBG(2)) commit(D_, chunk);
-        CCDM_STAMP(4);
-        if (!CCDM_DBG(256)) __syncthreads();
-        CCDM_STAMP(5);
+        commit(D_, chunk);
+        __syncthreads();
         // next tile-chunk's HBM reads fly during the MFMA phase (after the last iteration this requests a tile past the
-        // slice's last one: addresses are clamped into the tensor, the data is never committed — harmless, branch-free)
-        if (!CCDM_DBG(4)) {       // refill the set just committed: iteration it + DEPTH
-            issue(D_, pf_ch, pf_ty, pf_tx);
-            advance(pf_ch, pf_ty, pf_tx);
-        }
+        // slice's last one: addresses are clamped into the tensor, the data is never committed — harmless, branch-free);
+        // this refills the set just committed: iteration it + DEPTH
+        issue(D_, pf_ch, pf_ty, pf_tx);
+        advance(pf_ch, pf_ty, pf_tx);
 
-        CCDM_STAMP(6);
         const bool skc = chunk >= nchunk_main;                   // uniform
         const int c0 = (skc ? chunk - nchunk_main : chunk) * CK;
-        if (CCDM_DBG(1)) {
-        } else if (PREC == CCDM_PREC_F32) {
+        if (PREC == CCDM_PREC_F32) {
             // taps x 16 k-steps of v_mfma_f32_32x32x2_f32; B: [tap][cin_pad/2][ntiles][64] floats
             const float* wc = reinterpret_cast<const float*>(skc ? a.skip_w : a.w) + ((size_t)(c0 >> 1) * k.ntiles + nt0) * 64 + lane;
             const size_t wtap = (size_t)(k.cin_pad >> 1) * k.ntiles * 64;
@@ -798,7 +763,6 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
             }
         }
 
-        CCDM_STAMP(7);
         if (chunk == nchunk - 1) {
             // ---- epilogue: (x 2^-e) + bias (+ emb) (+ residual), store NHWC, accumulate output statistics ----
             const int oy0 = cur_ty * TH, ox0 = cur_tx * TW;
@@ -807,8 +771,7 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
             if (fast_epi) {
                 // ---- fast path: accumulators -> wave-private LDS rows [pixel][32 ch] -> float4 per lane
                 //      (8 lanes cover one pixel's 128-byte row: residual loads and stores move 16 B per lane) ----
-                if (!CCDM_DBG(256)) __syncthreads();                 // every wave is done reading the A/B tiles
-                CCDM_STAMP(9);
+                __syncthreads();                 // every wave is done reading the A/B tiles
                 const int cq = lane_ & 7, prow = lane_ >> 3;
 #pragma unroll
                 for (int ni = 0; ni < NI; ++ni) {
@@ -865,7 +828,6 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
                             }
                     }
                     if (KSP > 1) __syncthreads();                  // all row groups' partials are in LDS
-                    CCDM_STAMP(10);
                     const float* epi0 = reinterpret_cast<const float*>(halo_b) + wave * (MI * 32 * EPS);   // row group 0 of this sub-tile
                     {
 #pragma unroll
@@ -879,15 +841,14 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
                                 v += *reinterpret_cast<const f32x4*>(epi0 + g * (WAVES * MI * 32 * EPS) + pl * EPS + 4 * cq);
                             if (RESID) v += rs[j];
                             if (FULL) {
-                                if (!CCDM_DBG(8)) store16_uniform_base(reinterpret_cast<char*>(outn) + row_base(j), lane_off, v);
+                                store16_uniform_base(reinterpret_cast<char*>(outn) + row_base(j), lane_off, v);
 #pragma unroll
                                 for (int e = 0; e < 4; ++e) { t1[e] += v[e]; t2[e] = fmaf(v[e], v[e], t2[e]); }
                             } else {
                                 const int oy = row_of(j), ox = ox0 + (j * 8) % TW + prow;
                                 if (cv4 && oy < eH && ox < eW) {
-                                    if (!CCDM_DBG(8))
-                                        *reinterpret_cast<f32x4*>(reinterpret_cast<char*>(outn) +
-                                                                  ((pix_of(oy, ox) * (unsigned)aCout + (unsigned)co4) << 2)) = v;
+                                    *reinterpret_cast<f32x4*>(reinterpret_cast<char*>(outn) +
+                                                              ((pix_of(oy, ox) * (unsigned)aCout + (unsigned)co4) << 2)) = v;
 #pragma unroll
                                     for (int e = 0; e < 4; ++e) { t1[e] += v[e]; t2[e] = fmaf(v[e], v[e], t2[e]); }
                                 }
@@ -900,7 +861,6 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
                     else { if (full) epi_ni(std::true_type{}, std::false_type{}); else epi_ni(std::false_type{}, std::false_type{}); }
 #pragma unroll
                     for (int e = 0; e < 4; ++e) { s1[ni][e] += t1[e]; s2[ni][e] += t2[e]; }
-                    CCDM_STAMP(11);
                 }
             } else {
 #pragma unroll
@@ -922,7 +882,7 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
                             const size_t idx = ((size_t)(n * a.Hout + oy) * a.Wout + ox) * a.Cout + co;
                             float v = (PREC == CCDM_PREC_F32 ? acc[mi][ni][r] : acc[mi][ni][r] * wsc) + add;
                             if (a.resid) v += a.resid[idx];
-                            if (!CCDM_DBG(8)) a.out[idx] = v;
+                            a.out[idx] = v;
                             t1 += v;
                             t2 = fmaf(v, v, t2);
                         }
@@ -937,8 +897,6 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
     };
     for (int it = 0; it < n_iter; ++it) iterate(std::integral_constant<int, 0>{});
 
-    CCDM_STAMP(8);
-    if (CCDM_DBG(16) && blockIdx.x == gridDim.x / 2 && blockIdx.y == 0 && tid == 0) g_timeline[1023] = tl;
     if (a.out_stats) {
         // fold the lanes that hold the same channel, then the block's waves; fixed order everywhere
         __syncthreads();
@@ -1003,7 +961,7 @@ static int chunk_ck(const ccdm_conv_args& a, const ConvGeo& g) {
     const bool ok64 = ok32 && g.TW == 8 && C % 64 == 0 && (a.C1 == 0 || a.C0 % 64 == 0) &&
                       (!a.skip0 || (SC % 64 == 0 && (a.SC1 == 0 || a.SC0 % 64 == 0))) &&
                       (a.ksize == 1 || tap_split(a, g));
-    return ok64 && !exp_env("CCDM_NO_CK64") ? 64 : (ok32 ? 32 : 16);
+    return ok64 ? 64 : (ok32 ? 32 : 16);
 }
 
 static bool tap_split(const ccdm_conv_args& a, const ConvGeo& g) {
@@ -1068,16 +1026,8 @@ static int launch_geo(const ConvK& k, const ConvGeo& g, int NI, int ck, dim3 gri
 
 template <int PREC>
 static int launch_prec(const ConvK& k, const ConvGeo& g, int NI, int ck, dim3 grid, size_t lds, hipStream_t s) {
-#ifdef CCDM_EXPERIMENT   // compile one instantiation only (register/ISA experiments)
-#ifndef CCDM_EXPERIMENT_THREADS
-#define CCDM_EXPERIMENT_THREADS 256
-#endif
-    hipLaunchKernelGGL((k_conv<CCDM_PREC_F16X3, CCDM_EXPERIMENT_CK, 3, 1, CCDM_EXPERIMENT_GEO>), grid, dim3(CCDM_EXPERIMENT_THREADS), lds, s, k);
-    return 0;
-#else
     if (k.a.ksize == 3) return launch_geo<PREC, 3>(k, g, NI, ck, grid, lds, s);
     return launch_geo<PREC, 1>(k, g, NI, ck, grid, lds, s);
-#endif
 }
 
 static int conv_slices_default(int tiles, bool up2, int stride);
@@ -1100,18 +1050,15 @@ static int conv_slices_default(int tiles, bool up2, int stride) {
     // 48 blocks on 256 CUs).  More than CCDM_STATS_MAX_SLICES partials are folded to 16 by ccdm_stats_fold before a GroupNorm
     // reads them.  A function of the spatial size only (never of N): sharding the batch must not change the order in which
     // statistics partials are added.
-    const int ovr = exp_env("CCDM_SLICES");
-    if (ovr > 0 && ovr <= CCDM_STATS_MAX_SLICES && tiles >= ovr) return ovr;
     // Tile counts that only Cityscapes-sized images produce (64x128 and 32x64 with 8x16 tiles: 32 tiles; 128x256: 128 tiles) come with
     // batches of 4-16 samples: one slice per tile / per four tiles there (C5 shard 14.26 -> 13.24 ms, C4 7.13 -> 6.84 ms per step)
     // (not for the sub-pixel upsample form, whose 8x16 tiling gives LIDC's 64x64 input the same 32 tiles at batch 64)
     if (!up2 && tiles >= 128 && tiles < 256) return 32;
-#ifndef CCDM_NO_S2_SLICES
     // stride-2 convs of a 32-tile output (LIDC's Downsample 128x128 -> 64x64 on 8x16 tiles): one slice per FOUR tiles.  The rule below
     // was made for Cityscapes batches of 4-16; at LIDC's batch its 2048 one-tile blocks were four rounds of 512 resident blocks, each
-    // paying the block prologue for one tile (round 6: 59 -> 5x us).  Still a function of the layer's shape only.
+    // paying the block prologue for one tile (round 6: 57.3 -> 53.4 us, profiles/r06_verdict_items.md).  Still a function of the
+    // layer's shape only.
     if (!up2 && stride == 2 && tiles == 32) return 8;
-#endif
     if (!up2 && tiles >= 24 && tiles < 48) return tiles < 32 ? tiles : 32;
     if (tiles >= 128) return tiles / 16 * 3;
     if (tiles >= 48) return 12;
@@ -1136,7 +1083,7 @@ static size_t packed_frag_bytes(int Cout, int Cin, int ksize, int prec) {
 // does this conv run the K-split few-pixel kernel?  (a function of the layer's shape and operands only — the host sizes the
 // statistics buffer by it through ccdm_conv_out_slices)
 static bool conv_takes_ks(const ccdm_conv_args& a) {
-    return a.up != 2 && !a.fine_slices && !exp_env("CCDM_NO_KS") && conv_ks_eligible(a);
+    return a.up != 2 && !a.fine_slices && conv_ks_eligible(a);
 }
 
 int conv_out_slices(const ccdm_conv_args& a) {
@@ -1181,7 +1128,6 @@ int launch_conv(const ccdm_conv_args& a, hipStream_t s) {
 
     ConvK k;
     k.a = a;
-    k.timeline = nullptr;
     k.core_unmasked = 0;
     const int prec = a.prec & 255;
     k.cin_pad = cin_pad_for(C, prec);
@@ -1235,7 +1181,7 @@ int launch_conv(const ccdm_conv_args& a, hipStream_t s) {
     const int HP = ((g.TH - 1) * a.stride + a.ksize) * ((g.TW - 1) * a.stride + a.ksize);
     const int ck = chunk_ck(a, g);
     {   // wide skip chunks (k_conv, SKW): the wide-tile F16X3 one-n-tile variant, skip sources in multiples of 32 channels
-        k.skip_wide = (!exp_env("CCDM_NO_SKIP_WIDE") && a.skip0 && prec == CCDM_PREC_F16X3 && a.ksize == 3 && a.stride == 1 && !a.up && g.TW == 32 && NI == 1 && ck == 16 &&
+        k.skip_wide = (a.skip0 && prec == CCDM_PREC_F16X3 && a.ksize == 3 && a.stride == 1 && !a.up && g.TW == 32 && NI == 1 && ck == 16 &&
                        a.SC0 % 32 == 0 && a.SC1 % 32 == 0 && !(a.prec >> 8)) ? 1 : 0;
     }
     {   // core halo items need no per-lane padding mask when every tile column and every channel quad exists (see ConvK)
@@ -1261,17 +1207,7 @@ int launch_conv(const ccdm_conv_args& a, hipStream_t s) {
         if (lds < ex * 16) lds = ex * 16;
         lds += (size_t)C * 8;
     }
-    if ((a.prec >> 8) & 512) lds = 60 * 1024;      // diagnostics (tools/bench_conv.py): at most 2 blocks per CU
-    if ((a.prec >> 8) & 1024) lds = 100 * 1024;    //                                   1 block per CU
     CCDM_REQUIRE(lds <= 160 * 1024, "conv: LDS %zu too large", lds);
-#ifdef CCDM_EXPERIMENTS
-    if (conv_pc_eligible(k, g, NI)) {          // full-width 3x3 stages: producer/consumer form (tools/experiments/ccdm_conv_pc.hip, CCDM_PC=1)
-        const int rc_pc = launch_conv_pc(k, s);
-        if (rc_pc) return rc_pc;
-        CCDM_CHECK_LAUNCH("conv(pc)");
-        return 0;
-    }
-#endif
     dim3 grid(a.N * k.slices, k.ntiles / NI);
     const int rc = prec == CCDM_PREC_F32 ? launch_prec<CCDM_PREC_F32>(k, g, NI, ck, grid, lds, s)
                    : prec == CCDM_PREC_F16 ? launch_prec<CCDM_PREC_F16>(k, g, NI, ck, grid, lds, s)
@@ -1305,19 +1241,6 @@ extern "C" int ccdm_conv_slices_ex(int Hin, int Win, int ksize, int stride, int 
     if (up == 2) return (ccdm::conv_geo(Hin, Win, 1, true).TW == 16 ? 1 : 4) * ccdm::conv_slices(Hin, Win, 1, true, fine);
     const int Hc = up ? 2 * Hin : Hin, Wc = up ? 2 * Win : Win, pad = ksize / 2;
     return ccdm::conv_slices((Hc + 2 * pad - ksize) / stride + 1, (Wc + 2 * pad - ksize) / stride + 1, stride, false, fine);
-}
-
-extern "C" int ccdm_debug_read_timeline(unsigned long long* host, int n) {
-    if (!host || n <= 0 || n > 1024) return ccdm::fail("debug_read_timeline: bad args");
-#ifdef CCDM_ABLATION
-    if (ccdm::conv_ks_timeline_read(host, n)) return 0;
-#endif
-#ifdef CCDM_EXPERIMENTS
-    if (ccdm::conv_pc_timeline_read(host, n)) return 0;
-#endif
-    if (hipMemcpyFromSymbol(host, HIP_SYMBOL(ccdm::g_timeline), (size_t)n * 8, 0, hipMemcpyDeviceToHost) != hipSuccess)
-        return ccdm::fail("debug_read_timeline: copy failed");
-    return 0;
 }
 
 extern "C" int ccdm_conv2d(const ccdm_conv_args* a, void* stream) {

@@ -4,7 +4,7 @@
 //
 // The general kernel (ccdm_conv.hip) stages every input through LDS — two barrier-separated round trips per channel chunk,
 // a halo walk, a commit pass — which is what a 3x3 conv with GroupNorm on load needs and what a 64-pixel x 128-channel GEMM
-// does not: such a launch is one round of blocks and its time is one block's chain (tools/timeline_op.py: 14 000 cycles, of
+// does not: such a launch is one round of blocks and its time is one block's chain (block timeline: 14 000 cycles, of
 // which the arithmetic is under 2 000).  Here a wave's A operand never touches LDS: lane (pixel = lane & 31, k-group = lane >> 5)
 // reads its 8 consecutive channels of every 16-channel k-step straight into registers (2 x 16 B), splits them (x = hi + lo) and
 // feeds the MFMA; the B fragments are read in their packed layout (ccdm_pack_conv_weight: [k-step][n-tile][hi|lo][lane] x 16 B,

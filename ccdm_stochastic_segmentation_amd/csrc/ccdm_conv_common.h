@@ -60,7 +60,7 @@ struct ConvK {   // kernel-side copy of ccdm_conv_args (+ derived)
     const float* wscale;     // F16X3: [ntiles*32] powers of two undoing the per-output-channel weight pre-scale
     int core_unmasked;       // every core column of every tile lies inside the image and every channel quad exists (W % TW == 0, C % CK == 0):
                              // core halo items need no per-lane padding mask, only the wave-uniform row test
-    unsigned long long* timeline;   // diagnostics of the producer/consumer experiment (CCDM_EXPERIMENTS builds), else NULL
+    void* reserved;          // unused; kept so that the hidden kernel arguments behind ConvK, and so the code of k_conv, stay where they are
 };
 
 // plain 1x1 conv (+bias +residual +statistics) of a low-resolution tensor without LDS staging (ccdm_conv1x1.hip)
@@ -74,16 +74,6 @@ int launch_conv_ks(const ccdm_conv_args& a, int ntiles, const float* wscale, hip
 // Upsample + conv 3x3 in sub-pixel form at the low-resolution decoder levels: wave = phase, weight fragments straight from L2 (ccdm_upconv.hip)
 bool upconv_eligible(const ccdm_conv_args& a);
 int launch_upconv(const ccdm_conv_args& a, int slices, int ntiles, const float* wscale, hipStream_t s);
-#ifdef CCDM_ABLATION
-bool conv_ks_timeline_read(unsigned long long* host, int n);
-#endif
-
-#ifdef CCDM_EXPERIMENTS
-// producer/consumer form of the full-width 3x3 stages (tools/experiments/ccdm_conv_pc.hip: measured slower, never in the shipped library)
-bool conv_pc_eligible(const ConvK& k, const ConvGeo& g, int NI);
-int launch_conv_pc(const ConvK& k, hipStream_t s);
-bool conv_pc_timeline_read(unsigned long long* host, int n);
-#endif
 
 // ---------------------------------------------------------------------------------------------------
 // GroupNorm affine for sample n:  ab[c] = (scale, shift) such that  y = scale*x + shift

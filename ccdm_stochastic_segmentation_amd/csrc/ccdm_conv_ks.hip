@@ -3,7 +3,7 @@
 // (reference unet.py:242-262, :137-146; LIDC: the 8x8 stage — 13 launches per denoise step).
 //
 // Why another kernel.  At 8x8 pixels per sample a conv launch is ONE round of single-tile blocks and its time is the length of one
-// block's dependent chain (tools/timeline_op.py on the general kernel, 128 -> 128 @ 8x8: 26 000 cycles for 2 300 cycles of matrix
+// block's dependent chain (block timeline of the general kernel, 128 -> 128 @ 8x8: 26 000 cycles for 2 300 cycles of matrix
 // work: two channel chunks, each a weight-fragment round trip global -> registers -> LDS -> registers with two barriers, a commit
 // pass that is mostly copying those fragments, 6 waves on 4 SIMDs).  Here the chain is: every load of the block issued up front ->
 // GroupNorm table -> ONE commit of the whole halo tile (all input channels) -> ONE barrier -> matrix phase -> cross-wave reduction.
@@ -22,7 +22,7 @@
 // Round 4 — NI output-channel tiles per block (16x16 images: LIDC's second-deepest stage, 21 launches per denoise step).  There a
 // launch of the general kernel is ONE round of 1.5 blocks per CU and its time is one block's chain — per 32-channel chunk a commit
 // (3 900 cycles), two barriers and a matrix phase (2 950), with the same halo tile normalised, activated and split by each of the
-// three n-tile blocks of a pixel tile (tools/timeline_op.py: 96 -> 96 35 800 cycles, 224 -> 96 74 800).  With all n-tiles of an
+// three n-tile blocks of a pixel tile (block timelines: 96 -> 96 35 800 cycles, 224 -> 96 74 800).  With all n-tiles of an
 // 8x8 pixel tile in ONE block the grid is 64 samples x 4 tiles = 256 blocks = one per CU: the tile is staged once, every weight
 // fragment of the layer is read by exactly one wave of the block, a step feeds 2 x NI accumulators (6 NI matrix instructions per
 // A / B fragment set), and the partial accumulators meet in LDS one n-tile at a time (the exchange buffer holds one).
@@ -46,15 +46,6 @@ struct ConvKS {
     int red_off;                   // LDS offset (within the staging region) of the statistics fold buffer
 };
 
-// phase timeline of one block (CCDM_ABLATION builds, diagnostic bit 16 of prec >> 8; read back with ccdm_debug_read_timeline)
-#ifdef CCDM_ABLATION
-__device__ unsigned long long g_timeline_ks[64];
-static bool g_ks_stamped = false;
-#define KS_STAMP(slot) do { if (tl_on && tid == 0 && tl < 60) g_timeline_ks[tl++] = ((unsigned long long)(slot) << 56) | (__builtin_amdgcn_s_memtime() & 0x00ffffffffffffffull); } while (0)
-#else
-#define KS_STAMP(slot) do { } while (0)
-#endif
-
 constexpr int KS_NT = 512, KS_NW = 8, KS_PART_BYTES = 8 * 2 * 4 * 64 * 16;
 // weight-fragment sets in flight per wave (one set = NI hi|lo pairs = 8 NI registers): ~80-96 registers of queue whatever NI
 constexpr int ks_bq(int ni) { return ni == 1 ? 10 : (ni == 2 ? 6 : (ni == 3 ? 4 : 2)); }
@@ -77,11 +68,6 @@ __global__ __launch_bounds__(KS_NT, NI == 1 ? 2 : 1) void k_conv_ks(const ConvKS
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int g = __builtin_amdgcn_readfirstlane(tid >> 6);                              // wave = K group
-#ifdef CCDM_ABLATION
-    const bool tl_on = ((a.prec >> 8) & 16) && blockIdx.x == gridDim.x / 2 && blockIdx.y == 0;
-    int tl = 0;
-#endif
-    KS_STAMP(1);
     const int ntile_sp = k.tiles_x * k.tiles_y;
     // several tiles per sample: block b runs on XCD b % 8 — give each XCD a contiguous range of (sample, tile) pairs so that the tiles
     // of a sample (shared halo rows, the same statistics partials) meet in one L2 (speed only)
@@ -119,7 +105,6 @@ __global__ __launch_bounds__(KS_NT, NI == 1 ? 2 : 1) void k_conv_ks(const ConvKS
         g_beta = a.beta[tid];
     }
 
-    KS_STAMP(20);
     // ---- 2. halo requests: item i of wave g covers staged pixels (g + 8 i) * PPW .. + PPW - 1, lane = (pixel within the item, channel quad) ----
     const int lgq_m = k.lgq_m, lgq_s = k.lgq_s;
     const int sub_m = lane >> lgq_m, q_m = lane & ((1 << lgq_m) - 1);
@@ -173,7 +158,6 @@ __global__ __launch_bounds__(KS_NT, NI == 1 ? 2 : 1) void k_conv_ks(const ConvKS
         }
     }
 
-    KS_STAMP(2);
     // ---- 3. this wave's weight fragments: steps s = g, g + 8, ...; the first batch is requested now ----
     const int nstep = k.nstep, nmain = 9 * k.nks_m;
     const int nsw = (nstep - g + KS_NW - 1) / KS_NW;                                     // steps of this wave (>= 1: nstep >= 9)
@@ -200,7 +184,6 @@ __global__ __launch_bounds__(KS_NT, NI == 1 ? 2 : 1) void k_conv_ks(const ConvKS
     };
 #pragma unroll
     for (int jj = 0; jj < KS_B0; ++jj) load_set(jj, jj);
-    KS_STAMP(22);
 
     // ---- 4. epilogue constants and residual of the output row this wave will finish (row g of the tile).  One n-tile per block: requested
     //         here, early.  Several: behind the matrix phase (their 7 NI registers would not fit beside 2 NI accumulators and the fragment
@@ -231,7 +214,6 @@ __global__ __launch_bounds__(KS_NT, NI == 1 ? 2 : 1) void k_conv_ks(const ConvKS
     };
     if constexpr (NI == 1) request_epilogue_operands();
 
-    KS_STAMP(3);
     // ---- 5. GroupNorm (scale, shift) table (the staging region is free until the commit) ----
     if (has_gn) {
         f64x2* scratch = reinterpret_cast<f64x2*>(region);
@@ -257,7 +239,6 @@ __global__ __launch_bounds__(KS_NT, NI == 1 ? 2 : 1) void k_conv_ks(const ConvKS
         __syncthreads();
     }
 
-    KS_STAMP(4);
     // ---- 6. commit: registers -> affine -> SiLU -> fp16 hi | lo -> LDS; one weight-fragment pair requested behind every item ----
     {
         constexpr float PS = ACT_PRESCALE;
@@ -302,7 +283,6 @@ __global__ __launch_bounds__(KS_NT, NI == 1 ? 2 : 1) void k_conv_ks(const ConvKS
                 hp += dhp; dm += ddm;
             }
             next_pair(KS_B0 + i);
-            KS_STAMP(30 + i);
         }
         if constexpr (NITS > 0) {
             const int dpx = KS_NW << (6 - lgq_s);
@@ -321,9 +301,7 @@ __global__ __launch_bounds__(KS_NT, NI == 1 ? 2 : 1) void k_conv_ks(const ConvKS
 #pragma unroll
         for (int jj = KS_B0 + NIT; jj < KS_BQ; ++jj) next_pair(jj);     // (instantiations with fewer items than fragment pairs)
     }
-    KS_STAMP(5);
     __syncthreads();
-    KS_STAMP(6);
 
     // ---- 7. matrix phase: this wave's steps, both sub-tiles, fragments from registers (B) and LDS (A) ----
     f32x16 acc[2][NI];
@@ -395,9 +373,7 @@ __global__ __launch_bounds__(KS_NT, NI == 1 ? 2 : 1) void k_conv_ks(const ConvKS
 
     if constexpr (NI > 1) request_epilogue_operands();
     // ---- 8. cross-wave reduction, one n-tile at a time: partial [wave][sub-tile][row quad][lane] x 16 B, then wave g finishes tile row g ----
-    KS_STAMP(7);
     __syncthreads();                         // every wave is done reading the A tile
-    KS_STAMP(8);
     float t1[NI], t2[NI];
 #pragma unroll
     for (int ni = 0; ni < NI; ++ni) {
@@ -414,7 +390,6 @@ __global__ __launch_bounds__(KS_NT, NI == 1 ? 2 : 1) void k_conv_ks(const ConvKS
                 }
         }
         __syncthreads();
-        if (ni == 0) KS_STAMP(9);
         t1[ni] = 0.f; t2[ni] = 0.f;
         {
             // accumulator register 4 rq + j of sub-tile mi holds pixel mi*32 + 8 rq + 4 (lane >> 5) + j, i.e. tile row 4 mi + rq, column 4 (lane >> 5) + j
@@ -434,7 +409,6 @@ __global__ __launch_bounds__(KS_NT, NI == 1 ? 2 : 1) void k_conv_ks(const ConvKS
             }
         }
     }
-    KS_STAMP(10);
     if (a.out_stats) {
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni) {
@@ -452,10 +426,6 @@ __global__ __launch_bounds__(KS_NT, NI == 1 ? 2 : 1) void k_conv_ks(const ConvKS
             o[0] = s1; o[1] = s2;
         }
     }
-    KS_STAMP(11);
-#ifdef CCDM_ABLATION
-    if (tl_on && tid == 0) g_timeline_ks[63] = tl;
-#endif
 }
 
 static int pow2_lg_quads(int nks) {          // lanes per staged pixel: 4 nks channel quads rounded up to 16 / 32 / 64
@@ -476,15 +446,10 @@ static int conv_ks_ni(const ccdm_conv_args& a) {
 
 // geometry and resources of a launch; false = not for this kernel
 static bool conv_ks_plan(const ccdm_conv_args& a, ConvKS& k, size_t& lds, int& nit_max, int& NI) {
-#ifdef CCDM_ABLATION
-    if ((a.prec & ~(16 << 8)) != CCDM_PREC_F16X3) return false;           // (the timeline bit is this kernel's too)
-#else
     if (a.prec != CCDM_PREC_F16X3) return false;                          // (a diagnostic bit in prec >> 8: the general kernel)
-#endif
     if (a.ksize != 3 || a.up || a.film || (a.stride != 1 && a.stride != 2)) return false;
     if ((a.stats0 != nullptr) != (a.act == CCDM_ACT_SILU)) return false;  // built for GroupNorm + SiLU on load, or neither
-    const int max_area = exp_env("CCDM_KS_MAX_AREA") ? exp_env("CCDM_KS_MAX_AREA") : 256;      // (A/B hook of experiments builds: 128 = round 3)
-    if (a.Hout % 8 || a.Wout % 8 || a.Hout * a.Wout > max_area) return false;   // a rule of the geometry, never of N
+    if (a.Hout % 8 || a.Wout % 8 || a.Hout * a.Wout > 256) return false;         // a rule of the geometry, never of N (round 3: 128)
     if (a.Cout % 32) return false;
     const int C = a.C0 + a.C1, SC = a.skip0 ? a.SC0 + a.SC1 : 0;
     if (C > 256 || SC > 256 || (a.stride == 2 && a.skip0)) return false;
@@ -546,9 +511,6 @@ int launch_conv_ks(const ccdm_conv_args& a, int ntiles, const float* wscale, hip
     k.wscale = wscale;
     k.ntiles = ntiles;
     const dim3 grid(a.N * k.tiles_x * k.tiles_y, a.Cout / (32 * NI)), block(KS_NT);
-#ifdef CCDM_ABLATION
-    if ((a.prec >> 8) & 16) g_ks_stamped = true;
-#endif
     if (NI == 4) { launch_conv_ks_ni<4>(k, grid, block, lds, s); return 0; }
     if (NI == 3) { launch_conv_ks_ni<3>(k, grid, block, lds, s); return 0; }
     if (NI == 2) { launch_conv_ks_ni<2>(k, grid, block, lds, s); return 0; }
@@ -567,18 +529,5 @@ int launch_conv_ks(const ccdm_conv_args& a, int ntiles, const float* wscale, hip
     }
     return 0;
 }
-
-#ifdef CCDM_ABLATION
-bool conv_ks_timeline_read(unsigned long long* host, int n) {
-    if (!g_ks_stamped) return false;
-    g_ks_stamped = false;
-    for (int i = 0; i < n; ++i) host[i] = 0;
-    unsigned long long tmp[64];
-    if (hipMemcpyFromSymbol(tmp, HIP_SYMBOL(g_timeline_ks), sizeof(tmp), 0, hipMemcpyDeviceToHost) != hipSuccess) return false;
-    for (int i = 0; i < 63 && i < n; ++i) host[i] = tmp[i];
-    if (n >= 1024) host[1023] = tmp[63];
-    return true;
-}
-#endif
 
 }  // namespace ccdm

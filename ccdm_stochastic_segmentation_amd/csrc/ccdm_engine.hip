@@ -70,8 +70,6 @@ struct ccdm_engine {
     hipGraphExec_t exec = nullptr;
     bool graph_valid = false;
     int graph_with_epilogue = -1;
-    int graph_steps = 1;         // denoise steps per captured graph
-    int exp_id = 0;              // creation index (experiments builds: per-stream op skipping)
     int captures = 0;            // how often the step has been captured and instantiated (tests: a new Philox key must not re-capture)
     // timing taps: HIP events around every launch of the tapped ops (op index -> events, launches recorded)
     struct Tap { std::vector<hipEvent_t> ev; int n = 0; };
@@ -86,44 +84,9 @@ static void drop_graph(ccdm_engine* e) {
     e->graph_valid = false;
 }
 
-#ifdef CCDM_EXPERIMENTS
-// sensitivity probe (experiments builds only; results are garbage): CCDM_SKIP_OPS="a-b,c,d-e" leaves those ops of the step out, to see
-// how much of the step time — in whatever launch mode — a stage is worth before anyone rewrites its kernels.  CCDM_SKIP_OPS_B, when
-// set, is the list for every second engine created (the second of two sub-batch streams): one stream can run only the
-// full-resolution ops and the other only the low-resolution ones.
-static int g_exp_engines = 0;
-static bool exp_skip_op(int engine_id, size_t i) {
-    static std::vector<std::pair<int, int>> ranges[2];
-    static bool parsed = false;
-    if (!parsed) {
-        parsed = true;
-        const char* va = getenv("CCDM_SKIP_OPS");
-        const char* vb = getenv("CCDM_SKIP_OPS_B");
-        const char* vs[2] = {va, vb ? vb : va};
-        for (int q = 0; q < 2; ++q) {
-            const char* v = vs[q];
-            while (v && *v) {
-                char* end;
-                const int a = (int)strtol(v, &end, 10);
-                int b = a;
-                if (*end == '-') b = (int)strtol(end + 1, &end, 10);
-                ranges[q].push_back({a, b});
-                if (end == v) break;
-                v = *end == ',' ? end + 1 : end;
-            }
-        }
-    }
-    for (auto& r : ranges[engine_id & 1]) if ((int)i >= r.first && (int)i <= r.second) return true;
-    return false;
-}
-#endif
-
 static int launch_step(ccdm_engine* e, int with_epilogue, hipStream_t s, bool profile) {
     for (size_t i = 0; i < e->ops.size(); ++i) {
         const Op& op = e->ops[i];
-#ifdef CCDM_EXPERIMENTS
-        if (exp_skip_op(e->exp_id, i)) continue;
-#endif
         ccdm_engine::Tap* tp = nullptr;
         if (profile) {
             auto it = e->taps.find((int)i);
@@ -151,9 +114,6 @@ extern "C" ccdm_engine* ccdm_engine_create(int32_t* step_counter) {
     if (!step_counter) { fail("engine_create: null step counter"); return nullptr; }
     ccdm_engine* e = new ccdm_engine();
     e->step = step_counter;
-#ifdef CCDM_EXPERIMENTS
-    e->exp_id = g_exp_engines++;
-#endif
     return e;
 }
 
@@ -316,12 +276,7 @@ extern "C" int ccdm_engine_run(ccdm_engine* e, int first_row, int n_steps, int w
             drop_graph(e);
             hipError_t err = hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed);
             if (err != hipSuccess) return fail("engine_run: BeginCapture: %s", hipGetErrorString(err));
-            int rc = 0;
-            e->graph_steps = 1;
-#ifdef CCDM_EXPERIMENTS
-            if (exp_env("CCDM_GRAPH_STEPS") > 1) e->graph_steps = exp_env("CCDM_GRAPH_STEPS");      // probe: several denoise steps per captured graph
-#endif
-            for (int g = 0; g < e->graph_steps && !rc; ++g) rc = launch_step(e, with_epilogue, s, false);
+            const int rc = launch_step(e, with_epilogue, s, false);
             err = hipStreamEndCapture(s, &e->graph);
             if (rc) { if (e->graph) { (void)hipGraphDestroy(e->graph); e->graph = nullptr; } return rc; }
             if (err != hipSuccess) return fail("engine_run: EndCapture: %s", hipGetErrorString(err));
@@ -331,14 +286,9 @@ extern "C" int ccdm_engine_run(ccdm_engine* e, int first_row, int n_steps, int w
             e->graph_with_epilogue = with_epilogue;
             e->captures++;
         }
-        int i = 0;
-        for (; i + e->graph_steps <= n_steps; i += e->graph_steps) {
+        for (int i = 0; i < n_steps; ++i) {
             hipError_t err = hipGraphLaunch(e->exec, s);
             if (err != hipSuccess) return fail("engine_run: GraphLaunch: %s", hipGetErrorString(err));
-        }
-        for (; i < n_steps; ++i) {                  // (a remainder shorter than the captured graph: eager)
-            int rc = launch_step(e, with_epilogue, s, false);
-            if (rc) return rc;
         }
         return 0;
     }

@@ -8,7 +8,7 @@
 // a 2x2 conv with 4*Cout output channels, n-tile = 4 * channel tile + phase).
 //
 // The general kernel's form of this layer (k_conv<.., NI = 4, UP2>) walks 16-channel chunks, each with the chunk's four phases of weight
-// fragments staged through LDS (32 KB per chunk, by LDS-DMA behind barrier A): its block timeline (tools/timeline_op.py, 64 -> 64 at
+// fragments staged through LDS (32 KB per chunk, by LDS-DMA behind barrier A): its block timeline (64 -> 64 at
 // 32x32 -> 64x64) is 4 chunks x (3 200-4 500 cycles of commit = waiting for that DMA, + two barriers) around 48 matrix instructions per
 // wave, 57 000 cycles per block in 1.33 rounds: 52.6 us for a layer whose bytes take 13 us and whose matrix work takes 12.
 // Here:

@@ -8,7 +8,6 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import os
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -17,9 +16,6 @@ import torch
 
 from . import hip
 from .unet_spec import GN_EPS, UNetSpec
-
-_TIMELINE_OP = int(os.environ.get("CCDM_TIMELINE_OP", "-1"))          # tools/timeline_op.py
-_NO_SUBPIXEL = bool(int(os.environ.get("CCDM_NO_SUBPIXEL", "0")))     # same-box A/B hook: Upsample convs in the direct (9-tap) form
 
 
 @dataclass
@@ -143,7 +139,6 @@ class SamplerEngine:
             bias_np = bias_np + sd[skip_key + ".bias"].numpy()
         # Upsample + conv 3x3 runs in sub-pixel form (4 taps of the low-resolution input per output pixel instead of 9) where built
         subpixel = bool(up) and ksize == 3 and stride == 1 and resid is None and skip_src is None and gn is None and emb_off < 0 and \
-            not _NO_SUBPIXEL and \
             bool(self.lib.ccdm_upconv_supported(cin, cout, prec))
         wdev = self._upload(hip.pack_upconv_weight(w, prec) if subpixel else hip.pack_conv_weight(w, ksize, pack_prec, absmax))
         bias = self._upload(bias_np)
@@ -179,8 +174,6 @@ class SamplerEngine:
             args.skip0, args.SC0 = sa.ptr, sa.C
             args.skip1, args.SC1 = (sb.ptr, sb.C) if sb else (0, 0)
             args.skip_w = skip_w.data_ptr()
-        if len(self.op_names) == _TIMELINE_OP:      # diagnostics: phase stamps of one block of this op (-DCCDM_ABLATION library only);
-            args.prec |= 16 << 8                    # set BEFORE the slice query: the bit may change the kernel the layer selects
         # the statistics slices this launch will leave: the library's answer for the fully described layer (the kernel it selects owns the tiling)
         out = self._act(cout, hout, wout, stats, hip.check(self.lib.ccdm_conv_out_slices(C.byref(args)), "conv_out_slices " + wkey))
         args.out = out.ptr
@@ -303,7 +296,6 @@ class SamplerEngine:
         # cost grows with T^2 on the vector pipe; beyond, the core keeps the matrix kernel and its operand range.
         core_f32 = (p + ".attention") in self.f32_layers or (self.prec == hip.PREC_F32 and T_ <= 2048)
         fused = (self.prec == hip.PREC_F16X3 and (p + ".qkv") not in self.f32_layers and not core_f32 and x.stats is not None
-                 and not os.environ.get("CCDM_NO_ATTN_BLOCK")
                  and self.lib.ccdm_norm_qkv_attention_supported(T_, l.ch, l.heads))
         if fused:
             # GroupNorm + qkv + attention core in one launch (low-resolution stages): the 3C-wide qkv tensor stays on chip

@@ -16,9 +16,6 @@ ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get("CCDM_LIB") or os.path.join(_HERE, "libccdm_hip.so")      # CCDM_LIB: A/B two builds on one GPU box
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["ccdm_conv.hip", "ccdm_conv_ks.hip", "ccdm_upconv.hip", "ccdm_stem.hip", "ccdm_head.hip", "ccdm_conv1x1.hip", "ccdm_misc.hip", "ccdm_attention.hip", "ccdm_attn_block.hip", "ccdm_sampler.hip", "ccdm_metrics.hip", "ccdm_range.hip", "ccdm_resample.hip", "ccdm_engine.hip"]
-# CCDM_EXPERIMENTS=1 builds add the measured-and-rejected kernels of tools/experiments/ and the environment switches the A/B tools use
-# (exp_env in ccdm_common.h); the shipped library contains neither
-EXPERIMENT_SOURCES = [os.path.join(ROOT, "tools", "experiments", "ccdm_conv_pc.hip"), os.path.join(ROOT, "tools", "experiments", "ccdm_attention_split.hip")]
 # -amdgpu-mfma-vgpr-form: MFMA accumulators stay in the (unified) VGPR file.  The default heuristic parks them in AccVGPRs and pays a
 # v_accvgpr_read/_write for every vector op that touches a score or an output accumulator: 240 extra instructions per key tile in
 # the attention kernels (2066 in ccdm_attention.hip, 576 in ccdm_attn_block.hip; the conv kernels have none either way).
@@ -35,7 +32,7 @@ STEP_SAMPLE, STEP_LAST_CONFIDENCE, STEP_LAST_MAJORITY, STEP_LAST_KEEP, STEP_SOFT
 STATS_MAX_SLICES = 64       # CCDM_STATS_MAX_SLICES: what a GroupNorm consumer reads
 F16X3_LIMIT = 4094.0        # CCDM_F16X3_LIMIT: the fp16 split is exact for staged |a| below this
 STATS_FOLD_SLICES = 16      # CCDM_STATS_FOLD_SLICES: what the engine folds a larger slice count to
-ABI_VERSION = 10         # CCDM_ABI_VERSION of include/ccdm_hip.h
+ABI_VERSION = 11         # CCDM_ABI_VERSION of include/ccdm_hip.h
 MAX_CLASSES = 255        # CCDM_MAX_CLASSES: x_t is a uint8 class index (K <= 32 in registers, more through LDS rows)
 POST_DIAG_MANY = 256     # CCDM_POST_DIAG_MANY: OR into PostArgs.softmax to run the many-class epilogue kernel at any K (parity tests)
 
@@ -166,7 +163,6 @@ SIGNATURES = {
     "ccdm_mix_uniform": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "ccdm_theta_post": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "ccdm_kl_clamped": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p]),
-    "ccdm_debug_read_timeline": (C.c_int, [C.c_void_p, C.c_int]),
     "ccdm_nchw_to_nhwc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "ccdm_onehot_to_xin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "ccdm_engine_create": (C.c_void_p, [C.c_void_p]),
@@ -196,50 +192,18 @@ class CcdmRangeError(CcdmHipError):
     split's range (|a| >= 4094, include/ccdm_hip.h).  Outputs of that run are invalid."""
 
 
-def clean_build_tree(keep: Optional[str] = None) -> None:
-    """Remove the object directories of every build flavour except `keep` and the default one (build/obj).  Never called implicitly
-    by an incremental build: another process may be compiling into one of them."""
-    import shutil
-    root = os.path.join(_HERE, "build")
-    if not os.path.isdir(root):
-        return
-    for d in os.listdir(root):
-        p = os.path.join(root, d)
-        if d.startswith("obj_") and p != keep and os.path.isdir(p):
-            shutil.rmtree(p, ignore_errors=True)
-
-
 def build(force: bool = False, verbose: bool = False) -> str:
     """Compile libccdm_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).  One object per source,
     compiled in parallel into <package>/build/ (only the sources that changed), then linked."""
     from concurrent.futures import ThreadPoolExecutor
-    import hashlib
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
     hdrs = [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".h")] + [os.path.join(ROOT, "include", "ccdm_hip.h")]
-    extra = ["-DCCDM_ABLATION"] if os.environ.get("CCDM_ABLATION") else []      # tools/bench_conv.py ABLATE / TIMELINE modes
-    if os.environ.get("CCDM_EXPERIMENTS"):
-        extra += ["-DCCDM_EXPERIMENTS", "-I" + CSRC]
-        srcs += EXPERIMENT_SOURCES
-    extra += os.environ.get("CCDM_HIPCC_EXTRA", "").split()                     # one-off experiments
-    # one object directory per build flavour (stable name), and a stamp next to the library saying which flavour it was linked from:
-    # a plain build after an ablation / experiments build must relink, not return the other flavour's library
-    flavour = hashlib.sha1(" ".join(extra).encode()).hexdigest()[:10] if extra else "default"
-    objdir = os.path.join(_HERE, "build", "obj" + ("" if flavour == "default" else "_" + flavour))
+    objdir = os.path.join(_HERE, "build", "obj")
     os.makedirs(objdir, exist_ok=True)
-    # prune: objects whose source left the list; the object directories of OTHER flavours only on force=True (clean_build_tree() does the
-    # same explicitly) — alternating ablation / experiment / default builds keep their incremental caches, and a concurrent build of
-    # another flavour (the A/B tools) never loses its directory mid-compile
     wanted = {os.path.basename(s) + ".o" for s in srcs}
-    for f in os.listdir(objdir):
+    for f in os.listdir(objdir):          # objects whose source left the list
         if f.endswith(".o") and f not in wanted:
             os.remove(os.path.join(objdir, f))
-    if force:
-        clean_build_tree(keep=objdir)
-    stamp = LIB_PATH + ".flavour"
-    try:
-        linked_flavour = open(stamp).read().strip()
-    except OSError:
-        linked_flavour = None
     newest_hdr = max(os.path.getmtime(h) for h in hdrs)
     flags = [f for f in HIPCC_FLAGS if f != "-shared"]
 
@@ -247,7 +211,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
         if not force and os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(src), newest_hdr):
             return obj, False
-        cmd = ["hipcc", *flags, *extra, "-I" + os.path.join(ROOT, "include"), "-c", src, "-o", obj]
+        cmd = ["hipcc", *flags, "-I" + os.path.join(ROOT, "include"), "-c", src, "-o", obj]
         if verbose:
             print(" ".join(cmd))
         r = subprocess.run(cmd, capture_output=True, text=True)
@@ -258,7 +222,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     with ThreadPoolExecutor(max_workers=min(len(srcs), os.cpu_count() or 1)) as ex:
         res = list(ex.map(compile_one, srcs))
     objs = [o for o, _ in res]
-    if not force and not any(c for _, c in res) and os.path.exists(LIB_PATH) and linked_flavour == flavour and \
+    if not force and not any(c for _, c in res) and os.path.exists(LIB_PATH) and \
             all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(o) for o in objs):
         return LIB_PATH
     cmd = ["hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", *objs, "-o", LIB_PATH]
@@ -267,8 +231,6 @@ def build(force: bool = False, verbose: bool = False) -> str:
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise CcdmHipError("hipcc link failed:\n" + r.stdout + r.stderr)
-    with open(stamp, "w") as fh:
-        fh.write(flavour + "\n")
     return LIB_PATH
 
 

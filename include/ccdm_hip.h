@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define CCDM_ABI_VERSION 10
+#define CCDM_ABI_VERSION 11
 #define CCDM_MAX_CHANNELS 1024      /* max C0+C1 of a GroupNorm'ed conv input */
 #define CCDM_STATS_MAX_SLICES 64    /* partial-statistics slices per sample a GroupNorm consumer reads (more: ccdm_stats_fold) */
 #define CCDM_STATS_FOLD_SLICES 16   /* what ccdm_stats_fold reduces a larger slice count to */
@@ -346,9 +346,6 @@ int ccdm_attention_ex(const float* qkv /*dev [N,T_alloc,3C]*/, float* out /*dev 
                       int heads, int order, void* stream);
 int ccdm_layernorm(const float* x, const float* gamma, const float* beta, float eps, long rows, int C, float* out, void* stream);
 int ccdm_gelu(const float* x, size_t n, float* out, void* stream);
-
-/* debugging aid: phase timestamps (s_memtime) one block of the last conv launched with ablation bit 16 recorded */
-int ccdm_debug_read_timeline(unsigned long long* host, int n);
 
 /* boundary re-layout helpers */
 int ccdm_nchw_to_nhwc(const float* src, float* dst, int N, int C, int HW, int dst_stride, int dst_off, void* stream);

@@ -23,7 +23,7 @@ SHAPES = [
 ]
 
 
-def run(prec, shape, iters=20, dbg=0):
+def run(prec, shape, iters=20):
     cnt, c0, c1, cout, H, W, k, stride, up, gn = shape
     lib = hip.load()
     g = torch.Generator(device="cpu").manual_seed(0)
@@ -32,7 +32,6 @@ def run(prec, shape, iters=20, dbg=0):
     cin = c0 + c1
     w = (torch.randn((cout, cin, k, k), generator=g) / np.sqrt(cin * k * k)).numpy()
     wd = torch.from_numpy(hip.pack_conv_weight(w, k, hip.PREC_F16X3 if prec == hip.PREC_F16 else prec)).to(DEV)      # (the single-pass mode reads the hi halves of the F16X3 packing)
-    prec = prec | (dbg << 8)
     bias = torch.zeros(cout, device=DEV)
     gam, bet = torch.ones(cin, device=DEV), torch.zeros(cin, device=DEV)
     Hc, Wc = (2 * H, 2 * W) if up else (H, W)
@@ -74,25 +73,6 @@ def run(prec, shape, iters=20, dbg=0):
     return ms, flops / ms / 1e9, byts / ms / 1e6
 
 
-def timeline(prec, shape):
-    """Phase durations (cycles) of one mid-grid block: stamps 2..7 per iteration = loop top | barrier A | commit | barrier B |
-    issue | MFMA phase | (epilogue)."""
-    run(prec, shape, iters=1, dbg=16 | int(os.environ.get("TLDBG", "0")))
-    lib = hip.load()
-    buf = (C.c_ulonglong * 1024)()
-    hip.check(lib.ccdm_debug_read_timeline(buf, 1024))
-    n = int(buf[1023])
-    ev = [(int(buf[i]) >> 56, int(buf[i]) & ((1 << 56) - 1)) for i in range(min(n, 1020))]
-    names = {12: "kernel-entry", 1: "start", 2: "top(prev phase end)", 3: "barrierA", 4: "commit", 5: "barrierB", 6: "issue", 7: "mfma", 8: "end", 9: "epi-barrier", 10: "epi-transpose", 11: "epi-rows", 13: "first-issue", 14: "gn-affine"}
-    t0 = ev[0][1]
-    prev = t0
-    out = []
-    for slot, t in ev[1:]:
-        out.append(f"{names.get(slot, slot)}+{t - prev}")
-        prev = t
-    print(f"timeline total {prev - t0} cycles (100 MHz-ish s_memtime ticks): " + " ".join(out[:64]))
-
-
 def run_fused_skip(prec, c0, c1, cout, H, W):
     """ResBlock tail: conv3x3(SiLU(GN(h))) + conv1x1([xa|xb]) + residual-free, one launch (tests/hip_util.conv2d does the packing)."""
     from tests import hip_util as U
@@ -109,54 +89,16 @@ def run_fused_skip(prec, c0, c1, cout, H, W):
     return b["ms"]
 
 
-def timeline_pc(prec, shape):
-    """Producer/consumer kernel (CCDM_PC_TIMELINE=1): stamps of loader wave 0 and matrix wave 0 of one mid-grid block."""
-    run(prec, shape, iters=1)
-    lib = hip.load()
-    buf = (C.c_ulonglong * 1024)()
-    hip.check(lib.ccdm_debug_read_timeline(buf, 1024))
-    names = {1: "start", 2: "prologue-issued", 3: "barA", 4: "commit0+issue", 5: "barB", 10: "commit", 11: "issueB+issue", 12: "rows", 14: "barrier", 15: "tail-rows",
-             20: "mfma", 21: "acc->epi", 22: "barrier"}
-    for role, off in (("loader", 0), ("matrix", 512)):
-        n = int(buf[off])
-        ev = [(int(buf[off + 1 + i]) >> 56, int(buf[off + 1 + i]) & ((1 << 56) - 1)) for i in range(n)]
-        if not ev:
-            print(role, "no stamps"); continue
-        prev = ev[0][1]
-        out = []
-        for slot, t in ev[1:]:
-            out.append(f"{names.get(slot, slot)}+{t - prev}")
-            prev = t
-        print(f"{role}: total {prev - ev[0][1]} cycles: " + " ".join(out[:90]))
-
-
 if __name__ == "__main__":
     precs = [hip.PREC_F16X3] if len(sys.argv) < 2 else [int(v) for v in sys.argv[1].split(",")]
     only = int(sys.argv[2]) if len(sys.argv) > 2 else None
-    if os.environ.get("CCDM_PC_TIMELINE"):
-        for i in [int(v) for v in os.environ.get("TIMELINE", "0").split(",")]:
-            print(SHAPES[i]); timeline_pc(precs[0], SHAPES[i])
-        sys.exit(0)
-    if os.environ.get("PMCRUN"):          # one (shape, ablation bits) pair, a few launches: the unit tools/pmc_traffic.sh counts
-        i, d = [int(v) for v in os.environ["PMCRUN"].split(",")]
-        print(SHAPES[i], "dbg", d, run(precs[0], SHAPES[i], iters=5, dbg=d))
-        sys.exit(0)
-    if os.environ.get("TIMELINE"):
-        for i in [int(v) for v in os.environ["TIMELINE"].split(",")]:
-            print(SHAPES[i]); timeline(precs[0], SHAPES[i])
-        sys.exit(0)
     for prec in precs:
         total = 0.0
         print(f"--- prec={prec} N={N}")
         for i, sh in enumerate(SHAPES if only is None else SHAPES[:only]):
             ms, tf, gbs = run(prec, sh)
             total += sh[0] * ms
-            abl = ""
-            if os.environ.get("ABLATE"):
-                # 1: no MFMA, 2: no commit (VALU+LDS writes), 4: no prefetch loads, 8: no stores
-                abl = "  | " + " ".join(f"{nm}={run(prec, sh, dbg=d)[0]*1e3:6.1f}" for nm, d in
-                                        [("-Bstage", 32), ("-mfma", 1), ("-commit", 2), ("-loads", 4), ("-stores", 8), ("ld+st only", 3), ("st only", 7), ("ld only", 11), ("nothing", 15), ("no-barriers(wrong)", 256), ("2blk/CU", 512), ("1blk/CU", 1024), ("2blk ld+st", 512 | 3), ("1blk ld+st", 1024 | 3)])
-            print(f"{sh[0]:2d}x {sh[1]+sh[2]:3d}->{sh[3]:3d} @{sh[4]:3d}x{sh[5]:3d} k{sh[6]} s{sh[7]} up{sh[8]} gn{sh[9]}: {ms*1e3:8.1f} us  {tf:7.1f} TF/s  {gbs:7.0f} GB/s(io){abl}")
+            print(f"{sh[0]:2d}x {sh[1]+sh[2]:3d}->{sh[3]:3d} @{sh[4]:3d}x{sh[5]:3d} k{sh[6]} s{sh[7]} up{sh[8]} gn{sh[9]}: {ms*1e3:8.1f} us  {tf:7.1f} TF/s  {gbs:7.0f} GB/s(io)")
         print(f"weighted conv total per denoise step: {total:.3f} ms")
         if only is None:
             for cnt, c0, c1, cout, H, W in [(3, 32, 32, 32, 128, 128), (3, 32, 32, 32, 64, 64), (3, 64, 64, 64, 32, 32), (3, 96, 96, 96, 16, 16), (3, 128, 128, 128, 8, 8)]:

@@ -1,7 +1,7 @@
 #!/bin/bash
-# Build the working-tree sources into tools/abx/<name>.so with extra hipcc flags (same-box A/B / ablation flavours that travel to the GPU
-# box: tools/ab/ is .gpurunignore'd, tools/abx/ is not; *.so stays out of git either way).
-#   tools/build_variant.sh abl -DCCDM_ABLATION        tools/build_variant.sh new
+# Build the working-tree sources into tools/abx/<name>.so with extra hipcc flags, out of tree (same-box A/B of library builds through
+# CCDM_LIB; *.so stays out of git).
+#   tools/build_variant.sh <name> [hipcc flags...]      e.g.  tools/build_variant.sh new   |   tools/build_variant.sh up1 -DCCDM_UP_CTB1
 set -e
 cd "$(dirname "$0")/.."
 NAME=${1:?name}; shift

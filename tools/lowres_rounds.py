@@ -1,9 +1,8 @@
 #!/usr/bin/env python3
 """Round 6: for every launch of ONE denoise step (C2) — blocks, resident block slots (256 CUs x blocks per CU), rounds, launch time —
-and, where a block timeline exists (tools/timeline_op.py, ablation build), the chain of one block in cycles, to show which launches
-are "rounds x one block's chain" and which are throughput-bound.
+to show which launches are one round of blocks and which are throughput-bound.
 
-    python tools/lowres_rounds.py <rocprofv3 kernel trace csv> <bench --per-op json> [<timelines txt>] > profiles/r06_lowres_rounds.md
+    python tools/lowres_rounds.py <rocprofv3 kernel trace csv> <bench --per-op json> > profiles/rNN_lowres_rounds.md
 
 Blocks per CU = min over: VGPRs (512 per SIMD lane; the trace reports the allocation / 2), LDS (160 KB per CU; dynamic LDS is not in the
 trace: recomputed here from the kernels' own formulas, cited below), 32 waves per CU.
@@ -55,12 +54,6 @@ def lds_bytes(name, static_lds, op, prev_op):
 
 def main():
     trace, per_op = sys.argv[1], json.load(open(sys.argv[2]))
-    chains = {}
-    if len(sys.argv) > 3:
-        for line in open(sys.argv[3]):
-            m = re.match(r"op (\d+): total (\d+) cycles", line)
-            if m:
-                chains[int(m.group(1))] = int(m.group(2))
     rows = [r for r in csv.DictReader(open(trace)) if r["Kernel_Name"].startswith(("ccdm::", "void ccdm::"))]
     stems = [i for i, r in enumerate(rows) if "k_stem" in r["Kernel_Name"]]
     nper = stems[1] - stems[0]
@@ -68,12 +61,10 @@ def main():
     steps = steps[len(steps) // 2:]                                      # the later denoise steps (warm)
     print("# Every launch of one C2 denoise step: blocks, resident slots, rounds, time (round 6)\n")
     print(f"Source: rocprofv3 kernel trace of `bench.py --graph 0 --substreams 1` ({len(steps)} denoise steps averaged), the `--per-op` table of the same "
-          "build, block timelines of `tools/timeline_op.py` (s_memtime cycles of one mid-grid block inside the real step; the clock under the "
-          "bench is 1.6–2.0 GHz).  `slots` = 256 CUs × blocks per CU (limited by: v = registers, l = LDS, w = waves); `rounds` = blocks ÷ slots; "
-          "`chain` = one block's timeline; `chain µs` = chain ÷ 2.0 GHz — where a launch is one round of blocks, its time is one block's "
-          "chain plus the launch boundary (≈ 1.7 µs), not its bytes or FLOPs.\n")
-    print("| op | layer | kernel | grid × wg | VGPR | LDS KB | blk/CU | slots | rounds | µs | chain cycles | chain µs @2 GHz |")
-    print("|---|---|---|---|---|---|---|---|---|---|---|---|")
+          "build.  `slots` = 256 CUs × blocks per CU (limited by: v = registers, l = LDS, w = waves); `rounds` = blocks ÷ slots — where a launch "
+          "is one round of blocks, its time is one block's chain plus the launch boundary (≈ 1.7 µs), not its bytes or FLOPs.\n")
+    print("| op | layer | kernel | grid × wg | VGPR | LDS KB | blk/CU | slots | rounds | µs |")
+    print("|---|---|---|---|---|---|---|---|---|---|")
     tot = {}
     for i in range(nper):
         r = steps[0][i]
@@ -102,13 +93,10 @@ def main():
         lim = "v" if bpc == by_v else ("l" if bpc == by_l else "w")
         slots = 256 * bpc
         us = sum((int(s[i]["End_Timestamp"]) - int(s[i]["Start_Timestamp"])) / 1e3 for s in steps) / len(steps)
-        ch = chains.get(i)
         stage = op.get("shape", "").split("@")[-1] if "@" in op.get("shape", "") else op.get("shape", "")
         tot[stage] = tot.get(stage, 0.0) + us
         print(f"| {i} | {op['name']} {op.get('shape', '')} | `{short[:46]}` | {gx}×{gy} × {wg} | {vg} | {lds / 1024:.0f} | {bpc}{lim} | {slots} | "
-              f"{blocks / slots:.2f} | {us:.1f} | {ch if ch else ''} | {ch / 2000:.1f} |" if ch else
-              f"| {i} | {op['name']} {op.get('shape', '')} | `{short[:46]}` | {gx}×{gy} × {wg} | {vg} | {lds / 1024:.0f} | {bpc}{lim} | {slots} | "
-              f"{blocks / slots:.2f} | {us:.1f} | | |")
+              f"{blocks / slots:.2f} | {us:.1f} |")
     print("\nKernel-trace time per stage (µs; the HIP-event taps of bench.py add the launch boundary, ≈ 2 µs per launch): "
           + ", ".join(f"{k}: {v:.0f}" for k, v in tot.items()))
 
