@@ -3,6 +3,7 @@ parameter-file keys.
 
     eval_lidc_uncertainty(params)      /root/reference/evaluation/evaluate_lidc_uncertainty.py:164-216 (Tester.test_step :89-136)
     eval_lidc_sampling_speed(params)   /root/reference/evaluation/evaluate_lidc_sampling_speed.py:165-223 (t = 10000 + K sweep)
+    predict_multiple(model, image, params)  /root/reference/evaluation/eval_cdm.py:206-212 (Evaluator: predict_single / predict_multiple)
 
 No ignite: the loop is a plain `for batch in loader`.  The dataset is `datasets.lidc`'s Test_LIDC re-stated on h5py
 when `data_lidc.hdf5` is available, or a deterministic synthetic stand-in (`dataset_file: synthetic.lidc`) so the
@@ -254,3 +255,36 @@ def eval_lidc_sampling_speed(params: dict, timesteps: Sequence[int] = (250, 200,
         LOGGER.info("Evaluate model with sampling step %d...", k)
         out[k] = eval_lidc_uncertainty(params, init_t=10000 + k, **kw)
     return out
+
+
+VOTE_STRATEGIES = ("confidence", "majority")
+
+
+def vote_settings(params: dict):
+    """(evaluations, evaluation_vote_strategy) as the reference's Evaluator reads them (eval_cdm.py:111-114: the `evaluation`
+    section, defaults 1 and "confidence"), falling back to the top-level keys of the LIDC-style params files.  A list of
+    evaluations (the LIDC evaluator's sweep) means its largest entry."""
+    section = params.get("evaluation") or {}
+    evaluations = section.get("evaluations", params.get("evaluations", 1))
+    strategy = section.get("evaluation_vote_strategy", params.get("evaluation_vote_strategy", "confidence"))
+    n = max(_as_list(evaluations))
+    if n < 1:
+        raise ValueError(f"evaluations: {evaluations!r} (expected >= 1)")
+    if strategy not in VOTE_STRATEGIES:
+        raise ValueError(f"evaluation_vote_strategy: {strategy!r} is not in {list(VOTE_STRATEGIES)}")
+    return n, strategy
+
+
+@torch.no_grad()
+def predict_multiple(model, image: torch.Tensor, params: dict, feature_condition: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The prediction of the reference Evaluator's inference step (eval_cdm.py:206-212): one sample from a uniform one-hot x_T
+    (`predict_single`, :160-165) when `evaluations` is 1, else the mean of `evaluations` samples voted with
+    `evaluation_vote_strategy` (`predict_multiple`, :176-193) — computed on the device by DenoisingModel.predict_multiple.
+    "confidence" gives the reference's `prediction_onehot_total` bit for bit; "majority" (NotImplementedError in the reference)
+    gives the class frequencies.  Returns [B,K,H,W]."""
+    n, strategy = vote_settings(params)
+    if n == 1:
+        K = model.diffusion.num_classes
+        x = OneHotCategoricalBCHW(logits=torch.zeros((image.shape[0], K, *image.shape[2:]), device=image.device)).sample()
+        return model(x, image, feature_condition)["diffusion_out"]
+    return model.predict_multiple(image, feature_condition, num_evaluations=n, voting=strategy, maps=("mean",))["mean"]

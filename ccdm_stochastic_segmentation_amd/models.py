@@ -14,7 +14,7 @@ from __future__ import annotations
 
 import logging
 import math
-from typing import Any, Dict, List, Optional, Tuple, Union, cast
+from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple, Union, cast
 
 import numpy as np
 import torch
@@ -534,10 +534,136 @@ class DenoisingModel(nn.Module):
         return self._with_range_fallback(lambda: self._forward_step(x, condition, feature_condition, t))
 
     def forward_denoising(self, x: Optional[Tensor], condition: Tensor, feature_condition: Tensor,
-                          init_t: Optional[int] = None, label_ref_logits: Optional[Tensor] = None) -> dict:
-        out = self._with_range_fallback(lambda: self._forward_denoising(x, condition, feature_condition, init_t, label_ref_logits))
+                          init_t: Optional[int] = None, label_ref_logits: Optional[Tensor] = None, *,
+                          consume: Optional[Callable[[SamplerEngine, int, int], None]] = None) -> dict:
+        """`consume` (predict_multiple): instead of returning the call's output, hand every sub-batch engine (eng, lo, hi) to
+        consume(eng, lo, hi) once the call has succeeded, with the engine's stream current; the result is then {}."""
+        out = self._with_range_fallback(lambda: self._forward_denoising(x, condition, feature_condition, init_t, label_ref_logits,
+                                                                        consume))
         if self.philox_advance:
             self.philox_call += 1           # the next call draws from a fresh stream (a range-error re-run above replayed this one)
+        return out
+
+    # ------------------------------------------------------------------ multi-sample prediction
+    MULTI_MAPS = ("mean", "vote", "entropy", "mutual_info", "counts")
+
+    @torch.no_grad()
+    def predict_multiple(self, condition: Tensor, feature_condition: Optional[Tensor] = None, *, num_evaluations: int,
+                         voting: Optional[str] = None, x: Optional[Tensor] = None, t: Optional[Tensor] = None, batched: bool = False,
+                         maps: Sequence[str] = ("mean", "vote", "entropy", "mutual_info")) -> Dict[str, Tensor]:
+        """S = `num_evaluations` samples of every image of `condition` [B,C,H,W], combined on the device into one prediction and
+        per-pixel uncertainty maps — the reference's Evaluator.predict_multiple (evaluation/eval_cdm.py:176-193), which sums S
+        `predict_single` outputs as `total += prediction_i * (1 / S)`.
+
+        voting (default `step_T_sample`, the params key `evaluation_vote_strategy`):
+          "confidence": every pass ends in the posterior probabilities; `mean` is the reference's `prediction_onehot_total` bit for bit
+                        (fp32 multiply by fp32(1/S), then fp32 add, pass by pass); `vote` its argmax;
+          "majority":   every pass ends in the argmax class (the reference raises NotImplementedError here); `mean` holds the class
+                        frequencies counts / S, `vote` the majority class (ties to the lowest class index), `counts` the int32 counts.
+        `entropy` is H(mean) in nats; `mutual_info` is H(mean) - (1/S) sum_s H(p_s) (the spread between the samples; with one-hot
+        majority passes every H(p_s) is 0, so it equals `entropy`).
+        x: optional one-hot x_T [S,B,K,H,W]; default: drawn per pass as predict_single does (uniform one-hot on condition's device).
+        t: as in forward (e.g. 10000 + steps for a strided walk).
+        batched=False: S sampling calls of B samples, each advancing `philox_call` exactly like S calls of model(x_i, condition);
+          after each call the pass is folded into device accumulators straight from the engine (ccdm_vote_accumulate), so memory
+          is one pass plus the accumulators.  The range-error fallback and the execution-mode choice apply per pass.
+        batched=True: one call of B*S samples (condition repeat-interleaved, sample b*S + s = pass s of image b, as
+          eval_lidc_uncertainty lays them out), reduced by ccdm_vote_reduce_stack (majority) or S strided accumulations
+          (confidence).  Faster for small B; its noise differs from the sequential mode's because the Philox stream is keyed by
+          call and global sample index — a different, equally valid draw.
+        Returns the requested `maps` on the model's device: mean / counts [B,K,H,W] (fp32 / int32, BCHW views of channels-last
+        memory like the sampler's output), vote [B,H,W] int64, entropy / mutual_info [B,H,W] fp32."""
+        voting = self.step_T_sample if voting is None else voting
+        if voting not in ("confidence", "majority"):
+            raise ValueError(f"voting: {voting!r} (expected 'confidence' or 'majority')")
+        if isinstance(num_evaluations, bool) or int(num_evaluations) != num_evaluations or int(num_evaluations) < 1:
+            raise ValueError(f"num_evaluations: {num_evaluations!r} (expected an integer >= 1)")
+        S = int(num_evaluations)
+        maps = tuple(maps)
+        bad = [m for m in maps if m not in self.MULTI_MAPS or (m == "counts" and voting != "majority")]
+        if bad:
+            raise ValueError(f"maps: {bad} not available (choose from {self.MULTI_MAPS}; 'counts' with voting='majority')")
+        if condition.ndim != 4:
+            raise ValueError(f"condition: expected [B,C,H,W], got {tuple(condition.shape)}")
+        B, H, W = int(condition.shape[0]), int(condition.shape[2]), int(condition.shape[3])
+        K, HW = self.diffusion.num_classes, H * W
+        if x is not None and tuple(x.shape) != (S, B, K, H, W):
+            raise ValueError(f"x: expected one-hot x_T of shape {(S, B, K, H, W)} = [S,B,K,H,W], got {tuple(x.shape)}")
+        init_t = None if t is None else int(t.item() if isinstance(t, Tensor) else t)
+        dev = next(self.unet.parameters()).device
+        lib = hip.load()
+        majority = voting == "majority"
+        want_mi = "mutual_info" in maps
+        w = float(np.float32(1.0 / S))          # the reference's (1 / S) as the fp32 scalar torch multiplies an fp32 tensor by
+
+        def draw(n: int) -> Tensor:             # predict_single's x_T (eval_cdm.py:160-165)
+            return OneHotCategoricalBCHW(logits=torch.zeros((n, K, H, W), device=condition.device)).sample()
+
+        def stream() -> int:
+            return torch.cuda.current_stream(dev).cuda_stream
+
+        total = None if majority else torch.zeros((B, H, W, K), dtype=torch.float32, device=dev)
+        counts = torch.zeros((B, H, W, K), dtype=torch.int32, device=dev) if majority else None
+        ent_sum = torch.zeros((B, H, W), dtype=torch.float32, device=dev) if (want_mi and not majority) else None
+
+        def ptr(a: Optional[Tensor], off: int = 0):
+            return None if a is None else a.data_ptr() + off * a.element_size()
+
+        saved = self.step_T_sample
+        self.step_T_sample = voting
+        try:
+            if not batched:
+                def consume(eng, lo: int, hi: int) -> None:
+                    src_cls, src_probs = (eng.xt, None) if majority else (None, eng.out_probs)
+                    hip.check(lib.ccdm_vote_accumulate(ptr(src_cls), ptr(src_probs), 0, hi - lo, HW, K, w, ptr(total, lo * HW * K),
+                                                       ptr(counts, lo * HW * K), ptr(ent_sum, lo * HW), stream()), "vote_accumulate")
+
+                for i in range(S):
+                    self.forward_denoising(x[i] if x is not None else draw(B), condition, feature_condition, init_t, consume=consume)
+            else:
+                xr = x.transpose(0, 1).reshape(B * S, K, H, W) if x is not None else draw(B * S)
+                cond = condition.repeat_interleave(S, dim=0)
+                fc = feature_condition.repeat_interleave(S, dim=0) if feature_condition is not None else None
+                # the pass outputs of all B*S samples: class maps (1 byte a pixel) or probabilities
+                buf = torch.empty((B * S, HW) if majority else (B * S, HW, K), dtype=torch.uint8 if majority else torch.float32, device=dev)
+
+                def consume(eng, lo: int, hi: int) -> None:
+                    buf[lo:hi].copy_(eng.xt if majority else eng.out_probs.reshape(hi - lo, HW, K))
+
+                self.forward_denoising(xr, cond, fc, init_t, consume=consume)
+                if majority:
+                    vote8 = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+                    mean = torch.empty((B, H, W, K), dtype=torch.float32, device=dev) if "mean" in maps else None
+                    ent = torch.empty((B, H, W), dtype=torch.float32, device=dev) if ("entropy" in maps or want_mi) else None
+                    hip.check(lib.ccdm_vote_reduce_stack(buf.data_ptr(), B, S, HW, K, ptr(counts), ptr(mean), vote8.data_ptr(),
+                                                         ptr(ent), stream()), "vote_reduce_stack")
+                    # one-hot passes: every H(p_s) is 0, the mutual information is the entropy of the mean
+                    return self._multi_maps(maps, mean=mean, counts=counts, vote8=vote8, entropy=ent,
+                                            mutual_info=ent.clone() if (want_mi and "entropy" in maps) else ent)
+                for s in range(S):          # pass s of image b is sample b*S + s: image stride S*HW*K
+                    hip.check(lib.ccdm_vote_accumulate(None, ptr(buf, s * HW * K), S * HW * K, B, HW, K, w, ptr(total), None,
+                                                       ptr(ent_sum), stream()), "vote_accumulate")
+                del buf
+        finally:
+            self.step_T_sample = saved
+        vote8 = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+        ent = torch.empty((B, H, W), dtype=torch.float32, device=dev) if "entropy" in maps else None
+        mi = torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_mi else None
+        mean = torch.empty((B, H, W, K), dtype=torch.float32, device=dev) if (majority and "mean" in maps) else total
+        hip.check(lib.ccdm_vote_finalize(ptr(total), ptr(counts), ptr(ent_sum), B, HW, K, S, ptr(mean) if majority else None,
+                                         vote8.data_ptr(), ptr(ent), ptr(mi), stream()), "vote_finalize")
+        return self._multi_maps(maps, mean=mean, counts=counts, vote8=vote8, entropy=ent, mutual_info=mi)
+
+    @staticmethod
+    def _multi_maps(maps: Sequence[str], **got: Optional[Tensor]) -> Dict[str, Tensor]:
+        out: Dict[str, Tensor] = {}
+        for m in maps:
+            if m in ("mean", "counts"):
+                out[m] = cast(Tensor, got[m]).permute(0, 3, 1, 2)
+            elif m == "vote":
+                out[m] = cast(Tensor, got["vote8"]).long()
+            else:
+                out[m] = cast(Tensor, got[m])
         return out
 
     def _forward_step(self, x: Tensor, condition: Tensor, feature_condition: Tensor, t: Tensor) -> dict:
@@ -561,7 +687,7 @@ class DenoisingModel(nn.Module):
         return {"diffusion_out": out, "logits": logits}
 
     def _forward_denoising(self, x: Optional[Tensor], condition: Tensor, feature_condition: Tensor,
-                           init_t: Optional[int] = None, label_ref_logits: Optional[Tensor] = None) -> dict:
+                           init_t: Optional[int] = None, label_ref_logits: Optional[Tensor] = None, consume=None) -> dict:
         if label_ref_logits is not None:
             # the reference's guidance branch reads attributes that do not exist (guidance_scale_weights,
             # diffusion_denoising.py:172-174): it raises AttributeError there too.
@@ -644,7 +770,7 @@ class DenoisingModel(nn.Module):
             run_steps(parts, s0, s1, noises, s0, use_graph)
             self._probe_ranges([p_[0] for p_ in parts])
         outs = []
-        for eng, lo, hi in parts:
+        for eng, lo, hi in (parts if consume is None else []):
             with eng.enter():
                 if t_values[-1] > 1 or last_mode == hip.STEP_LAST_KEEP:
                     idx = eng.xt.reshape(hi - lo, H, W).long()
@@ -660,6 +786,12 @@ class DenoisingModel(nn.Module):
         flagged = [eng.check_and_clear_flag() for eng, lo, hi in parts]
         if any(flagged):
             parts[0][0].raise_range_error()
+        if consume is not None:            # (only after the flag check: a range-error re-run must not be consumed twice)
+            for eng, lo, hi in parts:
+                with eng.enter():
+                    consume(eng, lo, hi)
+                eng.leave()
+            return {}
         out = outs[0] if nsub == 1 else torch.cat(outs, 0)
         if out.device != x.device:
             out = out.to(x.device)

@@ -316,6 +316,39 @@ int ccdm_pairwise_class_counts(const uint8_t* a /*dev [B,S,HW]*/, const uint8_t*
                                int HW, int K, int32_t* out /*dev [B,S,L,K,2]*/, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Multi-sample prediction (DenoisingModel.predict_multiple): S sampling passes of the same B images folded into one
+ * mean map, a per-pixel vote and two uncertainty maps.  The reference's Evaluator.predict_multiple
+ * (evaluation/eval_cdm.py:176-193) accumulates `total += prediction_i * (1 / S)` on the host; these read a pass
+ * straight from the engine's uint8 class map or its probabilities.  Channels-last [B,HW,K] like out_probs;
+ * K in [1, CCDM_MAX_CLASSES].  Entropies are in nats (0 log 0 = 0), formed in fp64, stored fp32.
+ *   ccdm_vote_accumulate   : add one pass, in place.  Source: cls (class map, one-hot meaning) XOR probs (fp32);
+ *                            src_stride = elements from one image's source to the next (0 = dense: HW resp. HW*K).
+ *                            total[b,p,k] += src[b,p,k] * w as one rounded fp32 multiply and one rounded fp32 add
+ *                            (w = fp32 1/S: bit-identical to torch-CPU's `total += pred * (1 / S)`);
+ *                            counts[b,p,k] += (cls == k) (class-map source only);
+ *                            ent_sum[b,p] += H(probs[b,p,:]) (probability source only; a one-hot pass adds 0).
+ *                            Each accumulator may be NULL.
+ *   ccdm_vote_finalize     : vote = argmax of counts (if given) else of total, ties to the lowest class index;
+ *                            entropy = H(mean) with mean = counts / S or total; mutual_info = max(0, H(mean) - ent_sum / S)
+ *                            (ent_sum NULL: 0, one-hot passes); mean (needs counts) = (float)counts / (float)S.
+ *                            Each output may be NULL.
+ *   ccdm_vote_reduce_stack : the one-shot form over an S-sample stack [B,S,HW] (S samples of an image contiguous):
+ *                            counts, mean = counts / S, vote, entropy in one read of the stack (each output may be NULL).
+ * Bytes (fp32 total, per pass): accumulate reads HW*B bytes (class map) or 4*B*HW*K (probabilities) and reads and
+ * writes each accumulator once; finalize reads the accumulators once and writes the maps once.
+ * ------------------------------------------------------------------------------------------------- */
+int ccdm_vote_accumulate(const uint8_t* cls /*dev [B,HW] or NULL*/, const float* probs /*dev [B,HW,K] or NULL*/, int64_t src_stride,
+                         int B, int HW, int K, float w, float* total /*dev [B,HW,K] or NULL*/,
+                         int32_t* counts /*dev [B,HW,K] or NULL*/, float* ent_sum /*dev [B,HW] or NULL*/, void* stream);
+int ccdm_vote_finalize(const float* total /*dev [B,HW,K] or NULL*/, const int32_t* counts /*dev [B,HW,K] or NULL*/,
+                       const float* ent_sum /*dev [B,HW] or NULL*/, int B, int HW, int K, int S,
+                       float* mean /*dev [B,HW,K] or NULL*/, uint8_t* vote /*dev [B,HW] or NULL*/,
+                       float* entropy /*dev [B,HW] or NULL*/, float* mutual_info /*dev [B,HW] or NULL*/, void* stream);
+int ccdm_vote_reduce_stack(const uint8_t* stack /*dev [B,S,HW]*/, int B, int S, int HW, int K,
+                           int32_t* counts /*dev [B,HW,K] or NULL*/, float* mean /*dev [B,HW,K] or NULL*/,
+                           uint8_t* vote /*dev [B,HW] or NULL*/, float* entropy /*dev [B,HW] or NULL*/, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Training-time forward pieces of the categorical diffusion, BCHW fp32 like the reference's
  * tensors, per-sample coefficients (the host resolves t -> alpha_t / cumalpha_{t-1} incl. the t == 1 override).
  *   ccdm_mix_uniform : out = s[n]*x + (1-s[n])/K.   With s = 1-beta_t it is the probability table of
