@@ -160,10 +160,10 @@ __global__ __launch_bounds__((T / 32) * 64) void k_qkv_attention(const AttnBlock
             f64x2 g = {0.0, 0.0};
 #pragma unroll
             for (int j = 0; j < cpg; ++j) g += scratch[c_lo + j];
-            float meanf, rstd;
-            gn_mean_rstd(g[0], g[1], (double)cpg * (double)T, a.eps, meanf, rstd);
-            const float sc = rstd * (c == tid ? pf_gamma : a.gamma[c]);
-            const float sh = (c == tid ? pf_beta : a.beta[c]) - sc * meanf;
+            double mean, rs;
+            gn_mean_rstd64(g[0], g[1], (double)cpg * (double)T, a.eps, mean, rs);
+            const float sc = (float)rs * (c == tid ? pf_gamma : a.gamma[c]);
+            const float sh = (float)((double)(c == tid ? pf_beta : a.beta[c]) - (double)sc * mean);     // fp64, rounded once (gn_finalize)
             ab[c] = make_float2(sc * ACT_PRESCALE, sh * ACT_PRESCALE);       // activation pre-scale 2^4, undone through wsq
         }
         for (int i = tid; i < 96; i += NT) { tb[i] = i == tid ? pf_bias : a.bqkv[96 * hd + i]; tb[96 + i] = i == tid ? pf_wsq : k.wsq[96 * hd + i]; }

@@ -158,13 +158,16 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
         base[mi] = PREC == CCDM_PREC_F32 ? hpix * 33 + (lane >> 5) : hpix * PIXB + (lane >> 5) * 16;   // floats | bytes
         if (UP2 && NI == 1) base[mi] += ((phase_of(0) >> 1) * HWt + (phase_of(0) & 1)) * PIXB;   // this phase's 2x2 window starts at halo offset (dy, dx)
     }
-    // output statistics: slow epilogue -> lane = channel (index 0 used); fast epilogue -> lane = (pixel, channel quad)
-    // (fp32 per lane: <= a few hundred values each; widened to fp64 before lanes, waves and slices are combined)
-    float s1[NI][4], s2[NI][4];
+    // Output statistics in fp64, every stored value added in fp64 (v * v is exact there): var = sum x^2 / n - mean^2 cancels in
+    // proportion to mean^2 / var of the group, so fp32 sums (even 8-value fp32 tile partials) left rstd errors of 1e-5 at mean/std = 100
+    // and of order 1 at 1000 — a conv bias or a residual puts a group there (tests/test_gn_statistics.py).
+    // A tile's sums are fp64 temporaries of its epilogue; they are then reduce-scattered over the lanes that hold the same channels, so
+    // that the running sums cost ONE fp64 register pair per lane and n-tile (16 pairs per lane would make the exact-fp32 two-n-tile
+    // variant spill): st[ni] of lane (prow = lane >> 3, cq = lane & 7) is component prow = 4 * (sum x^2 ? 1 : 0) + e of channel
+    // 4 cq + e (fast epilogue); of lane (h = lane >> 5, c = lane & 31) it is sum x (h = 0) or sum x^2 (h = 1) of channel c (slow one).
+    double st[NI];
 #pragma unroll
-    for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { s1[ni][j] = 0.f; s2[ni][j] = 0.f; }
+    for (int ni = 0; ni < NI; ++ni) st[ni] = 0.0;
     const bool fast_epi = (a.Cout & 3) == 0;       // uniform: float4 rows through an LDS transpose
     // per-lane epilogue constants of output channel (n-tile, lane & 31): bias (+ emb row) and the power of two that undoes
     // the weight / activation pre-scales.  Fetched once per block — inside the tile loop their L2 latency sat in every
@@ -800,7 +803,7 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
                     // residual rows: the first half is requested before the transpose (its latency hides behind the LDS
                     // writes), the second half behind the first half's stores — all of them live at once together with the
                     // accumulators and the next tile's prefetch would not fit the registers
-                    float t1[4] = {0.f, 0.f, 0.f, 0.f}, t2[4] = {0.f, 0.f, 0.f, 0.f};
+                    double t1[4] = {0.0, 0.0, 0.0, 0.0}, t2[4] = {0.0, 0.0, 0.0, 0.0};
                     auto epi_ni = [&](auto FULL_, auto RESID_) {
                     constexpr bool FULL = decltype(FULL_)::value, RESID = decltype(RESID_)::value;
                     auto load_resid = [&](const int j0, const int j1) {
@@ -843,14 +846,14 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
                             if (FULL) {
                                 store16_uniform_base(reinterpret_cast<char*>(outn) + row_base(j), lane_off, v);
 #pragma unroll
-                                for (int e = 0; e < 4; ++e) { t1[e] += v[e]; t2[e] = fmaf(v[e], v[e], t2[e]); }
+                                for (int e = 0; e < 4; ++e) { const double d = v[e]; t1[e] += d; t2[e] = fma(d, d, t2[e]); }
                             } else {
                                 const int oy = row_of(j), ox = ox0 + (j * 8) % TW + prow;
                                 if (cv4 && oy < eH && ox < eW) {
                                     *reinterpret_cast<f32x4*>(reinterpret_cast<char*>(outn) +
                                                               ((pix_of(oy, ox) * (unsigned)aCout + (unsigned)co4) << 2)) = v;
 #pragma unroll
-                                    for (int e = 0; e < 4; ++e) { t1[e] += v[e]; t2[e] = fmaf(v[e], v[e], t2[e]); }
+                                    for (int e = 0; e < 4; ++e) { const double d = v[e]; t1[e] += d; t2[e] = fma(d, d, t2[e]); }
                                 }
                             }
                         }
@@ -859,8 +862,17 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
                     // one straight-line copy per (full tile, residual) combination: uniform branches taken once
                     if (a.resid) { if (full) epi_ni(std::true_type{}, std::true_type{}); else epi_ni(std::false_type{}, std::true_type{}); }
                     else { if (full) epi_ni(std::true_type{}, std::false_type{}); else epi_ni(std::false_type{}, std::false_type{}); }
+                    // reduce-scatter of the 8 components {t1[0..3], t2[0..3]} over the 8 lanes of channel quad cq (xor 32, 16, 8), fixed order:
+                    // lane prow keeps component prow
+                    {
+                        const bool b2 = (lane_ >> 5) & 1, b1 = (lane_ >> 4) & 1, b0 = (lane_ >> 3) & 1;
+                        double u[4], w[2];
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) { s1[ni][e] += t1[e]; s2[ni][e] += t2[e]; }
+                        for (int i = 0; i < 4; ++i) u[i] = (b2 ? t2[i] : t1[i]) + __shfl_xor(b2 ? t1[i] : t2[i], 32);
+#pragma unroll
+                        for (int i = 0; i < 2; ++i) w[i] = (b1 ? u[2 + i] : u[i]) + __shfl_xor(b1 ? u[i] : u[2 + i], 16);
+                        st[ni] += (b0 ? w[1] : w[0]) + __shfl_xor(b0 ? w[0] : w[1], 8);
+                    }
                 }
             } else {
 #pragma unroll
@@ -868,8 +880,7 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
                 const int co = (nt0 + ni) * 32 + (lane_ & 31);
                 const bool cv = co < a.Cout;
                 const float add = epi_add[ni], wsc = epi_wsc[ni];
-                // per-tile partial statistics in fp32 (<= 32 values per lane), folded into the fp64 running sums once per tile
-                float t1 = 0.f, t2 = 0.f;
+                double t1 = 0.0, t2 = 0.0;
 #pragma unroll
                 for (int mi = 0; mi < MI; ++mi) {
                     // pixel of accumulator register r: p = msub*32 + (r&3) + 8*(r>>2) + 4*(lane>>5)
@@ -883,13 +894,15 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
                             float v = (PREC == CCDM_PREC_F32 ? acc[mi][ni][r] : acc[mi][ni][r] * wsc) + add;
                             if (a.resid) v += a.resid[idx];
                             a.out[idx] = v;
-                            t1 += v;
-                            t2 = fmaf(v, v, t2);
+                            const double d = v;
+                            t1 += d;
+                            t2 = fma(d, d, t2);
                         }
                     }
                 }
-                s1[ni][0] += t1;
-                s2[ni][0] += t2;
+                // the two lanes of channel c: lane c keeps sum x, lane c + 32 sum x^2
+                const bool h = lane_ >> 5;
+                st[ni] += (h ? t2 : t1) + __shfl_xor(h ? t1 : t2, 32);
             }
             }
         }
@@ -901,30 +914,10 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
         // fold the lanes that hold the same channel, then the block's waves; fixed order everywhere
         __syncthreads();
         double* red = reinterpret_cast<double*>(halo_b);     // [WAVES*KSP][NI][32][2]
-        if (fast_epi) {
+        // (the lanes already hold the wave's sums, one component each — see st)
+        const int ch = fast_epi ? 4 * (lane & 7) + ((lane >> 3) & 3) : lane & 31, comp = lane >> 5;
 #pragma unroll
-            for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    double v1 = (double)s1[ni][e], v2 = (double)s2[ni][e];
-#pragma unroll
-                    for (int off = 8; off < 64; off <<= 1) { v1 += __shfl_xor(v1, off); v2 += __shfl_xor(v2, off); }
-                    if (lane < 8) {
-                        red[((wave_all * NI + ni) * 32 + 4 * lane + e) * 2 + 0] = v1;
-                        red[((wave_all * NI + ni) * 32 + 4 * lane + e) * 2 + 1] = v2;
-                    }
-                }
-        } else {
-#pragma unroll
-            for (int ni = 0; ni < NI; ++ni) {
-                const double m1 = (double)s1[ni][0], m2 = (double)s2[ni][0];
-                const double o1 = __shfl_xor(m1, 32), o2 = __shfl_xor(m2, 32);
-                if (lane < 32) {
-                    red[((wave_all * NI + ni) * 32 + lane) * 2 + 0] = m1 + o1;
-                    red[((wave_all * NI + ni) * 32 + lane) * 2 + 1] = m2 + o2;
-                }
-            }
-        }
+        for (int ni = 0; ni < NI; ++ni) red[((wave_all * NI + ni) * 32 + ch) * 2 + comp] = st[ni];
         __syncthreads();
         // (sub-pixel form with all four phases in the block: they are n-tiles of ONE 32-channel tile and fold into one partial,
         //  phase 0..3 in order; with one phase per block each phase leaves its own slot)

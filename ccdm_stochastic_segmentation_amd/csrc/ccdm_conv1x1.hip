@@ -118,18 +118,19 @@ __global__ __launch_bounds__(MAXT) void k_conv1x1(const Conv1x1K k) {
         if (ks0 + KSB < nks) issue(ks0 + KSB);                                 // wide inputs (C > 16 * KSB): next batch
     }
 
-    float t1 = 0.f, t2 = 0.f;
+    double t1 = 0.0, t2 = 0.0;                                                 // statistics: every stored value added in fp64 (see ccdm_conv.hip)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         float v = fmaf(acc[r], wsc, add);                                      // wsc is a power of two: exact product
         if (k.resid) v += rs[r];
         k.out[obase + (size_t)((r & 3) + 8 * (r >> 2)) * k.Cout] = v;
-        t1 += v;
-        t2 = fmaf(v, v, t2);
+        const double d = v;
+        t1 += d;
+        t2 = fma(d, d, t2);
     }
     if (k.out_stats) {
         __shared__ double red[(MAXT / 64) * 32 * 2];
-        double v1 = (double)t1, v2 = (double)t2;
+        double v1 = t1, v2 = t2;
         v1 += __shfl_xor(v1, 32);
         v2 += __shfl_xor(v2, 32);
         if (lane < 32) { red[(wave * 32 + lane) * 2] = v1; red[(wave * 32 + lane) * 2 + 1] = v2; }

@@ -118,19 +118,17 @@ __device__ __forceinline__ void gn_group_sums(const ccdm_conv_args& a, int n, in
 // square-root expansions (three v_div sequences and a v_sqrt: ~800 cycles of a block prologue that small-spatial launches cannot
 // hide): hardware reciprocal / reciprocal-square-root estimates refined by two Newton steps each — relative error < 2^-50,
 // invisible after the rounding to fp32.
-__device__ __forceinline__ void gn_mean_rstd(double sum, double sq, double cnt, float eps, float& meanf, float& rstd) {
+__device__ __forceinline__ void gn_mean_rstd64(double sum, double sq, double cnt, float eps, double& mean, double& rs) {
     double ic = __builtin_amdgcn_rcp(cnt);
     ic = ic * (2.0 - cnt * ic);
     ic = ic * (2.0 - cnt * ic);
-    const double mean = sum * ic;
+    mean = sum * ic;
     double var = sq * ic - mean * mean;
     if (var < 0.0) var = 0.0;
     const double ve = var + (double)eps;
-    double rs = __builtin_amdgcn_rsq(ve);
+    rs = __builtin_amdgcn_rsq(ve);
     rs = rs * (1.5 - 0.5 * ve * rs * rs);
     rs = rs * (1.5 - 0.5 * ve * rs * rs);
-    meanf = (float)mean;
-    rstd = (float)rs;
 }
 
 // per-channel parameters of the affine, fetched ahead of the arithmetic (gn_params) so that a kernel can issue every small load
@@ -148,16 +146,19 @@ __device__ __forceinline__ GnParams gn_params(const ccdm_conv_args& a, int emb_r
 __device__ __forceinline__ float2 gn_finalize(const ccdm_conv_args& a, const GnParams& p, double sum, double sq) {
     const int C = a.C0 + a.C1;
     const int cpg = C / 32;
-    float meanf, rstd;
-    gn_mean_rstd(sum, sq, (double)cpg * (double)a.Hin * (double)a.Win, a.eps, meanf, rstd);
-    float sc = rstd * p.gamma;
-    float sh = p.beta - sc * meanf;
+    double mean, rs;
+    gn_mean_rstd64(sum, sq, (double)cpg * (double)a.Hin * (double)a.Win, a.eps, mean, rs);
+    float sc = (float)rs * p.gamma;
+    double base = p.beta;
     if (a.film) {   // h = GN(h) * (1 + scale) + shift          unet.py:254-258
         const float one_plus = 1.0f + p.film_scale;
         sc = sc * one_plus;
-        sh = sh * one_plus + p.film_shift;
+        base = (double)p.beta * one_plus + p.film_shift;
     }
-    return make_float2(sc, sh);
+    // the shift in fp64 from the scale as rounded, then rounded once: y = sc * x + sh is then sc * (x - mean) + base up to that one
+    // rounding.  (In fp32 — sc * meanf, then beta minus that — a group of variance <= eps, rstd ~ 300, lost ~2e-5 of its normalised
+    // value to the roundings at |sc * mean| ~ 10^2, tests/test_gn_statistics.py.)
+    return make_float2(sc, (float)(base - (double)sc * mean));
 }
 
 // Prologue form for k_conv.  gn_prefetch issues EVERY load the affine of channel c needs — gamma, beta, the FiLM row and the

@@ -374,7 +374,7 @@ __global__ __launch_bounds__(KS_NT, NI == 1 ? 2 : 1) void k_conv_ks(const ConvKS
     if constexpr (NI > 1) request_epilogue_operands();
     // ---- 8. cross-wave reduction, one n-tile at a time: partial [wave][sub-tile][row quad][lane] x 16 B, then wave g finishes tile row g ----
     __syncthreads();                         // every wave is done reading the A tile
-    float t1[NI], t2[NI];
+    double t1[NI], t2[NI];                   // statistics: every stored value added in fp64 (see ccdm_conv.hip)
 #pragma unroll
     for (int ni = 0; ni < NI; ++ni) {
         if (ni > 0) __syncthreads();         // the previous n-tile's partials have been consumed
@@ -390,7 +390,7 @@ __global__ __launch_bounds__(KS_NT, NI == 1 ? 2 : 1) void k_conv_ks(const ConvKS
                 }
         }
         __syncthreads();
-        t1[ni] = 0.f; t2[ni] = 0.f;
+        t1[ni] = 0.0; t2[ni] = 0.0;
         {
             // accumulator register 4 rq + j of sub-tile mi holds pixel mi*32 + 8 rq + 4 (lane >> 5) + j, i.e. tile row 4 mi + rq, column 4 (lane >> 5) + j
             const f32x4* part = reinterpret_cast<const f32x4*>(region) + ((g >> 2) * 4 + (g & 3)) * 64 + lane;
@@ -404,15 +404,16 @@ __global__ __launch_bounds__(KS_NT, NI == 1 ? 2 : 1) void k_conv_ks(const ConvKS
                 float o = fmaf(v[j], wsc[ni], add);                                           // wsc is a power of two: exact product
                 if (a.resid) o += rs[ni][j];
                 a.out[obase + (size_t)j * a.Cout + 32 * ni] = o;
-                t1[ni] += o;
-                t2[ni] = fmaf(o, o, t2[ni]);
+                const double d = o;
+                t1[ni] += d;
+                t2[ni] = fma(d, d, t2[ni]);
             }
         }
     }
     if (a.out_stats) {
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni) {
-            double v1 = (double)t1[ni], v2 = (double)t2[ni];
+            double v1 = t1[ni], v2 = t2[ni];
             v1 += __shfl_xor(v1, 32);
             v2 += __shfl_xor(v2, 32);
             if (lane < 32) { red[((ni * KS_NW + g) * 32 + lane) * 2] = v1; red[((ni * KS_NW + g) * 32 + lane) * 2 + 1] = v2; }

@@ -112,7 +112,7 @@ __global__ __launch_bounds__(256) void k_stem(const StemK k) {
             const int tap = min(4 * j + 2 * g + e, 8);  // slots past tap 8 carry zero weights: any finite value will do
             aoff[j][e] = ((tap / 3) * ST_HW + tap % 3) * 16;
         }
-    float t1 = 0.f, t2 = 0.f;
+    double t1 = 0.0, t2 = 0.0;        // statistics: every stored value added in fp64 (see ccdm_conv.hip)
     // name the block-resident operands here: inside the tile loop the compiler cannot tell these loads from the loop's own prefetch and
     // would wait for everything in flight (vmcnt(0): the next tile's request, just issued) at their first use of every tile
     float addv = add, wscv = wsc;
@@ -158,13 +158,14 @@ __global__ __launch_bounds__(256) void k_stem(const StemK k) {
             for (int r = 0; r < 16; ++r) {
                 const float v = fmaf(acc[mi][r], wscv, addv);                 // wsc is a power of two: exact product
                 orow[(size_t)((r & 3) + 8 * (r >> 2)) * a.Cout] = v;
-                t1 += v;
-                t2 = fmaf(v, v, t2);
+                const double d = v;
+                t1 += d;
+                t2 = fma(d, d, t2);
             }
         }
     }
     if (a.out_stats) {
-        double v1 = (double)t1, v2 = (double)t2;
+        double v1 = t1, v2 = t2;
         v1 += __shfl_xor(v1, 32);
         v2 += __shfl_xor(v2, 32);
         if (lane < 32) { red[(wave * 32 + lane) * 2] = v1; red[(wave * 32 + lane) * 2 + 1] = v2; }

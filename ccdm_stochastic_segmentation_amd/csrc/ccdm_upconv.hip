@@ -90,11 +90,12 @@ __global__ __launch_bounds__(256, 2) void k_upconv(const UpK k) {
     float* const epi = epi_all + wave * (32 * UP_EPS);
     const int cq = lane & 7, prow = lane >> 3;
 
-    float s1[UP_CTB_MAX][4], s2[UP_CTB_MAX][4];
+    // statistics: every stored value added in fp64, a tile's sums reduce-scattered over the 8 lanes of a channel quad into one fp64 running
+    // component per lane and channel tile, exactly as k_conv's fast epilogue does (ccdm_conv.hip, `st`): lane prow holds component
+    // prow = 4 * (sum x^2 ? 1 : 0) + e of channel 4 cq + e
+    double st[UP_CTB_MAX];
 #pragma unroll
-    for (int c = 0; c < UP_CTB_MAX; ++c)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { s1[c][e] = 0.f; s2[c][e] = 0.f; }
+    for (int c = 0; c < UP_CTB_MAX; ++c) st[c] = 0.0;
 
     const int ntile_sp = k.tiles_x * k.tiles_y;
 #pragma unroll 1
@@ -193,7 +194,7 @@ __global__ __launch_bounds__(256, 2) void k_upconv(const UpK k) {
             }
             // ---- epilogue: (x 2^-e) + bias -> wave-private transpose -> float4 rows to pixel (2y + dy, 2x + dx), statistics ----
             if (ALIAS) __syncthreads();                    // every wave is done reading the halo tile
-            float t1[4] = {0.f, 0.f, 0.f, 0.f}, t2[4] = {0.f, 0.f, 0.f, 0.f};
+            double t1[4] = {0.0, 0.0, 0.0, 0.0}, t2[4] = {0.0, 0.0, 0.0, 0.0};
             // lane (prow, cq): tile column col0 + prow = 2 prow output pixels to the right of the row pass's first one, channel quad cq
             const unsigned lane_off = ((unsigned)(2 * prow) * (unsigned)Cout + (unsigned)((ct0 + ct) * 32 + 4 * cq)) << 2;
 #pragma unroll
@@ -212,13 +213,19 @@ __global__ __launch_bounds__(256, 2) void k_upconv(const UpK k) {
                     const unsigned rb = (unsigned)(((2 * (oy0 + row) + dy) * Wout + 2 * (ox0 + col0) + dx) * Cout) << 2;      // uniform
                     store16_uniform_base(out_n + rb, lane_off, o);
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) { t1[e] += o[e]; t2[e] = fmaf(o[e], o[e], t2[e]); }
+                    for (int e = 0; e < 4; ++e) { const double d = o[e]; t1[e] += d; t2[e] = fma(d, d, t2[e]); }
                 }
             }
+            {
+                const bool b2 = (lane >> 5) & 1, b1 = (lane >> 4) & 1, b0 = (lane >> 3) & 1;
+                double u[4], w[2];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                if (ct == 0) { s1[0][e] += t1[e]; s2[0][e] += t2[e]; }
-                else { s1[UP_CTB_MAX - 1][e] += t1[e]; s2[UP_CTB_MAX - 1][e] += t2[e]; }
+                for (int i = 0; i < 4; ++i) u[i] = (b2 ? t2[i] : t1[i]) + __shfl_xor(b2 ? t1[i] : t2[i], 32);
+#pragma unroll
+                for (int i = 0; i < 2; ++i) w[i] = (b1 ? u[2 + i] : u[i]) + __shfl_xor(b1 ? u[i] : u[2 + i], 16);
+                const double z = (b0 ? w[1] : w[0]) + __shfl_xor(b0 ? w[0] : w[1], 8);
+                if (ct == 0) st[0] += z;
+                else st[UP_CTB_MAX - 1] += z;
             }
         }
     }
@@ -229,16 +236,7 @@ __global__ __launch_bounds__(256, 2) void k_upconv(const UpK k) {
         double* red = reinterpret_cast<double*>(epi_all);                               // [4 waves][ctb][32][2]
 #pragma unroll
         for (int c = 0; c < UP_CTB_MAX; ++c)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                double v1 = (double)s1[c][e], v2 = (double)s2[c][e];
-#pragma unroll
-                for (int off = 8; off < 64; off <<= 1) { v1 += __shfl_xor(v1, off); v2 += __shfl_xor(v2, off); }
-                if (lane < 8 && c < k.ctb) {
-                    red[((wave * UP_CTB_MAX + c) * 32 + 4 * lane + e) * 2 + 0] = v1;
-                    red[((wave * UP_CTB_MAX + c) * 32 + 4 * lane + e) * 2 + 1] = v2;
-                }
-            }
+            if (c < k.ctb) red[((wave * UP_CTB_MAX + c) * 32 + 4 * cq + (prow & 3)) * 2 + (prow >> 2)] = st[c];
         __syncthreads();
         if constexpr (TW == 8) {
             // one partial per (slice, phase): slot = 4 * slice + phase, as the general kernel's one-phase-per-block form leaves them
