@@ -44,7 +44,7 @@ template <int PREC, int CKT> struct Lds {
     static constexpr int PIXB = PREC == CCDM_PREC_F32 ? 33 * 4 : CKT * 4 + 16;
 };
 
-// (ACT_PRESCALE, ConvK, compute_gn_affine, load16/store16_uniform_base: ccdm_conv_common.h)
+// (ACT_PRESCALE, ConvK, load16/store16_uniform_base: ccdm_conv_common.h; GroupNorm statistics and affine: ccdm_gn.h)
 
 // register budget: >= 3 waves per SIMD (<= 168 VGPRs) when the accumulator tile is small — matches the 3 blocks
 // per CU the LDS footprint (A tile 27 KB + B chunk 18 KB) admits
@@ -591,7 +591,7 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
     }
     // GroupNorm's (scale, shift) table for this sample, from the prefetched partials (the halo region of LDS is free until the
     // first commit, which sits behind the loop-top barrier)
-    if (has_gn) gn_affine_block(a, n, emb_row, gpf, reinterpret_cast<f64x2*>(halo_b), ab);
+    if (has_gn) gn_affine_block(a, n, emb_row, gpf, reinterpret_cast<f64x2*>(halo_b), ab, blockDim.x);
     // one iteration = one (tile, chunk); D_ = the register set it consumes (static: the loop below is unrolled by DEPTH)
     auto iterate = [&](auto D_) {
         if (chunk == 0) {
@@ -925,11 +925,7 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
         for (int i = tid; i < NI / NFOLD * 32; i += NT) {
             const int ni = (i >> 5) * NFOLD, l = i & 31;
             double t1 = 0.0, t2 = 0.0;
-            for (int f = 0; f < NFOLD; ++f)
-                for (int w = 0; w < WAVES * KSP; ++w) {
-                    t1 += red[((w * NI + ni + f) * 32 + l) * 2 + 0];
-                    t2 += red[((w * NI + ni + f) * 32 + l) * 2 + 1];
-                }
+            for (int f = 0; f < NFOLD; ++f) gn_fold_waves(red, ni + f, NI, WAVES * KSP, l, t1, t2);
             const int co = tile_of(ni) * 32 + l;
             if (co < a.Cout) {
                 const int nslot = UP2 && NI == 1 ? 4 * k.slices : k.slices, slot = UP2 && NI == 1 ? 4 * slice + phase_of(ni) : slice;

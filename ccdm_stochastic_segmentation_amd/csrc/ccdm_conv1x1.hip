@@ -36,7 +36,7 @@ struct Conv1x1K {
 // KSB k-steps (16 channels each) are in flight at a time: C <= 16 * KSB runs with every load issued up front
 // (MAXT: the block size bound the register budget is planned for — 4 waves with 8 k-steps in flight, 16 waves with 4)
 // GN: the input is normalised on load — (scale, shift) table of this sample in LDS, built in the prologue from the producer's
-// statistics partials exactly like ccdm_conv.hip does (gn_prefetch / gn_affine_block), one fma per element before the split.
+// statistics partials exactly like ccdm_conv.hip does (gn_prefetch / gn_affine_block, ccdm_gn.h), one fma per element before the split.
 template <int KSB, int MAXT, bool GN>
 __global__ __launch_bounds__(MAXT) void k_conv1x1(const Conv1x1K k) {
     extern __shared__ __attribute__((aligned(16))) char smem1[];
@@ -80,7 +80,7 @@ __global__ __launch_bounds__(MAXT) void k_conv1x1(const Conv1x1K k) {
     const float add = k.bias ? k.bias[co] : 0.f;
     const float wsc = k.wscale[co];
     if (GN) {
-        gn_affine_block(k.a, n, 0, gpf, reinterpret_cast<f64x2*>(smem1 + (size_t)k.C * 8), ab);
+        gn_affine_block(k.a, n, 0, gpf, reinterpret_cast<f64x2*>(smem1 + (size_t)k.C * 8), ab, blockDim.x);
         __syncthreads();
     }
     const float2* abl = ab + 8 * kg;
@@ -118,7 +118,7 @@ __global__ __launch_bounds__(MAXT) void k_conv1x1(const Conv1x1K k) {
         if (ks0 + KSB < nks) issue(ks0 + KSB);                                 // wide inputs (C > 16 * KSB): next batch
     }
 
-    double t1 = 0.0, t2 = 0.0;                                                 // statistics: every stored value added in fp64 (see ccdm_conv.hip)
+    double t1 = 0.0, t2 = 0.0;                                                 // statistics: every stored value added in fp64 (ccdm_gn.h)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         float v = fmaf(acc[r], wsc, add);                                      // wsc is a power of two: exact product
@@ -129,7 +129,7 @@ __global__ __launch_bounds__(MAXT) void k_conv1x1(const Conv1x1K k) {
         t2 = fma(d, d, t2);
     }
     if (k.out_stats) {
-        __shared__ double red[(MAXT / 64) * 32 * 2];
+        __shared__ double red[(MAXT / 64) * 32 * 2];                           // [wave][32][2]
         double v1 = t1, v2 = t2;
         v1 += __shfl_xor(v1, 32);
         v2 += __shfl_xor(v2, 32);
@@ -137,7 +137,7 @@ __global__ __launch_bounds__(MAXT) void k_conv1x1(const Conv1x1K k) {
         __syncthreads();
         if (tid < 32) {
             double s1 = 0.0, s2 = 0.0;
-            for (int w = 0; w < nwaves; ++w) { s1 += red[(w * 32 + tid) * 2]; s2 += red[(w * 32 + tid) * 2 + 1]; }
+            gn_fold_waves(red, 0, 1, nwaves, tid, s1, s2);
             double* o = k.out_stats + (((size_t)n * k.slices + slice) * k.Cout + nt * 32 + tid) * 2;
             o[0] = s1; o[1] = s2;
         }
@@ -185,7 +185,7 @@ __global__ __launch_bounds__(256) void k_conv1x1_multi(const Conv1x1K k, const i
     };
     issueB(0, nt_first);
     if (GN) {
-        gn_affine_block(k.a, n, 0, gpf, reinterpret_cast<f64x2*>(smem1 + (size_t)k.C * 8), ab);
+        gn_affine_block(k.a, n, 0, gpf, reinterpret_cast<f64x2*>(smem1 + (size_t)k.C * 8), ab, blockDim.x);
         __syncthreads();
     }
     const float2* abl = ab + 8 * kg;

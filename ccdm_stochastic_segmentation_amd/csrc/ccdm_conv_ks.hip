@@ -89,7 +89,8 @@ __global__ __launch_bounds__(KS_NT, NI == 1 ? 2 : 1) void k_conv_ks(const ConvKS
 
     // ---- 1. GroupNorm operands: thread c < C requests gamma, beta and the first 4 statistics partials of channel c (few-pixel images
     //         have 1-4 slices; a clamped 16-slice prefetch by all 512 threads, as the general kernel does, is 128 redundant 1 KB requests
-    //         through a vector-memory front end that moves ~40 B/clk — 2 000 cycles of this block's chain) ----
+    //         through a vector-memory front end that moves ~40 B/clk — 2 000 cycles of this block's chain).  Not on gn_prefetch /
+    //         gn_affine_block: with a 4-deep prefetch its instantiations compiled with more SGPRs and up to 16 SGPR spills ----
     const bool gn_thread = has_gn && tid < C;                            // (waves beyond C / 64 skip the requests: wave-uniform)
     f64x2 gsl[4];
     float g_gamma = 1.f, g_beta = 0.f;
@@ -374,7 +375,7 @@ __global__ __launch_bounds__(KS_NT, NI == 1 ? 2 : 1) void k_conv_ks(const ConvKS
     if constexpr (NI > 1) request_epilogue_operands();
     // ---- 8. cross-wave reduction, one n-tile at a time: partial [wave][sub-tile][row quad][lane] x 16 B, then wave g finishes tile row g ----
     __syncthreads();                         // every wave is done reading the A tile
-    double t1[NI], t2[NI];                   // statistics: every stored value added in fp64 (see ccdm_conv.hip)
+    double t1[NI], t2[NI];                   // statistics: every stored value added in fp64 (ccdm_gn.h)
 #pragma unroll
     for (int ni = 0; ni < NI; ++ni) {
         if (ni > 0) __syncthreads();         // the previous n-tile's partials have been consumed
@@ -410,7 +411,7 @@ __global__ __launch_bounds__(KS_NT, NI == 1 ? 2 : 1) void k_conv_ks(const ConvKS
             }
         }
     }
-    if (a.out_stats) {
+    if (a.out_stats) {                       // red: [n-tile][wave][32][2]
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni) {
             double v1 = t1[ni], v2 = t2[ni];
@@ -422,7 +423,7 @@ __global__ __launch_bounds__(KS_NT, NI == 1 ? 2 : 1) void k_conv_ks(const ConvKS
         if (tid < 32 * NI) {
             const int ni = tid >> 5, l = tid & 31;
             double s1 = 0.0, s2 = 0.0;
-            for (int w = 0; w < KS_NW; ++w) { s1 += red[((ni * KS_NW + w) * 32 + l) * 2]; s2 += red[((ni * KS_NW + w) * 32 + l) * 2 + 1]; }
+            gn_fold_waves(red, ni * KS_NW, 1, KS_NW, l, s1, s2);
             double* o = a.out_stats + (((size_t)n * ntile_sp + tile) * a.Cout + (nt + ni) * 32 + l) * 2;
             o[0] = s1; o[1] = s2;
         }

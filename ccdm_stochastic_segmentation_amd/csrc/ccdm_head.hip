@@ -30,7 +30,6 @@ int conv_slices(int Hout, int Wout, int stride, bool up2, int fine);
 struct HeadK {
     ccdm_head_args a;
     ccdm_post_args post;
-    ccdm_conv_args gn;          // GroupNorm operands in the form gn_prefetch / gn_affine_block take
     const float* wscale;        // [K] powers of two undoing the weight / activation pre-scales
     int slices, tiles_x, tiles_y;
 };
@@ -69,8 +68,9 @@ __global__ __launch_bounds__(256, 3) void k_head(const HeadK k) {
     }
 
     // ---- small loads first: GroupNorm operands, then the weight fragments (2 k-steps x hi|lo, resident), bias / un-scale of this lane's class ----
+    const GnSrc gs{a.stats, nullptr, a.slices, 0, a.C, 0, a.H, a.W, a.eps, a.gamma, a.beta, false, nullptr, 0, 0};
     GnPrefetch gpf;
-    gn_prefetch(k.gn, true, n, 0, tid, 256, a.w, gpf);
+    gn_prefetch(gs, true, n, 0, tid, 256, a.w, gpf);
     f16x8 wh[2], wl[2];
     {
         const char* wp = static_cast<const char*>(a.w) + ((size_t)lane << 4);
@@ -108,7 +108,7 @@ __global__ __launch_bounds__(256, 3) void k_head(const HeadK k) {
     };
     if (my_tiles > 0) request(slice);
     __builtin_amdgcn_sched_barrier(0);
-    gn_affine_block(k.gn, n, 0, gpf, reinterpret_cast<f64x2*>(tileb), ab);
+    gn_affine_block(gs, n, 0, gpf, reinterpret_cast<f64x2*>(tileb), ab, blockDim.x);
     __syncthreads();
     // name the block-resident operands here: inside the tile loop the compiler cannot tell these loads from the loop's own prefetch and
     // would wait for EVERYTHING in flight (vmcnt(0): the next tile's halo request, just issued) at their first use of every tile
@@ -234,9 +234,6 @@ int launch_head(const ccdm_head_args& a, const ccdm_post_args& post, hipStream_t
     HeadK k;
     k.a = a;
     k.post = post;
-    k.gn = ccdm_conv_args{};
-    k.gn.C0 = a.C; k.gn.stats0 = a.stats; k.gn.slices0 = a.slices; k.gn.gamma = a.gamma; k.gn.beta = a.beta; k.gn.eps = a.eps;
-    k.gn.Hin = a.H; k.gn.Win = a.W; k.gn.N = a.N;
     k.slices = conv_slices(a.H, a.W, 1, false, 0);
     k.tiles_x = a.W / HD_TW; k.tiles_y = a.H / HD_TH;
     k.wscale = reinterpret_cast<const float*>(static_cast<const char*>(a.w) + 2 * 2048);

@@ -112,7 +112,7 @@ __global__ __launch_bounds__(256) void k_stem(const StemK k) {
             const int tap = min(4 * j + 2 * g + e, 8);  // slots past tap 8 carry zero weights: any finite value will do
             aoff[j][e] = ((tap / 3) * ST_HW + tap % 3) * 16;
         }
-    double t1 = 0.0, t2 = 0.0;        // statistics: every stored value added in fp64 (see ccdm_conv.hip)
+    double t1 = 0.0, t2 = 0.0;        // statistics: every stored value added in fp64 (ccdm_gn.h)
     // name the block-resident operands here: inside the tile loop the compiler cannot tell these loads from the loop's own prefetch and
     // would wait for everything in flight (vmcnt(0): the next tile's request, just issued) at their first use of every tile
     float addv = add, wscv = wsc;
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(256) void k_stem(const StemK k) {
         __syncthreads();
         if (tid < 32) {
             double s1 = 0.0, s2 = 0.0;
-            for (int w = 0; w < 4; ++w) { s1 += red[(w * 32 + tid) * 2]; s2 += red[(w * 32 + tid) * 2 + 1]; }
+            gn_fold_waves(red, 0, 1, 4, tid, s1, s2);
             double* o = a.out_stats + (((size_t)n * k.slices + slice) * a.Cout + nt * 32 + tid) * 2;
             o[0] = s1; o[1] = s2;
         }

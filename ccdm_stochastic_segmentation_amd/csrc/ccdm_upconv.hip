@@ -250,10 +250,7 @@ __global__ __launch_bounds__(256, 2) void k_upconv(const UpK k) {
             for (int i = tid; i < k.ctb * 32; i += 256) {
                 const int c = i >> 5, l = i & 31;
                 double a1 = 0.0, a2 = 0.0;
-                for (int w = 0; w < 4; ++w) {
-                    a1 += red[((w * UP_CTB_MAX + c) * 32 + l) * 2 + 0];
-                    a2 += red[((w * UP_CTB_MAX + c) * 32 + l) * 2 + 1];
-                }
+                gn_fold_waves(red, c, UP_CTB_MAX, 4, l, a1, a2);
                 double* o = k.out_stats + (((size_t)n * k.slices + slice) * Cout + (ct0 + c) * 32 + l) * 2;
                 o[0] = a1; o[1] = a2;
             }

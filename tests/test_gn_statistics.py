@@ -1,7 +1,7 @@
 """GroupNorm statistics against float64 at offset and low-variance activations.
 
 Every GroupNorm of the U-Net reads (sum x, sum x^2) partials [N][slices][C][2] that the previous kernel's epilogue left, and forms
-var = sum x^2 / n - mean^2 (gn_mean_rstd, csrc/ccdm_conv_common.h).  That difference loses digits in proportion to mean^2 / var of the
+var = sum x^2 / n - mean^2 (gn_mean_rstd64, csrc/ccdm_gn.h).  That difference loses digits in proportion to mean^2 / var of the
 group: a conv bias or a residual that moves a group's mean to tens or hundreds of standard deviations turns any fp32 rounding of the
 running sums into an error of rstd.  The producer sweep drives every kernel that writes partials with its output offset at
 mean/std in {0, 10, 100, 1000} and compares the (mean, rstd) the partials give with float64 statistics of the tensor the kernel stored;
