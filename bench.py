@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: categorical reverse-diffusion sampling throughput (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--config c2|c3shard|c4|c4b64|c5shard]
+    python bench.py --gpus N --steps K --warmup W [--config c2|c3shard|c4|c4b64|c5shard] [--full]
 
 One "step" = one full pass of the hot path over one batch: the complete T-step sampling of one per-GPU batch
 (default BASELINE config C2: 64 LIDC-shaped samples, 128x128, 2 classes, T=250, base-32 U-Net, synthetic image,
@@ -10,6 +10,9 @@ final RCCL all_gather of the predictions.  Inputs are resident in HBM when timin
 rank 0.  With --gpus N > 1 and no launcher environment the script starts its own ranks
 (torch.distributed.run, one process per GPU, 127.0.0.1 rendezvous).  --dump-outputs DIR writes what the last timed step
 returned (dump_outputs): with the same arguments the inputs are identical from run to run, so two builds compare output for output.
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the dump, the JSON line.  --full adds what
+takes runs of its own: rank 0's untimed tapped pass (roofline, per-stage table, --per-op, single-stream figure, the rocprofv3
+PMC child passes) and the CPU baseline.
 """
 import argparse
 import json
@@ -315,8 +318,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", choices=sorted(CONFIGS), default="c2",
                     help="workload (BASELINE.json configs); the headline metric is quoted on c2")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the untimed extras (roofline taps, per-stage table, single-stream figure)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also run the untimed extras (roofline taps, per-stage table, "
+                                                         "single-stream figure, PMC passes) and the CPU baseline; a plain run skips them")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the untimed extras (roofline taps, per-stage table, single-stream figure)")
     ap.add_argument("--graph", type=int, default=-1, help="1 / 0: replay each denoise step as a HIP graph / launch eagerly (default: the product default, graph)")
     ap.add_argument("--batch", type=int, default=0, help="samples per GPU (default: the config's)")
     ap.add_argument("--denoise-steps", type=int, default=0, help="strided walk of this many denoise steps instead of the full T (diagnostics; not the metric)")
@@ -331,23 +336,26 @@ def main():
                          "f16 = the OPT-IN single-pass fast mode (operands rounded to fp16, outside the parity contract: a diagnostic line, never the metric)")
     ap.add_argument("--slicing", default="throughput", choices=["throughput", "latency"],
                     help="DenoisingModel.slicing: 'latency' = more, shorter conv workgroups per sample (small batches)")
-    ap.add_argument("--per-op", default="", help="write the per-op table of the tapped pass to this file (JSON)")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the two rocprofv3 --pmc child passes that measure roofline.traffic")
+    ap.add_argument("--per-op", default="", help="with --full: write the per-op table of the tapped pass to this file (JSON)")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: skip the rocprofv3 --pmc child passes that measure roofline.traffic")
     ap.add_argument("--digest", action="store_true", help="add the SHA-256 of every rank's last prediction shard to per_rank (tests: a shard of the "
                                                           "N-rank job equals the same shard sampled alone)")
     ap.add_argument("--emulate-rank", default="", metavar="R/W", help="one process plays rank R of a W-rank job (its inputs, its Philox sample "
                                                                      "offset), without a process group: the single-process side of the shard test")
     ap.add_argument("--ref-value", type=float, default=0.0, help="samples/s of the N = 1 line of the same bench (BENCH-style): the N > 1 line then carries "
                                                                  "weak_scaling_efficiency = value_N / (N x ref)")
-    ap.add_argument("--secondary", action="store_true", help="N > 1 only: run rank 0's untimed secondary pass (roofline taps, per-stage table) although the "
-                                                             "other ranks wait in the final barrier meanwhile (default at N > 1: skipped; at N = 1 it always runs "
-                                                             "unless --no-secondary)")
+    ap.add_argument("--secondary", action="store_true", help="with --full, N > 1 only: run rank 0's untimed secondary pass (roofline taps, per-stage table) "
+                                                             "although the other ranks wait in the final barrier meanwhile (default at N > 1: skipped; at N = 1 "
+                                                             "--full runs it unless --no-secondary)")
     ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last one returned as DIR/<name>.npy "
                                                                       "(float32; at most 64 MB in all, a fixed seeded sample of a larger output)")
     ap.add_argument("--cpu-probe", type=int, default=0, help=argparse.SUPPRESS)      # child mode of cpu_baseline's all-cores probe
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    for flag, given in (("--per-op", args.per_op), ("--secondary", args.secondary)):
+        if given and not args.full:
+            ap.error(f"{flag} asks for the untimed extras: add --full")
     if args.cpu_probe:
         _cpu_probe_child(args.cpu_probe, 1, args.config)
         return
@@ -513,7 +521,7 @@ def main():
                                 "algorithmic_tflops": cfg["gflop"] * n / ms_dstep, "mfma_util": (3.0 if f16 else (1.0 if single else 16.0)) * cfg["gflop"] * n / ms_dstep / MFMA_PEAK_TFLOPS}
         res["roofline"] = None
 
-    # ---- untimed, rank 0 at N = 1: ONE single-stream eager pass with HIP-event taps on every op (on the engine's stream) -> the dominant
+    # ---- untimed, --full, rank 0 at N = 1: ONE single-stream eager pass with HIP-event taps on every op (on the engine's stream) -> the dominant
     #      kernel's roofline, the per-stage split, the per-op table; then the single-stream figure of the same product path ----
     def secondary():
         # (N > 1: rank 0 alone, on its own shard, without the gather — the other ranks wait at the final barrier)
@@ -645,11 +653,11 @@ def main():
                                 "note": "same workload on one stream (substreams = 1), same launch mode: secondary figure"}
         model.substreams = substreams
 
-    # N > 1: the untimed extras are opt-IN (--secondary) — while rank 0 runs them (about a minute) the other ranks sit in the final barrier,
-    # under RCCL's watchdog; the roofline objects belong to the N = 1 line anyway
+    # the untimed extras run with --full only; at N > 1 they are opt-IN besides (--secondary) — while rank 0 runs them (about a minute)
+    # the other ranks sit in the final barrier, under RCCL's watchdog; the roofline objects belong to the N = 1 line anyway
     if rank == 0 and res is not None and world > 1 and not args.secondary:
-        res["secondary_note"] = "N > 1: rank 0's untimed roofline / per-stage pass skipped (pass --secondary to run it); those objects are on the N = 1 line"
-    if rank == 0 and not args.no_secondary and (world == 1 or args.secondary):
+        res["secondary_note"] = "N > 1: rank 0's untimed roofline / per-stage pass skipped (pass --full --secondary to run it); those objects are on the N = 1 --full line"
+    if rank == 0 and args.full and not args.no_secondary and (world == 1 or args.secondary):
         if world == 1:
             secondary()
         else:                                                      # the N-rank line must not die on an untimed extra
@@ -658,7 +666,7 @@ def main():
             except Exception as e:       # noqa: BLE001
                 res["secondary_error"] = f"{type(e).__name__}: {e}"
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1 and args.config in ("c2", "c3shard"):
+        if args.full and not args.no_cpu_baseline and world == 1 and args.config in ("c2", "c3shard"):
             res["cpu_baseline"] = cpu_baseline(sd, torch.from_numpy(image_all[:4]), cfg, args.config)
         print(json.dumps(res))
     if world > 1:

@@ -2550,7 +2550,7 @@ def test_bench_two_ranks_is_the_command_the_driver_runs(U, tmp_path):
     assert abs(two["weak_scaling_efficiency"] - two["value"] / 20.0) < 1e-9
     assert all(p["ms_per_denoise_step"] > 0 and p["samples_per_s"] > 0 for p in two["per_rank"]) and two["slowest_rank"] in (0, 1)
     assert "rccl_probe_first_ms" in two["distributed"] and 0 <= two["gather_share_of_pass"] <= 1
-    two = run(["--gpus", "2", "--secondary"])
+    two = run(["--gpus", "2", "--full", "--secondary"])
     assert two["n_gpus"] == 2 and two["config"]["global_batch"] == 12 and two["scaling"] == "weak"
     assert np.isfinite(two["value"]) and two["value"] > 0 and abs(two["value"] - 12 / (two["ms_per_step"] * 1e-3)) < 1e-6 * two["value"]
     pr = two["per_rank"]
@@ -2564,6 +2564,34 @@ def test_bench_two_ranks_is_the_command_the_driver_runs(U, tmp_path):
         alone = run(["--emulate-rank", f"{r_}/2", "--no-secondary"])
         assert alone["n_gpus"] == 1 and alone["out_sha256"] == pr[r_]["out_sha256"], (r_, alone["out_sha256"], pr[r_]["out_sha256"])
     assert pr[0]["out_sha256"] != pr[1]["out_sha256"]
+
+
+def test_bench_plain_run_skips_the_extras_full_runs_them(U, tmp_path):
+    """A plain `python bench.py` line holds the headline and nothing that takes runs of its own; `--full` adds rank 0's untimed tapped
+    pass (roofline, per-stage table, the --per-op file, the single-stream figure) after the same timed steps, which sample the same
+    predictions."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    common = ["--steps", "1", "--warmup", "1", "--denoise-steps", "4", "--batch", "6", "--digest"]
+
+    def run(extra):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + extra + common, capture_output=True, text=True, timeout=900, cwd=root)
+        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+        return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+
+    plain = run([])
+    assert plain["n_gpus"] == 1 and plain["value"] > 0 and abs(plain["value"] - 6 / (plain["ms_per_step"] * 1e-3)) < 1e-6 * plain["value"]
+    assert plain["roofline"] is None and plain["roofline_step"]["achieved"] > 0
+    for key in ("roofline_shapes", "roofline_attention", "per_stage_us", "single_stream", "cpu_baseline"):
+        assert key not in plain, key
+    per_op = tmp_path / "per_op.json"
+    full = run(["--full", "--no-pmc", "--no-cpu-baseline", "--per-op", str(per_op)])
+    assert full["roofline"] is not None and full["per_stage_us"] and full["single_stream"]["value"] > 0 and "cpu_baseline" not in full
+    assert len(json.loads(per_op.read_text())) > 0
+    assert full["out_sha256"] == plain["out_sha256"]
 
 
 # ------------------------------------------------------------------------------------------ N2 harness vs the reference's Tester

@@ -477,6 +477,19 @@ def test_bench_self_launch_retries_once_without_its_own_ipc_override(monkeypatch
         assert e.value.code == 7 and envs == want, (preset, stderr, envs)
 
 
+def test_bench_extras_need_full(monkeypatch, capsys):
+    """--per-op and --secondary ask for what only a --full run makes: without --full they are refused before anything starts."""
+    import bench
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setattr(bench, "_run_ranks", lambda cmd, env=None: pytest.fail("no ranks may start"))
+    for argv in (["--per-op", "x.json"], ["--gpus", "2", "--secondary"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+        with pytest.raises(SystemExit) as e:
+            bench.main()
+        assert e.value.code == 2 and "--full" in capsys.readouterr().err, argv
+
+
 def test_bench_dump_outputs_within_budget(tmp_path):
     """--dump-outputs: a small output is written whole as float32; a larger one as the same seeded sample of its rows on every call,
     with the row indices beside it, within the byte budget; a row over the budget falls back to a seeded sample of elements."""

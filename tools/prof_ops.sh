@@ -1,6 +1,11 @@
 #!/bin/bash
+# rocprofv3 kernel trace of the C2 bench command with its untimed tapped pass (--full), summarised per kernel and engine op:
+#   OUT=<dir> bash tools/prof_ops.sh TAG
 set -u
 TAG=${1:-x}
+OUT=${OUT:?set OUT to the directory the results go to}
+mkdir -p $OUT
+OUT=$(cd $OUT && pwd); ROOT=$PWD
 export TMPDIR=/tmp
-cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/gpurun_out/prof_$TAG -o trace -- python $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 1 --no-cpu-baseline > $GRAFT_REPO_ROOT/gpurun_out/rocprof_$TAG.log 2>&1
-cd $GRAFT_REPO_ROOT && python tools/rocprof_summary.py gpurun_out/prof_$TAG/trace_kernel_trace.csv gpurun_out/prof_$TAG/summary.md && tail -1 gpurun_out/prof_$TAG/summary.md
+cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$TAG -o trace -- python $ROOT/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline > $OUT/rocprof_$TAG.log 2>&1
+cd $ROOT && python tools/rocprof_summary.py $OUT/prof_$TAG/trace_kernel_trace.csv $OUT/prof_$TAG/summary.md && tail -1 $OUT/prof_$TAG/summary.md
