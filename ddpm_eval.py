@@ -4,8 +4,9 @@
     python ddpm_eval.py [params_<anything>.yml]
 
 `dataset_file` in the YAML selects the evaluator: "...lidc_sampling_speed" -> the T-sweep timing run,
-"...lidc" -> GED / HM-IoU over the LIDC test split.  Everything runs through the MI355X sampler; the result
-dictionary is also printed as one JSON line so scripts can pick it up."""
+"...lidc" -> GED / HM-IoU over the LIDC test split, "...cityscapes_miou" -> mIoU over the Cityscapes validation split
+("datasets.cityscapes_miou": the data at dataset_path; "synthetic.cityscapes_miou": a stand-in).  Everything runs through
+the MI355X sampler; the result dictionary is also printed as one JSON line so scripts can pick it up."""
 import json
 import logging
 import os
@@ -38,14 +39,18 @@ def _params_path(argv):
 
 
 def _pick_evaluator(dataset_file):
-    """-> (evaluator, dataset_file to hand it).  Order matters: the speed sweep's name contains 'lidc'."""
+    """-> (evaluator, dataset_file to hand it).  Order matters: the speed sweep's name contains 'lidc', the mIoU evaluator's
+    'cityscapes'."""
     if "lidc_sampling_speed" in dataset_file:
         return evaluation.eval_lidc_sampling_speed, dataset_file.replace("lidc_sampling_speed", "lidc")
     if "lidc" in dataset_file:
         return evaluation.eval_lidc_uncertainty, dataset_file
+    if "cityscapes_miou" in dataset_file:
+        from ccdm_stochastic_segmentation_amd import segmentation
+        return segmentation.eval_segmentation, dataset_file
     if "cityscapes" in dataset_file:
-        raise NotImplementedError("the Cityscapes evaluator is broken on the reference's main branch "
-                                  "(SURVEY §2 #22) and is out of scope")
+        raise NotImplementedError("the reference's Cityscapes evaluator is broken on its main branch (SURVEY §2 #22); "
+                                  "dataset_file: datasets.cityscapes_miou runs this project's mIoU evaluator")
     raise ValueError("Unknown dataset")
 
 

@@ -316,6 +316,27 @@ int ccdm_pairwise_class_counts(const uint8_t* a /*dev [B,S,HW]*/, const uint8_t*
                                int HW, int K, int32_t* out /*dev [B,S,L,K,2]*/, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Segmentation evaluation, device part (Cityscapes mIoU): the reference Evaluator's `infer_step` / `update_cm`
+ * (evaluation/eval_cdm.py) in one pass, without a full-resolution probability tensor.  Per output pixel of [B,H,W]:
+ *   - bilinear sample of the prediction [B,h,w] as ATen's upsample_bilinear2d (align_corners=False, no antialias) in fp32:
+ *     src = max((in/out) * (dst + 0.5) - 0.5, 0), i0 = (int)src, i1 = i0 + (i0 < in-1), l1 = src - i0, l0 = 1 - l1,
+ *     v = lh0 * (lw0 * x00 + lw1 * x01) + lh1 * (lw0 * x10 + lw1 * x11); (H,W) == (h,w) reads the pixel itself;
+ *   - argmax over the first C = K-1 channels (the ignore channel K-1 is dropped), ties to the lowest index;
+ *   - pixels whose label is >= C are not counted (ignite's ConfusionMatrix target mask);
+ *   - hard[t][pred] += 1 (int64 [C,C], rows = target, ACCUMULATED across calls);
+ *   - soft[c][t] = sum of v_c over the counted pixels of target t (fp64 [C,C], rows = prediction, OVERWRITTEN per call).
+ * Prediction: probs (fp32 channels-last, pixel (b,y,x) channel c at probs[((b*h + y)*w + x)*pixel_stride + c],
+ * pixel_stride >= K) XOR cls (uint8 class map [B,h,w], read as its one-hot: bit-identical to probs holding that one-hot).
+ * labels: uint8 train ids [B,H,W].  K in [2,32].  The workspace (device, ccdm_seg_confusion_workspace_bytes(B,H,W,K) bytes)
+ * holds per-block partial sums; no float atomics: two identical calls return bit-identical matrices.
+ * ------------------------------------------------------------------------------------------------- */
+size_t ccdm_seg_confusion_workspace_bytes(int B, int H, int W, int K);
+int ccdm_seg_confusion(const float* probs /*dev or NULL*/, int64_t pixel_stride, const uint8_t* cls /*dev [B,h,w] or NULL*/,
+                       const uint8_t* labels /*dev [B,H,W]*/, int B, int h, int w, int H, int W, int K,
+                       int64_t* hard /*dev [K-1,K-1]*/, double* soft /*dev [K-1,K-1]*/, void* workspace, size_t workspace_bytes,
+                       void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Multi-sample prediction (DenoisingModel.predict_multiple): S sampling passes of the same B images folded into one
  * mean map, a per-pixel vote and two uncertainty maps.  The reference's Evaluator.predict_multiple
  * (evaluation/eval_cdm.py:176-193) accumulates `total += prediction_i * (1 / S)` on the host; these read a pass
