@@ -378,6 +378,65 @@ __global__ __launch_bounds__(256) void k_gelu(const float* __restrict__ x, size_
     }
 }
 
+// Keys of one ViT layer -> [N, dim, Ht, Wt] descriptors (dino.py:297-305): the class token dropped, channel d_index * heads + head,
+// bilinear resize of the h0 x w0 token grid to Ht x Wt (F.interpolate 'bilinear', align_corners=False: torch's index and weight
+// rule, with the source coordinate in double — in fp32 its rounding, ~1e-6 of a coordinate near 40, moves a downsampled output by
+// 1e-5 of the keys' range).  Block = (n, output row y, 64 output columns, 64 key channels).  Phase 1: a wave's lanes are 64 consecutive
+// key channels of one token row (coalesced), the interpolated values go to an LDS tile [x][c]; phase 2: lanes are 64 consecutive
+// output columns of one channel (coalesced writes), reading the tile by columns (row pitch 65: conflict-free).
+constexpr int KR_TILE = 64;
+__device__ __forceinline__ void kr_source(int dst, int in, int out, int& i0, int& i1, float& l0, float& l1) {
+    if (in == out) { i0 = i1 = dst; l0 = 1.f; l1 = 0.f; return; }
+    const double scale = (double)in / (double)out;
+    double src = scale * ((double)dst + 0.5) - 0.5;
+    src = src < 0.0 ? 0.0 : src;
+    i0 = min((int)floor(src), in - 1);
+    const double frac = fmin(fmax(src - (double)i0, 0.0), 1.0);
+    i1 = i0 + (i0 < in - 1 ? 1 : 0);
+    l1 = (float)frac;
+    l0 = (float)(1.0 - frac);
+}
+
+__global__ __launch_bounds__(256) void k_vit_key_resize(const float* __restrict__ qkv, int Ta, int h0, int w0, int dim, int heads,
+                                                        int Ht, int Wt, float* __restrict__ out) {
+    __shared__ float tile[KR_TILE][KR_TILE + 1];
+    const int ctiles = (dim + KR_TILE - 1) / KR_TILE;
+    const int n = blockIdx.z / ctiles, c0 = (blockIdx.z % ctiles) * KR_TILE;
+    const int y = blockIdx.y, x0 = blockIdx.x * KR_TILE;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int y0, y1;
+    float ly0, ly1;
+    kr_source(y, h0, Ht, y0, y1, ly0, ly1);
+    const size_t C3 = 3 * (size_t)dim;
+    const float* base = qkv + (size_t)n * Ta * C3 + C3 + dim;          // token 1 (the first patch), key third
+    const float* r0 = base + (size_t)y0 * w0 * C3;
+    const float* r1 = base + (size_t)y1 * w0 * C3;
+    const int c = c0 + lane;
+    for (int xi = wave; xi < KR_TILE; xi += 4) {
+        const int x = x0 + xi;
+        float v = 0.f;
+        if (x < Wt && c < dim) {
+            int xa, xb;
+            float lx0, lx1;
+            kr_source(x, w0, Wt, xa, xb, lx0, lx1);
+            const float v00 = r0[(size_t)xa * C3 + c], v01 = r0[(size_t)xb * C3 + c];
+            const float v10 = r1[(size_t)xa * C3 + c], v11 = r1[(size_t)xb * C3 + c];
+            v = ly0 * (lx0 * v00 + lx1 * v01) + ly1 * (lx0 * v10 + lx1 * v11);
+        }
+        tile[xi][lane] = v;
+    }
+    __syncthreads();
+    const int hd = dim / heads;
+    const int x = x0 + lane;
+    if (x >= Wt) return;
+    for (int ci = wave; ci < KR_TILE; ci += 4) {
+        const int cc = c0 + ci;
+        if (cc >= dim) break;
+        const int oc = (cc % hd) * heads + cc / hd;
+        out[(((size_t)n * dim + oc) * Ht + y) * Wt + x] = tile[lane][ci];
+    }
+}
+
 }  // namespace ccdm
 
 extern "C" int ccdm_attention_ex(const float* qkv, float* out, int N, int T, int T_alloc, int C, int heads, int order, void* stream) {
@@ -398,5 +457,20 @@ extern "C" int ccdm_gelu(const float* x, size_t n, float* out, void* stream) {
     const size_t blocks = (n + 255) / 256;
     hipLaunchKernelGGL(ccdm::k_gelu, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, (hipStream_t)stream, x, n, out);
     CCDM_CHECK_LAUNCH("gelu");
+    return 0;
+}
+
+extern "C" int ccdm_vit_key_resize(const float* qkv, int N, int T_alloc, int h0, int w0, int dim, int heads, int Ht, int Wt, float* out,
+                                   void* stream) {
+    CCDM_REQUIRE(qkv && out, "vit_key_resize: null pointer");
+    CCDM_REQUIRE(N > 0 && h0 > 0 && w0 > 0 && Ht > 0 && Wt > 0, "vit_key_resize: N=%d grid %dx%d target %dx%d", N, h0, w0, Ht, Wt);
+    CCDM_REQUIRE(heads > 0 && dim > 0 && dim % heads == 0, "vit_key_resize: dim=%d not divisible by heads=%d", dim, heads);
+    CCDM_REQUIRE((long long)h0 * w0 + 1 <= T_alloc, "vit_key_resize: 1 + %dx%d tokens > %d allocated rows", h0, w0, T_alloc);
+    CCDM_REQUIRE(Ht <= 65535, "vit_key_resize: target height %d", Ht);
+    const int ctiles = (dim + ccdm::KR_TILE - 1) / ccdm::KR_TILE;
+    CCDM_REQUIRE((long long)N * ctiles <= 65535, "vit_key_resize: N=%d x %d channel tiles", N, ctiles);
+    dim3 grid((unsigned)((Wt + ccdm::KR_TILE - 1) / ccdm::KR_TILE), (unsigned)Ht, (unsigned)(N * ctiles));
+    hipLaunchKernelGGL(ccdm::k_vit_key_resize, grid, dim3(256), 0, (hipStream_t)stream, qkv, T_alloc, h0, w0, dim, heads, Ht, Wt, out);
+    CCDM_CHECK_LAUNCH("vit_key_resize");
     return 0;
 }

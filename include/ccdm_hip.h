@@ -395,11 +395,16 @@ int ccdm_kl_clamped(const float* p, const float* q, size_t n, float floor, float
  *   ccdm_attention_ex : ccdm_attention with T_alloc >= T token rows allocated per sample (only the first T are tokens)
  *   ccdm_layernorm    : nn.LayerNorm(C, eps) over the last axis of [rows, C]
  *   ccdm_gelu         : nn.GELU(), exact erf form
+ *   ccdm_vit_key_resize : the keys of token rows 1 .. h0*w0 of a [N, T_alloc, 3*dim] qkv buffer (the middle third) as
+ *                       [N, dim, Ht, Wt] descriptors, channel d_index * heads + head, bilinearly resized from the h0 x w0
+ *                       token grid (F.interpolate 'bilinear', align_corners=False; dino.py:297-305).  Padding rows are not read.
  * ------------------------------------------------------------------------------------------------- */
 int ccdm_attention_ex(const float* qkv /*dev [N,T_alloc,3C]*/, float* out /*dev [N,T_alloc,C]*/, int N, int T, int T_alloc, int C,
                       int heads, int order, void* stream);
 int ccdm_layernorm(const float* x, const float* gamma, const float* beta, float eps, long rows, int C, float* out, void* stream);
 int ccdm_gelu(const float* x, size_t n, float* out, void* stream);
+int ccdm_vit_key_resize(const float* qkv /*dev [N,T_alloc,3*dim]*/, int N, int T_alloc, int h0, int w0, int dim, int heads, int Ht, int Wt,
+                        float* out /*dev [N,dim,Ht,Wt]*/, void* stream);
 
 /* boundary re-layout helpers */
 int ccdm_nchw_to_nhwc(const float* src, float* dst, int N, int C, int HW, int dst_stride, int dst_off, void* stream);
