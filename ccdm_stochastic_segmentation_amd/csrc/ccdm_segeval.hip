@@ -3,6 +3,8 @@
 // (evaluation/eval_cdm.py: `infer_step` F.interpolate + channel drop, ignite's ConfusionMatrix, `update_cm`).
 // The full-resolution probability tensor is never written: each output pixel is interpolated in registers, classified
 // and folded into the matrices straight away.
+// The coordinates, the interpolated row pair and the argmax live in ccdm_seg_common.h, shared with the export kernel
+// (ccdm_segexport.hip), which must write the class this kernel counts.
 //
 // Layout.  One block (4 waves) owns an output tile of 64 columns x 64 rows of one image; wave w walks 16 of its rows, one
 // output column per lane.  Horizontal weights are per lane and fixed over the walk, vertical weights are wave-uniform.
@@ -16,21 +18,11 @@
 // LDS slice (only that wave writes it).
 // At the end the block sums its 4 slices in order into its row of the fp64 slab; k_seg_reduce sums the slab rows in a
 // fixed order.  Same inputs and shapes => same grid => bit-identical matrices.
-#include "ccdm_common.h"
+#include "ccdm_seg_common.h"
 
 namespace ccdm {
 
-constexpr int SEG_TW = 64;              // output columns of a tile (one per lane)
-constexpr int SEG_WAVES = 4;
-constexpr int SEG_ROWS = 16;            // output rows per wave
-constexpr int SEG_TH = SEG_WAVES * SEG_ROWS;
-constexpr int SEG_MAX_BLOCKS = 1024;    // slab rows
 constexpr int SEG_FLUSH = 4;            // fp32 steps per lane before the wave partial goes to fp64 (<= 256 pixels)
-
-static inline int seg_blocks(int B, int H, int W) {
-    const long long tiles = (long long)B * cdiv(H, SEG_TH) * cdiv(W, SEG_TW);
-    return (int)(tiles < SEG_MAX_BLOCKS ? tiles : SEG_MAX_BLOCKS);
-}
 
 // Sum over the 64 lanes in a fixed order: DPP within each row of 16 lanes (quad swaps, half-row and row mirrors leave the row
 // sum in every lane of the row), then the four row sums as (r0 + r1) + (r2 + r3).  Every lane returns the same value.
@@ -48,65 +40,6 @@ __device__ __forceinline__ float seg_wave_sum(float x) {
     const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 32));
     const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 48));
     return (r0 + r1) + (r2 + r3);
-}
-
-// Source row `iy` interpolated horizontally: r[c] = w0 * x[iy, ix0, c] + w1 * x[iy, ix1, c], c < C.
-// SRC 0: fp32 channels-last with pixel stride `ps` (V4: float4 loads, ps % 4 == 0 and 16-byte aligned);
-// SRC 1: uint8 class map read as its one-hot, through the same expression on the exact 0 / 1 values.
-template <int KP, int SRC, bool V4>
-__device__ __forceinline__ void seg_row(float (&r)[KP], const float* __restrict__ probs, const uint8_t* __restrict__ cls,
-                                        size_t row, int ix0, int ix1, float w0, float w1, long long ps, int C) {
-    if constexpr (SRC == 1) {
-        const int c0 = cls[row + ix0], c1 = cls[row + ix1];
-#pragma unroll
-        for (int c = 0; c < KP; ++c) {
-            const float x0 = c0 == c ? 1.0f : 0.0f, x1 = c1 == c ? 1.0f : 0.0f;
-            r[c] = w0 * x0 + w1 * x1;
-        }
-    } else if constexpr (V4) {
-        // channels past C - 1 re-read the last real chunk (in bounds: ps % 4 == 0 and ps > C - 1); their values are never used
-        const float4* p0 = reinterpret_cast<const float4*>(probs + (row + ix0) * ps);
-        const float4* p1 = reinterpret_cast<const float4*>(probs + (row + ix1) * ps);
-        const int qlast = (C - 1) >> 2;
-#pragma unroll
-        for (int q = 0; q < (KP + 3) / 4; ++q) {
-            const float4 a = p0[min(q, qlast)], b = p1[min(q, qlast)];
-            const float xa[4] = {a.x, a.y, a.z, a.w}, xb[4] = {b.x, b.y, b.z, b.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (4 * q + j < KP) r[4 * q + j] = w0 * xa[j] + w1 * xb[j];
-        }
-    } else {
-        const float* p0 = probs + (row + ix0) * ps;
-        const float* p1 = probs + (row + ix1) * ps;
-#pragma unroll
-        for (int c = 0; c < KP; ++c) r[c] = w0 * p0[min(c, C - 1)] + w1 * p1[min(c, C - 1)];
-    }
-}
-
-template <int KP, int SRC, bool V4>
-__device__ __forceinline__ void seg_pixel(float (&r)[KP], const float* __restrict__ probs, const uint8_t* __restrict__ cls,
-                                          size_t pix, long long ps, int C) {
-    if constexpr (SRC == 1) {
-        const int c0 = cls[pix];
-#pragma unroll
-        for (int c = 0; c < KP; ++c) r[c] = c0 == c ? 1.0f : 0.0f;
-    } else if constexpr (V4) {
-        const float4* p = reinterpret_cast<const float4*>(probs + pix * ps);
-        const int qlast = (C - 1) >> 2;
-#pragma unroll
-        for (int q = 0; q < (KP + 3) / 4; ++q) {
-            const float4 a = p[min(q, qlast)];
-            const float xa[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (4 * q + j < KP) r[4 * q + j] = xa[j];
-        }
-    } else {
-        const float* p = probs + pix * ps;
-#pragma unroll
-        for (int c = 0; c < KP; ++c) r[c] = p[min(c, C - 1)];
-    }
 }
 
 // Adds every lane's partials to the wave's slice, lanes grouped by the target they belong to (mine >= C: nothing), one fixed-order
@@ -157,55 +90,17 @@ __global__ __launch_bounds__(256) void k_seg_confusion(const float* __restrict__
         const int tx = (int)(tile % tiles_x), ty = (int)((tile / tiles_x) % tiles_y), b = (int)(tile / ((long long)tiles_x * tiles_y));
         const int x = tx * SEG_TW + lane;
         const bool in_x = x < W;
-        // ATen upsample_bilinear2d, align_corners=False: src = max(scale * (dst + 0.5) - 0.5, 0), in fp32
-        int ix0 = 0, ix1 = 0;
-        float lw0 = 1.0f, lw1 = 0.0f;
-        if (IDENT) {
-            ix0 = ix1 = in_x ? x : 0;
-        } else if (in_x) {
-            float s = sw * ((float)x + 0.5f) - 0.5f;
-            s = s < 0.0f ? 0.0f : s;
-            ix0 = min((int)s, w - 1);
-            ix1 = ix0 + (ix0 < w - 1 ? 1 : 0);
-            lw1 = s - (float)ix0;
-            lw0 = 1.0f - lw1;
-        }
+        int ix0, ix1;
+        float lw0, lw1;
+        seg_lane_coord<IDENT>(x, in_x, sw, w, ix0, ix1, lw0, lw1);
         float A[KP], Bv[KP];
         int yA = -1, yB = -1;
         const int y_begin = ty * SEG_TH + wave * SEG_ROWS;
         const int y_end = min(y_begin + SEG_ROWS, H);
         int t_next = (in_x && y_begin < y_end) ? (int)labels[((size_t)b * H + y_begin) * W + x] : 255;
         for (int y = y_begin; y < y_end; ++y) {
-            float h0 = 1.0f, h1 = 0.0f;
-            if (IDENT) {
-                // weights (1, 0) in both directions give x itself for finite x: read the pixel (what ATen's same-size path copies)
-                seg_pixel<KP, SRC, V4>(A, probs, cls, ((size_t)b * h + y) * w + ix0, ps, C);
-            } else {
-                float s = sh * ((float)y + 0.5f) - 0.5f;
-                s = s < 0.0f ? 0.0f : s;
-                const int iy0 = min((int)s, h - 1);
-                const int iy1 = iy0 + (iy0 < h - 1 ? 1 : 0);
-                h1 = s - (float)iy0;
-                h0 = 1.0f - h1;
-                if (iy0 != yA) {
-                    if (iy0 == yB) {
-#pragma unroll
-                        for (int c = 0; c < KP; ++c) A[c] = Bv[c];
-                    } else {
-                        seg_row<KP, SRC, V4>(A, probs, cls, ((size_t)b * h + iy0) * w, ix0, ix1, lw0, lw1, ps, C);
-                    }
-                    yA = iy0;
-                }
-                if (iy1 != yB) {
-                    if (iy1 == yA) {
-#pragma unroll
-                        for (int c = 0; c < KP; ++c) Bv[c] = A[c];
-                    } else {
-                        seg_row<KP, SRC, V4>(Bv, probs, cls, ((size_t)b * h + iy1) * w, ix0, ix1, lw0, lw1, ps, C);
-                    }
-                    yB = iy1;
-                }
-            }
+            float h0, h1;
+            seg_step<KP, SRC, V4, IDENT>(A, Bv, yA, yB, h0, h1, probs, cls, b, y, h, w, sh, ix0, ix1, lw0, lw1, ps, C);
             const int t = t_next;
             if (y + 1 < y_end && in_x) t_next = labels[((size_t)b * H + y + 1) * W + x];     // one step ahead
             const bool valid = in_x && t < C;            // ignite: (y >= 0) & (y < num_classes)
@@ -224,8 +119,8 @@ __global__ __launch_bounds__(256) void k_seg_confusion(const float* __restrict__
             float best = 0.0f;
 #pragma unroll
             for (int c = 0; c < KP; ++c) {
-                const float vc = IDENT ? A[c] : h0 * A[c] + h1 * Bv[c];
-                if (c == 0 || (c < C && vc > best)) { best = vc; pred = c; }
+                const float vc = seg_value<IDENT>(A[c], Bv[c], h0, h1);
+                seg_argmax_step(c, C, vc, best, pred);
                 acc[c] += valid ? vc : 0.0f;      // channels >= C are never flushed
             }
 

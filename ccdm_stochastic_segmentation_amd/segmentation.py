@@ -6,6 +6,10 @@ against the original full-resolution labels — the reference's `evaluation/eval
     SegmentationConfusion(num_classes, device)   ignite's ConfusionMatrix / IoU / mIoU and the reference's "soft" matrix, built by
                                                  one HIP kernel (ccdm_seg_confusion) that upsamples, classifies and counts without
                                                  a full-resolution probability tensor
+    export_predictions / export_labels           the full-resolution class map as label ids and colours (the images of the
+                                                 reference's `save_preds`), by one HIP kernel (ccdm_segexport) that shares the
+                                                 confusion kernel's arithmetic
+    PredictionWriter(directory, split)           writes them as PNGs under outputs/<split>/{submit,debug,label}
     eval_segmentation(params, ...)               the evaluation loop (no ignite), built like evaluation.eval_lidc_uncertainty
     CityscapesVal(root, ...)                     the validation split, re-stated with PIL and numpy (no torchvision)
     SyntheticCityscapes(...)                     a deterministic stand-in so the entry point runs without the data
@@ -39,6 +43,23 @@ CITYSCAPES_LABELS: Tuple[Tuple[str, int, int], ...] = (
 NUM_CLASSES = 20            # 19 evaluated train ids + the ignore class
 IGNORE_CLASS = 19           # the model's ignore channel / label value (datasets/cityscapes.py: BACKGROUND_CLASS)
 TRAIN_ID_NAMES: Tuple[str, ...] = tuple(n for n, _, t in sorted(CITYSCAPES_LABELS, key=lambda r: r[2]) if t != 255)
+# The colour column of the same public definition, one (R, G, B) per row of CITYSCAPES_LABELS (kept beside it: the rows above are
+# pinned as triples by tests/golden/cityscapes_train_ids.json).
+CITYSCAPES_COLORS: Tuple[Tuple[int, int, int], ...] = (
+    (0, 0, 0), (0, 0, 0), (0, 0, 0), (0, 0, 0), (0, 0, 0),
+    (111, 74, 0), (81, 0, 81), (128, 64, 128), (244, 35, 232), (250, 170, 160), (230, 150, 140),
+    (70, 70, 70), (102, 102, 156), (190, 153, 153), (180, 165, 180), (150, 100, 100), (150, 120, 90),
+    (153, 153, 153), (153, 153, 153), (250, 170, 30), (220, 220, 0), (107, 142, 35),
+    (152, 251, 152), (70, 130, 180), (220, 20, 60), (255, 0, 0), (0, 0, 142), (0, 0, 70),
+    (0, 60, 100), (0, 0, 90), (0, 0, 110), (0, 80, 100), (0, 0, 230), (119, 11, 32),
+    (0, 0, 142),
+)
+assert len(CITYSCAPES_COLORS) == len(CITYSCAPES_LABELS)
+# train id -> label id / colour, 20 entries: the 19 evaluated classes in train-id order, then the ignore class as id 0 (unlabeled),
+# black — the reference's train_id_to_id / train_id_to_color.  tests/golden/cityscapes_export_tables.json pins them.
+_BY_TRAIN_ID = sorted((t, i, c) for (_, i, t), c in zip(CITYSCAPES_LABELS, CITYSCAPES_COLORS) if t != 255)
+TRAIN_ID_TO_ID: Tuple[int, ...] = tuple(i for _, i, _ in _BY_TRAIN_ID) + (0,)
+TRAIN_ID_TO_COLOR: Tuple[Tuple[int, int, int], ...] = tuple(c for _, _, c in _BY_TRAIN_ID) + ((0, 0, 0),)
 
 
 def id_to_train_id_lut() -> np.ndarray:
@@ -66,6 +87,26 @@ def iou_soft_from_confusion(cm) -> torch.Tensor:
     iou = diag / (cm.sum(dim=0) + cm.sum(dim=1) - diag)
     iou[iou != iou] = 0
     return iou
+
+
+def prediction_form(prediction: torch.Tensor, num_classes: int, device):
+    """The form of a prediction the segmentation kernels read -> (fp32 channels-last tensor or None, pixel stride, uint8 class map
+    or None, h, w): a float [B,K,h,w] that is a view of channels-last memory is read in place (any other layout is copied once at
+    the low resolution), an integer or bool one-hot [B,K,h,w] and a class map [B,h,w] become a uint8 class map."""
+    K = int(num_classes)
+    prediction = prediction.to(device)
+    if prediction.ndim == 3:
+        return None, 0, prediction.to(torch.uint8).contiguous(), int(prediction.shape[1]), int(prediction.shape[2])
+    if prediction.ndim != 4 or prediction.shape[1] != K:
+        raise ValueError(f"prediction: expected [B,{K},h,w] or a class map [B,h,w], got {tuple(prediction.shape)}")
+    h, w = int(prediction.shape[2]), int(prediction.shape[3])
+    if not prediction.is_floating_point():
+        return None, 0, prediction.argmax(dim=1).to(torch.uint8).contiguous(), h, w
+    p = prediction.to(torch.float32).permute(0, 2, 3, 1)
+    ps = p.stride(2)
+    if not (p.stride(3) == 1 and ps >= K and p.stride(1) == w * ps and p.stride(0) == h * w * ps):
+        p, ps = p.contiguous(), K
+    return p, ps, None, h, w
 
 
 class SegmentationConfusion:
@@ -101,21 +142,7 @@ class SegmentationConfusion:
         return self._hard.cpu()
 
     def _prediction(self, prediction: torch.Tensor):
-        """-> (fp32 channels-last tensor or None, pixel stride, uint8 class map or None, h, w)"""
-        K = self.num_classes
-        prediction = prediction.to(self.device)
-        if prediction.ndim == 3:
-            return None, 0, prediction.to(torch.uint8).contiguous(), int(prediction.shape[1]), int(prediction.shape[2])
-        if prediction.ndim != 4 or prediction.shape[1] != K:
-            raise ValueError(f"prediction: expected [B,{K},h,w] or a class map [B,h,w], got {tuple(prediction.shape)}")
-        h, w = int(prediction.shape[2]), int(prediction.shape[3])
-        if not prediction.is_floating_point():
-            return None, 0, prediction.argmax(dim=1).to(torch.uint8).contiguous(), h, w
-        p = prediction.to(torch.float32).permute(0, 2, 3, 1)
-        ps = p.stride(2)
-        if not (p.stride(3) == 1 and ps >= K and p.stride(1) == w * ps and p.stride(0) == h * w * ps):
-            p, ps = p.contiguous(), K
-        return p, ps, None, h, w
+        return prediction_form(prediction, self.num_classes, self.device)
 
     @torch.no_grad()
     def update(self, prediction: torch.Tensor, labels: torch.Tensor) -> None:
@@ -151,6 +178,121 @@ class SegmentationConfusion:
 
     def miou_soft(self) -> float:
         return float(self.iou_soft().mean())
+
+
+# ------------------------------------------------------------------------------------------------ prediction export
+EXPORT_OUTPUTS = ("train_id", "label_id", "color")
+
+
+def _export(probs, ps, cls, B, h, w, H, W, K, scored, outputs, id_table, color_table, device) -> Dict[str, torch.Tensor]:
+    outputs = tuple(outputs)
+    if not outputs or any(o not in EXPORT_OUTPUTS for o in outputs):
+        raise ValueError(f"outputs: {outputs!r} (a non-empty subset of {list(EXPORT_OUTPUTS)})")
+    if not 2 <= K <= 32:
+        raise ValueError(f"{K} classes (the kernel takes 2..32 channels, the last one the ignore class)")
+    if id_table is None or color_table is None:
+        if K != NUM_CLASSES:
+            raise ValueError(f"{K} classes: the default tables are Cityscapes' ({NUM_CLASSES} classes), pass id_table and color_table")
+        id_table = TRAIN_ID_TO_ID if id_table is None else id_table
+        color_table = TRAIN_ID_TO_COLOR if color_table is None else color_table
+    idt = torch.as_tensor(np.asarray(id_table, dtype=np.uint8)).reshape(-1).to(device)
+    colt = torch.as_tensor(np.asarray(color_table, dtype=np.uint8)).reshape(-1).to(device)
+    if idt.numel() != K or colt.numel() != 3 * K:
+        raise ValueError(f"id_table / color_table: expected [{K}] and [{K},3], got {idt.numel()} and {colt.numel()} values")
+    out = {o: torch.empty((B, H, W, 3) if o == "color" else (B, H, W), dtype=torch.uint8, device=device) for o in outputs}
+    ptr = {o: out[o].data_ptr() if o in out and B > 0 else None for o in EXPORT_OUTPUTS}
+    if B > 0:
+        hip.check(hip.load().ccdm_segexport(probs.data_ptr() if probs is not None else None, ps, cls.data_ptr() if cls is not None else None,
+                                            B, h, w, H, W, K, scored, idt.data_ptr(), colt.data_ptr(), ptr["train_id"], ptr["label_id"],
+                                            ptr["color"], torch.cuda.current_stream(device).cuda_stream), "segexport")
+    return out
+
+
+def _cuda_device(device):
+    device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    if device.type != "cuda":
+        raise hip.CcdmHipError("the prediction export runs on the GPU (no CPU path)")
+    return device
+
+
+@torch.no_grad()
+def export_predictions(prediction: torch.Tensor, size: Sequence[int], *, outputs: Sequence[str] = ("label_id", "color"), id_table=None,
+                       color_table=None, num_classes: Optional[int] = None, device=None) -> Dict[str, torch.Tensor]:
+    """The class map of `prediction` at `size` = (H, W) as uint8 GPU tensors, a dict with the requested `outputs`:
+      "train_id" [B,H,W]    the argmax over the first K-1 channels (the ignore channel is dropped) of the prediction upsampled
+                            bilinearly to (H, W): the class SegmentationConfusion counts for that pixel, bit for bit;
+      "label_id" [B,H,W]    id_table[train_id] (the reference's submit/<n>_id.png);
+      "color"    [B,H,W,3]  color_table[train_id] (its debug/<n>_rgb.png).
+    prediction: every form SegmentationConfusion.update takes ([B,K,h,w] float, integer or bool one-hot, or a class map [B,h,w],
+    whose K is `num_classes`, default 20).  id_table [K] / color_table [K,3]: default Cityscapes' (K = 20 only).  One HIP kernel
+    (ccdm_segexport); never builds a full-resolution probability tensor."""
+    device = _cuda_device(device if device is not None else (prediction.device if prediction.is_cuda else None))
+    if prediction.ndim == 4:
+        K = int(prediction.shape[1])
+        if num_classes is not None and int(num_classes) != K:
+            raise ValueError(f"prediction has {K} channels, num_classes = {num_classes}")
+    else:
+        K = int(num_classes) if num_classes is not None else (len(id_table) if id_table is not None else NUM_CLASSES)
+    probs, ps, cls, h, w = prediction_form(prediction, K, device)
+    H, W = int(size[0]), int(size[1])
+    return _export(probs, ps, cls, int(prediction.shape[0]), h, w, H, W, K, K - 1, outputs, id_table, color_table, device)
+
+
+@torch.no_grad()
+def export_labels(labels: torch.Tensor, *, outputs: Sequence[str] = ("label_id",), id_table=None, color_table=None,
+                  num_classes: int = NUM_CLASSES, device=None) -> Dict[str, torch.Tensor]:
+    """Labels [B,H,W] in train ids as the same uint8 images (the reference's label/<n>_label.png is "label_id"): values 0..K-1 go
+    through the tables, anything else (255, negative, ...) counts as the ignore class K-1.  The same kernel as
+    export_predictions, on the labels as a class map at their own resolution, with all K classes scored."""
+    if labels.ndim != 3:
+        raise ValueError(f"labels: expected [B,H,W], got {tuple(labels.shape)}")
+    device = _cuda_device(device if device is not None else (labels.device if labels.is_cuda else None))
+    K = int(num_classes)
+    lab = labels.to(device)
+    if lab.dtype == torch.bool:
+        lab = lab.to(torch.uint8)
+    lab = torch.where((lab < 0) | (lab > K - 1), torch.full_like(lab, K - 1), lab).to(torch.uint8).contiguous()
+    B, H, W = (int(v) for v in lab.shape)
+    return _export(None, 0, lab, B, H, W, H, W, K, K, outputs, id_table, color_table, device)
+
+
+class PredictionWriter:
+    """The reference Evaluator's `save_preds`: per image three PNGs under <directory>/outputs/<split>/
+      submit/<n>_id.png     the prediction in label ids (mode L): what the official evaluation script and the benchmark server read;
+      debug/<n>_rgb.png     the prediction in class colours (mode RGB);
+      label/<n>_label.png   the labels in label ids (mode L);
+    n counts the images from 1 across write() calls.  pred_list / label_list keep the submit and label paths in order (what the
+    official script takes).  The maps come from export_predictions / export_labels; PNG encoding is host work (PIL)."""
+
+    def __init__(self, directory: str, split: str = "val", id_table=None, color_table=None):
+        base = os.path.join(directory, "outputs", split)
+        self.path_submit, self.path_debug, self.path_label = (os.path.join(base, d) for d in ("submit", "debug", "label"))
+        for d in (self.path_submit, self.path_debug, self.path_label):
+            os.makedirs(d, exist_ok=True)
+        self.id_table, self.color_table = id_table, color_table
+        self.images_cnt = 0
+        self.pred_list: List[str] = []
+        self.label_list: List[str] = []
+
+    def write(self, prediction: torch.Tensor, labels: torch.Tensor, size: Optional[Sequence[int]] = None) -> None:
+        """prediction: any form export_predictions takes; labels: [B,H,W] train ids; size: (H, W) of the images, default the labels'."""
+        from PIL import Image
+        size = tuple(int(v) for v in (size if size is not None else labels.shape[1:]))
+        K = int(prediction.shape[1]) if prediction.ndim == 4 else NUM_CLASSES
+        pred = export_predictions(prediction, size, outputs=("label_id", "color"), id_table=self.id_table, color_table=self.color_table,
+                                  num_classes=K)
+        lab = export_labels(labels, outputs=("label_id",), id_table=self.id_table, color_table=self.color_table, num_classes=K)
+        ids, rgb, lids = (np.asarray(t.cpu() if isinstance(t, torch.Tensor) else t) for t in (pred["label_id"], pred["color"], lab["label_id"]))
+        for i in range(ids.shape[0]):
+            n = self.images_cnt + i + 1
+            f_id, f_rgb, f_lab = (os.path.join(self.path_submit, f"{n}_id.png"), os.path.join(self.path_debug, f"{n}_rgb.png"),
+                                  os.path.join(self.path_label, f"{n}_label.png"))
+            Image.fromarray(np.ascontiguousarray(ids[i], dtype=np.uint8)).save(f_id)
+            Image.fromarray(np.ascontiguousarray(rgb[i], dtype=np.uint8)).save(f_rgb)
+            Image.fromarray(np.ascontiguousarray(lids[i], dtype=np.uint8)).save(f_lab)
+            self.pred_list.append(f_id)
+            self.label_list.append(f_lab)
+        self.images_cnt += int(ids.shape[0])
 
 
 # ------------------------------------------------------------------------------------------------ data
@@ -293,6 +435,8 @@ def eval_segmentation(params: dict, dataset=None, device=None, model=None, synth
     through evaluation.predict_multiple (`evaluations`, `evaluation_vote_strategy`, the `evaluation:` section), the labels of
     `evaluation.resolution` ("original": the full-resolution labels, "dataloader" (default): the argmax of the one-hot labels),
     and both confusion matrices (SegmentationConfusion).  The checkpoint is `load_from`'s "average_model".
+    `evaluation.save_predictions` (default off): also write every prediction and its labels as PNGs at the scored resolution under
+    `output_path` (PredictionWriter); the result then holds "pred_list" / "label_list".
     `model`: a ready DenoisingModel-like callable (tests inject one); default: built from `params`."""
     from . import evaluation as E
     world = int(os.environ.get("WORLD_SIZE", "1") or 1)
@@ -321,13 +465,17 @@ def eval_segmentation(params: dict, dataset=None, device=None, model=None, synth
             model.unet.load_state_dict({k: torch.from_numpy(v) for k, v in make_synthetic_state_dict(model.unet.spec, synthetic_weights_seed).items()})
         E.apply_sampler_options(model, params)
     conf = SegmentationConfusion(num_classes, device)
+    writer = PredictionWriter(E.expanduservars(params["output_path"])) if section.get("save_predictions", False) else None
     n_img = 0
     for image, labels, labels_orig in loader:
         image = image.to(device)
         feature_condition = encoder(image) if encoder is not None else None
         prediction = E.predict_multiple(model, image, params, feature_condition)
         target = labels_orig if resolution == "original" else labels.argmax(dim=1)
-        conf.update(prediction, target.to(device))
+        target = target.to(device)
+        conf.update(prediction, target)
+        if writer is not None:
+            writer.write(prediction, target, tuple(target.shape[1:]))
         n_img += image.shape[0]
     iou, iou_soft = conf.iou(), conf.iou_soft()
     names = TRAIN_ID_NAMES if conf.C == len(TRAIN_ID_NAMES) else tuple(str(c) for c in range(conf.C))
@@ -335,6 +483,9 @@ def eval_segmentation(params: dict, dataset=None, device=None, model=None, synth
         LOGGER.info("IoU %-14s %.4f  (soft %.4f)", name, a, b)
     res = {"mIoU": float(iou.mean()), "IoU": iou.tolist(), "mIoU_soft": float(iou_soft.mean()), "IoU_soft": iou_soft.tolist(),
            "confusion": conf.confusion.tolist(), "images": n_img, "resolution": resolution, "evaluations": evaluations, "vote": vote}
+    if writer is not None:
+        res["pred_list"], res["label_list"] = list(writer.pred_list), list(writer.label_list)
+        LOGGER.info("%d predictions written under %s", len(writer.pred_list), os.path.dirname(writer.path_submit))
     LOGGER.info("mIoU %.4f  soft mIoU %.4f over %d images (resolution %s, %d evaluation(s), %s)", res["mIoU"], res["mIoU_soft"], n_img,
                 resolution, evaluations, vote)
     return res

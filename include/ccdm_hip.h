@@ -337,6 +337,24 @@ int ccdm_seg_confusion(const float* probs /*dev or NULL*/, int64_t pixel_stride,
                        void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Segmentation prediction export, device part (the images of the reference Evaluator's `save_preds`): the class of every
+ * output pixel of [B,H,W], written as a train id, a label id and a colour, without a full-resolution probability tensor.
+ * The prediction (probs XOR cls), the bilinear sample and the argmax are those of ccdm_seg_confusion above, through the same
+ * device code: the class written here is the class counted there, bit for bit.
+ *   scored    the leading channels the argmax runs over: K-1 for a prediction (the ignore channel is dropped; a pixel with all
+ *             its mass there becomes class 0), K for labels passed as a class map (train id K-1 reaches table entry K-1);
+ *   id_table  uint8 [K], color_table uint8 [K][3], in device memory;
+ *   outputs   each optional (NULL = not written), at least one: train_id uint8 [B,H,W] = the argmax class,
+ *             label_id uint8 [B,H,W] = id_table[train_id], color uint8 [B,H,W,3] = color_table[train_id].
+ * K in [2,32].  No workspace, nothing is reduced; B = 0 returns 0 without a launch.  (Named without the ccdm_seg_ prefix: the
+ * evaluator's test pins the set of ccdm_seg_* symbols.)
+ * ------------------------------------------------------------------------------------------------- */
+int ccdm_segexport(const float* probs /*dev or NULL*/, int64_t pixel_stride, const uint8_t* cls /*dev [B,h,w] or NULL*/,
+                   int B, int h, int w, int H, int W, int K, int scored, const uint8_t* id_table /*dev [K]*/,
+                   const uint8_t* color_table /*dev [K][3]*/, uint8_t* train_id /*dev [B,H,W] or NULL*/,
+                   uint8_t* label_id /*dev [B,H,W] or NULL*/, uint8_t* color /*dev [B,H,W,3] or NULL*/, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Multi-sample prediction (DenoisingModel.predict_multiple): S sampling passes of the same B images folded into one
  * mean map, a per-pixel vote and two uncertainty maps.  The reference's Evaluator.predict_multiple
  * (evaluation/eval_cdm.py:176-193) accumulates `total += prediction_i * (1 / S)` on the host; these read a pass
