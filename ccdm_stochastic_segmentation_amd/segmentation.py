@@ -10,7 +10,9 @@ against the original full-resolution labels — the reference's `evaluation/eval
                                                  reference's `save_preds`), by one HIP kernel (ccdm_segexport) that shares the
                                                  confusion kernel's arithmetic
     PredictionWriter(directory, split)           writes them as PNGs under outputs/<split>/{submit,debug,label}
-    eval_segmentation(params, ...)               the evaluation loop (no ignite), built like evaluation.eval_lidc_uncertainty
+    eval_segmentation(params, ...)               the evaluation loop (no ignite), built like evaluation.eval_lidc_uncertainty; with
+                                                 evaluation.cityscapes_script also the official script's scores
+                                                 (cityscapes_scores.CityscapesScores, one more HIP launch per batch: ccdm_csscore)
     CityscapesVal(root, ...)                     the validation split, re-stated with PIL and numpy (no torchvision)
     SyntheticCityscapes(...)                     a deterministic stand-in so the entry point runs without the data
 """
@@ -310,10 +312,13 @@ class CityscapesVal(torch.utils.data.Dataset):
       original labels: the full-resolution train ids.  The reference hands `infer_step` the raw label ids here, which do not
               compare with train-id predictions; this is what its evaluator needs.
     max_size: the subset random_split(dataset, [max_size, n - max_size], generator=Generator().manual_seed(1)) keeps, in its order.
+    return_instances: items get a fourth entry, the values of *_gtFine_instanceIds.png [H0,W0] int32 (what the official script's
+    instance-level scores read).
     root defaults to ${TMPDIR}/cityscapes/ (the reference's BASE_PATH)."""
 
     def __init__(self, root: Optional[str] = None, split: str = "val", target_size: Sequence[int] = (256, 512),
-                 max_size: Optional[int] = None):
+                 max_size: Optional[int] = None, return_instances: bool = False):
+        self.return_instances = bool(return_instances)
         self.root = os.path.expandvars(root if root else "${TMPDIR}/cityscapes/")
         self.split = split
         self.target_size = (int(target_size[0]), int(target_size[1]))
@@ -327,6 +332,8 @@ class CityscapesVal(torch.utils.data.Dataset):
                                    os.path.basename(img)[:-len("_leftImg8bit.png")] + "_gtFine_labelIds.png")
                 if not os.path.exists(lbl):
                     raise FileNotFoundError(f"{lbl}: the label of {img} is missing")
+                if self.return_instances and not os.path.exists(lbl.replace("labelIds", "instanceIds")):
+                    raise FileNotFoundError(f"{lbl.replace('labelIds', 'instanceIds')}: the instance image of {img} is missing")
                 self.pairs.append((img, lbl))
         self.indices = list(range(len(self.pairs)))
         if max_size:
@@ -353,14 +360,25 @@ class CityscapesVal(torch.utils.data.Dataset):
         train = torch.from_numpy(self.lut[small.astype(np.int64) & 255].astype(np.int64))
         onehot = torch.nn.functional.one_hot(train, NUM_CLASSES).permute(2, 0, 1).float()
         original = torch.from_numpy(self.lut[ids.astype(np.int64) & 255].astype(np.int64))
+        if self.return_instances:
+            with Image.open(lbl_path.replace("labelIds", "instanceIds")) as im:
+                inst = np.array(im).astype(np.int32)
+            if inst.shape != ids.shape:
+                raise ValueError(f"{lbl_path}: the instance image is {inst.shape}, the labels are {ids.shape}")
+            return image, onehot, original, torch.from_numpy(inst)
         return image, onehot, original
 
 
 class SyntheticCityscapes(torch.utils.data.Dataset):
     """Cityscapes-shaped stand-in: image [3,h,w], one-hot labels [20,h,w] and original train-id labels at `original_size`:
-    a few class blobs over a background class, with ignore pixels (19 and 255) sprinkled in.  Deterministic per (seed, item)."""
+    a few class blobs over a background class, with ignore pixels (19 and 255) sprinkled in.  Deterministic per (seed, item).
+    instances: items get a fourth entry, an instance image [H0,W0] int32 as Cityscapes writes it: blob number j of a class with
+    instances (person .. bicycle) is the instance label id * 1000 + j on the pixels it still owns, every other pixel holds its
+    label id (0 where the label is ignored).  The first three entries do not depend on it."""
 
-    def __init__(self, size: int = 4, resolution: Sequence[int] = (32, 32), original_size: Sequence[int] = (64, 96), seed: int = 0):
+    def __init__(self, size: int = 4, resolution: Sequence[int] = (32, 32), original_size: Sequence[int] = (64, 96), seed: int = 0,
+                 instances: bool = False):
+        self.instances = bool(instances)
         self.size, self.seed = int(size), int(seed)
         self.resolution = (int(resolution[0]), int(resolution[1]))
         self.original_size = (int(original_size[0]), int(original_size[1]))
@@ -373,9 +391,11 @@ class SyntheticCityscapes(torch.utils.data.Dataset):
         H0, W0 = self.original_size
         yy, xx = np.mgrid[0:H0, 0:W0] / np.array([H0, W0])[:, None, None]
         lab = np.full((H0, W0), rng.integers(0, 19), dtype=np.int64)
+        blobs = []
         for _ in range(4):
             cy, cx, r = rng.uniform(0.1, 0.9), rng.uniform(0.1, 0.9), rng.uniform(0.1, 0.3)
-            lab[(yy - cy) ** 2 + (xx - cx) ** 2 <= r * r] = rng.integers(0, 19)
+            blobs.append(((yy - cy) ** 2 + (xx - cx) ** 2 <= r * r, int(rng.integers(0, 19))))
+            lab[blobs[-1][0]] = blobs[-1][1]
         lab[rng.random((H0, W0)) < 0.03] = IGNORE_CLASS
         lab[rng.random((H0, W0)) < 0.01] = 255
         h, w = self.resolution
@@ -386,19 +406,30 @@ class SyntheticCityscapes(torch.utils.data.Dataset):
         onehot = torch.nn.functional.one_hot(torch.from_numpy(small), NUM_CLASSES).permute(2, 0, 1).float()
         colour = rng.uniform(-1, 1, (NUM_CLASSES, 3)).astype(np.float32)
         image = colour[small].transpose(2, 0, 1) + 0.2 * rng.standard_normal((3, h, w)).astype(np.float32)
-        return torch.from_numpy(np.ascontiguousarray(image, dtype=np.float32)), onehot, torch.from_numpy(lab)
+        item = (torch.from_numpy(np.ascontiguousarray(image, dtype=np.float32)), onehot, torch.from_numpy(lab))
+        if not self.instances:
+            return item
+        ids = np.asarray(TRAIN_ID_TO_ID, dtype=np.int32)
+        inst = ids[np.where((lab < 0) | (lab > IGNORE_CLASS), IGNORE_CLASS, lab)]
+        for j, (mask, c) in enumerate(blobs, start=1):            # a later blob owns the pixels it painted over
+            if ids[c] >= 24:                                        # the labels with instances: person (24) .. bicycle (33)
+                inst[mask & (lab == c)] = ids[c] * 1000 + j
+        return item + (torch.from_numpy(inst),)
 
 
 def make_segmentation_dataset(params: dict):
     """`dataset_file` "...synthetic..." -> SyntheticCityscapes, else CityscapesVal at dataset_path (default ${TMPDIR}/cityscapes/).
     The size comes from dataset_pipeline_val_settings.target_size (the reference's "resize" setting), the subset from
-    dataset_val_max_size; the stand-in's original label size from the build-owned key `original_size`."""
+    dataset_val_max_size; the stand-in's original label size from the build-owned key `original_size`.  With
+    evaluation.cityscapes_script_instances the items carry the instance image as a fourth entry."""
     settings = params.get("dataset_pipeline_val_settings") or {}
     max_size = params.get("dataset_val_max_size", None)
+    instances = bool((params.get("evaluation") or {}).get("cityscapes_script_instances", False))
     if "synthetic" in params["dataset_file"]:
         return SyntheticCityscapes(size=max_size or 4, resolution=settings.get("target_size", (32, 32)),
-                                   original_size=params.get("original_size", (64, 96)))
-    return CityscapesVal(params.get("dataset_path") or None, "val", settings.get("target_size", (256, 512)), max_size)
+                                   original_size=params.get("original_size", (64, 96)), instances=instances)
+    return CityscapesVal(params.get("dataset_path") or None, "val", settings.get("target_size", (256, 512)), max_size,
+                         return_instances=instances)
 
 
 # ------------------------------------------------------------------------------------------------ evaluation
@@ -437,6 +468,13 @@ def eval_segmentation(params: dict, dataset=None, device=None, model=None, synth
     and both confusion matrices (SegmentationConfusion).  The checkpoint is `load_from`'s "average_model".
     `evaluation.save_predictions` (default off): also write every prediction and its labels as PNGs at the scored resolution under
     `output_path` (PredictionWriter); the result then holds "pred_list" / "label_list".
+    `evaluation.cityscapes_script` (default off): also score every batch as the official Cityscapes script scores the written PNGs
+    (cityscapes_scores.CityscapesScores: the prediction's label ids against id_table[labels], the label ids PredictionWriter
+    writes, every ignored label as id 0; what the reference's `run_inference` hands its vendored cs_eval.py).  The result then
+    holds "cs_script", the script's result dictionary, also written to <output_path>/cs_script_results.json; perImageScores is
+    keyed by the written submit/<n>_id.png paths when save_predictions is on, else by the image number.
+    `evaluation.cityscapes_script_instances` (default off): the instance-weighted scores (iIoU) too, from the dataset's instance
+    images; needs `resolution: original` (resized labels have no instance image).
     `model`: a ready DenoisingModel-like callable (tests inject one); default: built from `params`."""
     from . import evaluation as E
     world = int(os.environ.get("WORLD_SIZE", "1") or 1)
@@ -444,15 +482,23 @@ def eval_segmentation(params: dict, dataset=None, device=None, model=None, synth
         raise NotImplementedError(f"eval_segmentation runs on one rank: sharding the evaluation over WORLD_SIZE = {world} ranks is not "
                                   "built yet (launch it without torchrun)")
     device = torch.device(device if device is not None else "cuda")
-    dataset = dataset if dataset is not None else make_segmentation_dataset(params)
-    LOGGER.info("%d images in validation dataset '%s'", len(dataset), params["dataset_file"])
     section = params.get("evaluation") or {}
     resolution = section.get("resolution", "dataloader")
+    script, script_instances = bool(section.get("cityscapes_script", False)), bool(section.get("cityscapes_script_instances", False))
+    if script_instances and not script:
+        raise ValueError("evaluation.cityscapes_script_instances needs evaluation.cityscapes_script")
+    if script_instances and resolution != "original":
+        raise ValueError(f"evaluation.cityscapes_script_instances needs evaluation.resolution: original (got {resolution!r}): "
+                         "resized labels have no instance image")
+    dataset = dataset if dataset is not None else make_segmentation_dataset(params)
+    LOGGER.info("%d images in validation dataset '%s'", len(dataset), params["dataset_file"])
     if resolution not in RESOLUTIONS:
         raise ValueError(f"evaluation.resolution: {resolution!r} is not in {list(RESOLUTIONS)}")
     evaluations, vote = E.vote_settings(params)
     loader = torch.utils.data.DataLoader(dataset, batch_size=params["batch_size"], shuffle=False, num_workers=params.get("mp_loaders", 0))
-    image0, labels0, _ = dataset[0]
+    image0, labels0 = dataset[0][:2]
+    if script_instances and len(dataset[0]) < 4:
+        raise ValueError("evaluation.cityscapes_script_instances: the dataset's items carry no instance image (return_instances / instances)")
     input_shapes = [tuple(image0.shape), tuple(labels0.shape)]
     num_classes = input_shapes[1][0]
     encoder = _feature_encoder(params, synthetic_weights_seed, device)
@@ -466,8 +512,12 @@ def eval_segmentation(params: dict, dataset=None, device=None, model=None, synth
         E.apply_sampler_options(model, params)
     conf = SegmentationConfusion(num_classes, device)
     writer = PredictionWriter(E.expanduservars(params["output_path"])) if section.get("save_predictions", False) else None
+    scores = None
+    if script:
+        from .cityscapes_scores import CityscapesScores
+        scores = CityscapesScores(num_classes, device)
     n_img = 0
-    for image, labels, labels_orig in loader:
+    for image, labels, labels_orig, *rest in loader:
         image = image.to(device)
         feature_condition = encoder(image) if encoder is not None else None
         prediction = E.predict_multiple(model, image, params, feature_condition)
@@ -476,6 +526,10 @@ def eval_segmentation(params: dict, dataset=None, device=None, model=None, synth
         conf.update(prediction, target)
         if writer is not None:
             writer.write(prediction, target, tuple(target.shape[1:]))
+        if scores is not None:
+            gt_ids = export_labels(target, outputs=("label_id",), num_classes=num_classes)["label_id"]
+            scores.update(prediction, gt_ids, rest[0] if script_instances else None,
+                          writer.pred_list[-image.shape[0]:] if writer is not None else None)
         n_img += image.shape[0]
     iou, iou_soft = conf.iou(), conf.iou_soft()
     names = TRAIN_ID_NAMES if conf.C == len(TRAIN_ID_NAMES) else tuple(str(c) for c in range(conf.C))
@@ -486,6 +540,16 @@ def eval_segmentation(params: dict, dataset=None, device=None, model=None, synth
     if writer is not None:
         res["pred_list"], res["label_list"] = list(writer.pred_list), list(writer.label_list)
         LOGGER.info("%d predictions written under %s", len(writer.pred_list), os.path.dirname(writer.path_submit))
+    if scores is not None:
+        import json
+        res["cs_script"] = scores.result()
+        out_dir = E.expanduservars(params["output_path"])
+        os.makedirs(out_dir, exist_ok=True)
+        with open(os.path.join(out_dir, "cs_script_results.json"), "w") as f:
+            json.dump(res["cs_script"], f, indent=2, sort_keys=True)
+        LOGGER.info("Cityscapes script: IoU classes %.4f  iIoU classes %.4f  IoU categories %.4f  iIoU categories %.4f (%s)",
+                    *(res["cs_script"][k] for k in ("averageScoreClasses", "averageScoreInstClasses", "averageScoreCategories",
+                                                    "averageScoreInstCategories")), os.path.join(out_dir, "cs_script_results.json"))
     LOGGER.info("mIoU %.4f  soft mIoU %.4f over %d images (resolution %s, %d evaluation(s), %s)", res["mIoU"], res["mIoU_soft"], n_img,
                 resolution, evaluations, vote)
     return res

@@ -355,6 +355,45 @@ int ccdm_segexport(const float* probs /*dev or NULL*/, int64_t pixel_stride, con
                    uint8_t* label_id /*dev [B,H,W] or NULL*/, uint8_t* color /*dev [B,H,W,3] or NULL*/, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Cityscapes script scores, device part: the integer counts behind the result file of the official pixel-level evaluation
+ * script (the reference's evaluation/cs_eval.py, `evaluatePair`), in one pass over the output pixels of [B,H,W], without a
+ * full-resolution probability tensor and without an id image.
+ * ccdm_csscore: the prediction (probs XOR cls), the bilinear sample and the argmax over the first K-1 channels are those of
+ * ccdm_seg_confusion and ccdm_segexport above, through the same device code; the predicted id of a pixel is id_table[class],
+ * the byte ccdm_segexport writes as label_id, bit for bit.  ccdm_csscore_ids: the predicted ids are read from pred_ids
+ * uint8 [B,H,W] instead (what the script reads from the PNGs).  Everything below is in device memory.
+ *   id_table        uint8 [K];  gt_ids uint8 [B,H,W]: ground truth in label ids;
+ *   inst_ids        uint16 [B,H,W] or NULL: the values of *_gtFine_instanceIds.png (label id * 1000 + running number for an
+ *                   instance, the plain label id otherwise);
+ *   ignore_in_eval, category, has_instances   uint8 [L], per label id; L <= CCDM_CSSCORE_MAX_LABELS (34 for Cityscapes);
+ *   conf            int64 [L][L], rows = ground-truth id, columns = predicted id, ACCUMULATED across calls.  Every pixel is
+ *                   counted, ignored ground truth included (the script's check: conf.sum() == pixels);
+ *   per_image       int64 [B][4], OVERWRITTEN per call: {pixels whose ground truth is ignored in evaluation; of those, pixels
+ *                   where prediction != ground truth; pixels whose ground truth is evaluated; of those, pixels where
+ *                   prediction == ground truth}.  (The first two are what the script stores as nbNotIgnoredPixels and
+ *                   nbCorrectPixels: its np.in1d(..., invert=True) inverts the mask.)
+ *   instances       int32 [B][NI][3], only with inst_ids, OVERWRITTEN per call.  Slot layout: instance id i lives in slot
+ *                   i - inst_base of its image, for inst_base <= i < inst_base + NI (Cityscapes: inst_base 24000, NI 10000:
+ *                   the ids of the labels 24..33 that have instances).  Per slot {size of the instance; pixels whose predicted
+ *                   id is the instance's label i / 1000; pixels whose predicted id is a label of that label's category}.  An
+ *                   instance whose label is ignored in evaluation keeps a zero slot (the script's `continue`);
+ *   unknown         int32 [2], OVERWRITTEN per call: {pixels whose ground-truth or predicted id is >= L (not counted in conf;
+ *                   the script's "Unknown label with id"); pixels of an instance id > 1000 that has no slot or whose label has
+ *                   no instances (the script's KeyError)}.  A caller treats a non-zero entry as an error.
+ * Integer atomics only, after an on-chip reduction (an LDS copy of conf per block; per-wave groups of equal instance keys):
+ * every count is exact in any order, two identical calls are bit-identical.  K in [2,32].  gt_ids, pred_ids (4 bytes) and
+ * inst_ids (8 bytes) must be aligned when W % 4 == 0 (vector loads).  No workspace; B = 0 returns 0 without a launch.
+ * ------------------------------------------------------------------------------------------------- */
+#define CCDM_CSSCORE_MAX_LABELS 64
+int ccdm_csscore(const float* probs /*dev or NULL*/, int64_t pixel_stride, const uint8_t* cls /*dev [B,h,w] or NULL*/,
+                 int B, int h, int w, int H, int W, int K, const uint8_t* id_table, const uint8_t* gt_ids, const uint16_t* inst_ids,
+                 int L, const uint8_t* ignore_in_eval, const uint8_t* category, const uint8_t* has_instances, int inst_base, int NI,
+                 int64_t* conf, int64_t* per_image, int32_t* instances, int32_t* unknown, void* stream);
+int ccdm_csscore_ids(const uint8_t* pred_ids, int B, int H, int W, const uint8_t* gt_ids, const uint16_t* inst_ids,
+                     int L, const uint8_t* ignore_in_eval, const uint8_t* category, const uint8_t* has_instances, int inst_base, int NI,
+                     int64_t* conf, int64_t* per_image, int32_t* instances, int32_t* unknown, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Multi-sample prediction (DenoisingModel.predict_multiple): S sampling passes of the same B images folded into one
  * mean map, a per-pixel vote and two uncertainty maps.  The reference's Evaluator.predict_multiple
  * (evaluation/eval_cdm.py:176-193) accumulates `total += prediction_i * (1 / S)` on the host; these read a pass
