@@ -9,6 +9,9 @@ against the original full-resolution labels — the reference's `evaluation/eval
     export_predictions / export_labels           the full-resolution class map as label ids and colours (the images of the
                                                  reference's `save_preds`), by one HIP kernel (ccdm_segexport) that shares the
                                                  confusion kernel's arithmetic
+    SegmentationCalibration(num_classes, ...)    ECE / MCE, NLL, Brier score, reliability diagram and error-detection AUROC of the
+                                                 probabilities (beyond the reference), from the counts of one HIP kernel
+                                                 (ccdm_segcalib) on the same walk; calibration_from_counts is the host formula
     PredictionWriter(directory, split)           writes them as PNGs under outputs/<split>/{submit,debug,label}
     eval_segmentation(params, ...)               the evaluation loop (no ignite), built like evaluation.eval_lidc_uncertainty; with
                                                  evaluation.cityscapes_script also the official script's scores
@@ -111,6 +114,15 @@ def prediction_form(prediction: torch.Tensor, num_classes: int, device):
     return p, ps, None, h, w
 
 
+def _labels_u8(labels: torch.Tensor, device) -> torch.Tensor:
+    """Labels [B,H,W] as the contiguous uint8 tensor the kernels read: anything outside [0, 255] is not counted either way, 255
+    stands for it."""
+    lab = labels.to(device)
+    if lab.dtype != torch.uint8:
+        lab = torch.where((lab < 0) | (lab > 255), torch.full_like(lab, 255), lab).to(torch.uint8)
+    return lab.contiguous()
+
+
 class SegmentationConfusion:
     """The two confusion matrices of the reference's Cityscapes evaluator over `num_classes` = K model channels, of which the
     first C = K - 1 are scored (the last is the ignore class, dropped as `prediction_onehot[:, 0:K-1]` drops it):
@@ -151,10 +163,7 @@ class SegmentationConfusion:
         if labels.ndim != 3 or labels.shape[0] != prediction.shape[0]:
             raise ValueError(f"labels: expected [B,H,W] with B = {prediction.shape[0]}, got {tuple(labels.shape)}")
         probs, ps, cls, h, w = self._prediction(prediction)
-        lab = labels.to(self.device)
-        if lab.dtype != torch.uint8:      # anything outside [0, 255] is not counted either way: 255 stands for it
-            lab = torch.where((lab < 0) | (lab > 255), torch.full_like(lab, 255), lab).to(torch.uint8)
-        lab = lab.contiguous()
+        lab = _labels_u8(labels, self.device)
         B, H, W = (int(s) for s in lab.shape)
         lib = hip.load()
         need = int(lib.ccdm_seg_confusion_workspace_bytes(B, H, W, self.num_classes)) if B > 0 else 0
@@ -180,6 +189,123 @@ class SegmentationConfusion:
 
     def miou_soft(self) -> float:
         return float(self.iou_soft().mean())
+
+
+# ------------------------------------------------------------------------------------------------ calibration
+def calibration_from_counts(bins, conf_sum, sums, class_names: Optional[Sequence[str]] = None) -> Dict[str, object]:
+    """The calibration scores behind the counts of ccdm_segcalib, in float64 numpy (no GPU):
+      bins      [C,M,2] by (predicted class, confidence bin): {pixels, correct pixels};
+      conf_sum  [C,M]   by (predicted class, confidence bin): the sum of the confidence (the renormalised probability of the
+                        predicted class);
+      sums      [3]     {sum of -log q_t, sum of the Brier score, sum of q_t} over the counted pixels.
+    Returns a dict of plain Python values (JSON as it stands):
+      pixels, accuracy, mean_confidence, nll, brier, mean_true_class_probability    totals and means over the counted pixels;
+      ece       sum over the bins b of n_b / n * |acc_b - conf_b| (top label, the class axis summed out);  mce: the largest
+                |acc_b - conf_b| of a non-empty bin;
+      reliability            {"count", "accuracy", "confidence"}, one entry per bin, accuracy / confidence None in an empty bin;
+      ece_per_class          the same ECE over the pixels predicted as class p (a list, or a dict keyed by class_names); None for
+                             a class never predicted;
+      auroc_error_detection  the confidence as the score that separates correct from wrong pixels: P(conf of a correct pixel >
+                             conf of a wrong one) + P(same bin) / 2 from the [M,2] histogram, exact for the binned score; None
+                             when there is no correct or no wrong pixel;
+      bins      M.
+    Without counted pixels every score is None."""
+    bins = np.asarray(bins, dtype=np.float64)
+    conf_sum = np.asarray(conf_sum, dtype=np.float64)
+    sums = np.asarray(sums, dtype=np.float64).reshape(-1)
+    if bins.ndim != 3 or bins.shape[2] != 2 or conf_sum.shape != bins.shape[:2] or sums.shape != (3,):
+        raise ValueError(f"expected bins [C,M,2], conf_sum [C,M], sums [3], got {bins.shape}, {conf_sum.shape}, {sums.shape}")
+    C, M = bins.shape[:2]
+    if class_names is not None and len(class_names) != C:
+        raise ValueError(f"class_names: {len(class_names)} names for {C} classes")
+
+    def ece_mce(count, right, csum):
+        """(ece, mce, accuracy per bin, confidence per bin) of one [M] histogram with at least one pixel"""
+        acc = [right[b] / count[b] if count[b] else None for b in range(M)]
+        conf = [csum[b] / count[b] if count[b] else None for b in range(M)]
+        gaps = [abs(acc[b] - conf[b]) for b in range(M) if count[b]]
+        ece = sum(count[b] / count.sum() * abs(acc[b] - conf[b]) for b in range(M) if count[b])
+        return float(ece), float(max(gaps)), acc, conf
+
+    count, right, csum = bins[:, :, 0].sum(0), bins[:, :, 1].sum(0), conf_sum.sum(0)
+    n = count.sum()
+    res: Dict[str, object] = {"pixels": int(n), "bins": int(M)}
+    per_class = [ece_mce(bins[p, :, 0], bins[p, :, 1], conf_sum[p])[0] if bins[p, :, 0].sum() else None for p in range(C)]
+    res["ece_per_class"] = per_class if class_names is None else dict(zip(class_names, per_class))
+    if n == 0:
+        res.update(accuracy=None, mean_confidence=None, ece=None, mce=None, nll=None, brier=None, mean_true_class_probability=None,
+                   auroc_error_detection=None,
+                   reliability={"count": [0] * M, "accuracy": [None] * M, "confidence": [None] * M})
+        return res
+    ece, mce, acc, conf = ece_mce(count, right, csum)
+    wrong = count - right
+    n_right, n_wrong = right.sum(), wrong.sum()
+    auroc = None
+    if n_right and n_wrong:
+        below = np.concatenate([[0.0], np.cumsum(wrong)[:-1]])          # wrong pixels in the lower bins
+        auroc = float((right * (below + 0.5 * wrong)).sum() / (n_right * n_wrong))
+    res.update(accuracy=float(n_right / n), mean_confidence=float(csum.sum() / n), ece=ece, mce=mce, nll=float(sums[0] / n),
+               brier=float(sums[1] / n), mean_true_class_probability=float(sums[2] / n), auroc_error_detection=auroc,
+               reliability={"count": [int(c) for c in count], "accuracy": [None if a is None else float(a) for a in acc],
+                            "confidence": [None if c is None else float(c) for c in conf]})
+    return res
+
+
+class SegmentationCalibration:
+    """Calibration of a segmentation prediction against the labels (beyond the reference, whose scores are all hard): over the
+    pixels SegmentationConfusion counts, with the class it counts, the confidence is the probability of that class renormalised
+    over the C = K - 1 scored channels; one HIP kernel (ccdm_segcalib) upsamples, classifies, bins and sums without a
+    full-resolution probability tensor.  `bins` equal-width confidence bins, 2..64.
+      bins_count  int64 [C,bins,2] by (predicted class, bin): {pixels, correct pixels}, accumulated on the device;
+      conf_sum    float64 [C,bins], sums float64 [3] ({-log q_t, Brier, q_t}): per update from the device, added on the host.
+    update(prediction, labels) takes what SegmentationConfusion.update takes; a one-hot or class map has confidence 1 wherever
+    the upsampled map is not mixed (class_map_updates counts such updates).  result() is calibration_from_counts."""
+
+    def __init__(self, num_classes: int, device=None, bins: int = 15):
+        if not 2 <= int(num_classes) <= 32:
+            raise ValueError(f"num_classes: {num_classes} (the kernel takes 2..32 channels, the last one the ignore class)")
+        if not 2 <= int(bins) <= 64:
+            raise ValueError(f"bins: {bins} (the kernel takes 2..64 confidence bins)")
+        self.num_classes, self.bins = int(num_classes), int(bins)
+        self.C = self.num_classes - 1
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        if self.device.type != "cuda":
+            raise hip.CcdmHipError("SegmentationCalibration runs on the GPU (no CPU path)")
+        self._bins = torch.zeros((self.C, self.bins, 2), dtype=torch.int64, device=self.device)
+        self.conf_sum = torch.zeros((self.C, self.bins), dtype=torch.float64)
+        self.sums = torch.zeros(3, dtype=torch.float64)
+        self.class_map_updates = 0
+        self._ws: Optional[torch.Tensor] = None
+
+    @property
+    def bins_count(self) -> torch.Tensor:
+        return self._bins.cpu()
+
+    @torch.no_grad()
+    def update(self, prediction: torch.Tensor, labels: torch.Tensor) -> None:
+        if labels.ndim != 3 or labels.shape[0] != prediction.shape[0]:
+            raise ValueError(f"labels: expected [B,H,W] with B = {prediction.shape[0]}, got {tuple(labels.shape)}")
+        probs, ps, cls, h, w = prediction_form(prediction, self.num_classes, self.device)
+        lab = _labels_u8(labels, self.device)
+        B, H, W = (int(s) for s in lab.shape)
+        self.class_map_updates += int(cls is not None)
+        if B == 0:
+            return
+        lib = hip.load()
+        need = int(lib.ccdm_segcalib_workspace_bytes(B, H, W, self.num_classes, self.bins))
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        out = torch.empty(self.C * self.bins + 3, dtype=torch.float64, device=self.device)      # conf_sum, then sums
+        hip.check(lib.ccdm_segcalib(probs.data_ptr() if probs is not None else None, ps, cls.data_ptr() if cls is not None else None,
+                                    lab.data_ptr(), B, h, w, H, W, self.num_classes, self.bins, self._bins.data_ptr(), out.data_ptr(),
+                                    out.data_ptr() + 8 * self.C * self.bins, self._ws.data_ptr(), need,
+                                    torch.cuda.current_stream(self.device).cuda_stream), "segcalib")
+        out = out.cpu()
+        self.conf_sum += out[:-3].reshape(self.C, self.bins)
+        self.sums += out[-3:]
+
+    def result(self, class_names: Optional[Sequence[str]] = None) -> Dict[str, object]:
+        return calibration_from_counts(self.bins_count.numpy(), self.conf_sum.numpy(), self.sums.numpy(), class_names)
 
 
 # ------------------------------------------------------------------------------------------------ prediction export
@@ -475,6 +601,11 @@ def eval_segmentation(params: dict, dataset=None, device=None, model=None, synth
     keyed by the written submit/<n>_id.png paths when save_predictions is on, else by the image number.
     `evaluation.cityscapes_script_instances` (default off): the instance-weighted scores (iIoU) too, from the dataset's instance
     images; needs `resolution: original` (resized labels have no instance image).
+    `evaluation.calibration` (default off): also score how well the probabilities are calibrated (SegmentationCalibration, one
+    more HIP launch pair per batch on the tensor and labels the confusion matrices get; `evaluation.calibration_bins`, default
+    15).  The result then holds "calibration" (calibration_from_counts), also written to <output_path>/calibration.json.  A
+    one-hot prediction (`step_T_sample: majority` with one evaluation) is scored too: its confidence is 1 wherever the
+    upsampled map is not mixed, which the log says.
     `model`: a ready DenoisingModel-like callable (tests inject one); default: built from `params`."""
     from . import evaluation as E
     world = int(os.environ.get("WORLD_SIZE", "1") or 1)
@@ -516,6 +647,7 @@ def eval_segmentation(params: dict, dataset=None, device=None, model=None, synth
     if script:
         from .cityscapes_scores import CityscapesScores
         scores = CityscapesScores(num_classes, device)
+    calib = SegmentationCalibration(num_classes, device, int(section.get("calibration_bins", 15))) if section.get("calibration", False) else None
     n_img = 0
     for image, labels, labels_orig, *rest in loader:
         image = image.to(device)
@@ -524,6 +656,8 @@ def eval_segmentation(params: dict, dataset=None, device=None, model=None, synth
         target = labels_orig if resolution == "original" else labels.argmax(dim=1)
         target = target.to(device)
         conf.update(prediction, target)
+        if calib is not None:
+            calib.update(prediction, target)
         if writer is not None:
             writer.write(prediction, target, tuple(target.shape[1:]))
         if scores is not None:
@@ -550,6 +684,19 @@ def eval_segmentation(params: dict, dataset=None, device=None, model=None, synth
         LOGGER.info("Cityscapes script: IoU classes %.4f  iIoU classes %.4f  IoU categories %.4f  iIoU categories %.4f (%s)",
                     *(res["cs_script"][k] for k in ("averageScoreClasses", "averageScoreInstClasses", "averageScoreCategories",
                                                     "averageScoreInstCategories")), os.path.join(out_dir, "cs_script_results.json"))
+    if calib is not None:
+        import json
+        res["calibration"] = cal = calib.result(names)
+        out_dir = E.expanduservars(params["output_path"])
+        os.makedirs(out_dir, exist_ok=True)
+        with open(os.path.join(out_dir, "calibration.json"), "w") as f:
+            json.dump(cal, f, indent=2, sort_keys=True)
+        if calib.class_map_updates:
+            LOGGER.info("calibration: the prediction is a one-hot map (confidence 1 wherever the upsampled map is not mixed): "
+                        "the scores below are degenerate")
+        LOGGER.info("calibration over %d pixels, %d bins: ECE %s  NLL %s  Brier %s  AUROC (error detection) %s (%s)", cal["pixels"],
+                    cal["bins"], *("n/a" if cal[k] is None else f"{cal[k]:.4f}" for k in ("ece", "nll", "brier", "auroc_error_detection")),
+                    os.path.join(out_dir, "calibration.json"))
     LOGGER.info("mIoU %.4f  soft mIoU %.4f over %d images (resolution %s, %d evaluation(s), %s)", res["mIoU"], res["mIoU_soft"], n_img,
                 resolution, evaluations, vote)
     return res

@@ -394,6 +394,31 @@ int ccdm_csscore_ids(const uint8_t* pred_ids, int B, int H, int W, const uint8_t
                      int64_t* conf, int64_t* per_image, int32_t* instances, int32_t* unknown, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Calibration scores of a segmentation prediction, device part (beyond the reference, which scores hard classes only): the
+ * counts behind ECE / MCE, NLL, the Brier score and the reliability diagram, in one pass over the output pixels of [B,H,W],
+ * without a full-resolution probability tensor.  The prediction (probs XOR cls), the labels, the counted pixels (label < C,
+ * C = K-1), the bilinear sample v_c and the argmax `pred` are those of ccdm_seg_confusion above, through the same device code:
+ * the class binned here is the class counted there, bit for bit.  Per counted pixel with label t:
+ *   s = v_0 + v_1 + ... + v_{C-1}, ascending in fp32;  q_c = v_c / s (IEEE division);  s == 0 (all mass on the ignore channel):
+ *   q_c = 1/C for every c (pred is 0 there);
+ *   conf = q_pred;  correct = (pred == t);  bin = min((int)(conf * M), M-1) in fp32;
+ *   nll = -log(max((double)q_t, 1e-12));  brier = sum over c of (q_c - [c == t])^2, ascending in fp32.
+ * Outputs (device):
+ *   bins      int64 [C][M][2], by (pred, bin): {pixels, correct pixels}.  ACCUMULATED across calls;
+ *   conf_sum  fp64 [C][M], by (pred, bin): sum of conf.  OVERWRITTEN per call;
+ *   sums      fp64 [3]: {sum of nll, sum of brier, sum of q_t}.  OVERWRITTEN per call.
+ * K in [2,32], M in [2,64].  The workspace (device, ccdm_segcalib_workspace_bytes(B,H,W,K,M) bytes) holds exact fixed-point
+ * confidence sums (conf is a multiple of 2^-28) and per-block fp64 partial sums; integer atomics only, no float atomics: two
+ * identical calls return bit-identical outputs.  B = 0 returns 0 without a launch and leaves all three outputs as they are.
+ * (Named without the ccdm_seg_ prefix: the evaluator's test pins the set of ccdm_seg_* symbols.)
+ * ------------------------------------------------------------------------------------------------- */
+size_t ccdm_segcalib_workspace_bytes(int B, int H, int W, int K, int M);
+int ccdm_segcalib(const float* probs /*dev or NULL*/, int64_t pixel_stride, const uint8_t* cls /*dev [B,h,w] or NULL*/,
+                  const uint8_t* labels /*dev [B,H,W]*/, int B, int h, int w, int H, int W, int K, int M,
+                  int64_t* bins /*dev [K-1][M][2]*/, double* conf_sum /*dev [K-1][M]*/, double* sums /*dev [3]*/, void* workspace,
+                  size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Multi-sample prediction (DenoisingModel.predict_multiple): S sampling passes of the same B images folded into one
  * mean map, a per-pixel vote and two uncertainty maps.  The reference's Evaluator.predict_multiple
  * (evaluation/eval_cdm.py:176-193) accumulates `total += prediction_i * (1 / S)` on the host; these read a pass
