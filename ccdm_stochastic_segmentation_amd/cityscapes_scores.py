@@ -18,7 +18,8 @@ import numpy as np
 import torch
 
 from . import hip
-from .segmentation import CITYSCAPES_LABELS, NUM_CLASSES, TRAIN_ID_TO_ID, prediction_form
+from .segmentation import (CITYSCAPES_LABELS, NUM_CLASSES, TRAIN_ID_TO_ID, _check_num_classes, _cuda_device, _labels_u8,
+                           prediction_args, prediction_form)
 
 # ------------------------------------------------------------------------------------------------ label definition
 # The category column of the public definition, one per row of segmentation.CITYSCAPES_LABELS, in the order the categories first
@@ -183,18 +184,14 @@ class CityscapesScores:
     before that update."""
 
     def __init__(self, num_classes: int = NUM_CLASSES, device=None, id_table=None):
-        if not 2 <= int(num_classes) <= 32:
-            raise ValueError(f"num_classes: {num_classes} (the kernel takes 2..32 channels, the last one the ignore class)")
-        self.num_classes = int(num_classes)
+        self.num_classes = _check_num_classes(num_classes)
         if id_table is None:
             if self.num_classes != NUM_CLASSES:
                 raise ValueError(f"{num_classes} classes: the default id table is Cityscapes' ({NUM_CLASSES} classes), pass id_table")
             id_table = TRAIN_ID_TO_ID
         if len(id_table) != self.num_classes:
             raise ValueError(f"id_table: expected {self.num_classes} entries, got {len(id_table)}")
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if self.device.type != "cuda":
-            raise hip.CcdmHipError("CityscapesScores runs on the GPU (no CPU path)")
+        self.device = _cuda_device(device, "CityscapesScores")
         self.label_names, ign, cat, has, _ = label_tables()
         self.L = len(self.label_names)
         self._tables = [torch.as_tensor(np.asarray(t, np.uint8)).to(self.device) for t in (id_table, ign, cat, has)]
@@ -211,10 +208,7 @@ class CityscapesScores:
     def _targets(self, gt_ids, inst_ids, B):
         if gt_ids.ndim != 3 or gt_ids.shape[0] != B:
             raise ValueError(f"gt_ids: expected [B,H,W] with B = {B}, got {tuple(gt_ids.shape)}")
-        gt = torch.as_tensor(gt_ids).to(self.device)
-        if gt.dtype != torch.uint8:         # anything outside [0, 255] is outside the label definition either way: 255 stands for it
-            gt = torch.where((gt < 0) | (gt > 255), torch.full_like(gt, 255), gt).to(torch.uint8)
-        gt = gt.contiguous()
+        gt = _labels_u8(torch.as_tensor(gt_ids), self.device)      # outside [0, 255] is outside the label definition: 255 stands for it
         inst = None
         if inst_ids is not None:
             inst = torch.as_tensor(inst_ids)
@@ -265,8 +259,7 @@ class CityscapesScores:
         H, W = int(gt.shape[1]), int(gt.shape[2])
         conf, per_image, instances, unknown = self._outputs(B, inst is not None)
         idt, ign, cat, has = self._tables
-        hip.check(hip.load().ccdm_csscore(probs.data_ptr() if probs is not None else None, ps, cls.data_ptr() if cls is not None else None,
-                                          B, h, w, H, W, self.num_classes, idt.data_ptr(), gt.data_ptr(),
+        hip.check(hip.load().ccdm_csscore(*prediction_args(probs, ps, cls), B, h, w, H, W, self.num_classes, idt.data_ptr(), gt.data_ptr(),
                                           inst.data_ptr() if inst is not None else None, self.L, ign.data_ptr(), cat.data_ptr(),
                                           has.data_ptr(), INSTANCE_BASE, INSTANCE_SLOTS, conf.data_ptr(), per_image.data_ptr(),
                                           instances.data_ptr() if instances is not None else None, unknown.data_ptr(),
@@ -280,10 +273,7 @@ class CityscapesScores:
         gt, inst = self._targets(gt_ids, inst_ids, B)
         if tuple(pred.shape) != tuple(gt.shape):
             raise ValueError(f"pred_ids: expected {tuple(gt.shape)}, got {tuple(pred.shape)}")
-        pred = pred.to(self.device)
-        if pred.dtype != torch.uint8:
-            pred = torch.where((pred < 0) | (pred > 255), torch.full_like(pred, 255), pred).to(torch.uint8)
-        pred = pred.contiguous()
+        pred = _labels_u8(pred, self.device)
         H, W = int(gt.shape[1]), int(gt.shape[2])
         conf, per_image, instances, unknown = self._outputs(B, inst is not None)
         _, ign, cat, has = self._tables

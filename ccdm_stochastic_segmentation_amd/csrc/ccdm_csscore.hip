@@ -1,9 +1,8 @@
 // Cityscapes script scores, device part: the integer counts behind the official pixel-level evaluation script's result file
 // (the reference's evaluation/cs_eval.py: evaluatePair), in one pass over the output pixels of [B,H,W], without a
-// full-resolution probability tensor and without an id image.  The walk is k_seg_confusion's and k_seg_export's
-// (ccdm_seg_common.h): the same tiles, source coordinates, interpolated row pair and argmax, so the class counted here is the
-// class counted there and written as a PNG, bit for bit.  A pixel ends as its predicted label id (id_table[class]) and goes,
-// together with the ground-truth label id and the ground-truth instance id, into three sets of counts:
+// full-resolution probability tensor and without an id image.  The walk is ccdm_seg_common.h's.  A pixel ends as its predicted
+// label id (id_table[class]) and goes, together with the ground-truth label id and the ground-truth instance id, into three
+// sets of counts:
 //   conf       [L][L] label-id confusion matrix, every pixel counted (ignored ground truth included);
 //   per_image  four pixel counts per image;
 //   instances  per ground-truth instance its size, its true positives on class and on category level.
@@ -14,9 +13,9 @@
 //   per_image  ballots and scalar bit counts per row (wave-uniform counters), four global adds per (wave, tile);
 //   instances  instances are large connected regions, so a lane walking down its column stays inside one instance for many
 //              rows: each lane counts in registers while its key (the instance's slot) stays the same.  The lanes whose key
-//              changes, and every lane at the end of a tile, are grouped by equal key with a ballot and readlane loop (as
-//              seg_flush groups by target), summed over the wave by DPP, and one instruction of three lanes adds the group's
-//              three counts: one global atomic per (wave, key, run), not one per pixel.
+//              changes, and every lane at the end of a tile, are grouped by equal key (seg_for_each_group, as seg_flush groups
+//              by target), summed over the wave by DPP, and one instruction of three lanes adds the group's three counts: one
+//              global atomic per (wave, key, run), not one per pixel.
 //
 // Loads.  Ground truth is 1 byte and the instance id 2 bytes per pixel.  When W % 4 == 0 every row starts at a multiple of 4
 // bytes: a lane then loads, once per 4 rows, the dword (ids) and the 8 bytes (instance ids) of its quad's 4 columns in row
@@ -26,32 +25,9 @@
 
 namespace ccdm {
 
-constexpr int CSS_MAX_K = 32;
+constexpr int CSS_MAX_K = SEG_MAX_K;
 constexpr int CSS_MAX_L = CCDM_CSSCORE_MAX_LABELS;
 
-template <int CTRL>
-__device__ __forceinline__ int css_dpp(int x) {
-    return __builtin_amdgcn_update_dpp(0, x, CTRL, 0xF, 0xF, false);
-}
-// lane Q of the caller's quad, in every lane of the quad (all lanes must be active)
-template <int Q>
-__device__ __forceinline__ uint32_t css_quad(uint32_t x) {
-    return (uint32_t)css_dpp<Q * 0x55>((int)x);
-}
-// lane `s` (wave-uniform, 0..3) of the caller's quad
-__device__ __forceinline__ uint32_t css_quad_sel(uint32_t x, int s) {
-    const uint32_t a = css_quad<0>(x), b = css_quad<1>(x), c = css_quad<2>(x), d = css_quad<3>(x);
-    return s == 0 ? a : s == 1 ? b : s == 2 ? c : d;
-}
-// Integer sum over the 64 lanes (all must be active); every lane returns it.
-__device__ __forceinline__ int css_wave_sum(int x) {
-    x += css_dpp<0xB1>(x);       // quad_perm [1,0,3,2]
-    x += css_dpp<0x4E>(x);       // quad_perm [2,3,0,1]
-    x += css_dpp<0x141>(x);      // row_half_mirror
-    x += css_dpp<0x140>(x);      // row_mirror
-    return __builtin_amdgcn_readlane(x, 0) + __builtin_amdgcn_readlane(x, 16) + __builtin_amdgcn_readlane(x, 32) +
-           __builtin_amdgcn_readlane(x, 48);
-}
 __device__ __forceinline__ int css_count(bool p) { return __popcll(__ballot(p)); }
 
 // The label tables, one word per label id: bit 0 ignore_in_eval, bit 1 has_instances, bits 8.. category.
@@ -68,19 +44,15 @@ struct CssRun {
 
 // Adds the runs of the lanes with `f` set to instances[key][0..2], grouped by key, and closes them.  Wave-uniform call.
 __device__ __forceinline__ void css_flush(bool f, CssRun& r, int32_t* __restrict__ instances, int lane) {
-    unsigned long long rest = __ballot(f);
-    while (rest) {
-        const int g = __builtin_amdgcn_readlane(r.key, __ffsll((long long)rest) - 1);
-        const bool in_g = f && r.key == g;
+    seg_for_each_group(f, r.key, [&](int g, bool in_g) {
         // a lane holds at most SEG_ROWS = 16 pixels: the wave sums stay below 2^11
-        const int s0 = css_wave_sum(in_g ? (r.n | r.tp << 16) : 0);
-        const int s1 = css_wave_sum(in_g ? r.cat : 0);
+        const int s0 = seg_wave_sum(in_g ? (r.n | r.tp << 16) : 0);
+        const int s1 = seg_wave_sum(in_g ? r.cat : 0);
         if (lane < 3) {
             const int v = lane == 0 ? (s0 & 0xFFFF) : lane == 1 ? (s0 >> 16) : s1;
             if (v) atomicAdd(&instances[(size_t)g * 3 + lane], v);
         }
-        rest &= ~__ballot(in_g);
-    }
+    });
     if (f) r = CssRun{-1, 0, 0, 0};
 }
 
@@ -163,10 +135,10 @@ __device__ __forceinline__ void css_load(CssLoader& ld, bool vec, bool with_inst
                 }
             }
         }
-        gt = (int)((css_quad_sel(ld.g4, slot) >> (8 * q)) & 0xFFu);
+        gt = (int)((seg_quad_sel(ld.g4, slot) >> (8 * q)) & 0xFFu);
         iid = 0;
         if (with_inst) {
-            const uint32_t lo = css_quad_sel(ld.i4[0], slot), hi = css_quad_sel(ld.i4[1], slot);
+            const uint32_t lo = seg_quad_sel(ld.i4[0], slot), hi = seg_quad_sel(ld.i4[1], slot);
             iid = (int)(((q & 2 ? hi : lo) >> (16 * (q & 1))) & 0xFFFFu);
         }
     } else {
@@ -209,37 +181,33 @@ __device__ __forceinline__ void css_block_end(CssShared& sh, const CssCounts& c,
 }
 
 // The fused form.  SRC: 0 fp32 probabilities, 1 class map.  IDENT: (H, W) == (h, w).  C = K - 1: the channels the argmax runs over.
+// The fields of SegSrc arrive as loose arguments: with the struct as one argument two of the scalar-load instantiations (KP 20 and 32)
+// take 9 to 20 more VGPRs and lose a wave per SIMD.
 template <int KP, int SRC, bool V4, bool IDENT>
 __global__ __launch_bounds__(256) void k_csscore(const float* __restrict__ probs, long long ps, const uint8_t* __restrict__ cls, int B, int h,
-                                                 int w, int H, int W, int C, int K, float sh_, float sw, const uint8_t* __restrict__ id_table,
+                                                 int w, int H, int W, int C, float sh_, float sw, int K, const uint8_t* __restrict__ id_table,
                                                  const uint8_t* __restrict__ ign, const uint8_t* __restrict__ cat,
                                                  const uint8_t* __restrict__ has, CssArgs a) {
+    const SegSrc s{probs, ps, cls, B, h, w, H, W, C, sh_, sw};
     __shared__ CssShared sh;
     css_init(sh, a, ign, cat, has, id_table, K);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int q = lane & 3;
+    const int lane = threadIdx.x & 63, q = lane & 3;
     const bool vec = (W & 3) == 0, with_inst = a.inst_ids != nullptr;
-    const int tiles_x = (W + SEG_TW - 1) / SEG_TW, tiles_y = (H + SEG_TH - 1) / SEG_TH;
-    const long long ntiles = (long long)B * tiles_x * tiles_y;
     CssCounts c = {0, 0, 0, 0, 0, 0};
     CssRun run = {-1, 0, 0, 0};
     CssLoader ld = {0, {0, 0}};
 
-    for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int tx = (int)(tile % tiles_x), ty = (int)((tile / tiles_x) % tiles_y), b = (int)(tile / ((long long)tiles_x * tiles_y));
-        const int x = tx * SEG_TW + lane;
-        const bool in_x = x < W;
-        int ix0, ix1;
-        float lw0, lw1;
-        seg_lane_coord<IDENT>(x, in_x, sw, w, ix0, ix1, lw0, lw1);
+    for (SegTiles tiles(B, H, W); tiles.more(); tiles.advance()) {
+        const SegTile tile = tiles.get();
+        const int b = tile.b, x = tile.x, y_begin = tile.y_begin, y_end = tile.y_end;
+        const bool in_x = tile.in_x;
+        const SegLane<IDENT> ln(s, tile);
         float A[KP], Bv[KP];
         int yA = -1, yB = -1;
-        const int y_begin = ty * SEG_TH + wave * SEG_ROWS;
-        const int y_end = min(y_begin + SEG_ROWS, H);
         for (int y = y_begin; y < y_end; ++y) {
             float h0, h1;
-            seg_step<KP, SRC, V4, IDENT>(A, Bv, yA, yB, h0, h1, probs, cls, b, y, h, w, sh_, ix0, ix1, lw0, lw1, ps, C);
-            const int pred = seg_argmax<KP, IDENT>(A, Bv, h0, h1, C);
+            seg_step<KP, SRC, V4, IDENT>(A, Bv, yA, yB, h0, h1, s, ln, b, y);
+            const int pred = seg_argmax<KP, IDENT>(A, Bv, h0, h1, s.C);
             int gt, iid;
             css_load(ld, vec, with_inst, a.gt_ids, a.inst_ids, b, y, y_begin, y_end, x, in_x, H, W, q, gt, iid);
             css_pixel(in_x, (int)sh.pred_id[pred], gt, iid, b, with_inst, a, sh, c, run, lane);
@@ -254,21 +222,16 @@ __global__ __launch_bounds__(256) void k_csscore_ids(const uint8_t* __restrict__
                                                      const uint8_t* __restrict__ cat, const uint8_t* __restrict__ has, CssArgs a) {
     __shared__ CssShared sh;
     css_init(sh, a, ign, cat, has, nullptr, 0);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int q = lane & 3;
+    const int lane = threadIdx.x & 63, q = lane & 3;
     const bool vec = (W & 3) == 0, with_inst = a.inst_ids != nullptr;
-    const int tiles_x = (W + SEG_TW - 1) / SEG_TW, tiles_y = (H + SEG_TH - 1) / SEG_TH;
-    const long long ntiles = (long long)B * tiles_x * tiles_y;
     CssCounts c = {0, 0, 0, 0, 0, 0};
     CssRun run = {-1, 0, 0, 0};
     CssLoader ld = {0, {0, 0}}, lp = {0, {0, 0}};
 
-    for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int tx = (int)(tile % tiles_x), ty = (int)((tile / tiles_x) % tiles_y), b = (int)(tile / ((long long)tiles_x * tiles_y));
-        const int x = tx * SEG_TW + lane;
-        const bool in_x = x < W;
-        const int y_begin = ty * SEG_TH + wave * SEG_ROWS;
-        const int y_end = min(y_begin + SEG_ROWS, H);
+    for (SegTiles tiles(B, H, W); tiles.more(); tiles.advance()) {
+        const SegTile tile = tiles.get();
+        const int b = tile.b, x = tile.x, y_begin = tile.y_begin, y_end = tile.y_end;
+        const bool in_x = tile.in_x;
         for (int y = y_begin; y < y_end; ++y) {
             int gt, iid, pid, none;
             css_load(ld, vec, with_inst, a.gt_ids, a.inst_ids, b, y, y_begin, y_end, x, in_x, H, W, q, gt, iid);
@@ -280,33 +243,11 @@ __global__ __launch_bounds__(256) void k_csscore_ids(const uint8_t* __restrict__
     css_block_end(sh, c, a, lane);
 }
 
-template <int KP, int SRC, bool V4>
-static void css_launch(bool ident, int grid, hipStream_t st, const float* probs, long long ps, const uint8_t* cls, int B, int h, int w, int H,
-                       int W, int C, int K, float sh, float sw, const uint8_t* idt, const uint8_t* ign, const uint8_t* cat, const uint8_t* has,
-                       const CssArgs& a) {
-    if (ident)
-        hipLaunchKernelGGL((k_csscore<KP, SRC, V4, true>), dim3(grid), dim3(256), 0, st, probs, ps, cls, B, h, w, H, W, C, K, sh, sw, idt, ign,
-                           cat, has, a);
-    else
-        hipLaunchKernelGGL((k_csscore<KP, SRC, V4, false>), dim3(grid), dim3(256), 0, st, probs, ps, cls, B, h, w, H, W, C, K, sh, sw, idt, ign,
-                           cat, has, a);
-}
-
-template <int KP>
-static void css_dispatch(bool ident, int grid, hipStream_t st, const float* probs, long long ps, const uint8_t* cls, int B, int h, int w, int H,
-                         int W, int C, int K, float sh, float sw, const uint8_t* idt, const uint8_t* ign, const uint8_t* cat, const uint8_t* has,
-                         const CssArgs& a) {
-    const bool v4 = probs && ps % 4 == 0 && (reinterpret_cast<uintptr_t>(probs) & 15) == 0;
-    if (cls) css_launch<KP, 1, false>(ident, grid, st, probs, ps, cls, B, h, w, H, W, C, K, sh, sw, idt, ign, cat, has, a);
-    else if (v4) css_launch<KP, 0, true>(ident, grid, st, probs, ps, cls, B, h, w, H, W, C, K, sh, sw, idt, ign, cat, has, a);
-    else css_launch<KP, 0, false>(ident, grid, st, probs, ps, cls, B, h, w, H, W, C, K, sh, sw, idt, ign, cat, has, a);
-}
-
 // The checks and the clearing both forms share; returns 1 when there is nothing to launch.
 static int css_prepare(const char* who, const uint8_t* gt_ids, const uint16_t* inst_ids, int B, int H, int W, int L, const uint8_t* ign,
                        const uint8_t* cat, const uint8_t* has, int inst_base, int NI, int64_t* conf, int64_t* per_image, int32_t* instances,
                        int32_t* unknown, hipStream_t st, CssArgs& a) {
-    CCDM_REQUIRE(B >= 0 && H > 0 && W > 0, "%s: bad shape B=%d H=%d W=%d", who, B, H, W);
+    if (const int rc = seg_check_out(who, B, H, W)) return rc;
     CCDM_REQUIRE(L >= 1 && L <= CSS_MAX_L, "%s: L=%d outside [1,%d]", who, L, CSS_MAX_L);
     CCDM_REQUIRE(ign && cat && has, "%s: null label table", who);
     if (B == 0) return 1;
@@ -315,9 +256,7 @@ static int css_prepare(const char* who, const uint8_t* gt_ids, const uint16_t* i
                  "%s: instance ids need a table (inst_base=%d NI=%d B=%d)", who, inst_base, NI, B);
     CCDM_REQUIRE((W & 3) != 0 || ((reinterpret_cast<uintptr_t>(gt_ids) & 3) == 0 && (reinterpret_cast<uintptr_t>(inst_ids) & 7) == 0),
                  "%s: gt_ids must be 4-byte and inst_ids 8-byte aligned when W %% 4 == 0", who);
-    // per-block int32 counts: a block covers at most ceil(tiles / SEG_MAX_BLOCKS) tiles of SEG_TW x SEG_TH pixels
-    const long long tiles = (long long)B * cdiv(H, SEG_TH) * cdiv(W, SEG_TW);
-    CCDM_REQUIRE((tiles + SEG_MAX_BLOCKS - 1) / SEG_MAX_BLOCKS * SEG_TW * SEG_TH < (1LL << 31), "%s: too many pixels", who);
+    if (const int rc = seg_check_block_counts(who, B, H, W)) return rc;
     a = CssArgs{gt_ids, inst_ids, L, inst_base, NI, reinterpret_cast<unsigned long long*>(conf), reinterpret_cast<unsigned long long*>(per_image),
                 instances, unknown};
     if (hipMemsetAsync(per_image, 0, (size_t)B * 4 * sizeof(int64_t), st) != hipSuccess ||
@@ -334,25 +273,18 @@ extern "C" int ccdm_csscore(const float* probs, int64_t pixel_stride, const uint
                             const uint8_t* category, const uint8_t* has_instances, int inst_base, int NI, int64_t* conf, int64_t* per_image,
                             int32_t* instances, int32_t* unknown, void* stream) {
     using namespace ccdm;
-    CCDM_REQUIRE((probs != nullptr) != (cls != nullptr), "csscore: pass exactly one of probs and cls");
-    CCDM_REQUIRE(K >= 2 && K <= CSS_MAX_K, "csscore: K=%d outside [2,32]", K);
-    CCDM_REQUIRE(h > 0 && w > 0, "csscore: bad shape h=%d w=%d", h, w);
-    CCDM_REQUIRE(!probs || pixel_stride >= K, "csscore: pixel_stride=%lld < K=%d", (long long)pixel_stride, K);
+    if (const int rc = seg_check_src("csscore", probs, pixel_stride, cls, h, w, K)) return rc;
     CCDM_REQUIRE(id_table, "csscore: null id_table");
     hipStream_t st = (hipStream_t)stream;
     CssArgs a;
     const int rc = css_prepare("csscore", gt_ids, inst_ids, B, H, W, L, ignore_in_eval, category, has_instances, inst_base, NI, conf, per_image,
                                instances, unknown, st, a);
     if (rc != 0) return rc < 0 ? rc : 0;
-    const int C = K - 1;
-    const int grid = seg_blocks(B, H, W);
-    const bool ident = H == h && W == w;
-    const float sh = (float)h / (float)H, sw = (float)w / (float)W;     // ATen's area_pixel_compute_scale, no scale factor given
-    // the ladder of ccdm_seg_confusion, on the scored channels
-    if (C <= 2) css_dispatch<2>(ident, grid, st, probs, pixel_stride, cls, B, h, w, H, W, C, K, sh, sw, id_table, ignore_in_eval, category, has_instances, a);
-    else if (C <= 8) css_dispatch<8>(ident, grid, st, probs, pixel_stride, cls, B, h, w, H, W, C, K, sh, sw, id_table, ignore_in_eval, category, has_instances, a);
-    else if (C <= 20) css_dispatch<20>(ident, grid, st, probs, pixel_stride, cls, B, h, w, H, W, C, K, sh, sw, id_table, ignore_in_eval, category, has_instances, a);
-    else css_dispatch<32>(ident, grid, st, probs, pixel_stride, cls, B, h, w, H, W, C, K, sh, sw, id_table, ignore_in_eval, category, has_instances, a);
+    const SegSrc s = seg_src(probs, pixel_stride, cls, B, h, w, H, W, K - 1);
+    seg_dispatch(s, [&](auto kp, auto src, auto v4, auto ident) {
+        hipLaunchKernelGGL((k_csscore<kp(), src(), v4(), ident()>), dim3(seg_blocks(B, H, W)), dim3(256), 0, st, s.probs, s.ps, s.cls, B, h, w, H, W,
+                           s.C, s.sh, s.sw, K, id_table, ignore_in_eval, category, has_instances, a);
+    });
     CCDM_CHECK_LAUNCH("csscore");
     return 0;
 }

@@ -1,6 +1,6 @@
-// Calibration scores of a segmentation prediction, device part: the walk of k_seg_confusion (ccdm_seg_common.h: the same tiles,
-// source coordinates, interpolated row pair and argmax) ending in calibration counts instead of confusion matrices.  Nothing in
-// the reference computes these; the definition below is the contract, tests/test_seg_calibration.py restates it in float64.
+// Calibration scores of a segmentation prediction, device part: the walk of ccdm_seg_common.h ending in calibration counts instead
+// of confusion matrices.  Nothing in the reference computes these; the definition below is the contract,
+// tests/test_seg_calibration.py restates it in float64.
 //
 // Definition.  For every output pixel of [B,H,W] whose label t < C (C = K - 1, the ignore channel dropped: the pixels
 // ccdm_seg_confusion counts):
@@ -35,41 +35,29 @@ constexpr double SEGC_UNFIX = 1.0 / 268435456.0;
 // SRC: 0 fp32 probabilities, 1 class map.  IDENT: (H, W) == (h, w), the value is the source pixel itself.
 // fix: uint64 [C*M] fixed-point confidence sums (cleared by the host); slab: fp64 [gridDim.x][3].
 template <int KP, int SRC, bool V4, bool IDENT>
-__global__ __launch_bounds__(256) void k_seg_calib(const float* __restrict__ probs, long long ps, const uint8_t* __restrict__ cls,
-                                                   const uint8_t* __restrict__ labels, int B, int h, int w, int H, int W, int C, int M,
-                                                   float sh, float sw, unsigned long long* __restrict__ bins,
+__global__ __launch_bounds__(256) void k_seg_calib(SegSrc s, const uint8_t* __restrict__ labels, int M, unsigned long long* __restrict__ bins,
                                                    unsigned long long* __restrict__ fix, double* __restrict__ slab) {
     extern __shared__ unsigned long long segc_lds[];
-    const int CM = C * M;
+    const int C = s.C, CM = C * M;
     unsigned long long* cnt = segc_lds;              // [CM]: pixels | correct pixels << 32
     unsigned long long* cf = segc_lds + CM;          // [CM]: sum of conf * 2^28
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int e = threadIdx.x; e < 2 * CM; e += blockDim.x) segc_lds[e] = 0;
     __syncthreads();
 
-    const int tiles_x = (W + SEG_TW - 1) / SEG_TW, tiles_y = (H + SEG_TH - 1) / SEG_TH;
-    const long long ntiles = (long long)B * tiles_x * tiles_y;
     const float uniform = 1.0f / (float)C, fM = (float)M;
     double s_nll = 0.0, s_brier = 0.0, s_qt = 0.0;
 
-    for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int tx = (int)(tile % tiles_x), ty = (int)((tile / tiles_x) % tiles_y), b = (int)(tile / ((long long)tiles_x * tiles_y));
-        const int x = tx * SEG_TW + lane;
-        const bool in_x = x < W;
-        int ix0, ix1;
-        float lw0, lw1;
-        seg_lane_coord<IDENT>(x, in_x, sw, w, ix0, ix1, lw0, lw1);
+    for (SegTiles tiles(s.B, s.H, s.W); tiles.more(); tiles.advance()) {
+        const SegTile tile = tiles.get();
+        const SegLane<IDENT> ln(s, tile);
+        SegLabels label(labels, s, tile);
         float A[KP], Bv[KP];
         int yA = -1, yB = -1;
-        const int y_begin = ty * SEG_TH + wave * SEG_ROWS;
-        const int y_end = min(y_begin + SEG_ROWS, H);
-        int t_next = (in_x && y_begin < y_end) ? (int)labels[((size_t)b * H + y_begin) * W + x] : 255;
-        for (int y = y_begin; y < y_end; ++y) {
+        for (int y = tile.y_begin; y < tile.y_end; ++y) {
             float h0, h1;
-            seg_step<KP, SRC, V4, IDENT>(A, Bv, yA, yB, h0, h1, probs, cls, b, y, h, w, sh, ix0, ix1, lw0, lw1, ps, C);
-            const int t = t_next;
-            if (y + 1 < y_end && in_x) t_next = labels[((size_t)b * H + y + 1) * W + x];     // one step ahead
-            if (!(in_x && t < C)) continue;              // ignite: (y >= 0) & (y < num_classes)
+            seg_step<KP, SRC, V4, IDENT>(A, Bv, yA, yB, h0, h1, s, ln, tile.b, y);
+            const int t = label.next(y);
+            if (!label.counted(t, C)) continue;
 
             // first pass over the first C channels: interpolate, argmax (ties to the lowest index, as torch.argmax), sum
             int pred = 0;
@@ -144,37 +132,11 @@ __global__ __launch_bounds__(256) void k_segcalib_finish(const unsigned long lon
     if (threadIdx.x < 3) sums[threadIdx.x] = part[threadIdx.x][0];
 }
 
-struct SegcArgs {
-    const float* probs; long long ps; const uint8_t* cls; const uint8_t* labels;
-    int B, h, w, H, W, C, M;
-    float sh, sw;
-    unsigned long long *bins, *fix;
-    double* slab;
-};
-
-template <int KP, int SRC, bool V4>
-static void segc_launch(bool ident, int grid, size_t lds, hipStream_t st, const SegcArgs& a) {
-    if (ident)
-        hipLaunchKernelGGL((k_seg_calib<KP, SRC, V4, true>), dim3(grid), dim3(256), lds, st, a.probs, a.ps, a.cls, a.labels, a.B, a.h, a.w, a.H,
-                           a.W, a.C, a.M, a.sh, a.sw, a.bins, a.fix, a.slab);
-    else
-        hipLaunchKernelGGL((k_seg_calib<KP, SRC, V4, false>), dim3(grid), dim3(256), lds, st, a.probs, a.ps, a.cls, a.labels, a.B, a.h, a.w, a.H,
-                           a.W, a.C, a.M, a.sh, a.sw, a.bins, a.fix, a.slab);
-}
-
-template <int KP>
-static void segc_dispatch(bool ident, int grid, size_t lds, hipStream_t st, const SegcArgs& a) {
-    const bool v4 = a.probs && a.ps % 4 == 0 && (reinterpret_cast<uintptr_t>(a.probs) & 15) == 0;
-    if (a.cls) segc_launch<KP, 1, false>(ident, grid, lds, st, a);
-    else if (v4) segc_launch<KP, 0, true>(ident, grid, lds, st, a);
-    else segc_launch<KP, 0, false>(ident, grid, lds, st, a);
-}
-
 }  // namespace ccdm
 
 extern "C" size_t ccdm_segcalib_workspace_bytes(int B, int H, int W, int K, int M) {
     using namespace ccdm;
-    if (B <= 0 || H <= 0 || W <= 0 || K < 2 || K > 32 || M < 2 || M > SEGC_MAX_BINS) return 0;
+    if (B <= 0 || H <= 0 || W <= 0 || K < 2 || K > SEG_MAX_K || M < 2 || M > SEGC_MAX_BINS) return 0;
     return ((size_t)(K - 1) * M + (size_t)seg_blocks(B, H, W) * 3) * sizeof(double);
 }
 
@@ -182,36 +144,28 @@ extern "C" int ccdm_segcalib(const float* probs, int64_t pixel_stride, const uin
                              int H, int W, int K, int M, int64_t* bins, double* conf_sum, double* sums, void* workspace,
                              size_t workspace_bytes, void* stream) {
     using namespace ccdm;
-    CCDM_REQUIRE((probs != nullptr) != (cls != nullptr), "segcalib: pass exactly one of probs and cls");
+    if (const int rc = seg_check_src("segcalib", probs, pixel_stride, cls, h, w, K)) return rc;
+    if (const int rc = seg_check_out("segcalib", B, H, W)) return rc;
     CCDM_REQUIRE(labels && bins && conf_sum && sums, "segcalib: null pointer");
-    CCDM_REQUIRE(K >= 2 && K <= 32, "segcalib: K=%d outside [2,32]", K);
     CCDM_REQUIRE(M >= 2 && M <= SEGC_MAX_BINS, "segcalib: M=%d outside [2,%d]", M, SEGC_MAX_BINS);
-    CCDM_REQUIRE(B >= 0 && h > 0 && w > 0 && H > 0 && W > 0, "segcalib: bad shape B=%d h=%d w=%d H=%d W=%d", B, h, w, H, W);
-    CCDM_REQUIRE(!probs || pixel_stride >= K, "segcalib: pixel_stride=%lld < K=%d", (long long)pixel_stride, K);
     if (B == 0) return 0;
-    // per-block 32-bit counts: a block covers at most ceil(tiles / SEG_MAX_BLOCKS) tiles of SEG_TW x SEG_TH pixels
-    const long long tiles = (long long)B * cdiv(H, SEG_TH) * cdiv(W, SEG_TW);
-    CCDM_REQUIRE((tiles + SEG_MAX_BLOCKS - 1) / SEG_MAX_BLOCKS * SEG_TW * SEG_TH < (1LL << 31), "segcalib: too many pixels");
+    if (const int rc = seg_check_block_counts("segcalib", B, H, W)) return rc;
     const size_t need = ccdm_segcalib_workspace_bytes(B, H, W, K, M);
     CCDM_REQUIRE(workspace && workspace_bytes >= need, "segcalib: workspace of %zu bytes, %zu needed", workspace_bytes, need);
-    const int C = K - 1, CM = C * M;
-    const int grid = seg_blocks(B, H, W);
+    const int CM = (K - 1) * M, grid = seg_blocks(B, H, W);
     hipStream_t st = (hipStream_t)stream;
-    SegcArgs a{probs, (long long)pixel_stride, cls, labels, B, h, w, H, W, C, M,
-               (float)h / (float)H, (float)w / (float)W,      // ATen's area_pixel_compute_scale, no scale factor given
-               reinterpret_cast<unsigned long long*>(bins), static_cast<unsigned long long*>(workspace), nullptr};
-    a.slab = reinterpret_cast<double*>(a.fix + CM);
-    CCDM_REQUIRE(hipMemsetAsync(a.fix, 0, (size_t)CM * sizeof(unsigned long long), st) == hipSuccess, "segcalib: clearing the workspace failed");
-    const bool ident = H == h && W == w;
+    const SegSrc s = seg_src(probs, pixel_stride, cls, B, h, w, H, W, K - 1);
+    unsigned long long* fix = static_cast<unsigned long long*>(workspace);
+    double* slab = reinterpret_cast<double*>(fix + CM);
+    CCDM_REQUIRE(hipMemsetAsync(fix, 0, (size_t)CM * sizeof(unsigned long long), st) == hipSuccess, "segcalib: clearing the workspace failed");
     // the two count tables, and room for the 256 lanes' triples that reuse them at the end
     const size_t lds = sizeof(double) * (size_t)(2 * CM > 3 * 256 ? 2 * CM : 3 * 256);
-    // the ladder of ccdm_seg_confusion
-    if (C <= 2) segc_dispatch<2>(ident, grid, lds, st, a);
-    else if (C <= 8) segc_dispatch<8>(ident, grid, lds, st, a);
-    else if (C <= 20) segc_dispatch<20>(ident, grid, lds, st, a);
-    else segc_dispatch<32>(ident, grid, lds, st, a);
+    seg_dispatch(s, [&](auto kp, auto src, auto v4, auto ident) {
+        hipLaunchKernelGGL((k_seg_calib<kp(), src(), v4(), ident()>), dim3(grid), dim3(256), lds, st, s, labels, M,
+                           reinterpret_cast<unsigned long long*>(bins), fix, slab);
+    });
     CCDM_CHECK_LAUNCH("segcalib");
-    hipLaunchKernelGGL(k_segcalib_finish, dim3(1), dim3(256), 0, st, a.fix, a.slab, grid, CM, conf_sum, sums);
+    hipLaunchKernelGGL(k_segcalib_finish, dim3(1), dim3(256), 0, st, fix, slab, grid, CM, conf_sum, sums);
     CCDM_CHECK_LAUNCH("segcalib finish");
     return 0;
 }

@@ -1,8 +1,7 @@
 // Cityscapes prediction export, device part: the class map of a low-resolution prediction at the label resolution, written as
 // train ids, as label ids and as colours (the three images of the reference's `save_preds`, evaluation/eval_cdm.py) without a
-// full-resolution probability tensor.  The walk is k_seg_confusion's (ccdm_seg_common.h): the same tiles, source coordinates,
-// interpolated row pair and argmax, so the class written here is the class counted there, bit for bit.  Instead of counting, a
-// pixel ends as one byte of class, one byte of label id and three bytes of colour.
+// full-resolution probability tensor.  The walk is ccdm_seg_common.h's; instead of counting, a pixel ends as one byte of class, one
+// byte of label id and three bytes of colour.
 //
 // Stores.  The kernel is write-bound (5 bytes out per pixel), and one output column per lane would give one- and three-byte
 // stores.  So the four lanes of a quad exchange their values by DPP (quad_perm broadcasts) before storing:
@@ -17,24 +16,16 @@
 
 namespace ccdm {
 
-constexpr int SEGX_MAX_K = 32;
+constexpr int SEGX_MAX_K = SEG_MAX_K;
 
 struct __attribute__((packed, aligned(1))) seg_u32_any { uint32_t v; };      // a dword at any byte address
 
 __device__ __forceinline__ void seg_store_u32(uint8_t* p, uint32_t v) { reinterpret_cast<seg_u32_any*>(p)->v = v; }
 
-// lane Q of the caller's quad, in every lane of the quad (all lanes must be active)
-template <int Q>
-__device__ __forceinline__ uint32_t seg_quad(uint32_t x) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, Q * 0x55, 0xF, 0xF, false);
-}
-
 // SRC: 0 fp32 probabilities, 1 class map.  IDENT: (H, W) == (h, w).  C: the channels the argmax runs over.
 // table[k] = r | g << 8 | b << 16 | label id << 24 of class k.
 template <int KP, int SRC, bool V4, bool IDENT>
-__global__ __launch_bounds__(256) void k_seg_export(const float* __restrict__ probs, long long ps, const uint8_t* __restrict__ cls,
-                                                    int B, int h, int w, int H, int W, int C, int K, float sh, float sw,
-                                                    const uint8_t* __restrict__ id_table, const uint8_t* __restrict__ color_table,
+__global__ __launch_bounds__(256) void k_seg_export(SegSrc s, int K, const uint8_t* __restrict__ id_table, const uint8_t* __restrict__ color_table,
                                                     uint8_t* __restrict__ train_id, uint8_t* __restrict__ label_id,
                                                     uint8_t* __restrict__ color) {
     __shared__ uint32_t table[SEGX_MAX_K];
@@ -44,30 +35,23 @@ __global__ __launch_bounds__(256) void k_seg_export(const float* __restrict__ pr
                              (uint32_t)id_table[k] << 24;
     }
     __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int q = lane & 3;
-    const int tiles_x = (W + SEG_TW - 1) / SEG_TW, tiles_y = (H + SEG_TH - 1) / SEG_TH;
-    const long long ntiles = (long long)B * tiles_x * tiles_y;
+    const int q = threadIdx.x & 3, H = s.H, W = s.W;
 
-    for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int tx = (int)(tile % tiles_x), ty = (int)((tile / tiles_x) % tiles_y), b = (int)(tile / ((long long)tiles_x * tiles_y));
-        const int x = tx * SEG_TW + lane;
-        const bool in_x = x < W;
+    for (SegTiles tiles(s.B, H, W); tiles.more(); tiles.advance()) {
+        const SegTile tile = tiles.get();
+        const int b = tile.b, x = tile.x, y_begin = tile.y_begin, y_end = tile.y_end;
+        const bool in_x = tile.in_x;
         const int gx = x - q;                         // first column of the lane's group of 4
         const bool full = gx + 3 < W;                 // the group lies inside the row: dword stores
         const bool edge = in_x && !full;              // the last partial group: this lane stores its own bytes
-        int ix0, ix1;
-        float lw0, lw1;
-        seg_lane_coord<IDENT>(x, in_x, sw, w, ix0, ix1, lw0, lw1);
+        const SegLane<IDENT> ln(s, tile);
         float A[KP], Bv[KP];
         int yA = -1, yB = -1;
-        const int y_begin = ty * SEG_TH + wave * SEG_ROWS;
-        const int y_end = min(y_begin + SEG_ROWS, H);
         uint32_t keep_t = 0, keep_i = 0;              // the group's train-id / label-id dword of row (batch start + q)
         for (int y = y_begin; y < y_end; ++y) {
             float h0, h1;
-            seg_step<KP, SRC, V4, IDENT>(A, Bv, yA, yB, h0, h1, probs, cls, b, y, h, w, sh, ix0, ix1, lw0, lw1, ps, C);
-            const uint32_t pred = (uint32_t)seg_argmax<KP, IDENT>(A, Bv, h0, h1, C);
+            seg_step<KP, SRC, V4, IDENT>(A, Bv, yA, yB, h0, h1, s, ln, b, y);
+            const uint32_t pred = (uint32_t)seg_argmax<KP, IDENT>(A, Bv, h0, h1, s.C);
             const uint32_t e = table[pred];
             const size_t pix = ((size_t)b * H + y) * W + x;
 
@@ -105,52 +89,23 @@ __global__ __launch_bounds__(256) void k_seg_export(const float* __restrict__ pr
     }
 }
 
-template <int KP, int SRC, bool V4>
-static void segx_launch(bool ident, int grid, hipStream_t st, const float* probs, long long ps, const uint8_t* cls, int B, int h, int w,
-                        int H, int W, int C, int K, float sh, float sw, const uint8_t* idt, const uint8_t* colt, uint8_t* train_id,
-                        uint8_t* label_id, uint8_t* color) {
-    if (ident)
-        hipLaunchKernelGGL((k_seg_export<KP, SRC, V4, true>), dim3(grid), dim3(256), 0, st, probs, ps, cls, B, h, w, H, W, C, K, sh, sw, idt,
-                           colt, train_id, label_id, color);
-    else
-        hipLaunchKernelGGL((k_seg_export<KP, SRC, V4, false>), dim3(grid), dim3(256), 0, st, probs, ps, cls, B, h, w, H, W, C, K, sh, sw, idt,
-                           colt, train_id, label_id, color);
-}
-
-template <int KP>
-static void segx_dispatch(bool ident, int grid, hipStream_t st, const float* probs, long long ps, const uint8_t* cls, int B, int h, int w,
-                          int H, int W, int C, int K, float sh, float sw, const uint8_t* idt, const uint8_t* colt, uint8_t* train_id,
-                          uint8_t* label_id, uint8_t* color) {
-    const bool v4 = probs && ps % 4 == 0 && (reinterpret_cast<uintptr_t>(probs) & 15) == 0;
-    if (cls) segx_launch<KP, 1, false>(ident, grid, st, probs, ps, cls, B, h, w, H, W, C, K, sh, sw, idt, colt, train_id, label_id, color);
-    else if (v4) segx_launch<KP, 0, true>(ident, grid, st, probs, ps, cls, B, h, w, H, W, C, K, sh, sw, idt, colt, train_id, label_id, color);
-    else segx_launch<KP, 0, false>(ident, grid, st, probs, ps, cls, B, h, w, H, W, C, K, sh, sw, idt, colt, train_id, label_id, color);
-}
-
 }  // namespace ccdm
 
 extern "C" int ccdm_segexport(const float* probs, int64_t pixel_stride, const uint8_t* cls, int B, int h, int w, int H, int W, int K,
                               int scored, const uint8_t* id_table, const uint8_t* color_table, uint8_t* train_id, uint8_t* label_id,
                               uint8_t* color, void* stream) {
     using namespace ccdm;
-    CCDM_REQUIRE((probs != nullptr) != (cls != nullptr), "segexport: pass exactly one of probs and cls");
-    CCDM_REQUIRE(K >= 2 && K <= SEGX_MAX_K, "segexport: K=%d outside [2,32]", K);
+    if (const int rc = seg_check_src("segexport", probs, pixel_stride, cls, h, w, K)) return rc;
+    if (const int rc = seg_check_out("segexport", B, H, W)) return rc;
     CCDM_REQUIRE(scored == K - 1 || scored == K, "segexport: scored=%d is neither K-1 nor K (K=%d)", scored, K);
-    CCDM_REQUIRE(B >= 0 && h > 0 && w > 0 && H > 0 && W > 0, "segexport: bad shape B=%d h=%d w=%d H=%d W=%d", B, h, w, H, W);
-    CCDM_REQUIRE(!probs || pixel_stride >= K, "segexport: pixel_stride=%lld < K=%d", (long long)pixel_stride, K);
     CCDM_REQUIRE(train_id || label_id || color, "segexport: no output requested");
     CCDM_REQUIRE(id_table && color_table, "segexport: null table");
     if (B == 0) return 0;
-    const int C = scored;
-    const int grid = seg_blocks(B, H, W);
-    const bool ident = H == h && W == w;
-    const float sh = (float)h / (float)H, sw = (float)w / (float)W;     // ATen's area_pixel_compute_scale, no scale factor given
-    hipStream_t st = (hipStream_t)stream;
-    // the ladder of ccdm_seg_confusion, on the scored channels
-    if (C <= 2) segx_dispatch<2>(ident, grid, st, probs, pixel_stride, cls, B, h, w, H, W, C, K, sh, sw, id_table, color_table, train_id, label_id, color);
-    else if (C <= 8) segx_dispatch<8>(ident, grid, st, probs, pixel_stride, cls, B, h, w, H, W, C, K, sh, sw, id_table, color_table, train_id, label_id, color);
-    else if (C <= 20) segx_dispatch<20>(ident, grid, st, probs, pixel_stride, cls, B, h, w, H, W, C, K, sh, sw, id_table, color_table, train_id, label_id, color);
-    else segx_dispatch<32>(ident, grid, st, probs, pixel_stride, cls, B, h, w, H, W, C, K, sh, sw, id_table, color_table, train_id, label_id, color);
+    const SegSrc s = seg_src(probs, pixel_stride, cls, B, h, w, H, W, scored);
+    seg_dispatch(s, [&](auto kp, auto src, auto v4, auto ident) {
+        hipLaunchKernelGGL((k_seg_export<kp(), src(), v4(), ident()>), dim3(seg_blocks(B, H, W)), dim3(256), 0, (hipStream_t)stream, s, K,
+                           id_table, color_table, train_id, label_id, color);
+    });
     CCDM_CHECK_LAUNCH("segexport");
     return 0;
 }

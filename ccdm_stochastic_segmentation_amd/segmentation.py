@@ -114,6 +114,38 @@ def prediction_form(prediction: torch.Tensor, num_classes: int, device):
     return p, ps, None, h, w
 
 
+def prediction_args(probs, ps, cls):
+    """The three leading arguments of every segmentation kernel (probs, pixel_stride, cls) from prediction_form's first three."""
+    return (probs.data_ptr() if probs is not None else None, ps, cls.data_ptr() if cls is not None else None)
+
+
+def _cuda_device(device, what: str) -> torch.device:
+    device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    if device.type != "cuda":
+        raise hip.CcdmHipError(f"{what} runs on the GPU (no CPU path)")
+    return device
+
+
+def _check_num_classes(num_classes) -> int:
+    if not 2 <= int(num_classes) <= 32:
+        raise ValueError(f"num_classes: {num_classes} (the kernel takes 2..32 channels, the last one the ignore class)")
+    return int(num_classes)
+
+
+def _grown(ws: Optional[torch.Tensor], need: int, device) -> Optional[torch.Tensor]:      # the grow-only workspace
+    return ws if need == 0 or (ws is not None and ws.numel() >= need) else torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def _write_json(output_path: str, name: str, obj) -> str:
+    """obj as <output_path>/<name>.json; returns the path."""
+    import json
+    os.makedirs(output_path, exist_ok=True)
+    path = os.path.join(output_path, name + ".json")
+    with open(path, "w") as f:
+        json.dump(obj, f, indent=2, sort_keys=True)
+    return path
+
+
 def _labels_u8(labels: torch.Tensor, device) -> torch.Tensor:
     """Labels [B,H,W] as the contiguous uint8 tensor the kernels read: anything outside [0, 255] is not counted either way, 255
     stands for it."""
@@ -139,13 +171,9 @@ class SegmentationConfusion:
     score those at resolution "original" (F.interpolate raises on the int64 one-hot).  Never builds a full-resolution tensor."""
 
     def __init__(self, num_classes: int, device=None):
-        if not 2 <= int(num_classes) <= 32:
-            raise ValueError(f"num_classes: {num_classes} (the kernel takes 2..32 channels, the last one the ignore class)")
-        self.num_classes = int(num_classes)
+        self.num_classes = _check_num_classes(num_classes)
         self.C = self.num_classes - 1
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if self.device.type != "cuda":
-            raise hip.CcdmHipError("SegmentationConfusion runs on the GPU (no CPU path)")
+        self.device = _cuda_device(device, "SegmentationConfusion")
         self._hard = torch.zeros((self.C, self.C), dtype=torch.int64, device=self.device)
         self.soft = torch.zeros((self.C, self.C), dtype=torch.int64)
         self.soft_exact = torch.zeros((self.C, self.C), dtype=torch.float64)
@@ -155,24 +183,20 @@ class SegmentationConfusion:
     def confusion(self) -> torch.Tensor:
         return self._hard.cpu()
 
-    def _prediction(self, prediction: torch.Tensor):
-        return prediction_form(prediction, self.num_classes, self.device)
-
     @torch.no_grad()
     def update(self, prediction: torch.Tensor, labels: torch.Tensor) -> None:
         if labels.ndim != 3 or labels.shape[0] != prediction.shape[0]:
             raise ValueError(f"labels: expected [B,H,W] with B = {prediction.shape[0]}, got {tuple(labels.shape)}")
-        probs, ps, cls, h, w = self._prediction(prediction)
+        probs, ps, cls, h, w = prediction_form(prediction, self.num_classes, self.device)
         lab = _labels_u8(labels, self.device)
         B, H, W = (int(s) for s in lab.shape)
         lib = hip.load()
         need = int(lib.ccdm_seg_confusion_workspace_bytes(B, H, W, self.num_classes)) if B > 0 else 0
-        if need and (self._ws is None or self._ws.numel() < need):
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self._ws = _grown(self._ws, need, self.device)
         soft = torch.empty((self.C, self.C), dtype=torch.float64, device=self.device)
         ws = self._ws.data_ptr() if need else None
-        hip.check(lib.ccdm_seg_confusion(probs.data_ptr() if probs is not None else None, ps, cls.data_ptr() if cls is not None else None,
-                                         lab.data_ptr(), B, h, w, H, W, self.num_classes, self._hard.data_ptr(), soft.data_ptr(), ws, need,
+        hip.check(lib.ccdm_seg_confusion(*prediction_args(probs, ps, cls), lab.data_ptr(), B, h, w, H, W, self.num_classes,
+                                         self._hard.data_ptr(), soft.data_ptr(), ws, need,
                                          torch.cuda.current_stream(self.device).cuda_stream), "seg_confusion")
         soft = soft.cpu()
         self.soft_exact += soft
@@ -262,15 +286,12 @@ class SegmentationCalibration:
     the upsampled map is not mixed (class_map_updates counts such updates).  result() is calibration_from_counts."""
 
     def __init__(self, num_classes: int, device=None, bins: int = 15):
-        if not 2 <= int(num_classes) <= 32:
-            raise ValueError(f"num_classes: {num_classes} (the kernel takes 2..32 channels, the last one the ignore class)")
+        self.num_classes = _check_num_classes(num_classes)
         if not 2 <= int(bins) <= 64:
             raise ValueError(f"bins: {bins} (the kernel takes 2..64 confidence bins)")
-        self.num_classes, self.bins = int(num_classes), int(bins)
+        self.bins = int(bins)
         self.C = self.num_classes - 1
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if self.device.type != "cuda":
-            raise hip.CcdmHipError("SegmentationCalibration runs on the GPU (no CPU path)")
+        self.device = _cuda_device(device, "SegmentationCalibration")
         self._bins = torch.zeros((self.C, self.bins, 2), dtype=torch.int64, device=self.device)
         self.conf_sum = torch.zeros((self.C, self.bins), dtype=torch.float64)
         self.sums = torch.zeros(3, dtype=torch.float64)
@@ -293,11 +314,10 @@ class SegmentationCalibration:
             return
         lib = hip.load()
         need = int(lib.ccdm_segcalib_workspace_bytes(B, H, W, self.num_classes, self.bins))
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self._ws = _grown(self._ws, need, self.device)
         out = torch.empty(self.C * self.bins + 3, dtype=torch.float64, device=self.device)      # conf_sum, then sums
-        hip.check(lib.ccdm_segcalib(probs.data_ptr() if probs is not None else None, ps, cls.data_ptr() if cls is not None else None,
-                                    lab.data_ptr(), B, h, w, H, W, self.num_classes, self.bins, self._bins.data_ptr(), out.data_ptr(),
+        hip.check(lib.ccdm_segcalib(*prediction_args(probs, ps, cls), lab.data_ptr(), B, h, w, H, W, self.num_classes, self.bins,
+                                    self._bins.data_ptr(), out.data_ptr(),
                                     out.data_ptr() + 8 * self.C * self.bins, self._ws.data_ptr(), need,
                                     torch.cuda.current_stream(self.device).cuda_stream), "segcalib")
         out = out.cpu()
@@ -330,17 +350,10 @@ def _export(probs, ps, cls, B, h, w, H, W, K, scored, outputs, id_table, color_t
     out = {o: torch.empty((B, H, W, 3) if o == "color" else (B, H, W), dtype=torch.uint8, device=device) for o in outputs}
     ptr = {o: out[o].data_ptr() if o in out and B > 0 else None for o in EXPORT_OUTPUTS}
     if B > 0:
-        hip.check(hip.load().ccdm_segexport(probs.data_ptr() if probs is not None else None, ps, cls.data_ptr() if cls is not None else None,
-                                            B, h, w, H, W, K, scored, idt.data_ptr(), colt.data_ptr(), ptr["train_id"], ptr["label_id"],
-                                            ptr["color"], torch.cuda.current_stream(device).cuda_stream), "segexport")
+        hip.check(hip.load().ccdm_segexport(*prediction_args(probs, ps, cls), B, h, w, H, W, K, scored, idt.data_ptr(), colt.data_ptr(),
+                                            ptr["train_id"], ptr["label_id"], ptr["color"],
+                                            torch.cuda.current_stream(device).cuda_stream), "segexport")
     return out
-
-
-def _cuda_device(device):
-    device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    if device.type != "cuda":
-        raise hip.CcdmHipError("the prediction export runs on the GPU (no CPU path)")
-    return device
 
 
 @torch.no_grad()
@@ -354,7 +367,7 @@ def export_predictions(prediction: torch.Tensor, size: Sequence[int], *, outputs
     prediction: every form SegmentationConfusion.update takes ([B,K,h,w] float, integer or bool one-hot, or a class map [B,h,w],
     whose K is `num_classes`, default 20).  id_table [K] / color_table [K,3]: default Cityscapes' (K = 20 only).  One HIP kernel
     (ccdm_segexport); never builds a full-resolution probability tensor."""
-    device = _cuda_device(device if device is not None else (prediction.device if prediction.is_cuda else None))
+    device = _cuda_device(device if device is not None else (prediction.device if prediction.is_cuda else None), "the prediction export")
     if prediction.ndim == 4:
         K = int(prediction.shape[1])
         if num_classes is not None and int(num_classes) != K:
@@ -374,7 +387,7 @@ def export_labels(labels: torch.Tensor, *, outputs: Sequence[str] = ("label_id",
     export_predictions, on the labels as a class map at their own resolution, with all K classes scored."""
     if labels.ndim != 3:
         raise ValueError(f"labels: expected [B,H,W], got {tuple(labels.shape)}")
-    device = _cuda_device(device if device is not None else (labels.device if labels.is_cuda else None))
+    device = _cuda_device(device if device is not None else (labels.device if labels.is_cuda else None), "the prediction export")
     K = int(num_classes)
     lab = labels.to(device)
     if lab.dtype == torch.bool:
@@ -675,28 +688,20 @@ def eval_segmentation(params: dict, dataset=None, device=None, model=None, synth
         res["pred_list"], res["label_list"] = list(writer.pred_list), list(writer.label_list)
         LOGGER.info("%d predictions written under %s", len(writer.pred_list), os.path.dirname(writer.path_submit))
     if scores is not None:
-        import json
         res["cs_script"] = scores.result()
-        out_dir = E.expanduservars(params["output_path"])
-        os.makedirs(out_dir, exist_ok=True)
-        with open(os.path.join(out_dir, "cs_script_results.json"), "w") as f:
-            json.dump(res["cs_script"], f, indent=2, sort_keys=True)
+        path = _write_json(E.expanduservars(params["output_path"]), "cs_script_results", res["cs_script"])
         LOGGER.info("Cityscapes script: IoU classes %.4f  iIoU classes %.4f  IoU categories %.4f  iIoU categories %.4f (%s)",
                     *(res["cs_script"][k] for k in ("averageScoreClasses", "averageScoreInstClasses", "averageScoreCategories",
-                                                    "averageScoreInstCategories")), os.path.join(out_dir, "cs_script_results.json"))
+                                                    "averageScoreInstCategories")), path)
     if calib is not None:
-        import json
         res["calibration"] = cal = calib.result(names)
-        out_dir = E.expanduservars(params["output_path"])
-        os.makedirs(out_dir, exist_ok=True)
-        with open(os.path.join(out_dir, "calibration.json"), "w") as f:
-            json.dump(cal, f, indent=2, sort_keys=True)
+        path = _write_json(E.expanduservars(params["output_path"]), "calibration", cal)
         if calib.class_map_updates:
             LOGGER.info("calibration: the prediction is a one-hot map (confidence 1 wherever the upsampled map is not mixed): "
                         "the scores below are degenerate")
         LOGGER.info("calibration over %d pixels, %d bins: ECE %s  NLL %s  Brier %s  AUROC (error detection) %s (%s)", cal["pixels"],
                     cal["bins"], *("n/a" if cal[k] is None else f"{cal[k]:.4f}" for k in ("ece", "nll", "brier", "auroc_error_detection")),
-                    os.path.join(out_dir, "calibration.json"))
+                    path)
     LOGGER.info("mIoU %.4f  soft mIoU %.4f over %d images (resolution %s, %d evaluation(s), %s)", res["mIoU"], res["mIoU_soft"], n_img,
                 resolution, evaluations, vote)
     return res
