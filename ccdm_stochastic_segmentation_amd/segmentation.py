@@ -12,6 +12,10 @@ against the original full-resolution labels — the reference's `evaluation/eval
     SegmentationCalibration(num_classes, ...)    ECE / MCE, NLL, Brier score, reliability diagram and error-detection AUROC of the
                                                  probabilities (beyond the reference), from the counts of one HIP kernel
                                                  (ccdm_segcalib) on the same walk; calibration_from_counts is the host formula
+    SegmentationBoundary(num_classes, ...)       Boundary IoU and the trimap IoU curve (beyond the reference) at band widths in
+                                                 pixels or as a ratio of the image diagonal, from the counts of one HIP kernel pair
+                                                 (ccdm_segboundary) on the class map ccdm_segexport writes; boundary_from_counts is
+                                                 the host formula, resolve_boundary_widths the width rule
     PredictionWriter(directory, split)           writes them as PNGs under outputs/<split>/{submit,debug,label}
     eval_segmentation(params, ...)               the evaluation loop (no ignite), built like evaluation.eval_lidc_uncertainty; with
                                                  evaluation.cityscapes_script also the official script's scores
@@ -328,6 +332,146 @@ class SegmentationCalibration:
         return calibration_from_counts(self.bins_count.numpy(), self.conf_sum.numpy(), self.sums.numpy(), class_names)
 
 
+# ------------------------------------------------------------------------------------------------ boundary scores
+BOUNDARY_MAX_WIDTH = 64             # the widest band ccdm_segboundary takes, in pixels
+BOUNDARY_DEFAULT_WIDTHS = ("ratio:0.02",)       # the Boundary IoU paper's 2 % of the image diagonal: 46 px at 1024 x 2048
+
+
+def _width_entry(entry):
+    """One entry of a width list -> ("px", int) or ("ratio", float); ValueError for anything else."""
+    if isinstance(entry, (int, np.integer)) and not isinstance(entry, bool):
+        if not 1 <= int(entry) <= BOUNDARY_MAX_WIDTH:
+            raise ValueError(f"boundary width {entry!r}: a width in pixels lies in [1, {BOUNDARY_MAX_WIDTH}]")
+        return "px", int(entry)
+    if isinstance(entry, str) and entry.startswith("ratio:"):
+        try:
+            ratio = float(entry[len("ratio:"):])
+        except ValueError:
+            ratio = float("nan")
+        if not (0.0 < ratio < float("inf")):
+            raise ValueError(f"boundary width {entry!r}: expected 'ratio:R' with a number R > 0")
+        return "ratio", ratio
+    raise ValueError(f"boundary width {entry!r}: expected an int in [1, {BOUNDARY_MAX_WIDTH}] (pixels) or the string 'ratio:R'")
+
+
+def resolve_boundary_widths(widths, size: Optional[Sequence[int]] = None) -> List[int]:
+    """The width rule of the boundary scores.  `widths` is a non-empty list without repeats whose entries are an int >= 1 (pixels) or
+    the string "ratio:R", which stands for max(1, round(R * sqrt(H^2 + W^2))) pixels at the scored size (H, W) (Python's round, as
+    the published Boundary IoU code).  Returns the widths in pixels, one per entry; without `size` the entries are only checked
+    and a ratio entry gives 0.  An entry that is neither, or a width outside [1, 64], is a ValueError that names the limit."""
+    if isinstance(widths, (str, bytes)) or not isinstance(widths, (list, tuple)) or len(widths) == 0:
+        raise ValueError(f"boundary widths {widths!r}: expected a non-empty list of ints (pixels) and 'ratio:R' strings")
+    if len({str(e) for e in widths}) != len(widths):
+        raise ValueError(f"boundary widths {list(widths)!r}: an entry is repeated")
+    out = []
+    for entry in widths:
+        kind, v = _width_entry(entry)
+        if kind == "ratio":
+            if size is None:
+                v = 0
+            else:
+                H, W = int(size[0]), int(size[1])
+                v = max(1, int(round(v * float(np.sqrt(float(H * H + W * W))))))
+                if v > BOUNDARY_MAX_WIDTH:
+                    raise ValueError(f"boundary width {entry!r} is {v} pixels at {H} x {W}: the widest band is {BOUNDARY_MAX_WIDTH} pixels")
+        out.append(v)
+    return out
+
+
+def boundary_from_counts(bcounts, trimap, class_names: Optional[Sequence[str]] = None) -> Dict[str, object]:
+    """The boundary scores behind the counts of ccdm_segboundary at one width, on the host (no GPU):
+      bcounts  [C,3] per class {|band_G|, |band_P|, |band_G & band_P|} (band: the pixels of the class within the width of its border);
+      trimap   [C,C] rows = target, columns = prediction: the hard confusion matrix over the counted pixels in the band of their
+               own target class.
+    Returns a dict of plain Python values (JSON as it stands):
+      boundary_iou       per class inter / (g + p - inter) (Boundary IoU, Cheng et al. 2021), None for a class whose two bands are
+                         both empty; a list, or a dict keyed by class_names;
+      mean_boundary_iou  the mean over the classes that have a value, None when there is none;
+      trimap_iou, trimap_miou   iou_from_confusion of `trimap` and its mean over all C classes (as mIoU: an absent class gives 0);
+      trimap_pixels      the pixels in `trimap`;
+      bcounts, trimap    the counts themselves."""
+    bc = np.asarray(bcounts, dtype=np.int64)
+    tm = np.asarray(trimap, dtype=np.int64)
+    if bc.ndim != 2 or bc.shape[1] != 3 or tm.shape != (bc.shape[0], bc.shape[0]):
+        raise ValueError(f"expected bcounts [C,3] and trimap [C,C], got {bc.shape} and {tm.shape}")
+    C = bc.shape[0]
+    if class_names is not None and len(class_names) != C:
+        raise ValueError(f"class_names: {len(class_names)} names for {C} classes")
+    union = bc[:, 0] + bc[:, 1] - bc[:, 2]
+    biou = [float(bc[c, 2]) / float(union[c]) if union[c] > 0 else None for c in range(C)]
+    have = [v for v in biou if v is not None]
+    tiou = iou_from_confusion(torch.from_numpy(tm))
+    named = (lambda v: list(v)) if class_names is None else (lambda v: dict(zip(class_names, v)))
+    return {"boundary_iou": named(biou), "mean_boundary_iou": float(np.mean(have)) if have else None,
+            "trimap_iou": named(tiou.tolist()), "trimap_miou": float(tiou.mean()), "trimap_pixels": int(tm.sum()),
+            "bcounts": bc.tolist(), "trimap": tm.tolist()}
+
+
+class SegmentationBoundary:
+    """Contour scores of a segmentation prediction against the labels (beyond the reference): Boundary IoU and the trimap confusion
+    matrix at every width of `widths` (resolve_boundary_widths; default the Boundary IoU paper's 2 % of the image diagonal), over
+    the pixels SegmentationConfusion counts, with the class it counts.  update(prediction, labels) takes what
+    SegmentationConfusion.update takes: one ccdm_segexport launch turns the prediction (probabilities or a class map, at any
+    size) into the class map at the labels' size, then one ccdm_segboundary launch per width counts:
+      bcounts  int64 [widths,C,3], trimap int64 [widths,C,C], accumulated on the device (the contract of include/ccdm_hip.h).
+    A ratio entry is resolved again at every update, at that update's (H, W), and its counts add up over the updates: an image is
+    scored at the width its own diagonal gives, as Boundary IoU prescribes for a data set of mixed sizes.  `pixels` keeps, per
+    entry, the distinct pixel widths used so far (one value for Cityscapes, whose images share one size).
+    result() is boundary_from_counts per entry."""
+
+    def __init__(self, num_classes: int, device=None, widths: Sequence = BOUNDARY_DEFAULT_WIDTHS):
+        self.num_classes = _check_num_classes(num_classes)
+        self.widths = list(widths) if isinstance(widths, (list, tuple)) else widths
+        resolve_boundary_widths(self.widths)
+        self.widths = [e if isinstance(e, str) else int(e) for e in self.widths]
+        self.C = self.num_classes - 1
+        self.device = _cuda_device(device, "SegmentationBoundary")
+        n = len(self.widths)
+        self._bc = torch.zeros((n, self.C, 3), dtype=torch.int64, device=self.device)
+        self._tm = torch.zeros((n, self.C, self.C), dtype=torch.int64, device=self.device)
+        self.pixels: List[List[int]] = [[] for _ in range(n)]
+        # ccdm_segexport wants both tables although only train_id is written
+        self._tables = torch.zeros(4 * self.num_classes, dtype=torch.uint8, device=self.device)
+        self._ws: Optional[torch.Tensor] = None
+
+    @property
+    def bcounts(self) -> torch.Tensor:
+        return self._bc.cpu()
+
+    @property
+    def trimap(self) -> torch.Tensor:
+        return self._tm.cpu()
+
+    @torch.no_grad()
+    def update(self, prediction: torch.Tensor, labels: torch.Tensor) -> None:
+        if labels.ndim != 3 or labels.shape[0] != prediction.shape[0]:
+            raise ValueError(f"labels: expected [B,H,W] with B = {prediction.shape[0]}, got {tuple(labels.shape)}")
+        probs, ps, cls, h, w = prediction_form(prediction, self.num_classes, self.device)
+        lab = _labels_u8(labels, self.device)
+        B, H, W = (int(s) for s in lab.shape)
+        px = resolve_boundary_widths(self.widths, (H, W))
+        if B == 0:
+            return
+        lib = hip.load()
+        K, stream = self.num_classes, torch.cuda.current_stream(self.device).cuda_stream
+        train_id = torch.empty((B, H, W), dtype=torch.uint8, device=self.device)
+        hip.check(lib.ccdm_segexport(*prediction_args(probs, ps, cls), B, h, w, H, W, K, K - 1, self._tables.data_ptr(),
+                                     self._tables.data_ptr() + K, train_id.data_ptr(), None, None, stream), "segexport")
+        need = int(lib.ccdm_segboundary_workspace_bytes(B, H, W))
+        self._ws = _grown(self._ws, need, self.device)
+        for i, d in enumerate(px):
+            hip.check(lib.ccdm_segboundary(train_id.data_ptr(), lab.data_ptr(), B, H, W, K, d, self._bc[i].data_ptr(), self._tm[i].data_ptr(),
+                                           self._ws.data_ptr(), need, stream), "segboundary")
+            if d not in self.pixels[i]:
+                self.pixels[i].append(d)
+
+    def result(self, class_names: Optional[Sequence[str]] = None) -> Dict[str, object]:
+        """{"widths": [{"entry", "pixels"} per entry], "by_width": {str(entry): boundary_from_counts(...)}}"""
+        bc, tm = self.bcounts.numpy(), self.trimap.numpy()
+        return {"widths": [{"entry": e, "pixels": list(p)} for e, p in zip(self.widths, self.pixels)],
+                "by_width": {str(e): boundary_from_counts(bc[i], tm[i], class_names) for i, e in enumerate(self.widths)}}
+
+
 # ------------------------------------------------------------------------------------------------ prediction export
 EXPORT_OUTPUTS = ("train_id", "label_id", "color")
 
@@ -619,6 +763,11 @@ def eval_segmentation(params: dict, dataset=None, device=None, model=None, synth
     15).  The result then holds "calibration" (calibration_from_counts), also written to <output_path>/calibration.json.  A
     one-hot prediction (`step_T_sample: majority` with one evaluation) is scored too: its confidence is 1 wherever the
     upsampled map is not mixed, which the log says.
+    `evaluation.boundary` (default off): also score the contours (SegmentationBoundary: one ccdm_segexport launch and one
+    ccdm_segboundary launch per width per batch, on the tensor and labels the confusion matrices get).
+    `evaluation.boundary_widths` (default ["ratio:0.02"]) lists the band widths, each an int (pixels, 1..64) or "ratio:R" (R times
+    the diagonal of the scored size); a bad list raises before anything is sampled.  The result then holds "boundary"
+    (SegmentationBoundary.result: Boundary IoU and trimap IoU per width), also written to <output_path>/boundary.json.
     `model`: a ready DenoisingModel-like callable (tests inject one); default: built from `params`."""
     from . import evaluation as E
     world = int(os.environ.get("WORLD_SIZE", "1") or 1)
@@ -634,6 +783,10 @@ def eval_segmentation(params: dict, dataset=None, device=None, model=None, synth
     if script_instances and resolution != "original":
         raise ValueError(f"evaluation.cityscapes_script_instances needs evaluation.resolution: original (got {resolution!r}): "
                          "resized labels have no instance image")
+    boundary_widths = None
+    if section.get("boundary", False):
+        boundary_widths = section.get("boundary_widths", list(BOUNDARY_DEFAULT_WIDTHS))
+        resolve_boundary_widths(boundary_widths)
     dataset = dataset if dataset is not None else make_segmentation_dataset(params)
     LOGGER.info("%d images in validation dataset '%s'", len(dataset), params["dataset_file"])
     if resolution not in RESOLUTIONS:
@@ -645,6 +798,8 @@ def eval_segmentation(params: dict, dataset=None, device=None, model=None, synth
         raise ValueError("evaluation.cityscapes_script_instances: the dataset's items carry no instance image (return_instances / instances)")
     input_shapes = [tuple(image0.shape), tuple(labels0.shape)]
     num_classes = input_shapes[1][0]
+    if boundary_widths is not None:            # a ratio that is too wide at the scored size, before anything is sampled
+        resolve_boundary_widths(boundary_widths, dataset[0][2].shape[-2:] if resolution == "original" else labels0.shape[-2:])
     encoder = _feature_encoder(params, synthetic_weights_seed, device)
     if model is None:
         model = E.build_from_params(params, input_shapes, device)
@@ -661,6 +816,7 @@ def eval_segmentation(params: dict, dataset=None, device=None, model=None, synth
         from .cityscapes_scores import CityscapesScores
         scores = CityscapesScores(num_classes, device)
     calib = SegmentationCalibration(num_classes, device, int(section.get("calibration_bins", 15))) if section.get("calibration", False) else None
+    boundary = SegmentationBoundary(num_classes, device, boundary_widths) if boundary_widths is not None else None
     n_img = 0
     for image, labels, labels_orig, *rest in loader:
         image = image.to(device)
@@ -671,6 +827,8 @@ def eval_segmentation(params: dict, dataset=None, device=None, model=None, synth
         conf.update(prediction, target)
         if calib is not None:
             calib.update(prediction, target)
+        if boundary is not None:
+            boundary.update(prediction, target)
         if writer is not None:
             writer.write(prediction, target, tuple(target.shape[1:]))
         if scores is not None:
@@ -702,6 +860,14 @@ def eval_segmentation(params: dict, dataset=None, device=None, model=None, synth
         LOGGER.info("calibration over %d pixels, %d bins: ECE %s  NLL %s  Brier %s  AUROC (error detection) %s (%s)", cal["pixels"],
                     cal["bins"], *("n/a" if cal[k] is None else f"{cal[k]:.4f}" for k in ("ece", "nll", "brier", "auroc_error_detection")),
                     path)
+    if boundary is not None:
+        res["boundary"] = bnd = boundary.result(names)
+        path = _write_json(E.expanduservars(params["output_path"]), "boundary", bnd)
+        for w in bnd["widths"]:
+            s = bnd["by_width"][str(w["entry"])]
+            LOGGER.info("boundary width %s (%s px): Boundary mIoU %s  trimap mIoU %.4f over %d pixels (%s)", w["entry"],
+                        ", ".join(str(p) for p in w["pixels"]), "n/a" if s["mean_boundary_iou"] is None else f"{s['mean_boundary_iou']:.4f}",
+                        s["trimap_miou"], s["trimap_pixels"], path)
     LOGGER.info("mIoU %.4f  soft mIoU %.4f over %d images (resolution %s, %d evaluation(s), %s)", res["mIoU"], res["mIoU_soft"], n_img,
                 resolution, evaluations, vote)
     return res

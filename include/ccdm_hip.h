@@ -419,6 +419,29 @@ int ccdm_segcalib(const float* probs /*dev or NULL*/, int64_t pixel_stride, cons
                   size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Boundary IoU (Cheng et al., CVPR 2021) and trimap counts of a segmentation prediction, device part (beyond the reference,
+ * whose scores are all region scores): a stencil of radius d over two class maps at the scored resolution [B,H,W].
+ *   pred    uint8 [B,H,W]: the class of every output pixel, the byte ccdm_segexport writes as train_id with scored = K-1;
+ *   labels  uint8 [B,H,W]: train ids; a label >= C = K-1 is not counted (the rule of ccdm_seg_confusion).
+ * Wherever the label is not counted the prediction is not counted either, so both maps share one ignore region, which makes a
+ * border in both alike; a predicted byte >= C is not counted either.  For a map X, a class c < C and a width d >= 1,
+ * band_X(c,d) = the pixels p with X[p] == c for which some pixel within Chebyshev distance d of p lies outside the image or has
+ * X != c: the mask of c minus its erosion by a 3x3 square, d iterations, zero border (the published Boundary IoU code).
+ *   bcounts  int64 [C][3], per class c: {|band_G(c,d)|, |band_P(c,d)|, |band_G(c,d) & band_P(c,d)|}.  ACCUMULATED across calls;
+ *   trimap   int64 [C][C], rows = label, columns = prediction: the hard matrix of ccdm_seg_confusion restricted to the counted
+ *            pixels p that lie in band_G(G[p], d).  ACCUMULATED across calls.
+ * K in [2,32], d in [1,64].  Two linear passes, whatever d: rows (one byte per pixel and map into the workspace: the class and
+ * whether its run covers [x-d, x+d]), then columns (a rolling run length over [y-d, y+d]).  The workspace (device, 2-byte
+ * aligned, ccdm_segboundary_workspace_bytes(B,H,W) = 2*B*H*W bytes) holds those bytes.  Integer atomics only, after a per-block
+ * count in LDS: every count is exact in any order, two identical calls are bit-identical.  B = 0 returns 0 without a launch.
+ * (Named without the ccdm_seg_ prefix: the evaluator's test pins the set of ccdm_seg_* symbols.)
+ * ------------------------------------------------------------------------------------------------- */
+size_t ccdm_segboundary_workspace_bytes(int B, int H, int W);
+int ccdm_segboundary(const uint8_t* pred /*dev [B,H,W] train ids*/, const uint8_t* labels /*dev [B,H,W]*/, int B, int H, int W,
+                     int K, int d, int64_t* bcounts /*dev [K-1][3]*/, int64_t* trimap /*dev [K-1][K-1]*/, void* workspace,
+                     size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Multi-sample prediction (DenoisingModel.predict_multiple): S sampling passes of the same B images folded into one
  * mean map, a per-pixel vote and two uncertainty maps.  The reference's Evaluator.predict_multiple
  * (evaluation/eval_cdm.py:176-193) accumulates `total += prediction_i * (1 / S)` on the host; these read a pass
