@@ -34,17 +34,9 @@
 
 namespace ccdm {
 
-// F32  : CK = 32 channels per chunk; LDS pixel = 33 floats (odd stride: conflict-free column reads).
-// F16X3: CK = 16 channels per chunk; LDS pixel = 16 hi halfs | 16 lo halfs | 16 B pad = 80 B = 20 dwords:
-//        the 16 pixels of a ds_read_b128 lane group land on 16 disjoint 4-bank slots (20*p mod 64).
-//        Small-spatial stages (few pixels, many channels) take CK = 32 per chunk instead (pixel = 32 hi | 32 lo | pad
-//        = 144 B = 36 dwords, also conflict-free): half as many barrier/latency round trips per tile.
-template <int PREC, int CKT> struct Lds {
-    static constexpr int CK = CKT;
-    static constexpr int PIXB = PREC == CCDM_PREC_F32 ? 33 * 4 : CKT * 4 + 16;
-};
-
-// (ACT_PRESCALE, ConvK, load16/store16_uniform_base: ccdm_conv_common.h; GroupNorm statistics and affine: ccdm_gn.h)
+// (ACT_PRESCALE, ConvK, the LDS layout constants, load16/store16_uniform_base: ccdm_conv_common.h; GroupNorm statistics and affine: ccdm_gn.h)
+// Chunk width CK: F32 32 channels; F16X3 16, or 32 / 64 at the small-spatial stages (few pixels, many channels: half / a quarter as
+// many barrier/latency round trips per tile).
 
 // register budget: >= 3 waves per SIMD (<= 168 VGPRs) when the accumulator tile is small — matches the 3 blocks
 // per CU the LDS footprint (A tile 27 KB + B chunk 18 KB) admits
@@ -73,30 +65,29 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
     static_assert(KSP == 1 || KSP == KS, "tap split is by kernel row");
     static_assert(!UP2 || (KS == 3 && STRIDE == 1 && KSP == 1 && (NI == 1 || NI == 4) && PREC != CCDM_PREC_F32), "sub-pixel form: 3x3, stride 1, F16X3, one phase or all four");
     constexpr int NTAP = UP2 ? 4 : KS * KS;
-    constexpr int CK = Lds<PREC, CKT>::CK, PIXB = Lds<PREC, CKT>::PIXB;
+    constexpr int CK = CKT, PIXB = conv_pixb(PREC, CKT);
     constexpr int KST = CK / 16;                                  // F16X3: 16-channel MFMA k-steps per chunk
     constexpr int PAD = KS / 2;
     constexpr int HHt = (TH - 1) * STRIDE + KS, HWt = (TW - 1) * STRIDE + KS, HP = HHt * HWt;
     constexpr int QPP = CK / 4;                                   // float4 items per halo pixel
     static_assert(NT % QPP == 0, "channel quad must be item-invariant");
-    // Stride-1 staging is row-structured: a pass of the block covers RPP whole rows of the TW core columns of the halo
+    // Staging is row-structured: a pass of the block covers RPP whole rows of the core columns of the halo
     // (thread -> (row in pass, column, channel quad), all item-invariant), the 2*PAD edge columns are one extra item for
     // the first few threads.  Row index and row validity are wave-uniform (scalar ALU), the column part of the address
     // is computed once per tile-chunk, every LDS address is thread-constant + immediate: staging costs no per-item VALU
-    // beyond the arithmetic on the data itself.  Stride 2 (round 3) walks the same way: the core is the CW = 2 TW columns the tile's
-    // outputs read from halo column PAD on, the single left padding column is the edge item (58.7 -> 5x us at 128x128 -> 64x64 with
-    // the generic item -> (hy, hx) walk before).
-    constexpr bool ROWS = true;
+    // beyond the arithmetic on the data itself.  Stride 2 walks the same way: the core is the CW = 2 TW columns the tile's
+    // outputs read from halo column PAD on, the single left padding column is the edge item (the generic item -> (hy, hx) walk
+    // it had before took the same time, 62 us at 128x128 -> 64x64: profiles/CHRONOLOGY.md, "Stride-2 convs").
     constexpr int CW = TW * STRIDE;                               // core columns of the halo (halo x = PAD + core column)
     constexpr int PXW = NT / QPP;                                 // halo pixels per pass
-    static_assert(!ROWS || PXW % CW == 0, "a pass must cover whole core rows");
-    constexpr int RPP = ROWS ? PXW / CW : 1;                      // core rows per pass
-    constexpr int NCORE = ROWS ? (HHt + RPP - 1) / RPP : 0;
+    static_assert(PXW % CW == 0, "a pass must cover whole core rows");
+    constexpr int RPP = PXW / CW;                                 // core rows per pass
+    constexpr int NCORE = (HHt + RPP - 1) / RPP;
     constexpr int ECOLS = HWt - CW > 0 ? HWt - CW : 1;            // edge columns: 2 PAD at stride 1, PAD (left only) at stride 2 (1: placeholder when there are none)
-    constexpr int EDGE_ITEMS = ROWS ? HHt * (HWt - CW) * QPP : 0;
+    constexpr int EDGE_ITEMS = HHt * (HWt - CW) * QPP;
     constexpr int NEDGE = (EDGE_ITEMS + NT - 1) / NT;
-    constexpr bool ROW_UNIFORM = ROWS && (CW * QPP) % 64 == 0;    // a wave never straddles two core rows
-    constexpr int NITEM = ROWS ? NCORE + NEDGE : (HP * QPP + NT - 1) / NT;   // staging items per thread
+    constexpr bool ROW_UNIFORM = (CW * QPP) % 64 == 0;            // a wave never straddles two core rows
+    constexpr int NITEM = NCORE + NEDGE;                          // staging items per thread
     static_assert(NITEM <= 32, "validity mask is 32 bits");
     // Wide skip chunks (SKW; run-time switch k.skip_wide).  A chunk of the fused 1x1 skip segment feeds the centre tap only: it needs no
     // halo, so the same LDS holds 32 channels of the TH x TW core pixels (144-byte pixels: 36.9 KB) + 2 k-steps of one tap's fragments
@@ -104,14 +95,14 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
     // and the 16-channel skip chunks were 45 % of the tile time of a decoder ResBlock's second conv — and no staging of halo pixels.
     // (its own instantiation, SKWT: 159 registers against the plain one's 149 — both keep 3 waves per SIMD)
     constexpr bool SKW = SKWT && PREC != CCDM_PREC_F32 && KS == 3 && STRIDE == 1 && TW == 32 && NI == 1 && KSP == 1 && !UP2 && CKT == 16;
-    constexpr int CKS = 32, PIXS = CKS * 4 + 16, QPS = CKS / 4;
+    constexpr int CKS = 32, PIXS = conv_pixb(CCDM_PREC_F16X3, CKS), QPS = CKS / 4;
     constexpr int NITEM_S = SKW ? TH * TW * QPS / NT : 0;          // core-only items per thread (8)
     constexpr int NITEM_R = NITEM_S > NITEM ? NITEM_S : NITEM;    // halo register set size
     static_assert(!SKW || (TH * TW * QPS) % NT == 0, "a wide skip chunk tiles the block");
     constexpr int A_BYTES = (HP * PIXB + 15) / 16 * 16;
     // F16X3: the chunk's B fragments, [tap][k-step] slabs of G = [ni][hi|lo][64 lanes] x 16 B, staged through registers
     // like the halo.  A pass covers MB whole slabs (or 1/DB of one); the slab index is wave-uniform.
-    constexpr int G = NI * 128;
+    constexpr int G = NI * FRAG_ITEMS;
     constexpr int NB4 = PREC == CCDM_PREC_F32 ? 0 : NTAP * KST * G;
     constexpr int NITEM_B = (NB4 + NT - 1) / NT;
     constexpr bool B_MULTI = NT % G == 0;
@@ -155,7 +146,7 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
     for (int mi = 0; mi < MI; ++mi) {
         const int p = (wave * MI + mi) * 32 + (lane & 31);
         const int hpix = (p / TW) * STRIDE * HWt + (p % TW) * STRIDE;
-        base[mi] = PREC == CCDM_PREC_F32 ? hpix * 33 + (lane >> 5) : hpix * PIXB + (lane >> 5) * 16;   // floats | bytes
+        base[mi] = PREC == CCDM_PREC_F32 ? hpix * PIX_F32 + (lane >> 5) : hpix * PIXB + (lane >> 5) * 16;   // floats | bytes
         if (UP2 && NI == 1) base[mi] += ((phase_of(0) >> 1) * HWt + (phase_of(0) & 1)) * PIXB;   // this phase's 2x2 window starts at halo offset (dy, dx)
     }
     // Output statistics in fp64, every stored value added in fp64 (v * v is exact there): var = sum x^2 / n - mean^2 cancels in
@@ -189,7 +180,7 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
     GnPrefetch gpf;
     gn_prefetch(a, has_gn, n, emb_row, tid, NT, a.w, gpf);
     __builtin_amdgcn_sched_barrier(0);             // the requests above stay above the halo request
-    constexpr int EPS = 36;                        // floats per pixel row of the transpose buffer (16-B aligned rows)
+    constexpr int EPS = EPI_ROW;                   // floats per pixel row of the transpose buffer
     float* epi = reinterpret_cast<float*>(halo_b) + wave_all * (MI * 32 * EPS);      // [krow][wave][MI*32][EPS]
 
     const int ntile_sp = k.tiles_x * k.tiles_y;
@@ -202,25 +193,25 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
 
     // Staging register sets: ONE halo set and one fragment set.  The halo of iteration i+1 is requested right after the commit of
     // iteration i; the weight fragments at the top of the iteration that consumes them (registers are the scarce resource of the
-    // wide-tile variants: 3 waves per SIMD).  Two-deep variants (a second halo set, fragments two iterations ahead, next-chunk fragments
-    // requested with the next halo) were built, parity-tested and measured neutral to slower in rounds 1-2; they are gone.
-    constexpr int DEPTH = 1;
-    f32x4 reg[DEPTH][NITEM_R];
+    // wide-tile variants: 3 waves per SIMD).  Two-deep staging (a second halo set, fragments two iterations ahead) was measured neutral
+    // to slower.
+    f32x4 reg[NITEM_R];
     // weight fragments by LDS-DMA instead of through registers — on the narrow-tile variants, where the B chunk (36-74 KB) outweighs the
     // halo tile: same-box A/B per stage 16x16 423 -> 402 us, 32x32 420 -> 414 us per denoise step; the wide-tile variants LOSE with it
     // (128x128 1358 -> 1378 us: the request sits behind barrier A instead of in front of it, and their chunk is only 18 KB)
     // (not the stride-2 variants: their commit is short — raw input — so the DMA's round trip sat exposed between the two barriers:
     //  Downsample 128x128 -> 64x64 61.2 -> 58.9 us, 64x64 -> 32x32 20.6 -> 19.8 us through registers, round 5)
     constexpr bool BDMA = PREC != CCDM_PREC_F32 && TW < 32 && STRIDE == 1;
-    f32x4 regB[1][(NITEM_B > 0 && !BDMA) ? NITEM_B : 1];
-    unsigned valid[DEPTH];         // generic walk: bit i = item i lies inside the image
-    unsigned rowmask[DEPTH];       // row-structured: bit i = core row of pass i inside the image (wave-uniform)
-    unsigned evalid[DEPTH];        //                 bit j = edge item j inside the image
-    bool xok[DEPTH];               //                 this thread's core column (and channel quad) exists
+    f32x4 regB[(NITEM_B > 0 && !BDMA) ? NITEM_B : 1];
+    // (These three stay one-element arrays cleared in an unrolled loop: as plain variables they move a few scalar instructions in
+    //  every instantiation — same registers, another schedule, profiles/r11_conv_refactor_isa.txt — which needs a timed A/B first.)
+    unsigned rowmask[1];           // bit i = core row of pass i inside the image (wave-uniform)
+    unsigned evalid[1];            // bit j = edge item j inside the image
+    bool xok[1];                   // this thread's core column (and channel quad) exists
 #pragma unroll
-    for (int d = 0; d < DEPTH; ++d) { valid[d] = 0; rowmask[d] = 0; evalid[d] = 0; xok[d] = false; }
+    for (int d = 0; d < 1; ++d) { rowmask[d] = 0; evalid[d] = 0; xok[d] = false; }
 
-    // thread -> staging coordinates (row-structured walk): channel quad tq, core column px, row within a pass rip.
+    // thread -> staging coordinates: channel quad tq, core column px, row within a pass rip.
     // tq and px are re-derived from an opaque copy of tid inside issue/commit: kept live across the MFMA phase and the
     // epilogue they cost registers the kernel does not have (3 waves per SIMD = 168), re-deriving them is 3 VALU ops.
     const int rip = ROW_UNIFORM ? __builtin_amdgcn_readfirstlane((tid / QPP) / CW) : (tid / QPP) / CW;
@@ -244,13 +235,12 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
         const unsigned long long sb = reinterpret_cast<unsigned long long>(srcsel + (size_t)n * (sk ? out_px : in_px) * Cs);
         T_lo = (unsigned)sb; T_hi = (unsigned)(sb >> 32);
         T_cc = (unsigned)Cs | ((unsigned)cb << 16);
-        const unsigned long long wb = reinterpret_cast<unsigned long long>(sk ? a.skip_w : a.w) + (((size_t)(c0 >> 4) * k.ntiles + nt0) * 128 << 4);
+        const unsigned long long wb = reinterpret_cast<unsigned long long>(sk ? a.skip_w : a.w) + (((size_t)(c0 >> 4) * k.ntiles + nt0) * FRAG_BYTES);
         T_wlo = (unsigned)wb; T_whi = (unsigned)(wb >> 32);
     }
 
     // ---- issue: global -> registers for iteration `it` (tile, chunk) ----
-    auto issue = [&](auto D_, const int ch, const int ty, const int tx) {
-        constexpr int d = decltype(D_)::value;
+    auto issue = [&](const int ch, const int ty, const int tx) {
         const unsigned cc = __builtin_amdgcn_readlane(T_cc, ch);
         const int Cs = cc & 0xffffu, cb = cc >> 16;
         const char* srcb = reinterpret_cast<const char*>(((unsigned long long)(unsigned)__builtin_amdgcn_readlane(T_hi, ch) << 32) |
@@ -266,15 +256,15 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
                 const unsigned c = (unsigned)cb + 4u * (unsigned)tq;
                 const unsigned cq = min(c, (unsigned)Cs - 4u);
                 const int ix = ox0 + px;
-                xok[d] = (c < (unsigned)Cs) & (ix < Wc);
+                xok[0] = (c < (unsigned)Cs) & (ix < Wc);
                 const unsigned colb = ((unsigned)min(ix, Wc - 1) * (unsigned)Cs + cq) << 2;
                 const unsigned rowb = (unsigned)aWin * (unsigned)Cs * 4u;
-                rowmask[d] = 0;
+                rowmask[0] = 0;
 #pragma unroll
                 for (int i = 0; i < NITEM_S; ++i) {
                     const int iy = oy0 + i;
-                    reg[d][i] = load16_uniform_base(srcb + (size_t)((unsigned)min(iy, Hc - 1) * rowb), colb);
-                    rowmask[d] |= (iy < Hc ? 1u : 0u) << i;
+                    reg[i] = load16_uniform_base(srcb + (size_t)((unsigned)min(iy, Hc - 1) * rowb), colb);
+                    rowmask[0] |= (iy < Hc ? 1u : 0u) << i;
                 }
                 return;
             }
@@ -287,86 +277,60 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
         //  pass then drains the whole prefetch (vmcnt(0)) at the join.)
         unsigned t_ = tid;
         asm volatile("" : "+v"(t_));     // recompute the item geometry each call: hoisting it costs more registers than ALU
-        if constexpr (ROWS) {
-            const int tq = t_ % QPP, px = (t_ / QPP) % CW;
-            const unsigned c = (unsigned)cb + 4u * (unsigned)tq;
-            const unsigned cq = min(c, (unsigned)Cs - 4u);
-            const bool cok = c < (unsigned)Cs;
-            const unsigned rowb = (unsigned)aWin * (unsigned)Cs * 4u;            // bytes per source row (uniform)
-            {
-                const int ix = ox0 * STRIDE + px;                                  // core columns: halo x = px + PAD
-                xok[d] = cok & (ix < Wc);
-                const int ixc = min(ix, Wc - 1);
-                const unsigned colb = ((unsigned)(ixc >> ups) * (unsigned)Cs + cq) << 2;
-                rowmask[d] = 0;
+        const int tq = t_ % QPP, px = (t_ / QPP) % CW;
+        const unsigned c = (unsigned)cb + 4u * (unsigned)tq;
+        const unsigned cq = min(c, (unsigned)Cs - 4u);
+        const bool cok = c < (unsigned)Cs;
+        const unsigned rowb = (unsigned)aWin * (unsigned)Cs * 4u;            // bytes per source row (uniform)
+        {
+            const int ix = ox0 * STRIDE + px;                                  // core columns: halo x = px + PAD
+            xok[0] = cok & (ix < Wc);
+            const int ixc = min(ix, Wc - 1);
+            const unsigned colb = ((unsigned)(ixc >> ups) * (unsigned)Cs + cq) << 2;
+            rowmask[0] = 0;
 #pragma unroll
-                for (int i = 0; i < NCORE; ++i) {
-                    const int row = rip + i * RPP;
-                    const int iy = oy0 * STRIDE - PAD + row;
-                    const bool rok = ((unsigned)iy < (unsigned)Hc) & ((i + 1) * RPP <= HHt || row < HHt);
-                    // (skip-segment chunks feed the centre tap only: their halo rows/columns are never read, so those requests
-                    //  are pointed at the nearest core row/column — a cache hit instead of 25 % more HBM lines)
-                    const int iyc = min(max(iy, ylo), yhi);
-                    const unsigned sy = (unsigned)(iyc >> ups);
-                    if constexpr (ROW_UNIFORM) reg[d][i] = load16_uniform_base(srcb + (size_t)(sy * rowb), colb);
-                    else reg[d][i] = load16_global(srcb + (sy * rowb + colb));
-                    rowmask[d] |= (rok ? 1u : 0u) << i;
-                }
+            for (int i = 0; i < NCORE; ++i) {
+                const int row = rip + i * RPP;
+                const int iy = oy0 * STRIDE - PAD + row;
+                const bool rok = ((unsigned)iy < (unsigned)Hc) & ((i + 1) * RPP <= HHt || row < HHt);
+                // (skip-segment chunks feed the centre tap only: their halo rows/columns are never read, so those requests
+                //  are pointed at the nearest core row/column — a cache hit instead of 25 % more HBM lines)
+                const int iyc = min(max(iy, ylo), yhi);
+                const unsigned sy = (unsigned)(iyc >> ups);
+                if constexpr (ROW_UNIFORM) reg[i] = load16_uniform_base(srcb + (size_t)(sy * rowb), colb);
+                else reg[i] = load16_global(srcb + (sy * rowb + colb));
+                rowmask[0] |= (rok ? 1u : 0u) << i;
             }
-            evalid[d] = 0;
+        }
+        evalid[0] = 0;
 #pragma unroll
-            for (int j = 0; j < NEDGE; ++j) {
-                const unsigned e = t_ + j * NT;
-                const unsigned side = (e / QPP) % ECOLS, row = e / (ECOLS * QPP);
-                const int hx = side < (unsigned)PAD ? (int)side : CW + (int)side;
-                const int iy = oy0 * STRIDE - PAD + (int)row, ix = ox0 * STRIDE - PAD + hx;
-                const bool ok = cok & (e < (unsigned)EDGE_ITEMS) & ((unsigned)iy < (unsigned)Hc) & ((unsigned)ix < (unsigned)Wc);
-                const int iyc = min(max(iy, ylo), yhi), ixc = min(max(ix, xlo), xhi);
-                const unsigned sy = (unsigned)(iyc >> ups), sx = (unsigned)(ixc >> ups);
-                reg[d][NCORE + j] = load16_global(srcb + (size_t)(sy * rowb + ((sx * (unsigned)Cs + cq) << 2)));
-                evalid[d] |= (ok ? 1u : 0u) << j;
-            }
-        } else {
-            valid[d] = 0;
-            // item = tid + i*NT  ->  halo pixel hp = item / QPP (hy = hp / HWt, hx = hp % HWt), channel quad q = item % QPP.
-            // NT % QPP == 0, so q is the same for every i and hp advances by NT/QPP: (hy, hx) are carried incrementally
-            // (unsigned, no per-item division).
-            constexpr unsigned DHP = NT / QPP, DHY = DHP / HWt, DHX = DHP % HWt;
-            const unsigned q = t_ % QPP, hp0 = t_ / QPP;
-            unsigned hy = hp0 / HWt, hx = hp0 % HWt;
-            const unsigned c = (unsigned)cb + 4u * q;
-            const unsigned cq = min(c, (unsigned)Cs - 4u);
-            const bool cok = c < (unsigned)Cs;
-#pragma unroll
-            for (int i = 0; i < NITEM; ++i) {
-                const int iy = oy0 * STRIDE - PAD + (int)hy, ix = ox0 * STRIDE - PAD + (int)hx;
-                // padding test: unsigned compare folds the < 0 and >= extent checks; no short-circuit branches
-                const bool ok = cok & ((unsigned)iy < (unsigned)Hc) & ((unsigned)ix < (unsigned)Wc) & (hy < (unsigned)HHt);
-                const int iyc = min(max(iy, 0), Hc - 1), ixc = min(max(ix, 0), Wc - 1);
-                const int sy = iyc >> ups, sx = ixc >> ups;
-                const unsigned off = ((unsigned)(sy * aWin + sx) * (unsigned)Cs + cq) << 2;      // bytes within the sample
-                reg[d][i] = load16_global(srcb + off);
-                valid[d] |= (ok ? 1u : 0u) << i;
-                hy += DHY; hx += DHX;
-                if (hx >= (unsigned)HWt) { hx -= HWt; hy += 1; }
-            }
+        for (int j = 0; j < NEDGE; ++j) {
+            const unsigned e = t_ + j * NT;
+            const unsigned side = (e / QPP) % ECOLS, row = e / (ECOLS * QPP);
+            const int hx = side < (unsigned)PAD ? (int)side : CW + (int)side;
+            const int iy = oy0 * STRIDE - PAD + (int)row, ix = ox0 * STRIDE - PAD + hx;
+            const bool ok = cok & (e < (unsigned)EDGE_ITEMS) & ((unsigned)iy < (unsigned)Hc) & ((unsigned)ix < (unsigned)Wc);
+            const int iyc = min(max(iy, ylo), yhi), ixc = min(max(ix, xlo), xhi);
+            const unsigned sy = (unsigned)(iyc >> ups), sx = (unsigned)(ixc >> ups);
+            reg[NCORE + j] = load16_global(srcb + (size_t)(sy * rowb + ((sx * (unsigned)Cs + cq) << 2)));
+            evalid[0] |= (ok ? 1u : 0u) << j;
         }
     };
     // ---- issueB: this chunk's weight fragments, global (L2-resident) -> registers.  Requested at the top of the
     //      iteration that consumes them — their (short) latency hides behind the commit's arithmetic — so that they
     //      do not occupy 4*NITEM_B registers across the MFMA phase and the epilogue like the halo prefetch does.
-    auto issueB = [&](auto D_, const int ch) {
-        constexpr int d = decltype(D_)::value;
+    auto issueB = [&](const int ch) {
         const bool sk = ch >= nchunk_main;
         unsigned t_ = tid;
         asm volatile("" : "+v"(t_));
         if (PREC != CCDM_PREC_F32 && !BDMA) {
             // B chunk: [tap][k-step] slabs; skip chunks carry one tap (1x1): only their first KST slabs are meaningful,
             // the passes beyond re-read slab 0 (the load stays unconditional: regB[] stays in registers)
+            // (wq .. nslab are derived here and again in issueB_dma: one shared derivation changed the code of every F16X3 instantiation)
             const char* wq = reinterpret_cast<const char*>(((unsigned long long)(unsigned)__builtin_amdgcn_readlane(T_whi, ch) << 32) |
                                                            (unsigned)__builtin_amdgcn_readlane(T_wlo, ch));
-            const unsigned wtap = (unsigned)((sk ? k.cin_pad_skip : k.cin_pad) >> 4) * k.ntiles * 128;
-            const unsigned wks = (unsigned)k.ntiles * 128;
+            const unsigned wtap = (unsigned)((sk ? k.cin_pad_skip : k.cin_pad) >> 4) * k.ntiles * FRAG_ITEMS;
+            const unsigned wks = (unsigned)k.ntiles * FRAG_ITEMS;
             const bool skwc = SKW && skw && sk;                          // wide skip chunk: 2 k-steps of the one tap
             const unsigned nslab = skwc ? (unsigned)(CKS / 16) : (sk ? KST : NTAP * KST);
             const unsigned remb = (B_MULTI ? t_ % G : t_) << 4;      // lane offset, 32-bit (hoisted as a 64-bit pair it defeats the saddr form)
@@ -376,7 +340,7 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
                 const unsigned rem = B_MULTI ? remb : remb + (unsigned)(NT * (i % DB) * 16);
                 ts = ts < nslab ? ts : 0u;
                 const unsigned slab = skwc ? ts * wks : (ts / KST) * wtap + (ts % KST) * wks;
-                regB[0][i] = load16_uniform_base(wq + ((size_t)slab << 4), rem);
+                regB[i] = load16_uniform_base(wq + ((size_t)slab << 4), rem);
             }
         }
     };
@@ -389,11 +353,11 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
         const bool sk = ch >= nchunk_main;
         const char* wq = reinterpret_cast<const char*>(((unsigned long long)(unsigned)__builtin_amdgcn_readlane(T_whi, ch) << 32) |
                                                        (unsigned)__builtin_amdgcn_readlane(T_wlo, ch));
-        const unsigned wtap = (unsigned)((sk ? k.cin_pad_skip : k.cin_pad) >> 4) * k.ntiles * 128;
-        const unsigned wks = (unsigned)k.ntiles * 128;
+        const unsigned wtap = (unsigned)((sk ? k.cin_pad_skip : k.cin_pad) >> 4) * k.ntiles * FRAG_ITEMS;
+        const unsigned wks = (unsigned)k.ntiles * FRAG_ITEMS;
         const bool skwc = SKW && skw && sk;
         const unsigned nslab = skwc ? (unsigned)(CKS / 16) : (sk ? KST : NTAP * KST);
-        constexpr int UPS = G / 64;                                   // 1 KB units per slab
+        constexpr int UPS = G / 64;                                   // 1 KB units per slab (one wave request = half an n-tile's fragment pair)
         constexpr int NWV = WAVES * KSP;
         constexpr int MAXU = (NTAP * KST * UPS + NWV - 1) / NWV;
         const unsigned nunit = nslab * UPS;
@@ -406,17 +370,16 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
             if (u < nunit) {
                 const unsigned ts = u / UPS, part = u % UPS;
                 const unsigned slab = skwc ? ts * wks : (ts / KST) * wtap + (ts % KST) * wks;
-                const char* src = wq + (((size_t)slab + part * 64) << 4) + (lane_ << 4);
+                const char* src = wq + (((size_t)slab + part * (FRAG_ITEMS / 2)) << 4) + (lane_ << 4);
                 __builtin_amdgcn_global_load_lds(reinterpret_cast<const __attribute__((address_space(1))) void*>(reinterpret_cast<unsigned long long>(src)),
-                                                 reinterpret_cast<__attribute__((address_space(3))) void*>(dst0 + u * 1024u), 16, 0, 0);
+                                                 reinterpret_cast<__attribute__((address_space(3))) void*>(dst0 + u * (unsigned)(FRAG_BYTES / 2)), 16, 0, 0);
             }
         }
     };
     // ---- commit: registers -> affine -> SiLU -> [fp16 hi|lo split] -> LDS (zero where padded) ----
     // The chunk's transform is uniform (GroupNorm / SiLU apply to the main segment only): one specialised, branch-free
     // body per combination; padding is a select, not a branch.
-    auto commit_body = [&](auto D_, auto GN_, auto ACT_, int c0) {
-        constexpr int d = decltype(D_)::value;
+    auto commit_body = [&](auto GN_, auto ACT_, int c0) {
         constexpr bool GN = decltype(GN_)::value, ACT = decltype(ACT_)::value;
         unsigned t_ = tid;
         asm volatile("" : "+v"(t_));
@@ -446,7 +409,7 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
             if (GN) { v.x = fmaf(v.x, t0.x, t0.y); v.y = fmaf(v.y, t1.x, t1.y); v.z = fmaf(v.z, t2.x, t2.y); v.w = fmaf(v.w, t3.x, t3.y); }
             v.x = act(v.x); v.y = act(v.y); v.z = act(v.z); v.w = act(v.w);
             if (PREC == CCDM_PREC_F32) {
-                float* d = halo + hp * 33 + 4 * tq;
+                float* d = halo + hp * PIX_F32 + 4 * tq;
                 d[0] = ok ? v.x : 0.f; d[1] = ok ? v.y : 0.f; d[2] = ok ? v.z : 0.f; d[3] = ok ? v.w : 0.f;
             } else {
                 // fp16 hi/lo split: x = hi + lo + O(2^-22 |x|); both halves round-to-nearest; full split precision holds for
@@ -485,49 +448,40 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
             *reinterpret_cast<u32x2*>(d) = z;
             *reinterpret_cast<u32x2*>(d + 2 * CK) = z;
         };
-        if constexpr (ROWS) {
-            const int hp0 = rip * HWt + PAD + px;
-            if (ROW_UNIFORM && PREC != CCDM_PREC_F32 && k.core_unmasked) {
-                // the row test is wave-uniform (scalar branch); inside the image nothing is masked
+        const int hp0 = rip * HWt + PAD + px;
+        if (ROW_UNIFORM && PREC != CCDM_PREC_F32 && k.core_unmasked) {
+            // the row test is wave-uniform (scalar branch); inside the image nothing is masked
 #pragma unroll
-                for (int i = 0; i < NCORE; ++i)
-                    if ((i + 1) * RPP <= HHt || rip + i * RPP < HHt) {
-                        if (__builtin_amdgcn_readfirstlane((rowmask[d] >> i) & 1u)) put(std::false_type{}, reg[d][i], true, hp0 + i * RPP * HWt);
-                        else put_zero(hp0 + i * RPP * HWt);
-                    }
-            } else {
-#pragma unroll
-                for (int i = 0; i < NCORE; ++i)
-                    if ((i + 1) * RPP <= HHt || rip + i * RPP < HHt)
-                        put(std::true_type{}, reg[d][i], xok[d] & (((rowmask[d] >> i) & 1u) != 0u), hp0 + i * RPP * HWt);
-            }
-#pragma unroll
-            for (int j = 0; j < NEDGE; ++j) {
-                const unsigned e = t_ + j * NT;
-                if (e < (unsigned)EDGE_ITEMS) {
-                    const unsigned side = (e / QPP) % ECOLS, row = e / (ECOLS * QPP);
-                    const int hx = side < (unsigned)PAD ? (int)side : CW + (int)side;
-                    put(std::true_type{}, reg[d][NCORE + j], ((evalid[d] >> j) & 1u) != 0u, (int)row * HWt + hx);
+            for (int i = 0; i < NCORE; ++i)
+                if ((i + 1) * RPP <= HHt || rip + i * RPP < HHt) {
+                    if (__builtin_amdgcn_readfirstlane((rowmask[0] >> i) & 1u)) put(std::false_type{}, reg[i], true, hp0 + i * RPP * HWt);
+                    else put_zero(hp0 + i * RPP * HWt);
                 }
-            }
         } else {
 #pragma unroll
-            for (int i = 0; i < NITEM; ++i) {
-                const unsigned item = t_ + i * NT;
-                if (item < (unsigned)(HP * QPP)) put(std::true_type{}, reg[d][i], ((valid[d] >> i) & 1u) != 0u, (int)(item / QPP));
+            for (int i = 0; i < NCORE; ++i)
+                if ((i + 1) * RPP <= HHt || rip + i * RPP < HHt)
+                    put(std::true_type{}, reg[i], xok[0] & (((rowmask[0] >> i) & 1u) != 0u), hp0 + i * RPP * HWt);
+        }
+#pragma unroll
+        for (int j = 0; j < NEDGE; ++j) {
+            const unsigned e = t_ + j * NT;
+            if (e < (unsigned)EDGE_ITEMS) {
+                const unsigned side = (e / QPP) % ECOLS, row = e / (ECOLS * QPP);
+                const int hx = side < (unsigned)PAD ? (int)side : CW + (int)side;
+                put(std::true_type{}, reg[NCORE + j], ((evalid[0] >> j) & 1u) != 0u, (int)row * HWt + hx);
             }
         }
         if (PREC != CCDM_PREC_F32 && !BDMA) {
 #pragma unroll
             for (int i = 0; i < NITEM_B; ++i) {
                 const int j = (int)t_ + i * NT;
-                if ((i + 1) * NT <= NB4 || j < NB4) ldsB[j] = regB[0][i];
+                if ((i + 1) * NT <= NB4 || j < NB4) ldsB[j] = regB[i];
             }
         }
     };
     // wide skip chunk: raw values (x 2^4), split, core pixel p = row * TW + px at 144-byte pitch; its two fragment slabs behind them
-    auto commit_skipw = [&](auto D_) {
-        constexpr int d = decltype(D_)::value;
+    auto commit_skipw = [&]() {
         if constexpr (SKW) {
             unsigned t_ = tid;
             asm volatile("" : "+v"(t_));
@@ -535,8 +489,8 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
             typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
             for (int i = 0; i < NITEM_S; ++i) {
-                const bool ok = xok[d] & (((rowmask[d] >> i) & 1u) != 0u);
-                const f32x4 r = reg[d][i];
+                const bool ok = xok[0] & (((rowmask[0] >> i) & 1u) != 0u);
+                const f32x4 r = reg[i];
                 const float lim = ok ? __builtin_inff() : 0.f;         // padding -> 0 (one select per item, as in the main path)
                 const float v0 = __builtin_amdgcn_fmed3f(r[0] * ACT_PRESCALE, -lim, lim), v1 = __builtin_amdgcn_fmed3f(r[1] * ACT_PRESCALE, -lim, lim);
                 const float v2 = __builtin_amdgcn_fmed3f(r[2] * ACT_PRESCALE, -lim, lim), v3 = __builtin_amdgcn_fmed3f(r[3] * ACT_PRESCALE, -lim, lim);
@@ -549,18 +503,18 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
                 *reinterpret_cast<u32x2*>(dd) = hi;
                 *reinterpret_cast<u32x2*>(dd + 2 * CKS) = lo;
             }
-            if (!BDMA) reinterpret_cast<f32x4*>(halo_b + TH * TW * PIXS)[t_] = regB[0][0];      // [k-step][hi|lo][64 lanes] x 16 B: NT = 2 * 128 items
+            if (!BDMA) reinterpret_cast<f32x4*>(halo_b + TH * TW * PIXS)[t_] = regB[0];      // [k-step][hi|lo][64 lanes] x 16 B: NT = 2 * FRAG_ITEMS
         }
     };
-    auto commit = [&](auto D_, const int ch) {
+    auto commit = [&](const int ch) {
         const bool sk = ch >= nchunk_main;
-        if (SKW && skw && sk) { commit_skipw(D_); return; }
+        if (SKW && skw && sk) { commit_skipw(); return; }
         const int c0 = (sk ? ch - nchunk_main : ch) * CK;
         const bool gn = has_gn && !sk, act = a.act == CCDM_ACT_SILU && !sk;
-        if (gn && act) commit_body(D_, std::true_type{}, std::true_type{}, c0);
-        else if (gn) commit_body(D_, std::true_type{}, std::false_type{}, c0);
-        else if (act) commit_body(D_, std::false_type{}, std::true_type{}, c0);
-        else commit_body(D_, std::false_type{}, std::false_type{}, c0);
+        if (gn && act) commit_body(std::true_type{}, std::true_type{}, c0);
+        else if (gn) commit_body(std::true_type{}, std::false_type{}, c0);
+        else if (act) commit_body(std::false_type{}, std::true_type{}, c0);
+        else commit_body(std::false_type{}, std::false_type{}, c0);
     };
 
     f32x16 acc[MI][NI];
@@ -577,7 +531,7 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
     int pf_ch = 0, pf_ty = cur_ty, pf_tx = cur_tx;
     // prologue: the first halo request
     // (a launch always has n_iter >= 1: slices <= tiles)
-    issue(std::integral_constant<int, 0>{}, pf_ch, pf_ty, pf_tx);
+    issue(pf_ch, pf_ty, pf_tx);
     advance(pf_ch, pf_ty, pf_tx);
     __builtin_amdgcn_sched_barrier(0);
     // the small loads issued at the top are consumed here, behind the first halo request
@@ -592,8 +546,8 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
     // GroupNorm's (scale, shift) table for this sample, from the prefetched partials (the halo region of LDS is free until the
     // first commit, which sits behind the loop-top barrier)
     if (has_gn) gn_affine_block(a, n, emb_row, gpf, reinterpret_cast<f64x2*>(halo_b), ab, blockDim.x);
-    // one iteration = one (tile, chunk); D_ = the register set it consumes (static: the loop below is unrolled by DEPTH)
-    auto iterate = [&](auto D_) {
+    // one iteration = one (tile, chunk)
+    auto iterate = [&]() {
         if (chunk == 0) {
 #pragma unroll
             for (int mi = 0; mi < MI; ++mi)
@@ -602,21 +556,21 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
 #pragma unroll
                     for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.0f;
         }
-        issueB(D_, chunk);
+        issueB(chunk);
         __syncthreads();          // previous MFMA phase has finished reading LDS (and ab[] is visible)
         if constexpr (BDMA) {
             // (the halo registers were requested an iteration ago; naming them here makes the compiler place its wait for them in
             //  front of the DMA requests — with a DMA in flight it would otherwise wait for EVERYTHING at the commit's first use)
 #pragma unroll
-            for (int i = 0; i < NITEM_R; ++i) asm volatile("" : "+v"(reg[0][i]));
+            for (int i = 0; i < NITEM_R; ++i) asm volatile("" : "+v"(reg[i]));
             issueB_dma(chunk);
         }
-        commit(D_, chunk);
+        commit(chunk);
         __syncthreads();
         // next tile-chunk's HBM reads fly during the MFMA phase (after the last iteration this requests a tile past the
         // slice's last one: addresses are clamped into the tensor, the data is never committed — harmless, branch-free);
-        // this refills the set just committed: iteration it + DEPTH
-        issue(D_, pf_ch, pf_ty, pf_tx);
+        // this refills the set just committed
+        issue(pf_ch, pf_ty, pf_tx);
         advance(pf_ch, pf_ty, pf_tx);
 
         const bool skc = chunk >= nchunk_main;                   // uniform
@@ -628,7 +582,7 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
 #pragma unroll
             for (int tap = 0; tap < KS * KS; ++tap) {
                 if (skc && tap != (KS * KS) / 2) continue;       // skip segment: centre tap only, its weights are tap 0
-                const int toff = ((tap / KS) * HWt + (tap % KS)) * 33;
+                const int toff = ((tap / KS) * HWt + (tap % KS)) * PIX_F32;
                 const float* wt = wc + (skc ? 0 : tap * wtap);
 #pragma unroll 4
                 for (int kk = 0; kk < CK / 2; ++kk) {
@@ -668,8 +622,8 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
                 frag_load_a(buf, toff, ks);
 #pragma unroll
                 for (int ni = 0; ni < NI; ++ni) {
-                    bh[buf][ni] = bq[((bt * KST + ks) * NI + ni) * 128];
-                    bl[buf][ni] = bq[((bt * KST + ks) * NI + ni) * 128 + 64];
+                    bh[buf][ni] = bq[((bt * KST + ks) * NI + ni) * FRAG_ITEMS];
+                    bl[buf][ni] = bq[((bt * KST + ks) * NI + ni) * FRAG_ITEMS + FRAG_ITEMS / 2];
                 }
             };
             auto frag_mfma = [&](const int buf) {
@@ -727,8 +681,8 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
                         }
 #pragma unroll
                         for (int ni = 0; ni < NI; ++ni) {
-                            bh[0][ni] = bsk[(ks * NI + ni) * 128];
-                            bl[0][ni] = bsk[(ks * NI + ni) * 128 + 64];
+                            bh[0][ni] = bsk[(ks * NI + ni) * FRAG_ITEMS];
+                            bl[0][ni] = bsk[(ks * NI + ni) * FRAG_ITEMS + FRAG_ITEMS / 2];
                         }
                         frag_mfma(0);
                     }
@@ -747,7 +701,7 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
                             const int ta = r - (ni >> 1), tb = c - (ni & 1);
                             if (ta < 0 || ta > 1 || tb < 0 || tb > 1) continue;
                             const int bt = ta * 2 + tb;
-                            const f16x8 wh = bq[((bt * KST + ks) * NI + ni) * 128], wl = bq[((bt * KST + ks) * NI + ni) * 128 + 64];
+                            const f16x8 wh = bq[((bt * KST + ks) * NI + ni) * FRAG_ITEMS], wl = bq[((bt * KST + ks) * NI + ni) * FRAG_ITEMS + FRAG_ITEMS / 2];
 #pragma unroll
                             for (int mi = 0; mi < MI; ++mi) {
                                 acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[0][mi], wh, acc[mi][ni], 0, 0, 0);
@@ -908,7 +862,7 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
         }
         advance(chunk, cur_ty, cur_tx);
     };
-    for (int it = 0; it < n_iter; ++it) iterate(std::integral_constant<int, 0>{});
+    for (int it = 0; it < n_iter; ++it) iterate();
 
     if (a.out_stats) {
         // fold the lanes that hold the same channel, then the block's waves; fixed order everywhere
@@ -1075,8 +1029,14 @@ static bool conv_takes_ks(const ccdm_conv_args& a) {
     return a.up != 2 && !a.fine_slices && conv_ks_eligible(a);
 }
 
+// statistics slots of the sub-pixel upsample form (tiled in the input space): one per slice with four phases per block (8x16 tiles),
+// one per (slice, phase) with one phase per block (8x8 tiles)
+static int upconv_out_slices(int Hin, int Win, int fine) {
+    return (conv_geo(Hin, Win, 1, true).TW == 16 ? 1 : 4) * conv_slices(Hin, Win, 1, true, fine);
+}
+
 int conv_out_slices(const ccdm_conv_args& a) {
-    if (a.up == 2) return (conv_geo(a.Hin, a.Win, 1, true).TW == 16 ? 1 : 4) * conv_slices(a.Hin, a.Win, 1, true, a.fine_slices);
+    if (a.up == 2) return upconv_out_slices(a.Hin, a.Win, a.fine_slices);
     if (conv_takes_ks(a)) return conv_ks_slices(a);
     return conv_slices(a.Hout, a.Wout, a.stride, false, a.fine_slices);
 }
@@ -1182,13 +1142,13 @@ int launch_conv(const ccdm_conv_args& a, hipStream_t s) {
     CCDM_REQUIRE(a.SC1 == 0 || a.SC0 % ck == 0, "conv: first skip source has %d channels; a concatenated input must split at a multiple of the %d-channel chunk", a.SC0, ck);
     CCDM_REQUIRE((k.cin_pad + k.cin_pad_skip) / ck <= 64, "conv: %d input (+%d skip) channels make more than 64 chunks of %d (chunk descriptors live in the 64 lanes of a register)",
                  k.cin_pad, k.cin_pad_skip, ck);
-    size_t lds = (size_t)HP * (prec == CCDM_PREC_F32 ? 33 * 4 : ck * 4 + 16);
+    size_t lds = (size_t)HP * conv_pixb(prec, ck);
     lds = (lds + 15) / 16 * 16;
-    if (prec != CCDM_PREC_F32) lds += (size_t)(up2 ? 4 : a.ksize * a.ksize) * (ck / 16) * NI * 128 * 16;     // staged B chunk
+    if (prec != CCDM_PREC_F32) lds += (size_t)(up2 ? 4 : a.ksize * a.ksize) * (ck / 16) * NI * FRAG_BYTES;     // staged B chunk
     const int ksp = tap_split(a, g) ? 3 : 1;
     const size_t red = (size_t)g.waves * ksp * NI * 32 * 16;
     if (lds < red) lds = red;
-    const size_t epi = (size_t)g.waves * ksp * g.MI * 32 * 36 * 4;        // epilogue transpose buffer (wave-private rows)
+    const size_t epi = (size_t)g.waves * ksp * g.MI * 32 * EPI_ROW * 4;   // epilogue transpose buffer (wave-private rows)
     if (lds < epi) lds = epi;
     if (a.stats0) {
         const size_t nthreads = (size_t)g.waves * ksp * 64;
@@ -1218,7 +1178,7 @@ extern "C" int ccdm_upconv_supported(int Cin, int Cout, int prec) {
 }
 
 extern "C" int ccdm_upconv_slices(int Hin, int Win) {
-    return (ccdm::conv_geo(Hin, Win, 1, true).TW == 16 ? 1 : 4) * ccdm::conv_slices(Hin, Win, 1, true);
+    return ccdm::upconv_out_slices(Hin, Win, 0);
 }
 
 extern "C" int ccdm_conv_out_slices(const ccdm_conv_args* a) {
@@ -1227,7 +1187,7 @@ extern "C" int ccdm_conv_out_slices(const ccdm_conv_args* a) {
 }
 
 extern "C" int ccdm_conv_slices_ex(int Hin, int Win, int ksize, int stride, int up, int fine) {
-    if (up == 2) return (ccdm::conv_geo(Hin, Win, 1, true).TW == 16 ? 1 : 4) * ccdm::conv_slices(Hin, Win, 1, true, fine);
+    if (up == 2) return ccdm::upconv_out_slices(Hin, Win, fine);
     const int Hc = up ? 2 * Hin : Hin, Wc = up ? 2 * Win : Win, pad = ksize / 2;
     return ccdm::conv_slices((Hc + 2 * pad - ksize) / stride + 1, (Wc + 2 * pad - ksize) / stride + 1, stride, false, fine);
 }

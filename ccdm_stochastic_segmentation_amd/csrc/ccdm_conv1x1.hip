@@ -50,8 +50,8 @@ __global__ __launch_bounds__(MAXT) void k_conv1x1(const Conv1x1K k) {
     const int p = slice * k.px_per_block + wave * 32 + row;                    // pixel within the sample
     const int nks = k.C >> 4;
     const char* ap = reinterpret_cast<const char*>(k.in + ((size_t)n * k.HW + p) * k.C + 8 * kg);
-    const char* bp = static_cast<const char*>(k.w) + (((size_t)nt * 128 + lane) << 4);
-    const size_t bks = (size_t)k.ntiles * 128 * 16;                            // bytes per k-step of the packed weights
+    const char* bp = static_cast<const char*>(k.w) + (((size_t)nt * FRAG_ITEMS + lane) << 4);
+    const size_t bks = (size_t)k.ntiles * FRAG_BYTES;                            // bytes per k-step of the packed weights
     const int co = nt * 32 + row;                                              // this lane's output channel
     // accumulator register r holds pixel wave*32 + (r & 3) + 8 * (r >> 2) + 4 * kg of the block
     const size_t obase = ((size_t)n * k.HW + slice * k.px_per_block + wave * 32 + 4 * kg) * k.Cout + co;
@@ -66,7 +66,7 @@ __global__ __launch_bounds__(MAXT) void k_conv1x1(const Conv1x1K k) {
             a0[i] = load16_global(ap + ks * 64);
             a1[i] = load16_global(ap + ks * 64 + 16);
             bh[i] = load16_global(bp + ks * bks);
-            bl[i] = load16_global(bp + ks * bks + 1024);
+            bl[i] = load16_global(bp + ks * bks + FRAG_BYTES / 2);
         }
     };
     issue(0);
@@ -160,7 +160,7 @@ __global__ __launch_bounds__(256) void k_conv1x1_multi(const Conv1x1K k, const i
     const int p = slice * k.px_per_block + wave * 32 + row;
     const int nks = k.C >> 4;
     const char* ap = reinterpret_cast<const char*>(k.in + ((size_t)n * k.HW + p) * k.C + 8 * kg);
-    const size_t bks = (size_t)k.ntiles * 128 * 16;
+    const size_t bks = (size_t)k.ntiles * FRAG_BYTES;
     const int nt_real = k.Cout >> 5;
     const int nt_first = blockIdx.y * ntb;
 
@@ -175,12 +175,12 @@ __global__ __launch_bounds__(256) void k_conv1x1_multi(const Conv1x1K k, const i
     }
     f32x4 bh[2][KSB], bl[2][KSB];
     auto issueB = [&](const int buf, const int nt) {
-        const char* bp = static_cast<const char*>(k.w) + (((size_t)min(nt, nt_real - 1) * 128 + lane) << 4);
+        const char* bp = static_cast<const char*>(k.w) + (((size_t)min(nt, nt_real - 1) * FRAG_ITEMS + lane) << 4);
 #pragma unroll
         for (int i = 0; i < KSB; ++i) {
             const int ks = min(i, nks - 1);
             bh[buf][i] = load16_global(bp + ks * bks);
-            bl[buf][i] = load16_global(bp + ks * bks + 1024);
+            bl[buf][i] = load16_global(bp + ks * bks + FRAG_BYTES / 2);
         }
     };
     issueB(0, nt_first);

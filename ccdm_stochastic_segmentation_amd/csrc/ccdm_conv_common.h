@@ -7,6 +7,19 @@ namespace ccdm {
 
 static constexpr float ACT_PRESCALE = 16.0f;       // F16X3 activation pre-scale (power of two)
 
+// LDS layout of the conv kernels, shared with the host code that sizes their launches.
+// Staged pixel of ck channels: F32 33 floats (odd stride: conflict-free column reads); F16X3 ck hi halfs | ck lo halfs | 16 B pad,
+// e.g. 80 B = 20 dwords at 16 channels: the 16 pixels of a ds_read_b128 lane group land on 16 disjoint 4-bank slots (20*p mod 64);
+// 144 B = 36 dwords at 32 channels, also conflict-free.
+constexpr int PIX_F32 = 33;
+constexpr int conv_pixb(int prec, int ck) { return prec == CCDM_PREC_F32 ? PIX_F32 * 4 : ck * 4 + 16; }      // bytes
+constexpr int EPI_ROW = 36;                        // floats per pixel row of the epilogues' transpose buffers (16-B aligned rows)
+// packed weight fragments of one (tap, k-step, n-tile): [hi|lo][64 lanes] x 16 B
+constexpr int FRAG_ITEMS = 128, FRAG_BYTES = FRAG_ITEMS * 16;
+// (The steps the four conv files repeat — the masked split-and-store of a staged quad, the lo*hi, hi*lo, hi*hi MFMA triple, the XCD
+//  block remap, the fp64 reduce-scatter over xor 32 / 16 / 8 — stay written out at each site: as __forceinline__ helpers here they
+//  changed the register allocation of k_conv and the schedule of k_conv_ks, k_upconv and k_conv1x1, profiles/r11_conv_refactor_isa.txt.)
+
 // Load 16 bytes from global memory at (wave-uniform pointer + 32-bit per-lane byte offset).  The pointer is passed
 // through readfirstlane so the compiler must keep it in scalar registers and select the saddr + voffset addressing
 // form: no 64-bit vector adds, one VGPR of address per load.
@@ -27,20 +40,13 @@ __device__ __forceinline__ f32x4 load16_global(const char* p) {
 }
 
 // NT: non-temporal (streaming) store — the line is marked evict-first in L2
-// CCDM_SC1_STORES (build-time probe): write-through stores (sc1: the line leaves the XCD's L2 at once) — what a kernel leaves dirty in
-// L2 is written back at the kernel boundary, B / 6 TB/s on the critical path of the next launch (MI355X_MICROARCH.md, "boundary")
 template <bool NT = false>
 __device__ __forceinline__ void store16_uniform_base(char* base, unsigned voff, const f32x4 v) {
     const unsigned long long u = reinterpret_cast<unsigned long long>(base);
     const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-#ifdef CCDM_SC1_STORES
-    const unsigned long long sb = ((unsigned long long)hi << 32) | lo;
-    asm volatile("global_store_dwordx4 %0, %1, %2 sc1" : : "v"(voff), "v"(v), "s"(sb) : "memory");
-#else
     __attribute__((address_space(1))) char* g = reinterpret_cast<__attribute__((address_space(1))) char*>(((unsigned long long)hi << 32) | lo);
     if (NT) __builtin_nontemporal_store(v, reinterpret_cast<__attribute__((address_space(1))) f32x4*>(g + voff));
     else *reinterpret_cast<__attribute__((address_space(1))) f32x4*>(g + voff) = v;
-#endif
 }
 // fp16 hi/lo split of two fp32 values: hi = RNE(x) packed, lo = RNE(x - hi) packed.  x - hi is one v_fma_mix_f32 (the fp16 half is
 // read straight out of the packed register and widened by the instruction: fma(hi, -1, x), exactly the subtraction's single rounding),
@@ -61,7 +67,6 @@ struct ConvK {   // kernel-side copy of ccdm_conv_args (+ derived)
     const float* wscale;     // F16X3: [ntiles*32] powers of two undoing the per-output-channel weight pre-scale
     int core_unmasked;       // every core column of every tile lies inside the image and every channel quad exists (W % TW == 0, C % CK == 0):
                              // core halo items need no per-lane padding mask, only the wave-uniform row test
-    void* reserved;          // unused; kept so that the hidden kernel arguments behind ConvK, and so the code of k_conv, stay where they are
 };
 
 // plain 1x1 conv (+bias +residual +statistics) of a low-resolution tensor without LDS staging (ccdm_conv1x1.hip)

@@ -38,7 +38,7 @@ struct ConvKS {
     int tiles_x, tiles_y;          // 8x8 output tiles per sample
     int C, SC;                     // input channels of the main / fused-skip segment
     int nks_m, nks_s;              // their 16-channel k-steps
-    int pitch_m, pitch_s;          // LDS bytes per staged pixel (64 * nks + 16)
+    int pitch_m, pitch_s;          // LDS bytes per staged pixel (conv_pixb of 16 * nks channels)
     int lgq_m, lgq_s;              // log2 of the lanes one staged pixel takes (channel quads rounded up to 16 / 32 / 64)
     int nit_m, nit_s;              // staging items per thread
     int skip_off;                  // LDS offset of the skip pixels within the staging region
@@ -167,7 +167,7 @@ __global__ __launch_bounds__(KS_NT, NI == 1 ? 2 : 1) void k_conv_ks(const ConvKS
         const bool sk = s >= nmain;
         const int ks = sk ? s - nmain : s / 9, tap = sk ? 0 : s - 9 * ks;
         const char* const base = static_cast<const char*>(sk ? a.skip_w : a.w);
-        return base + (((size_t)(tap * (sk ? k.nks_s : k.nks_m) + ks) * k.ntiles + nt) << 11);
+        return base + ((size_t)(tap * (sk ? k.nks_s : k.nks_m) + ks) * k.ntiles + nt) * FRAG_BYTES;
     };
     // The vector-memory front end of a CU takes ~40 B/clk from L2: the 147 KB of fragments a 128-channel block needs are ~3 700 cycles of
     // streaming.  Requested in one burst they stall every wave at issue for that long; so only the first pairs go out here, the rest
@@ -179,8 +179,8 @@ __global__ __launch_bounds__(KS_NT, NI == 1 ? 2 : 1) void k_conv_ks(const ConvKS
         const char* p = frag_ptr(j);
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni) {
-            bh[slot][ni] = load16_uniform_base(p, lane16 + 2048u * ni);
-            bl[slot][ni] = load16_uniform_base(p, lane16 + 2048u * ni + 1024u);
+            bh[slot][ni] = load16_uniform_base(p, lane16 + (unsigned)FRAG_BYTES * ni);
+            bl[slot][ni] = load16_uniform_base(p, lane16 + (unsigned)FRAG_BYTES * ni + FRAG_BYTES / 2);
         }
     };
 #pragma unroll
@@ -263,7 +263,7 @@ __global__ __launch_bounds__(KS_NT, NI == 1 ? 2 : 1) void k_conv_ks(const ConvKS
             *reinterpret_cast<u32x2*>(d + lo_off) = lo;
         };
         auto next_pair = [&](const int jj) {
-            if (jj < KS_BQ) load_set(jj < KS_BQ ? jj : 0, jj);
+            if (jj < KS_BQ) load_set(jj, jj);
         };
         const int Cm2 = 32 * k.nks_m, Cs2 = 32 * k.nks_s;               // bytes of a pixel's hi plane
         const bool wr_m = 4 * q_m < 16 * k.nks_m, wr_s = 4 * q_s < 16 * k.nks_s;      // lanes beyond the padded channel count write nothing
@@ -447,7 +447,7 @@ static int conv_ks_ni(const ccdm_conv_args& a) {
 }
 
 // geometry and resources of a launch; false = not for this kernel
-static bool conv_ks_plan(const ccdm_conv_args& a, ConvKS& k, size_t& lds, int& nit_max, int& NI) {
+static bool conv_ks_plan(const ccdm_conv_args& a, ConvKS& k, size_t& lds, int& NI) {
     if (a.prec != CCDM_PREC_F16X3) return false;                          // (a diagnostic bit in prec >> 8: the general kernel)
     if (a.ksize != 3 || a.up || a.film || (a.stride != 1 && a.stride != 2)) return false;
     if ((a.stats0 != nullptr) != (a.act == CCDM_ACT_SILU)) return false;  // built for GroupNorm + SiLU on load, or neither
@@ -461,14 +461,13 @@ static bool conv_ks_plan(const ccdm_conv_args& a, ConvKS& k, size_t& lds, int& n
     k.a = a;
     k.C = C; k.SC = SC;
     k.nks_m = cdiv(C, 16); k.nks_s = cdiv(SC, 16);
-    k.pitch_m = 64 * k.nks_m + 16; k.pitch_s = 64 * k.nks_s + 16;
+    k.pitch_m = conv_pixb(CCDM_PREC_F16X3, 16 * k.nks_m); k.pitch_s = conv_pixb(CCDM_PREC_F16X3, 16 * k.nks_s);
     k.lgq_m = pow2_lg_quads(k.nks_m); k.lgq_s = SC ? pow2_lg_quads(k.nks_s) : 6;
     const int HWt = 7 * a.stride + 3, HP = HWt * HWt;
     k.nit_m = cdiv(cdiv(HP, 64 >> k.lgq_m), KS_NW);
     k.nit_s = SC ? cdiv(64 >> (6 - k.lgq_s), KS_NW) : 0;
     // instantiations: stride 1: (13 halo items, no skip) or (8, 8); stride 2: (20, none)
-    nit_max = a.stride == 1 ? (SC ? 8 : 13) : 20;
-    if (k.nit_m > nit_max || k.nit_s > (a.stride == 1 && SC ? 8 : 0)) return false;
+    if (k.nit_m > (a.stride == 1 ? (SC ? 8 : 13) : 20) || k.nit_s > (a.stride == 1 && SC ? 8 : 0)) return false;
     k.skip_off = (HP * k.pitch_m + 15) / 16 * 16;
     k.nstep = 9 * k.nks_m + k.nks_s;
     k.tiles_x = a.Wout / 8; k.tiles_y = a.Hout / 8;
@@ -485,51 +484,47 @@ static bool conv_ks_plan(const ccdm_conv_args& a, ConvKS& k, size_t& lds, int& n
 bool conv_ks_eligible(const ccdm_conv_args& a) {
     ConvKS k;
     size_t lds;
-    int nit, ni;
-    return conv_ks_plan(a, k, lds, nit, ni);
+    int ni;
+    return conv_ks_plan(a, k, lds, ni);
 }
 
 // statistics slices a launch of this kernel leaves: one per 8x8 tile
 int conv_ks_slices(const ccdm_conv_args& a) { return (a.Hout / 8) * (a.Wout / 8); }
 
+// One launch table.  NI > 1 is built for the two combinations conv_ks_plan admits there: GroupNorm + SiLU on load at stride 1, raw at stride 2.
 template <int NI>
-static void launch_conv_ks_ni(const ConvKS& k, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
+static int launch_conv_ks_ni(const ConvKS& k, bool gnact, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
     const ccdm_conv_args& a = k.a;
-    const bool gnact = a.stats0 != nullptr;
-    if (a.stride == 1) {
+    if (a.stride == 1 && gnact) {
         if (a.skip0) hipLaunchKernelGGL((k_conv_ks<1, true, 8, 8, NI>), grid, block, lds, s, k);
         else hipLaunchKernelGGL((k_conv_ks<1, true, 13, 0, NI>), grid, block, lds, s, k);
-    } else {
-        hipLaunchKernelGGL((k_conv_ks<2, false, 20, 0, NI>), grid, block, lds, s, k);
+        return 0;
     }
-    (void)gnact;
+    if (a.stride == 2 && !gnact) { hipLaunchKernelGGL((k_conv_ks<2, false, 20, 0, NI>), grid, block, lds, s, k); return 0; }
+    if constexpr (NI == 1) {
+        if (a.stride == 2) hipLaunchKernelGGL((k_conv_ks<2, true, 20, 0, NI>), grid, block, lds, s, k);
+        else if (a.skip0) hipLaunchKernelGGL((k_conv_ks<1, false, 8, 8, NI>), grid, block, lds, s, k);
+        else hipLaunchKernelGGL((k_conv_ks<1, false, 13, 0, NI>), grid, block, lds, s, k);
+        return 0;
+    }
+    return fail("conv_ks: stride %d with%s GroupNorm is built for one n-tile per block only", a.stride, gnact ? "" : "out");
 }
 
 int launch_conv_ks(const ccdm_conv_args& a, int ntiles, const float* wscale, hipStream_t s) {
     ConvKS k;
     size_t lds;
-    int nit, NI;
-    if (!conv_ks_plan(a, k, lds, nit, NI)) return fail("conv_ks: geometry not built");
+    int NI;
+    if (!conv_ks_plan(a, k, lds, NI)) return fail("conv_ks: geometry not built");
     k.wscale = wscale;
     k.ntiles = ntiles;
     const dim3 grid(a.N * k.tiles_x * k.tiles_y, a.Cout / (32 * NI)), block(KS_NT);
-    if (NI == 4) { launch_conv_ks_ni<4>(k, grid, block, lds, s); return 0; }
-    if (NI == 3) { launch_conv_ks_ni<3>(k, grid, block, lds, s); return 0; }
-    if (NI == 2) { launch_conv_ks_ni<2>(k, grid, block, lds, s); return 0; }
     const bool gnact = a.stats0 != nullptr;
-    if (a.stride == 1) {
-        if (a.skip0) {
-            if (gnact) hipLaunchKernelGGL((k_conv_ks<1, true, 8, 8>), grid, block, lds, s, k);
-            else hipLaunchKernelGGL((k_conv_ks<1, false, 8, 8>), grid, block, lds, s, k);
-        } else {
-            if (gnact) hipLaunchKernelGGL((k_conv_ks<1, true, 13, 0>), grid, block, lds, s, k);
-            else hipLaunchKernelGGL((k_conv_ks<1, false, 13, 0>), grid, block, lds, s, k);
-        }
-    } else {
-        if (gnact) hipLaunchKernelGGL((k_conv_ks<2, true, 20, 0>), grid, block, lds, s, k);
-        else hipLaunchKernelGGL((k_conv_ks<2, false, 20, 0>), grid, block, lds, s, k);
+    switch (NI) {
+        case 4: return launch_conv_ks_ni<4>(k, gnact, grid, block, lds, s);
+        case 3: return launch_conv_ks_ni<3>(k, gnact, grid, block, lds, s);
+        case 2: return launch_conv_ks_ni<2>(k, gnact, grid, block, lds, s);
+        default: return launch_conv_ks_ni<1>(k, gnact, grid, block, lds, s);
     }
-    return 0;
 }
 
 }  // namespace ccdm

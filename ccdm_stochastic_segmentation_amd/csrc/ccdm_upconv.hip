@@ -42,18 +42,14 @@ struct UpK {
 };
 
 constexpr int UP_TH = 8, UP_HH = UP_TH + 2;
-constexpr int UP_EPS = 36;                                     // floats per pixel row of the transpose buffer
-constexpr int UP_EPI_BYTES = 4 * 32 * UP_EPS * 4;              // four wave-private [32 pixels][36] buffers
+constexpr int UP_EPI_BYTES = 4 * 32 * EPI_ROW * 4;             // four wave-private [32 pixels][EPI_ROW] transpose buffers
 constexpr int UP_CTB_MAX = 2;
-#ifndef CCDM_UP_BDEPTH
-#define CCDM_UP_BDEPTH 2
-#endif
-constexpr int UP_BD = CCDM_UP_BDEPTH;                         // weight fragments requested ahead of the one being multiplied
+constexpr int UP_BD = 2;                                       // weight fragments requested ahead of the one being multiplied
 
 // TW = 16: 8x16 input tiles, four 32-pixel sub-tiles per wave; TW = 8 (8-pixel-wide inputs: LIDC's 8x8 -> 16x16 launch): 8x8 tiles, two
 // sub-tiles per wave, and — like the general kernel's one-phase-per-block form there — one statistics partial per (slice, PHASE)
 template <int C, int TW> struct UpGeo {
-    static constexpr int PIXB = 4 * C + 16, QPP = C / 4, KS16 = C / 16, NF = KS16 * 4;
+    static constexpr int PIXB = conv_pixb(CCDM_PREC_F16X3, C), QPP = C / 4, KS16 = C / 16, NF = KS16 * 4;
     static constexpr int HW = TW + 2, HP = UP_HH * HW, MT = UP_TH * TW / 32;
     static constexpr int A_BYTES = HP * PIXB;
     static constexpr int NITEMS = (HP * QPP + 255) / 256;
@@ -87,7 +83,7 @@ __global__ __launch_bounds__(256, 2) void k_upconv(const UpK k) {
         const int p = mi * 32 + (lane & 31);
         hpb[mi] = ((p / UP_TW + dy) * UP_HW + (p % UP_TW + dx)) * PIXB + (lane >> 5) * 16;
     }
-    float* const epi = epi_all + wave * (32 * UP_EPS);
+    float* const epi = epi_all + wave * (32 * EPI_ROW);
     const int cq = lane & 7, prow = lane >> 3;
 
     // statistics: every stored value added in fp64, a tile's sums reduce-scattered over the 8 lanes of a channel quad into one fp64 running
@@ -145,8 +141,8 @@ __global__ __launch_bounds__(256, 2) void k_upconv(const UpK k) {
         for (int ct = 0; ct < k.ctb; ++ct) {
             const int nt = 4 * (ct0 + ct) + wave;                                      // this wave's n-tile of the packed 2x2 conv
             // fragment (k-step ks, window tap bt): slab ((bt * KS16 + ks) * ntiles + nt) of 2 KB, hi then lo
-            const char* const wb = static_cast<const char*>(k.w) + ((size_t)nt << 11);
-            const unsigned wstep = (unsigned)k.ntiles << 11;                            // bytes between consecutive (bt, ks) slabs
+            const char* const wb = static_cast<const char*>(k.w) + (size_t)nt * FRAG_BYTES;
+            const unsigned wstep = (unsigned)k.ntiles * FRAG_BYTES;                            // bytes between consecutive (bt, ks) slabs
             // walk order j -> (k-step, window tap): k-step outer, tap inner for the 8x16 tiles; for the 8x8 tiles pairs of k-steps outer, tap, then
             // the pair's two k-steps — each the order in which the general kernel's form of the same geometry accumulates (16- / 32-channel chunks)
             auto ks_of = [&](const int j) { return TW == 8 ? 2 * (j >> 3) + (j & 1) : j >> 2; };
@@ -155,7 +151,7 @@ __global__ __launch_bounds__(256, 2) void k_upconv(const UpK k) {
             f32x4 bq[UP_BD + 1][2];
             auto issue_b = [&](const int j) {
                 bq[j % (UP_BD + 1)][0] = load16_uniform_base(wb + frag_off(j), (unsigned)lane << 4);
-                bq[j % (UP_BD + 1)][1] = load16_uniform_base(wb + frag_off(j) + 1024, (unsigned)lane << 4);
+                bq[j % (UP_BD + 1)][1] = load16_uniform_base(wb + frag_off(j) + FRAG_BYTES / 2, (unsigned)lane << 4);
             };
 #pragma unroll
             for (int j = 0; j < UP_BD; ++j) issue_b(j);
@@ -202,13 +198,13 @@ __global__ __launch_bounds__(256, 2) void k_upconv(const UpK k) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int pl = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                    epi[pl * UP_EPS + (lane & 31)] = fmaf(acc[mi][r], wsc, add);        // wsc is a power of two: the product is exact
+                    epi[pl * EPI_ROW + (lane & 31)] = fmaf(acc[mi][r], wsc, add);        // wsc is a power of two: the product is exact
                 }
 #pragma unroll
                 for (int jr = 0; jr < 4; ++jr) {
                     // row pass jr: tile pixel p = 32 mi + 8 jr + prow -> tile row (32 mi + 8 jr) / TW, column (8 jr) % TW + prow
                     const int pl = jr * 8 + prow;
-                    const f32x4 o = *reinterpret_cast<const f32x4*>(epi + pl * UP_EPS + 4 * cq);
+                    const f32x4 o = *reinterpret_cast<const f32x4*>(epi + pl * EPI_ROW + 4 * cq);
                     const int row = (32 * mi + 8 * jr) / UP_TW, col0 = (8 * jr) % UP_TW;
                     const unsigned rb = (unsigned)(((2 * (oy0 + row) + dy) * Wout + 2 * (ox0 + col0) + dx) * Cout) << 2;      // uniform
                     store16_uniform_base(out_n + rb, lane_off, o);
@@ -263,9 +259,6 @@ bool upconv_eligible(const ccdm_conv_args& a) {
     if (a.C1 || a.in1 || a.stats0 || a.act != CCDM_ACT_NONE || a.film || a.emb_off >= 0 || a.resid || a.skip0 || a.fine_slices) return false;
     if (!(a.C0 == 32 || a.C0 == 64 || a.C0 == 96 || a.C0 == 128) || a.Cout % 32) return false;
     // a rule of the geometry, never of the batch: whole 8x16 tiles, or 8x8 tiles for 8-pixel-wide inputs (where the general rule tiles 8x8 too)
-#ifdef CCDM_UP_MAXPX
-    if (a.Hin * a.Win > CCDM_UP_MAXPX) return false;
-#endif
     return a.Hin % UP_TH == 0 && (a.Win % 16 == 0 || a.Win == 8);
 }
 
@@ -295,11 +288,7 @@ int launch_upconv(const ccdm_conv_args& a, int slices, int ntiles, const float* 
     // channel tiles per block: two from one staged tile while >= 512 blocks remain (a partitioning choice only: every output element
     // and every statistics partial is computed by the same instruction sequence either way)
     const int ctiles = a.Cout / 32;
-#ifdef CCDM_UP_CTB1
-    k.ctb = 1;
-#else
     k.ctb = (ctiles % 2 == 0 && (long)a.N * slices * (ctiles / 2) >= 512) ? 2 : 1;
-#endif
     const dim3 grid(a.N * slices, ctiles / k.ctb);
     const bool alias = k.ctb == 1;
     switch (a.C0) {

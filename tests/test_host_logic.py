@@ -111,6 +111,21 @@ def test_pack_conv_weight_layout():
     assert lib.ccdm_conv_slices_ex(256, 512, 3, 1, 0, 1) == lib.ccdm_conv_slices(256, 512, 1, 3) == 96
 
 
+@pytest.mark.parametrize("hin,win", [(8, 8), (8, 16), (16, 16), (32, 32), (64, 64), (128, 256)])
+def test_upconv_slice_counts_agree_across_entry_points(hin, win):
+    """The statistics slices an `up = 2` conv leaves, asked three ways (ccdm_conv_slices_ex from the input geometry,
+    ccdm_conv_out_slices from the argument struct, ccdm_upconv_slices for the default slicing), are one number.  8-wide inputs
+    tile with one phase per block (x 4 slots), wider ones with four phases per block.  Only the agreement is asserted."""
+    lib = hip.load()
+    for fine in (0, 1, 2):
+        a = hip.ConvArgs(C0=32, N=1, Hin=hin, Win=win, Hout=2 * hin, Wout=2 * win, ksize=3, stride=1, up=2, Cout=32,
+                         prec=hip.PREC_F16X3, emb_off=-1, fine_slices=fine)
+        ex = lib.ccdm_conv_slices_ex(hin, win, 3, 1, 2, fine)
+        assert lib.ccdm_conv_out_slices(ctypes.byref(a)) == ex, (fine, ex)
+        if fine == 0:
+            assert lib.ccdm_upconv_slices(hin, win) == ex
+
+
 def test_pack_upconv_weight_is_the_phase_summed_2x2_kernel():
     """ccdm_pack_upconv_weight (include/ccdm_hip.h, `up = 2`): Upsample + conv 3x3 (unet.py:106-116) as four 2x2 kernels — the 3x3 taps
     that fall on one low-resolution pixel added in fp64, rounded once, packed as a 2x2 conv with n-tile = 4 * (channel tile) + phase.  The

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Build the working-tree sources into tools/abx/<name>.so with extra hipcc flags, out of tree (same-box A/B of library builds through
 # CCDM_LIB; *.so stays out of git).
-#   tools/build_variant.sh <name> [hipcc flags...]      e.g.  tools/build_variant.sh new   |   tools/build_variant.sh up1 -DCCDM_UP_CTB1
+#   tools/build_variant.sh <name> [hipcc flags...]      e.g.  tools/build_variant.sh new   |   tools/build_variant.sh ilp -mllvm -amdgpu-sched-strategy=max-ilp
 set -e
 cd "$(dirname "$0")/.."
 NAME=${1:?name}; shift
