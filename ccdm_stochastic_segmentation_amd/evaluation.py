@@ -178,7 +178,14 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
     Launched under torchrun (WORLD_SIZE > 1, BASELINE config C3) every rank walks the same batches and samples its contiguous
     shard of the B_img*S flattened batch (distributed.sample_sharded: no collective inside the T loop, one gather of the
     predictions per batch); the metrics are then computed identically on every rank.
-    `model`: a ready DenoisingModel-like callable (tests inject fixed predictions); default: built from `params`."""
+    `model`: a ready DenoisingModel-like callable (tests inject fixed predictions); default: built from `params`.
+
+    Build-owned keys of the `evaluation` section (absent: the returned dict and everything else is as without them):
+         soft_labels: yes   the result gains "soft_labels": one dict per entry of `evaluations` with the scores of the first s
+                            samples' frequencies against the raters' soft labels (metrics.soft_label_scores_from_counts: calibration,
+                            Brier, cross-entropy, soft Dice, NCC; counts from one ccdm_lidcscore launch per batch and entry, kept per
+                            image and scored after the last batch); with `output_path` set, also written as lidc_soft_labels.json
+         soft_label_bins (10), soft_label_thresholds ([0.1, ..., 0.9])"""
     from . import distributed as D
     rank, local_rank, world = D.init_from_env()
     if device is None:
@@ -204,6 +211,8 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
     conf = torch.zeros((num_classes, num_classes), dtype=torch.int64)
     nonzero_total, n_img = 0, 0
     majority = getattr(model, "step_T_sample", None) in (None, "majority")
+    section = params.get("evaluation") or {}
+    soft = [([], []) for _ in evaluations] if section.get("soft_labels", False) else None       # per entry: (joint, moments) of every batch
     for image, labels, _ in loader:                                              # Tester.test_step, :89-136
         image = image.to(device).repeat_interleave(S, dim=0)
         # x_T: uniform one-hot from the CPU generator, full batch on every rank (same seed => same draw)
@@ -223,6 +232,9 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
             lcm = int(np.lcm(s, lab_idx.shape[1]))
             hm[i] += np.sum(M.batched_hungarian_matching(lab_idx.repeat_interleave(lcm // lab_idx.shape[1], dim=1),
                                                           pred_idx[:, :s].repeat_interleave(lcm // s, dim=1), num_classes))
+            if soft is not None:
+                joint, moments = M.vote_joint_counts(pred_idx[:, :s], lab_idx, num_classes)
+                soft[i][0].append(joint); soft[i][1].append(moments)
         # log-mean vote exactly as the reference takes it (:125): log(0) = -inf stays -inf (one-hot "majority" predictions:
         # a class any sample rejects is out; where every class is rejected by someone argmax falls to class 0)
         mean_pred = torch.log(prediction).mean(dim=1).argmax(dim=1)
@@ -243,6 +255,19 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
            "Dice": dice.tolist(), "nonzero": nonzero_total / (n_img * 4), "images": n_img, "world_size": world}
     for i, s in enumerate(evaluations):
         LOGGER.info("GED (%d): %.4g  diversity samples: %.4g  HM IoU: %.4g", s, res["GED"][i], res["diversity_samples"][i], res["HM_IoU"][i])
+    if soft is not None:
+        kw = {"bins": int(section.get("soft_label_bins", 10))}
+        if section.get("soft_label_thresholds") is not None:
+            kw["thresholds"] = [float(t) for t in section["soft_label_thresholds"]]
+        res["soft_labels"] = [M.soft_label_scores_from_counts(np.concatenate(j), np.concatenate(m), **kw) for j, m in soft]
+        for s, r in zip(evaluations, res["soft_labels"]):
+            LOGGER.info("soft labels (%d): ECE %.4g  Brier %.4g  Dice %.4g  NCC %s", s, r["ece_soft"], r["brier_soft"], r["dice_soft"], r["ncc"])
+        if params.get("output_path") and rank == 0:
+            import json
+            out_dir = expanduservars(params["output_path"])
+            os.makedirs(out_dir, exist_ok=True)
+            with open(os.path.join(out_dir, "lidc_soft_labels.json"), "w") as f:
+                json.dump(res["soft_labels"], f, indent=1)
     return res
 
 

@@ -316,6 +316,24 @@ int ccdm_pairwise_class_counts(const uint8_t* a /*dev [B,S,HW]*/, const uint8_t*
                                int HW, int K, int32_t* out /*dev [B,S,L,K,2]*/, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * LIDC soft-label scores, device part (beyond the reference, whose LIDC scores are all set scores): what the S samples of an
+ * image imply at a pixel, p_k = n_k / S, against the L raters' soft label there, q_k = m_k / L, in one read of both stacks.
+ * Per pixel p of image b:  n_k = #{s : samples[b,s,p] == k},  m_k = #{l : raters[b,l,p] == k}  for k < K; a byte >= K belongs
+ * to no class.  u = S*S - sum_k n_k^2 and v = L*L - sum_k m_k^2 are the Gini impurities of the two count vectors, scaled to
+ * integers.
+ *   joint    int32 [B][K][S+1][L+1]: joint[b][k][n][m] = the pixels of image b with n_k == n and m_k == m.  OVERWRITTEN per call;
+ *   moments  int64 [B][5]: {sum u, sum v, sum u^2, sum v^2, sum u*v} over the pixels of image b.  OVERWRITTEN per call.
+ * Either output may be NULL, not both.  1 <= S, L <= 255 (the four pixels a lane takes keep their counts of a class as the
+ * four bytes of a register), K in [1,32], 0 < HW < 2^31, K*(S+1)*(L+1) <= 16384 (one image's table as int32 in 64 KB of LDS;
+ * LIDC at K = 2, S = 100, L = 4 needs 1010 entries).  One dword per lane and map when HW % 4 == 0 and both pointers are 4-byte
+ * aligned, bytes otherwise: any alignment is accepted.  Integer arithmetic only: per-block counts in LDS, then integer atomics
+ * into the outputs after a hipMemsetAsync of them on `stream`: every count is exact in any order, two identical calls are
+ * bit-identical.  No workspace; B = 0 returns 0 without a launch and leaves the outputs as they are.
+ * ------------------------------------------------------------------------------------------------- */
+int ccdm_lidcscore(const uint8_t* samples /*dev [B,S,HW]*/, const uint8_t* raters /*dev [B,L,HW]*/, int B, int S, int L, int HW,
+                   int K, int32_t* joint /*dev [B][K][S+1][L+1] or NULL*/, int64_t* moments /*dev [B][5] or NULL*/, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Segmentation evaluation, device part (Cityscapes mIoU): the reference Evaluator's `infer_step` / `update_cm`
  * (evaluation/eval_cdm.py) in one pass, without a full-resolution probability tensor.  Per output pixel of [B,H,W]:
  *   - bilinear sample of the prediction [B,h,w] as ATen's upsample_bilinear2d (align_corners=False, no antialias) in fp32:
