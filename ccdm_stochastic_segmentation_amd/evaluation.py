@@ -185,7 +185,12 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
                             samples' frequencies against the raters' soft labels (metrics.soft_label_scores_from_counts: calibration,
                             Brier, cross-entropy, soft Dice, NCC; counts from one ccdm_lidcscore launch per batch and entry, kept per
                             image and scored after the last batch); with `output_path` set, also written as lidc_soft_labels.json
-         soft_label_bins (10), soft_label_thresholds ([0.1, ..., 0.9])"""
+         soft_label_bins (10), soft_label_thresholds ([0.1, ..., 0.9])
+         surface_distances: yes   the result gains "surface_distances": one dict per entry of `evaluations` with HD95, ASSD and
+                            the Hausdorff distance of the first s samples against the raters (metrics.surface_scores_from_stats; the
+                            per-cell integers from one ccdm_surfdist call per batch and entry, kept per image and scored after the
+                            last batch); with `output_path` set, also written as lidc_surface_distances.json
+         surface_distance_percentile (95): the percentile of HD95, read as the decimal it is written as"""
     from . import distributed as D
     rank, local_rank, world = D.init_from_env()
     if device is None:
@@ -213,6 +218,13 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
     majority = getattr(model, "step_T_sample", None) in (None, "majority")
     section = params.get("evaluation") or {}
     soft = [([], []) for _ in evaluations] if section.get("soft_labels", False) else None       # per entry: (joint, moments) of every batch
+    surf = [[] for _ in evaluations] if section.get("surface_distances", False) else None        # per entry: the stats of every batch
+    if surf is not None:
+        from fractions import Fraction
+        quantile = Fraction(str(section.get("surface_distance_percentile", 95))) / 100
+        if not 0 < quantile <= 1:
+            raise ValueError(f"surface_distance_percentile: {section.get('surface_distance_percentile')!r} (expected a value in (0, 100])")
+        surf_q = (quantile.numerator, quantile.denominator)
     for image, labels, _ in loader:                                              # Tester.test_step, :89-136
         image = image.to(device).repeat_interleave(S, dim=0)
         # x_T: uniform one-hot from the CPU generator, full batch on every rank (same seed => same draw)
@@ -235,6 +247,8 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
             if soft is not None:
                 joint, moments = M.vote_joint_counts(pred_idx[:, :s], lab_idx, num_classes)
                 soft[i][0].append(joint); soft[i][1].append(moments)
+            if surf is not None:
+                surf[i].append(M.surface_distance_stats(pred_idx[:, :s], lab_idx, num_classes, q=surf_q))
         # log-mean vote exactly as the reference takes it (:125): log(0) = -inf stays -inf (one-hot "majority" predictions:
         # a class any sample rejects is out; where every class is rejected by someone argmax falls to class 0)
         mean_pred = torch.log(prediction).mean(dim=1).argmax(dim=1)
@@ -268,6 +282,17 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
             os.makedirs(out_dir, exist_ok=True)
             with open(os.path.join(out_dir, "lidc_soft_labels.json"), "w") as f:
                 json.dump(res["soft_labels"], f, indent=1)
+    if surf is not None:
+        res["surface_distances"] = [M.surface_scores_from_stats(M.concat_surface_stats(parts)) for parts in surf]
+        for s, r in zip(evaluations, res["surface_distances"]):
+            LOGGER.info("surface distances (%d): HD%g %s  ASSD %s  HD %s  (%d of %d cells defined)", s, r["percentile"], r["hd_percentile"],
+                        r["assd"], r["hd"], r["cells_defined"], r["cells_defined"] + r["cells_undefined"])
+        if params.get("output_path") and rank == 0:
+            import json
+            out_dir = expanduservars(params["output_path"])
+            os.makedirs(out_dir, exist_ok=True)
+            with open(os.path.join(out_dir, "lidc_surface_distances.json"), "w") as f:
+                json.dump(res["surface_distances"], f, indent=1)
     return res
 
 

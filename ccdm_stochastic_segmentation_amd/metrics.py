@@ -9,7 +9,11 @@ problems with scipy, exactly as the reference does, so results are bit-identical
 Beyond the reference: the soft-label scores.  What the S samples imply at a pixel, p_k = (samples saying k) / S, against the
 raters' soft label there, q_k = (raters saying k) / L: `vote_joint_counts` (HIP kernel ccdm_lidcscore) counts the pixels of
 every image by (class, samples saying it, raters saying it), `soft_label_scores_from_counts` derives calibration, Brier score,
-cross-entropy, thresholded soft Dice and the uncertainty correlation (NCC) from those integers on the host."""
+cross-entropy, thresholded soft Dice and the uncertainty correlation (NCC) from those integers on the host.
+
+Also beyond the reference: the surface distances of every sample against every rater.  `surface_distance_stats` (HIP kernel
+ccdm_surfdist: an exact squared distance transform per map and class, then counts, maximum, two order statistics and two fp64 sums
+per (image, sample, rater, class)), `surface_scores_from_stats` derives HD95, ASSD and the Hausdorff distance on the host."""
 from __future__ import annotations
 
 import math
@@ -181,6 +185,95 @@ def soft_label_scores_from_counts(joint, moments, *, bins: int = 10, thresholds:
         "cross_entropy_soft": cross_entropy, "dice_soft": float(dice.mean()),
         "dice_soft_per_threshold": [float(x) for x in dice.mean(axis=(1, 2))],
         "ncc": float(np.mean(corr)) if corr else None, "ncc_images": len(corr), "reliability": reliability}
+    if class_names is not None:
+        res["class_names"] = [str(c) for c in class_names]
+    return res
+
+
+# ------------------------------------------------------------------------------------------------ surface distances
+SURFACE_STAT_FIELDS = ("n_ar", "n_ra", "d2_max", "d2_lo", "d2_hi")
+
+
+def surface_distance_stats(a_idx: torch.Tensor, b_idx: torch.Tensor, num_classes: int, q: Tuple[int, int] = (95, 100)) -> Dict[str, object]:
+    """a_idx [B,S,H,W] / b_idx [B,L,H,W] integer class maps on the GPU -> the per-cell arrays of ccdm_surfdist (include/ccdm_hip.h),
+    each of shape [B,S,L,C] over the scored classes C (1..K-1; class 0 when K == 1): int64 n_ar, n_ra (the sizes of the two
+    surfaces; a cell is defined iff both are > 0), d2_max, d2_lo, d2_hi (the maximum and the order statistics at the ranks
+    floor(pos), ceil(pos), pos = q[0]*(n-1)/q[1], of the pooled squared surface distances; 0 in an undefined cell) and float64
+    sum_ar, sum_ra (the sums of the distances of each direction); plus "q": [q[0], q[1]] and "classes": the scored classes."""
+    lib = hip.load()
+    if a_idx.device.type != "cuda" or b_idx.device.type != "cuda":
+        raise hip.CcdmHipError("surface_distance_stats needs GPU tensors (no CPU path)")
+    if a_idx.dim() != 4 or b_idx.dim() != 4 or a_idx.shape[0] != b_idx.shape[0] or a_idx.shape[2:] != b_idx.shape[2:]:
+        raise ValueError(f"surface_distance_stats: {tuple(a_idx.shape)} / {tuple(b_idx.shape)} (expected [B,S,H,W] and [B,L,H,W])")
+    B, S, H, W = a_idx.shape
+    L = b_idx.shape[1]
+    q_num, q_den = int(q[0]), int(q[1])
+    a8 = a_idx.to(torch.uint8).contiguous()
+    b8 = b_idx.to(device=a8.device, dtype=torch.uint8).contiguous()
+    classes = list(range(1, num_classes)) if num_classes > 1 else [0]
+    Cn = len(classes)
+    stats = torch.zeros((B, S, L, Cn, 5), dtype=torch.int32, device=a8.device)
+    sums = torch.zeros((B, S, L, Cn, 2), dtype=torch.float64, device=a8.device)
+    need = int(lib.ccdm_surfdist_workspace_bytes(B, S, L, H, W, num_classes))
+    ws = torch.empty((max(need, 4) + 3) // 4, dtype=torch.int32, device=a8.device)
+    hip.check(lib.ccdm_surfdist(a8.data_ptr(), b8.data_ptr(), B, S, L, H, W, num_classes, q_num, q_den, stats.data_ptr(), sums.data_ptr(),
+                                ws.data_ptr(), need, torch.cuda.current_stream(a8.device).cuda_stream), "surfdist")
+    st, sm = stats.cpu().numpy().astype(np.int64), sums.cpu().numpy()
+    out: Dict[str, object] = {name: st[..., f] for f, name in enumerate(SURFACE_STAT_FIELDS)}
+    out.update(sum_ar=sm[..., 0], sum_ra=sm[..., 1], q=[q_num, q_den], classes=classes)
+    return out
+
+
+def concat_surface_stats(parts: Sequence[Dict[str, object]]) -> Dict[str, object]:
+    """The stats of several batches as one (concatenated along the images)."""
+    out = {k: np.concatenate([p[k] for p in parts]) for k in SURFACE_STAT_FIELDS + ("sum_ar", "sum_ra")}
+    out.update(q=list(parts[0]["q"]), classes=list(parts[0]["classes"]))
+    return out
+
+
+def surface_scores_from_stats(stats: Dict[str, object], *, class_names: Optional[Sequence[str]] = None) -> Dict[str, object]:
+    """The surface-distance scores behind the per-cell arrays of `surface_distance_stats`, on the host in float64 (no GPU).  Per
+    defined cell (both surfaces non-empty), with n = n_ar + n_ra and pos = q_num*(n-1)/q_den taken in exact integer arithmetic:
+      hd             sqrt(d2_max), the Hausdorff distance
+      hd_percentile  sqrt(d2_lo) + frac(pos) * (sqrt(d2_hi) - sqrt(d2_lo)): numpy's linear-interpolation percentile of the pooled
+                     distances (HD95 at q = 95/100, as MedPy's hd95)
+      assd           (sum_ar/n_ar + sum_ra/n_ra) / 2 (MedPy's assd)
+    Each score is the mean over images of the mean over the image's defined cells (samples x raters x classes); an image
+    without a defined cell is left out; `*_per_class`: the same over one class's cells.  Undefined cells are counted
+    (cells_undefined, of which cells_both_empty have neither surface) and never folded into a mean; a score with no defined
+    cell is None.  The result holds lists, numbers and None only: it survives a JSON round trip."""
+    n_ar, n_ra = np.asarray(stats["n_ar"]).astype(np.int64), np.asarray(stats["n_ra"]).astype(np.int64)
+    if n_ar.ndim != 4 or n_ra.shape != n_ar.shape:
+        raise ValueError(f"n_ar {n_ar.shape} / n_ra {n_ra.shape}: expected [B,S,L,C]")
+    B, S, L, Cn = n_ar.shape
+    q_num, q_den = (int(x) for x in stats["q"])
+    if not 0 < q_num <= q_den:
+        raise ValueError(f"q: {q_num}/{q_den} (expected 0 < q_num <= q_den)")
+    classes = [int(c) for c in stats["classes"]]
+    if len(classes) != Cn:
+        raise ValueError(f"classes: {len(classes)} entries for {Cn} scored classes")
+    if class_names is not None and len(class_names) != Cn:
+        raise ValueError(f"class_names: {len(class_names)} names for {Cn} scored classes")
+    defined = (n_ar > 0) & (n_ra > 0)
+    safe_ar, safe_ra = np.where(defined, n_ar, 1), np.where(defined, n_ra, 1)
+    t = q_num * (n_ar + n_ra - 1)                                    # pos = t / q_den, exact
+    frac = (t % q_den).astype(np.float64) / q_den
+    lo, hi = np.sqrt(np.asarray(stats["d2_lo"], dtype=np.float64)), np.sqrt(np.asarray(stats["d2_hi"], dtype=np.float64))
+    cell = {"hd": np.sqrt(np.asarray(stats["d2_max"], dtype=np.float64)), "hd_percentile": lo + frac * (hi - lo),
+            "assd": (np.asarray(stats["sum_ar"], dtype=np.float64) / safe_ar + np.asarray(stats["sum_ra"], dtype=np.float64) / safe_ra) / 2.0}
+
+    def mean_of_image_means(values, mask):
+        per_image = [float(values[b][mask[b]].mean()) for b in range(B) if mask[b].any()]
+        return float(np.mean(per_image)) if per_image else None
+
+    res: Dict[str, object] = {"images": int(B), "samples": int(S), "raters": int(L), "classes": classes, "q": [q_num, q_den],
+                              "percentile": 100.0 * q_num / q_den, "cells_defined": int(defined.sum()),
+                              "cells_undefined": int((~defined).sum()), "cells_both_empty": int(((n_ar == 0) & (n_ra == 0)).sum()),
+                              "images_scored": int(defined.reshape(B, -1).any(axis=1).sum())}
+    for key, values in cell.items():
+        res[key] = mean_of_image_means(values, defined)
+        res[key + "_per_class"] = [mean_of_image_means(values[..., c], defined[..., c]) for c in range(Cn)]
+    res["cells_defined_per_class"] = [int(defined[..., c].sum()) for c in range(Cn)]
     if class_names is not None:
         res["class_names"] = [str(c) for c in class_names]
     return res

@@ -334,6 +334,39 @@ int ccdm_lidcscore(const uint8_t* samples /*dev [B,S,HW]*/, const uint8_t* rater
                    int K, int32_t* joint /*dev [B][K][S+1][L+1] or NULL*/, int64_t* moments /*dev [B][5] or NULL*/, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * LIDC surface-distance scores, device part (beyond the reference, whose LIDC scores are all overlap scores): the integers and
+ * the two fp64 sums behind HD95, the average symmetric surface distance (ASSD) and the Hausdorff distance of every sample
+ * against every rater.
+ * Definition, for a class map M of shape [H,W] and a class c.  The mask is M == c.  The surface S_c(M) is the set of mask pixels
+ * with at least one of their four neighbours outside the mask; a neighbour outside the image counts as outside the mask.  This
+ * is mask & ~scipy.ndimage.binary_erosion(mask) with the default cross structure and border_value=0, which is MedPy's
+ * __surface_distances with connectivity 1.  A byte >= K belongs to no class.
+ * For image b, map i of stack A (samples [B,S,H,W]), map j of stack R (raters [B,L,H,W]) and class c:  d2(p, T) is the smallest
+ * squared Euclidean pixel distance from p to a pixel of the set T, an integer.  The multiset D pools {d2(p, S_c(R_j)) : p in
+ * S_c(A_i)} and {d2(p, S_c(A_i)) : p in S_c(R_j)} (MedPy's hd95 pools the two directions the same way).
+ *   stats  int32 [B][S][L][C][5], C = the scored classes: 1..K-1, or class 0 when K == 1.  Per cell (b,i,j,c):
+ *          {n_ar, n_ra, d2_max, d2_lo, d2_hi}.  n_ar = |S_c(A_i)|, n_ra = |S_c(R_j)|; the cell is DEFINED iff both are > 0, an
+ *          undefined cell gets zeros in the remaining fields and in `sums`.  d2_max = max D.  d2_lo, d2_hi = the order statistics
+ *          of D at the 0-based ranks floor(pos) and ceil(pos), pos = q_num*(n-1)/q_den, n = n_ar + n_ra, the ranks in exact
+ *          integer arithmetic (q_num/q_den = 95/100: numpy's default linear-interpolation percentile).  OVERWRITTEN per call;
+ *   sums   fp64 [B][S][L][C][2]: {sum_ar, sum_ra} = the sums of sqrt(d2) over each direction.  OVERWRITTEN per call.
+ * The host derives  HD = sqrt(d2_max),  HDq = sqrt(d2_lo) + frac(pos)*(sqrt(d2_hi) - sqrt(d2_lo)),
+ * ASSD = (sum_ar/n_ar + sum_ra/n_ra)/2 (MedPy's assd).
+ * Limits: 1 <= K <= 32, 1 <= S, L <= 255, H, W <= 1024 (so d2 < 2^21), 0 < q_num <= q_den; checked before anything is launched
+ * or read.  Any alignment of the stacks is accepted: one dword per lane and map row when W % 4 == 0 and both pointers are 4-byte
+ * aligned, bytes otherwise.  Two stages on `stream`: once per (map, class) the exact squared distance transform to the surface
+ * (1-D nearest-surface distance along rows, then the lower envelope min over y' of g(x,y')^2 + (y-y')^2 down columns) as int32 in
+ * the workspace (device, 4-byte aligned, ccdm_surfdist_workspace_bytes(B,S,L,H,W,K) = 4*B*(S+L)*C*H*W bytes); then one
+ * workgroup per cell takes the counts, the maximum and the sums and finds the two order statistics by an MSB-first radix select
+ * over 256-bin histograms in LDS.  Integers are exact in any order; the fp64 sums are reduced in a fixed order (thread, wave,
+ * block) without floating atomics: two identical calls are bit-identical.  B = 0 returns 0 without a launch.
+ * ------------------------------------------------------------------------------------------------- */
+size_t ccdm_surfdist_workspace_bytes(int B, int S, int L, int H, int W, int K);
+int ccdm_surfdist(const uint8_t* samples /*dev [B,S,H,W]*/, const uint8_t* raters /*dev [B,L,H,W]*/, int B, int S, int L, int H, int W,
+                  int K, int q_num, int q_den, int32_t* stats /*dev [B][S][L][C][5]*/, double* sums /*dev [B][S][L][C][2]*/,
+                  void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Segmentation evaluation, device part (Cityscapes mIoU): the reference Evaluator's `infer_step` / `update_cm`
  * (evaluation/eval_cdm.py) in one pass, without a full-resolution probability tensor.  Per output pixel of [B,H,W]:
  *   - bilinear sample of the prediction [B,h,w] as ATen's upsample_bilinear2d (align_corners=False, no antialias) in fp32:
