@@ -190,7 +190,14 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
                             the Hausdorff distance of the first s samples against the raters (metrics.surface_scores_from_stats; the
                             per-cell integers from one ccdm_surfdist call per batch and entry, kept per image and scored after the
                             last batch); with `output_path` set, also written as lidc_surface_distances.json
-         surface_distance_percentile (95): the percentile of HD95, read as the decimal it is written as"""
+         surface_distance_percentile (95): the percentile of HD95, read as the decimal it is written as
+         lesions: yes       the result gains "lesions": one dict per entry of `evaluations` with lesion-wise recall, precision, F1
+                            and the agreement on the number of lesions of the first s samples against the raters
+                            (metrics.lesion_scores_from_stats; the per-cell integers from one ccdm_lesions call per batch and entry,
+                            kept per image and scored after the last batch); with `output_path` set, also written as
+                            lidc_lesions.json
+         lesion_connectivity (8): 4 or 8;  lesion_overlaps ([0, 0.5]): the shares of a lesion the other mask has to cover for a
+                            hit, each read as the decimal it is written as (0: any overlap)"""
     from . import distributed as D
     rank, local_rank, world = D.init_from_env()
     if device is None:
@@ -225,6 +232,18 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
         if not 0 < quantile <= 1:
             raise ValueError(f"surface_distance_percentile: {section.get('surface_distance_percentile')!r} (expected a value in (0, 100])")
         surf_q = (quantile.numerator, quantile.denominator)
+    les = [[] for _ in evaluations] if section.get("lesions", False) else None                   # per entry: the stats of every batch
+    if les is not None:
+        from fractions import Fraction
+        les_conn = int(section.get("lesion_connectivity", 8))
+        if les_conn not in (4, 8):
+            raise ValueError(f"lesion_connectivity: {section.get('lesion_connectivity')!r} (expected 4 or 8)")
+        shares = section.get("lesion_overlaps", [0, 0.5])
+        shares = list(shares) if isinstance(shares, (list, tuple)) else [shares]
+        fractions = [Fraction(str(v)) for v in shares]
+        if not fractions or any(not 0 <= f <= 1 for f in fractions):
+            raise ValueError(f"lesion_overlaps: {section.get('lesion_overlaps')!r} (expected values in [0, 1])")
+        les_overlaps = [(f.numerator, f.denominator) for f in fractions]
     for image, labels, _ in loader:                                              # Tester.test_step, :89-136
         image = image.to(device).repeat_interleave(S, dim=0)
         # x_T: uniform one-hot from the CPU generator, full batch on every rank (same seed => same draw)
@@ -249,6 +268,8 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
                 soft[i][0].append(joint); soft[i][1].append(moments)
             if surf is not None:
                 surf[i].append(M.surface_distance_stats(pred_idx[:, :s], lab_idx, num_classes, q=surf_q))
+            if les is not None:
+                les[i].append(M.lesion_stats(pred_idx[:, :s], lab_idx, num_classes, connectivity=les_conn, overlaps=les_overlaps))
         # log-mean vote exactly as the reference takes it (:125): log(0) = -inf stays -inf (one-hot "majority" predictions:
         # a class any sample rejects is out; where every class is rejected by someone argmax falls to class 0)
         mean_pred = torch.log(prediction).mean(dim=1).argmax(dim=1)
@@ -293,6 +314,17 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
             os.makedirs(out_dir, exist_ok=True)
             with open(os.path.join(out_dir, "lidc_surface_distances.json"), "w") as f:
                 json.dump(res["surface_distances"], f, indent=1)
+    if les is not None:
+        res["lesions"] = [M.lesion_scores_from_stats(M.concat_lesion_stats(parts)) for parts in les]
+        for s, r in zip(evaluations, res["lesions"]):
+            LOGGER.info("lesions (%d): recall %s  precision %s  F1 %s at overlaps %s  count error %.4g  (%d of %d cells without a lesion)", s,
+                        r["recall"], r["precision"], r["f1"], r["thresholds"], r["count_error"], r["cells_both_empty"], r["cells"])
+        if params.get("output_path") and rank == 0:
+            import json
+            out_dir = expanduservars(params["output_path"])
+            os.makedirs(out_dir, exist_ok=True)
+            with open(os.path.join(out_dir, "lidc_lesions.json"), "w") as f:
+                json.dump(res["lesions"], f, indent=1)
     return res
 
 

@@ -13,7 +13,11 @@ cross-entropy, thresholded soft Dice and the uncertainty correlation (NCC) from 
 
 Also beyond the reference: the surface distances of every sample against every rater.  `surface_distance_stats` (HIP kernel
 ccdm_surfdist: an exact squared distance transform per map and class, then counts, maximum, two order statistics and two fp64 sums
-per (image, sample, rater, class)), `surface_scores_from_stats` derives HD95, ASSD and the Hausdorff distance on the host."""
+per (image, sample, rater, class)), `surface_scores_from_stats` derives HD95, ASSD and the Hausdorff distance on the host.
+
+And the lesion-level scores: `lesion_stats` (HIP kernel ccdm_lesions: connected-component labels per map and class, then per
+(image, sample, rater, class) the lesions of each side and how many the other side's mask covers to each overlap threshold),
+`lesion_scores_from_stats` derives lesion-wise recall, precision, F1 and the agreement on the number of lesions on the host."""
 from __future__ import annotations
 
 import math
@@ -274,6 +278,105 @@ def surface_scores_from_stats(stats: Dict[str, object], *, class_names: Optional
         res[key] = mean_of_image_means(values, defined)
         res[key + "_per_class"] = [mean_of_image_means(values[..., c], defined[..., c]) for c in range(Cn)]
     res["cells_defined_per_class"] = [int(defined[..., c].sum()) for c in range(Cn)]
+    if class_names is not None:
+        res["class_names"] = [str(c) for c in class_names]
+    return res
+
+
+# ------------------------------------------------------------------------------------------------ lesion-level scores
+LESION_STAT_FIELDS = ("n_a", "n_r", "hit_a", "hit_r")
+LESION_OVERLAPS = ((0, 1), (1, 2))
+
+
+def lesion_stats(a_idx: torch.Tensor, b_idx: torch.Tensor, num_classes: int, connectivity: int = 8,
+                 overlaps: Sequence[Tuple[int, int]] = LESION_OVERLAPS) -> Dict[str, object]:
+    """a_idx [B,S,H,W] / b_idx [B,L,H,W] integer class maps on the GPU -> the per-cell arrays of ccdm_lesions (include/ccdm_hip.h)
+    over the scored classes C (1..K-1; class 0 when K == 1), all int64: n_a, n_r [B,S,L,C] (the lesions, i.e. connected components
+    under `connectivity`, of the sample map and of the rater map) and hit_a, hit_r [B,S,L,C,T] (how many of them the other map's
+    mask covers to overlaps[t] = (num, den): cov >= 1 and cov*den >= num*size); plus "overlaps": [[num, den], ...],
+    "connectivity" and "classes": the scored classes."""
+    lib = hip.load()
+    if a_idx.device.type != "cuda" or b_idx.device.type != "cuda":
+        raise hip.CcdmHipError("lesion_stats needs GPU tensors (no CPU path)")
+    if a_idx.dim() != 4 or b_idx.dim() != 4 or a_idx.shape[0] != b_idx.shape[0] or a_idx.shape[2:] != b_idx.shape[2:]:
+        raise ValueError(f"lesion_stats: {tuple(a_idx.shape)} / {tuple(b_idx.shape)} (expected [B,S,H,W] and [B,L,H,W])")
+    B, S, H, W = a_idx.shape
+    L = b_idx.shape[1]
+    ov = np.ascontiguousarray([[int(n), int(d)] for n, d in overlaps], dtype=np.int32).reshape(-1, 2)
+    T = int(ov.shape[0])
+    a8 = a_idx.to(torch.uint8).contiguous()
+    b8 = b_idx.to(device=a8.device, dtype=torch.uint8).contiguous()
+    classes = list(range(1, num_classes)) if num_classes > 1 else [0]
+    Cn = len(classes)
+    stats = torch.zeros((B, S, L, Cn, 2 + 2 * T), dtype=torch.int32, device=a8.device)
+    need = int(lib.ccdm_lesions_workspace_bytes(B, S, L, H, W, num_classes))
+    ws = torch.empty((max(need, 4) + 3) // 4, dtype=torch.int32, device=a8.device)
+    hip.check(lib.ccdm_lesions(a8.data_ptr(), b8.data_ptr(), B, S, L, H, W, num_classes, int(connectivity), ov.ctypes.data, T,
+                               stats.data_ptr(), ws.data_ptr(), need, torch.cuda.current_stream(a8.device).cuda_stream), "lesions")
+    st = stats.cpu().numpy().astype(np.int64)
+    return {"n_a": st[..., 0], "n_r": st[..., 1], "hit_a": st[..., 2:2 + T], "hit_r": st[..., 2 + T:], "overlaps": ov.tolist(),
+            "connectivity": int(connectivity), "classes": classes}
+
+
+def concat_lesion_stats(parts: Sequence[Dict[str, object]]) -> Dict[str, object]:
+    """The stats of several batches as one (concatenated along the images)."""
+    out = {k: np.concatenate([p[k] for p in parts]) for k in LESION_STAT_FIELDS}
+    out.update(overlaps=[list(o) for o in parts[0]["overlaps"]], connectivity=int(parts[0]["connectivity"]), classes=list(parts[0]["classes"]))
+    return out
+
+
+def lesion_scores_from_stats(stats: Dict[str, object], *, class_names: Optional[Sequence[str]] = None) -> Dict[str, object]:
+    """The lesion-level scores behind the per-cell arrays of `lesion_stats`, on the host in float64 (no GPU).  Per cell (sample x
+    rater x class of an image) and threshold:
+      recall     hit_r / n_r, defined iff n_r > 0: the share of the rater's lesions the sample finds
+      precision  hit_a / n_a, defined iff n_a > 0: the share of the sample's lesions the rater confirms
+      f1         (hit_a + hit_r) / (n_a + n_r), defined iff n_a + n_r > 0: the share of all lesions of both maps that the other map
+                 hits (2*TP / (n_a + n_r) where both sides agree on TP; 0 when one side has no lesion)
+    Each score is a list over the thresholds of the mean over images of the mean over the image's defined cells; an image without a
+    defined cell is left out; a score with no defined cell anywhere is None; `*_per_class`: the same over one class's cells.  Never
+    folded into a mean: cells, cells_both_empty (n_a == n_r == 0), cells_sample_empty (n_a == 0), cells_rater_empty (n_r == 0),
+    images_scored (images with a cell that has a lesion).  Over all cells: count_error = mean |n_a - n_r|, count_exact = the share
+    with n_a == n_r, lesions_per_sample_map / lesions_per_rater_map = mean n_a / mean n_r.  The result holds lists, numbers and None
+    only: it survives a JSON round trip."""
+    n_a, n_r = np.asarray(stats["n_a"]).astype(np.int64), np.asarray(stats["n_r"]).astype(np.int64)
+    if n_a.ndim != 4 or n_r.shape != n_a.shape:
+        raise ValueError(f"n_a {n_a.shape} / n_r {n_r.shape}: expected [B,S,L,C]")
+    B, S, L, Cn = n_a.shape
+    overlaps = [[int(n), int(d)] for n, d in stats["overlaps"]]
+    T = len(overlaps)
+    if T < 1 or any(not (d >= 1 and 0 <= n <= d) for n, d in overlaps):
+        raise ValueError(f"overlaps: {overlaps!r} (expected at least one num/den with 0 <= num <= den, den >= 1)")
+    hit_a, hit_r = np.asarray(stats["hit_a"]).astype(np.int64), np.asarray(stats["hit_r"]).astype(np.int64)
+    if hit_a.shape != n_a.shape + (T,) or hit_r.shape != hit_a.shape:
+        raise ValueError(f"hit_a {hit_a.shape} / hit_r {hit_r.shape}: expected {n_a.shape + (T,)}")
+    connectivity = int(stats["connectivity"])
+    if connectivity not in (4, 8):
+        raise ValueError(f"connectivity: {connectivity} (expected 4 or 8)")
+    classes = [int(c) for c in stats["classes"]]
+    if len(classes) != Cn:
+        raise ValueError(f"classes: {len(classes)} entries for {Cn} scored classes")
+    if class_names is not None and len(class_names) != Cn:
+        raise ValueError(f"class_names: {len(class_names)} names for {Cn} scored classes")
+    if B < 1:
+        raise ValueError("lesion_scores_from_stats: the stats hold no image")
+    cell = {"recall": (hit_r, n_r[..., None], n_r > 0), "precision": (hit_a, n_a[..., None], n_a > 0),
+            "f1": (hit_a + hit_r, (n_a + n_r)[..., None], (n_a + n_r) > 0)}
+
+    def mean_of_image_means(values, mask):
+        per_image = [float(values[b][mask[b]].mean()) for b in range(B) if mask[b].any()]
+        return float(np.mean(per_image)) if per_image else None
+
+    res: Dict[str, object] = {
+        "images": int(B), "samples": int(S), "raters": int(L), "classes": classes, "connectivity": connectivity, "overlaps": overlaps,
+        "thresholds": [n / d for n, d in overlaps], "cells": int(n_a.size), "cells_both_empty": int(((n_a == 0) & (n_r == 0)).sum()),
+        "cells_sample_empty": int((n_a == 0).sum()), "cells_rater_empty": int((n_r == 0).sum()),
+        "images_scored": int(((n_a + n_r) > 0).reshape(B, -1).any(axis=1).sum())}
+    for key, (num, den, defined) in cell.items():
+        values = num.astype(np.float64) / np.where(defined[..., None], den, 1).astype(np.float64)          # [B,S,L,C,T]
+        res[key] = [mean_of_image_means(values[..., t], defined) for t in range(T)]
+        res[key + "_per_class"] = [[mean_of_image_means(values[..., c, t], defined[..., c]) for t in range(T)] for c in range(Cn)]
+    res.update(count_error=float(np.abs(n_a - n_r).mean()), count_exact=float((n_a == n_r).mean()),
+               lesions_per_sample_map=float(n_a.mean()), lesions_per_rater_map=float(n_r.mean()))
     if class_names is not None:
         res["class_names"] = [str(c) for c in class_names]
     return res

@@ -367,6 +367,38 @@ int ccdm_surfdist(const uint8_t* samples /*dev [B,S,H,W]*/, const uint8_t* rater
                   void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * LIDC lesion-level scores, device part (beyond the reference, whose LIDC scores are all overlap scores): how many lesions every
+ * sample and every rater marks, and which of them the other one finds.
+ * Inputs: samples uint8 [B,S,H,W] and raters uint8 [B,L,H,W], device class maps as they lie in memory; K classes; connectivity 4
+ * or 8; T overlap thresholds, each a rational num/den (HOST array [T][2], read during the call).  The scored classes are 1..K-1,
+ * or class 0 when K == 1: C of them, as in ccdm_surfdist.  A byte >= K belongs to no class.
+ * Lesion: a lesion of a map and a class c is a connected component of the pixels equal to c under `connectivity` (4: the edge
+ * neighbours, scipy's generate_binary_structure(2,1); 8: the diagonal ones too, (2,2)).  Outside the image is outside the mask.
+ * Labels (stage 1, once per map and class, not per pair): int32 [H][W], 0 outside the mask, otherwise 1 + the number of lesions of
+ * that map and class whose smallest pixel index y*W + x is smaller than this lesion's: lesions numbered in raster order of their
+ * first pixel, which is what scipy.ndimage.label returns.
+ * Cell (stage 2, per image b, sample i, rater j, class c): n_a, n_r = the lesions of the sample map and of the rater map.  For a
+ * sample lesion a, size(a) is its pixel count and cov(a) the number of its pixels that have class c in the rater map; the same
+ * for a rater lesion against the sample map.  A lesion is HIT at num/den iff cov >= 1 and cov*den >= num*size, in 64-bit integers:
+ * 0/1 is any overlap, 1/2 at least half covered by the other mask, 1/1 wholly inside it.
+ *   stats  int32 [B][S][L][C][2+2T] = {n_a, n_r, hit_a[0..T), hit_r[0..T)}: the lesions of each side and how many of them are hit
+ *          at each threshold.  Every element is written, zeros included: OVERWRITTEN per call.
+ * Workspace (device, 4-byte aligned, ccdm_lesions_workspace_bytes(B,S,L,H,W,K) = 4*B*(S+L)*C*(H*W + 1) bytes): first the label
+ * planes int32 [B*S + B*L][C][H][W], map-major (the B*S sample maps, then the B*L rater maps), then class, then pixel; behind them
+ * the lesion counts int32 [B*S + B*L][C] in the same order.  Both are valid after the call.
+ * Limits, checked before anything is launched or read: 1 <= K <= 32, 1 <= S, L <= 255, H, W >= 1 and H*W <= 16384 (the LIDC map:
+ * a whole map stays in the LDS of one workgroup, and a lesion's size and cov fit 16 bits each), connectivity in {4, 8}, 1 <= T <= 8,
+ * 0 <= num <= den, 1 <= den <= 65536, B >= 0.  Any alignment of the stacks is accepted: one dword per lane when W % 4 == 0 and both
+ * pointers are 4-byte aligned, bytes otherwise.  Two kernels on `stream`: union-find labelling, one workgroup per (map, class); then
+ * one workgroup per cell counts size and cov per lesion in LDS and the hits per threshold.  Integers only, exact in any order: two
+ * identical calls are bit-identical.  B = 0 returns 0 without a launch and leaves the outputs as they are.
+ * ------------------------------------------------------------------------------------------------- */
+size_t ccdm_lesions_workspace_bytes(int B, int S, int L, int H, int W, int K);
+int ccdm_lesions(const uint8_t* samples /*dev [B,S,H,W]*/, const uint8_t* raters /*dev [B,L,H,W]*/, int B, int S, int L, int H, int W,
+                 int K, int connectivity, const int32_t* overlaps /*HOST [T][2]: num, den*/, int T,
+                 int32_t* stats /*dev [B][S][L][C][2+2T]*/, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Segmentation evaluation, device part (Cityscapes mIoU): the reference Evaluator's `infer_step` / `update_cm`
  * (evaluation/eval_cdm.py) in one pass, without a full-resolution probability tensor.  Per output pixel of [B,H,W]:
  *   - bilinear sample of the prediction [B,h,w] as ATen's upsample_bilinear2d (align_corners=False, no antialias) in fp32:
