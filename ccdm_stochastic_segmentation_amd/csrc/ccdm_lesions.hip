@@ -31,13 +31,10 @@
 // waves added in order.  A conn-4 checkerboard has ceil(H*W/2) lesions per map, the most any mask can have (one pixel of each lesion
 // is an independent set of the grid): 2 sides * 8192 * 4 B = 65,536 B of tables at the limit plus 256 B of wave sums: two workgroups
 // per CU.  Integers only: exact in any order, two identical calls are bit-identical.
-#include "ccdm_seg_common.h"
+#include "ccdm_lesions_common.h"
 
 namespace ccdm {
 
-constexpr int LES_MAX_PIXELS = 16384;     // H*W: a map and its bookkeeping stay in the LDS of one workgroup; size and cov fit 16 bits
-constexpr int LES_MAX_T = 8;              // thresholds of one call, by value in the kernel arguments
-constexpr int LES_MAX_DEN = 65536;
 constexpr int LES_THREADS = 512;          // of a label workgroup
 constexpr int LES_WAVES = LES_THREADS / 64;
 
@@ -45,9 +42,6 @@ struct LesOverlaps {
     int T;
     int num[LES_MAX_T], den[LES_MAX_T];
 };
-
-static inline int les_classes(int K) { return K > 1 ? K - 1 : 1; }
-static inline int les_max_lesions(int HW) { return (HW + 1) / 2; }
 
 // Another thread may lower the value at any time: never a cached read.
 __device__ __forceinline__ int les_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
@@ -248,17 +242,6 @@ __global__ __launch_bounds__(256) void k_lesions_pairs(const int32_t* __restrict
         const int side = threadIdx.x / ov.T, t = threadIdx.x % ov.T, k = side * LES_MAX_T + t;
         st[2 + threadIdx.x] = (wsum[0][k] + wsum[1][k]) + (wsum[2][k] + wsum[3][k]);
     }
-}
-
-// More than 48 KB of dynamic LDS for one workgroup is asked for once per kernel: what the kernel takes at LES_MAX_PIXELS (the static
-// LDS of the kernel comes on top and has to fit the CU's 160 KB with it).
-template <typename Kern>
-static int les_reserve_lds(Kern kern, size_t bytes, bool* done, const char* what) {
-    if (*done) return 0;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
-        return fail("lesions: cannot reserve %zu bytes of LDS for the %s kernel", bytes, what);
-    *done = true;
-    return 0;
 }
 
 }  // namespace ccdm

@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import logging
 import os
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -170,6 +170,36 @@ def _as_list(v) -> List[int]:
 
 
 # ------------------------------------------------------------------------------------------------ evaluation
+def lesion_connectivity(section: dict) -> int:
+    """`lesion_connectivity` of the `evaluation` section: 4 or 8 (8 when absent)."""
+    value = section.get("lesion_connectivity", 8)
+    if isinstance(value, bool) or not isinstance(value, int) or value not in (4, 8):
+        raise ValueError(f"lesion_connectivity: {value!r} (expected 4 or 8)")
+    return value
+
+
+def lesion_match_thresholds(values) -> List[Tuple[int, int]]:
+    """`lesion_match_ious` -> [(num, den), ...], each value read as the decimal it is written as (0.5 -> (1, 2), 0.75 -> (3, 4)).
+    A pair is matched when its IoU EXCEEDS the value; only above 1/2 is the matching unique, so the values lie in [0.5, 1)."""
+    from fractions import Fraction
+    values = list(values) if isinstance(values, (list, tuple)) else [values]
+    try:
+        fractions = [Fraction(str(v)) for v in values]
+    except (ValueError, ZeroDivisionError):
+        fractions = []
+    if not 1 <= len(fractions) <= 8 or any(isinstance(v, bool) for v in values) or any(not Fraction(1, 2) <= f < 1 for f in fractions) \
+            or any(f.denominator > 65536 for f in fractions):
+        raise ValueError(f"lesion_match_ious: {values!r} (expected 1 to 8 decimals in [0.5, 1) with denominators up to 65536)")
+    return [(f.numerator, f.denominator) for f in fractions]
+
+
+def lesion_min_size(value) -> int:
+    """`lesion_min_size`: a whole number of pixels, at least 1."""
+    if isinstance(value, bool) or not isinstance(value, int) or value < 1:
+        raise ValueError(f"lesion_min_size: {value!r} (expected a whole number of pixels, at least 1)")
+    return value
+
+
 @torch.no_grad()
 def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optional[int] = None, synthetic_weights_seed: Optional[int] = None,
                           model=None) -> Dict[str, object]:
@@ -197,7 +227,14 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
                             kept per image and scored after the last batch); with `output_path` set, also written as
                             lidc_lesions.json
          lesion_connectivity (8): 4 or 8;  lesion_overlaps ([0, 0.5]): the shares of a lesion the other mask has to cover for a
-                            hit, each read as the decimal it is written as (0: any overlap)"""
+                            hit, each read as the decimal it is written as (0: any overlap)
+         lesion_matching: yes   the result gains "lesion_matching": one dict per entry of `evaluations` with panoptic, segmentation
+                            and recognition quality of the first s samples' lesions paired one to one with the raters' by IoU
+                            (metrics.lesion_match_scores_from_stats; the per-cell integers from one ccdm_lesions and one
+                            ccdm_lesion_match call per batch and entry, kept per image and scored after the last batch); with
+                            `output_path` set, also written as lidc_lesion_matching.json
+         lesion_match_ious ([0.5, 0.75]): the IoUs a pair has to exceed, in [0.5, 1), each read as the decimal it is written as;
+                            lesion_min_size (1): lesions of fewer pixels are dropped; lesion_connectivity as above"""
     from . import distributed as D
     rank, local_rank, world = D.init_from_env()
     if device is None:
@@ -244,6 +281,11 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
         if not fractions or any(not 0 <= f <= 1 for f in fractions):
             raise ValueError(f"lesion_overlaps: {section.get('lesion_overlaps')!r} (expected values in [0, 1])")
         les_overlaps = [(f.numerator, f.denominator) for f in fractions]
+    match = [[] for _ in evaluations] if section.get("lesion_matching", False) else None         # per entry: the stats of every batch
+    if match is not None:
+        match_conn = lesion_connectivity(section)
+        match_thresholds = lesion_match_thresholds(section.get("lesion_match_ious", [0.5, 0.75]))
+        match_min_size = lesion_min_size(section.get("lesion_min_size", 1))
     for image, labels, _ in loader:                                              # Tester.test_step, :89-136
         image = image.to(device).repeat_interleave(S, dim=0)
         # x_T: uniform one-hot from the CPU generator, full batch on every rank (same seed => same draw)
@@ -270,6 +312,9 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
                 surf[i].append(M.surface_distance_stats(pred_idx[:, :s], lab_idx, num_classes, q=surf_q))
             if les is not None:
                 les[i].append(M.lesion_stats(pred_idx[:, :s], lab_idx, num_classes, connectivity=les_conn, overlaps=les_overlaps))
+            if match is not None:
+                match[i].append(M.lesion_match_stats(pred_idx[:, :s], lab_idx, num_classes, connectivity=match_conn,
+                                                     thresholds=match_thresholds, min_size=match_min_size))
         # log-mean vote exactly as the reference takes it (:125): log(0) = -inf stays -inf (one-hot "majority" predictions:
         # a class any sample rejects is out; where every class is rejected by someone argmax falls to class 0)
         mean_pred = torch.log(prediction).mean(dim=1).argmax(dim=1)
@@ -325,6 +370,17 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
             os.makedirs(out_dir, exist_ok=True)
             with open(os.path.join(out_dir, "lidc_lesions.json"), "w") as f:
                 json.dump(res["lesions"], f, indent=1)
+    if match is not None:
+        res["lesion_matching"] = [M.lesion_match_scores_from_stats(M.concat_lesion_match_stats(parts)) for parts in match]
+        for s, r in zip(evaluations, res["lesion_matching"]):
+            LOGGER.info("lesion matching (%d): PQ %s  SQ %s  RQ %s at IoU > %s  pooled PQ %s  (%d of %d cells without a lesion)", s,
+                        r["pq"], r["sq"], r["rq"], r["ious"], r["pq_pooled"], r["cells_both_empty"], r["cells"])
+        if params.get("output_path") and rank == 0:
+            import json
+            out_dir = expanduservars(params["output_path"])
+            os.makedirs(out_dir, exist_ok=True)
+            with open(os.path.join(out_dir, "lidc_lesion_matching.json"), "w") as f:
+                json.dump(res["lesion_matching"], f, indent=1)
     return res
 
 

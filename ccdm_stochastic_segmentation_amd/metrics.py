@@ -17,7 +17,10 @@ per (image, sample, rater, class)), `surface_scores_from_stats` derives HD95, AS
 
 And the lesion-level scores: `lesion_stats` (HIP kernel ccdm_lesions: connected-component labels per map and class, then per
 (image, sample, rater, class) the lesions of each side and how many the other side's mask covers to each overlap threshold),
-`lesion_scores_from_stats` derives lesion-wise recall, precision, F1 and the agreement on the number of lesions on the host."""
+`lesion_scores_from_stats` derives lesion-wise recall, precision, F1 and the agreement on the number of lesions on the host.
+`lesion_match_stats` pairs the lesions of the two maps one to one by IoU (HIP kernel ccdm_lesion_match on the same workspace: matched
+pairs and the fixed-point sum of their IoUs per threshold), `lesion_match_scores_from_stats` derives panoptic, segmentation and
+recognition quality on the host."""
 from __future__ import annotations
 
 import math
@@ -377,6 +380,125 @@ def lesion_scores_from_stats(stats: Dict[str, object], *, class_names: Optional[
         res[key + "_per_class"] = [[mean_of_image_means(values[..., c, t], defined[..., c]) for t in range(T)] for c in range(Cn)]
     res.update(count_error=float(np.abs(n_a - n_r).mean()), count_exact=float((n_a == n_r).mean()),
                lesions_per_sample_map=float(n_a.mean()), lesions_per_rater_map=float(n_r.mean()))
+    if class_names is not None:
+        res["class_names"] = [str(c) for c in class_names]
+    return res
+
+
+# ------------------------------------------------------------------------------------------------ matched-lesion scores
+LESION_MATCH_STAT_FIELDS = ("n_a", "n_r", "tp", "iou_sum")
+LESION_MATCH_THRESHOLDS = ((1, 2), (3, 4))
+LESION_IOU_ONE = 1 << 32                  # iou_sum is a sum of floor(inter * 2^32 / union)
+
+
+def lesion_match_stats(a_idx: torch.Tensor, b_idx: torch.Tensor, num_classes: int, connectivity: int = 8,
+                       thresholds: Sequence[Tuple[int, int]] = LESION_MATCH_THRESHOLDS, min_size: int = 1) -> Dict[str, object]:
+    """a_idx [B,S,H,W] / b_idx [B,L,H,W] integer class maps on the GPU -> the per-cell arrays of ccdm_lesion_match
+    (include/ccdm_hip.h) over the scored classes C (1..K-1; class 0 when K == 1), all int64: n_a, n_r [B,S,L,C] (the lesions of at
+    least `min_size` pixels of the sample map and of the rater map) and tp, iou_sum [B,S,L,C,T] (the pairs of them with
+    inter*den > num*union at thresholds[t] = (num, den) in [1/2, 1): at most one partner per lesion; and the sum of
+    floor(inter * 2^32 / union) over those pairs); plus "thresholds": [[num, den], ...], "connectivity", "min_size" and "classes".
+    ccdm_lesions labels the maps, ccdm_lesion_match reads its workspace: one buffer, one stream."""
+    lib = hip.load()
+    if a_idx.device.type != "cuda" or b_idx.device.type != "cuda":
+        raise hip.CcdmHipError("lesion_match_stats needs GPU tensors (no CPU path)")
+    if a_idx.dim() != 4 or b_idx.dim() != 4 or a_idx.shape[0] != b_idx.shape[0] or a_idx.shape[2:] != b_idx.shape[2:]:
+        raise ValueError(f"lesion_match_stats: {tuple(a_idx.shape)} / {tuple(b_idx.shape)} (expected [B,S,H,W] and [B,L,H,W])")
+    B, S, H, W = a_idx.shape
+    L = b_idx.shape[1]
+    th = np.ascontiguousarray([[int(n), int(d)] for n, d in thresholds], dtype=np.int32).reshape(-1, 2)
+    T = int(th.shape[0])
+    a8 = a_idx.to(torch.uint8).contiguous()
+    b8 = b_idx.to(device=a8.device, dtype=torch.uint8).contiguous()
+    classes = list(range(1, num_classes)) if num_classes > 1 else [0]
+    Cn = len(classes)
+    any_overlap = np.array([[0, 1]], dtype=np.int32)              # ccdm_lesions' own counts are not used here
+    hits = torch.zeros((B, S, L, Cn, 4), dtype=torch.int32, device=a8.device)
+    stats = torch.zeros((B, S, L, Cn, 2 + T), dtype=torch.int32, device=a8.device)
+    iou = torch.zeros((B, S, L, Cn, T), dtype=torch.int64, device=a8.device)
+    need = int(lib.ccdm_lesion_match_workspace_bytes(B, S, L, H, W, num_classes))
+    ws = torch.empty((max(need, 4) + 3) // 4, dtype=torch.int32, device=a8.device)
+    stream = torch.cuda.current_stream(a8.device).cuda_stream
+    hip.check(lib.ccdm_lesions(a8.data_ptr(), b8.data_ptr(), B, S, L, H, W, num_classes, int(connectivity), any_overlap.ctypes.data, 1,
+                               hits.data_ptr(), ws.data_ptr(), need, stream), "lesions")
+    hip.check(lib.ccdm_lesion_match(B, S, L, H, W, num_classes, th.ctypes.data, T, int(min_size), stats.data_ptr(), iou.data_ptr(),
+                                    ws.data_ptr(), need, stream), "lesion_match")
+    st = stats.cpu().numpy().astype(np.int64)
+    return {"n_a": st[..., 0], "n_r": st[..., 1], "tp": st[..., 2:], "iou_sum": iou.cpu().numpy(), "thresholds": th.tolist(),
+            "connectivity": int(connectivity), "min_size": int(min_size), "classes": classes}
+
+
+def concat_lesion_match_stats(parts: Sequence[Dict[str, object]]) -> Dict[str, object]:
+    """The stats of several batches as one (concatenated along the images)."""
+    out = {k: np.concatenate([p[k] for p in parts]) for k in LESION_MATCH_STAT_FIELDS}
+    out.update(thresholds=[list(t) for t in parts[0]["thresholds"]], connectivity=int(parts[0]["connectivity"]),
+               min_size=int(parts[0]["min_size"]), classes=list(parts[0]["classes"]))
+    return out
+
+
+def lesion_match_scores_from_stats(stats: Dict[str, object], *, class_names: Optional[Sequence[str]] = None) -> Dict[str, object]:
+    """Panoptic quality over lesions from the per-cell arrays of `lesion_match_stats`, on the host in float64 (no GPU).  Per cell
+    (sample x rater x class of an image) and threshold, with fp = n_a - tp, fn = n_r - tp and q = iou_sum / 2^32 (the summed IoU of
+    the matched pairs):
+      rq   2*tp / (n_a + n_r) = tp / (tp + fp/2 + fn/2), defined iff n_a + n_r > 0: recognition quality, the F1 of the matching
+      sq   q / tp, defined iff tp > 0: segmentation quality, the mean IoU of the matched pairs
+      pq   2*q / (n_a + n_r), defined iff n_a + n_r > 0: panoptic quality, sq * rq where both are defined, 0 where nothing matches
+    Each score is a list over the thresholds of the mean over images of the mean over the image's defined cells; an image without a
+    defined cell is left out; a score with no defined cell anywhere is None; `*_per_class`: the same over one class's cells.  The
+    pooled form of the panoptic paper over all cells: pq_pooled = sum q / (sum tp + sum fp / 2 + sum fn / 2), sq_pooled = sum q /
+    sum tp, rq_pooled = sum tp / (sum tp + sum fp / 2 + sum fn / 2), with tp_total, fp_total, fn_total per threshold beside them.
+    Never folded into a mean: cells, cells_both_empty (n_a == n_r == 0), cells_matched per threshold (tp > 0), images_scored
+    (images with a cell that has a lesion).  The result holds lists, numbers and None only: it survives a JSON round trip."""
+    n_a, n_r = np.asarray(stats["n_a"]).astype(np.int64), np.asarray(stats["n_r"]).astype(np.int64)
+    if n_a.ndim != 4 or n_r.shape != n_a.shape:
+        raise ValueError(f"n_a {n_a.shape} / n_r {n_r.shape}: expected [B,S,L,C]")
+    B, S, L, Cn = n_a.shape
+    thresholds = [[int(n), int(d)] for n, d in stats["thresholds"]]
+    T = len(thresholds)
+    if T < 1 or any(not (d <= 2 * n and n < d) for n, d in thresholds):
+        raise ValueError(f"thresholds: {thresholds!r} (expected at least one num/den with 1/2 <= num/den < 1)")
+    tp, iou_sum = np.asarray(stats["tp"]).astype(np.int64), np.asarray(stats["iou_sum"]).astype(np.int64)
+    if tp.shape != n_a.shape + (T,) or iou_sum.shape != tp.shape:
+        raise ValueError(f"tp {tp.shape} / iou_sum {iou_sum.shape}: expected {n_a.shape + (T,)}")
+    connectivity, min_size = int(stats["connectivity"]), int(stats["min_size"])
+    if connectivity not in (4, 8):
+        raise ValueError(f"connectivity: {connectivity} (expected 4 or 8)")
+    if min_size < 1:
+        raise ValueError(f"min_size: {min_size} (expected at least 1)")
+    classes = [int(c) for c in stats["classes"]]
+    if len(classes) != Cn:
+        raise ValueError(f"classes: {len(classes)} entries for {Cn} scored classes")
+    if class_names is not None and len(class_names) != Cn:
+        raise ValueError(f"class_names: {len(class_names)} names for {Cn} scored classes")
+    if B < 1:
+        raise ValueError("lesion_match_scores_from_stats: the stats hold no image")
+    q = iou_sum.astype(np.float64) / float(LESION_IOU_ONE)                                                # [B,S,L,C,T]
+    both = (n_a + n_r)[..., None]
+    some = np.broadcast_to(both > 0, tp.shape)
+    cell = {"rq": (2.0 * tp, both, some), "sq": (q, tp, tp > 0), "pq": (2.0 * q, both, some)}
+
+    def mean_of_image_means(values, mask):
+        per_image = [float(values[b][mask[b]].mean()) for b in range(B) if mask[b].any()]
+        return float(np.mean(per_image)) if per_image else None
+
+    res: Dict[str, object] = {
+        "images": int(B), "samples": int(S), "raters": int(L), "classes": classes, "connectivity": connectivity, "min_size": min_size,
+        "thresholds": thresholds, "ious": [n / d for n, d in thresholds], "cells": int(n_a.size),
+        "cells_both_empty": int(((n_a == 0) & (n_r == 0)).sum()), "cells_matched": [int((tp[..., t] > 0).sum()) for t in range(T)],
+        "images_scored": int(((n_a + n_r) > 0).reshape(B, -1).any(axis=1).sum())}
+    for key, (num, den, defined) in cell.items():
+        values = np.asarray(num, dtype=np.float64) / np.where(defined, den, 1).astype(np.float64)          # [B,S,L,C,T]
+        res[key] = [mean_of_image_means(values[..., t], defined[..., t]) for t in range(T)]
+        res[key + "_per_class"] = [[mean_of_image_means(values[..., c, t], defined[..., c, t]) for t in range(T)] for c in range(Cn)]
+    tp_total = [int(tp[..., t].sum()) for t in range(T)]
+    fp_total = [int(n_a.sum()) - n for n in tp_total]
+    fn_total = [int(n_r.sum()) - n for n in tp_total]
+    q_total = [int(iou_sum[..., t].sum()) / LESION_IOU_ONE for t in range(T)]
+    weight = [n + 0.5 * p + 0.5 * m for n, p, m in zip(tp_total, fp_total, fn_total)]
+    res.update(tp_total=tp_total, fp_total=fp_total, fn_total=fn_total,
+               pq_pooled=[s / w if w > 0 else None for s, w in zip(q_total, weight)],
+               sq_pooled=[s / n if n > 0 else None for s, n in zip(q_total, tp_total)],
+               rq_pooled=[n / w if w > 0 else None for n, w in zip(tp_total, weight)])
     if class_names is not None:
         res["class_names"] = [str(c) for c in class_names]
     return res

@@ -399,6 +399,43 @@ int ccdm_lesions(const uint8_t* samples /*dev [B,S,H,W]*/, const uint8_t* raters
                  int32_t* stats /*dev [B][S][L][C][2+2T]*/, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * LIDC matched-lesion scores, device part (beyond the reference): which lesion of a sample is which lesion of a rater, one to
+ * one, how well the matched pairs overlap and how many lesions stay unmatched: the integers behind panoptic quality (PQ),
+ * segmentation quality (SQ) and recognition quality (RQ) of every sample against every rater.
+ * Input: the workspace of a ccdm_lesions call with the same (B,S,L,H,W,K) on the same stream, i.e. its label planes int32
+ * [B*S + B*L][C][H][W] and the lesion counts behind them; nothing of the maps is read.  The scored classes are those of
+ * ccdm_lesions (1..K-1, or class 0 when K == 1: C of them); the lesions are those of the connectivity that call was given.
+ * T thresholds, each a rational num/den (HOST array [T][2], read during the call), and min_size.
+ * Cell (per image b, sample i, rater j, class c):
+ *   Kept lesions: a lesion of fewer than min_size pixels is dropped from its side; n_a, n_r = the kept lesions of the sample map
+ *   and of the rater map.  min_size = 1 keeps all.
+ *   Pair: for a kept sample lesion a and a kept rater lesion r, inter(a,r) = the pixels labelled a in the sample plane and r in
+ *   the rater plane, union = size(a) + size(r) - inter.  The pair is MATCHED at num/den iff inter*den > num*union in 64-bit
+ *   integers: strictly above the threshold, at every threshold.
+ *   Thresholds lie in [1/2, 1): den <= 2*num, num < den, 1 <= den <= 65536.  With IoU > 1/2 a lesion has at most one partner
+ *   (Kirillov et al., Panoptic Segmentation: two partners would each cover more than half of it), so the matching is unique
+ *   and no assignment problem is solved.
+ *   stats    int32 [B][S][L][C][2+T] = {n_a, n_r, tp[0..T)}: tp[t] = the matched pairs at threshold t (false positives n_a - tp,
+ *            false negatives n_r - tp).  Every element is written, zeros included: OVERWRITTEN per call.
+ *   iou_sum  int64 [B][S][L][C][T]: the sum over the matched pairs at t of floor(inter * 2^32 / union), the IoU of a pair as a
+ *            fixed-point integer: every sum is exact in any order (at most 8192 pairs: below 2^46).  OVERWRITTEN per call, every
+ *            element written.  8-byte aligned.
+ * Workspace (device, 4-byte aligned, ccdm_lesion_match_workspace_bytes(B,S,L,H,W,K) = ccdm_lesions_workspace_bytes(...) +
+ * 4*B*(S+L)*C*(ceil(H*W/2) + 1) bytes): what ccdm_lesions wrote, left as it is, then this call's lesion sizes int32
+ * [B*S + B*L][C][ceil(H*W/2)] and kept-lesion counts int32 [B*S + B*L][C].  Pass the same buffer, of this size, to both calls.  A
+ * label outside 1..count (a workspace ccdm_lesions did not write) is read as no lesion.
+ * Limits, checked before anything is launched or read, each refusal naming the argument: those of ccdm_lesions on K, S, L, H, W
+ * (H*W <= 16384) and B; 1 <= T <= 8; the threshold rule above; min_size >= 1.  Two kernels on `stream`: the lesion sizes once per
+ * (map, class); then one workgroup per cell counts the pixels of every (a, r) pair in an LDS hash table (a cell has at most
+ * ceil(H*W/2) distinct pairs: the table is never more than half full) and tests every pair found.  Integers only: two identical
+ * calls are bit-identical.  B = 0 returns 0 without a launch and leaves the outputs as they are.
+ * ------------------------------------------------------------------------------------------------- */
+size_t ccdm_lesion_match_workspace_bytes(int B, int S, int L, int H, int W, int K);
+int ccdm_lesion_match(int B, int S, int L, int H, int W, int K, const int32_t* thresholds /*HOST [T][2]: num, den*/, int T, int min_size,
+                      int32_t* stats /*dev [B][S][L][C][2+T]*/, int64_t* iou_sum /*dev [B][S][L][C][T]*/, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Segmentation evaluation, device part (Cityscapes mIoU): the reference Evaluator's `infer_step` / `update_cm`
  * (evaluation/eval_cdm.py) in one pass, without a full-resolution probability tensor.  Per output pixel of [B,H,W]:
  *   - bilinear sample of the prediction [B,h,w] as ATen's upsample_bilinear2d (align_corners=False, no antialias) in fp32:
