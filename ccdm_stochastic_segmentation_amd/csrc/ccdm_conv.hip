@@ -774,8 +774,16 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
                         }
                     };
                     if (RESID) load_resid(0, RS_FIRST);
+                    // 1x1 conv + bias + residual (F16X3): the three terms are added in fp64 in the final pass and rounded once, as in
+                    // ccdm_conv1x1.hip (identical outputs) — the transpose carries the bare product, the lane fetches its quad's bias
+                    constexpr bool EXACT3 = KS == 1 && RESID && PREC != CCDM_PREC_F32;
+                    float addq[4] = {0.f, 0.f, 0.f, 0.f};
+                    if (EXACT3) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) addq[e] = __shfl(epi_add[ni], 4 * cq + e);
+                    }
                     {
-                        const float add = epi_add[ni], wsc = epi_wsc[ni];
+                        const float add = EXACT3 ? 0.f : epi_add[ni], wsc = epi_wsc[ni];
 #pragma unroll
                         for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
@@ -796,7 +804,10 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
 #pragma unroll
                             for (int g = 1; g < KSP; ++g)               // fixed order: row 0 + row 1 + row 2
                                 v += *reinterpret_cast<const f32x4*>(epi0 + g * (WAVES * MI * 32 * EPS) + pl * EPS + 4 * cq);
-                            if (RESID) v += rs[j];
+                            if (EXACT3) {
+#pragma unroll
+                                for (int e = 0; e < 4; ++e) v[e] = (float)((double)v[e] + ((double)addq[e] + (double)rs[j][e]));
+                            } else if (RESID) v += rs[j];
                             if (FULL) {
                                 store16_uniform_base(reinterpret_cast<char*>(outn) + row_base(j), lane_off, v);
 #pragma unroll
@@ -845,8 +856,12 @@ __global__ __launch_bounds__(WAVES * KSP * 64, min_waves(MI, NI, PREC, CKT, WAVE
                         const int oy = oy0 + p / TW, ox = ox0 + p % TW;
                         if (cv && oy < a.Hout && ox < a.Wout) {
                             const size_t idx = ((size_t)(n * a.Hout + oy) * a.Wout + ox) * a.Cout + co;
-                            float v = (PREC == CCDM_PREC_F32 ? acc[mi][ni][r] : acc[mi][ni][r] * wsc) + add;
-                            if (a.resid) v += a.resid[idx];
+                            float v;
+                            if (KS == 1 && PREC != CCDM_PREC_F32 && a.resid) v = (float)((double)(acc[mi][ni][r] * wsc) + ((double)add + (double)a.resid[idx]));
+                            else {
+                                v = (PREC == CCDM_PREC_F32 ? acc[mi][ni][r] : acc[mi][ni][r] * wsc) + add;
+                                if (a.resid) v += a.resid[idx];
+                            }
                             a.out[idx] = v;
                             const double d = v;
                             t1 += d;

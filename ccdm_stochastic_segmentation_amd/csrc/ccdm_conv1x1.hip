@@ -12,7 +12,7 @@
 // first use: ONE memory round trip, no barrier before the statistics fold.
 //
 //   block = one statistics slice of one sample (HW / slices pixels, 32 per wave) x one 32-channel output tile
-//   same products in the same order as ccdm_conv.hip's 1x1 path (k-steps ascending; lo*hi, hi*lo, hi*hi): identical outputs.
+//   same products in the same order as ccdm_conv.hip's 1x1 path (k-steps ascending; lo*hi, hi*lo, hi*hi), same epilogue: identical outputs.
 //   statistics: lane = channel, 16 pixels per lane in fp32, widened to fp64 before lanes and waves are combined (fixed order).
 #include "ccdm_common.h"
 #include "ccdm_conv_common.h"
@@ -20,6 +20,15 @@
 #include <cstdlib>
 
 namespace ccdm {
+
+// acc * wsc + bias (+ residual), wsc a power of two (exact product).  With a residual the three terms are added in fp64 and rounded
+// once: fma(acc, wsc, bias) rounded in fp32 first loses up to half an ulp of the BIAS, which is all of the result's accuracy where the
+// residual cancels the bias and the product is small (tests/test_vit_kernels_float64.py).  The general kernel's 1x1 epilogue does the
+// same (ccdm_conv.hip): identical outputs.
+__device__ __forceinline__ float epi_bias_resid(float acc, float wsc, float add, float rs, bool resid) {
+    if (!resid) return fmaf(acc, wsc, add);
+    return (float)fma((double)acc, (double)wsc, (double)add + (double)rs);
+}
 
 struct Conv1x1K {
     const float* in;        // [N, HW, C]
@@ -121,8 +130,7 @@ __global__ __launch_bounds__(MAXT) void k_conv1x1(const Conv1x1K k) {
     double t1 = 0.0, t2 = 0.0;                                                 // statistics: every stored value added in fp64 (ccdm_gn.h)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        float v = fmaf(acc[r], wsc, add);                                      // wsc is a power of two: exact product
-        if (k.resid) v += rs[r];
+        const float v = epi_bias_resid(acc[r], wsc, add, rs[r], k.resid != nullptr);
         k.out[obase + (size_t)((r & 3) + 8 * (r >> 2)) * k.Cout] = v;
         const double d = v;
         t1 += d;
@@ -237,8 +245,7 @@ __global__ __launch_bounds__(256) void k_conv1x1_multi(const Conv1x1K k, const i
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            float v = fmaf(acc[r], wsc, add);
-            if (k.resid) v += rs[r];
+            const float v = epi_bias_resid(acc[r], wsc, add, rs[r], k.resid != nullptr);
             k.out[obase + (size_t)((r & 3) + 8 * (r >> 2)) * k.Cout] = v;
         }
     };

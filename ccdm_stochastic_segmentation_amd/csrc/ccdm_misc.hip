@@ -332,8 +332,8 @@ extern "C" int ccdm_onehot_to_xin(const uint8_t* idx, float* xin, int N, int HW,
 // ---------------------------------------------------------------------------------------------------
 namespace ccdm {
 
-// nn.LayerNorm(C, eps) over the last axis: one wave per token row, the row in registers, two passes (mean, then centred
-// variance) like ATen's; C <= 64 * LN_MAX_PER_LANE
+// nn.LayerNorm(C, eps) over the last axis: one wave per token row, the row in registers, mean then centred variance like ATen's,
+// with the mean corrected by the residuals' own mean in between; C <= 64 * LN_MAX_PER_LANE
 constexpr int LN_MAX_PER_LANE = 24;
 __global__ __launch_bounds__(256) void k_layernorm(const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
                                                    float eps, long rows, int C, float* __restrict__ out) {
@@ -352,12 +352,26 @@ __global__ __launch_bounds__(256) void k_layernorm(const float* __restrict__ x, 
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
     const float mean = sum / (float)C;
+    // The fp32 sum leaves `mean` off by up to ~C/64 ulps of the row's magnitude, which rstd amplifies: a row of 0.7s came out 6e-5 gamma
+    // away from beta (rstd = 1000 at eps = 1e-6), a row at mean / sigma = 1000 1e-4 off.  The residuals' own mean is that error: take
+    // it out.  The residuals are small, so their sum is good to ~1e-7 of their spread; on a constant row they are all the same
+    // d with every partial sum k d exact, (C d) / C = d, and the row is exactly beta.
+    float dsum = 0.f;
+#pragma unroll
+    for (int i = 0; i < LN_MAX_PER_LANE; ++i) {
+        const int c = lane + 64 * i;
+        v[i] = c < C ? v[i] - mean : 0.f;
+        dsum += v[i];
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) dsum += __shfl_xor(dsum, off);
+    const float dmean = dsum / (float)C;
     float sq = 0.f;
 #pragma unroll
     for (int i = 0; i < LN_MAX_PER_LANE; ++i) {
         const int c = lane + 64 * i;
-        const float d = c < C ? v[i] - mean : 0.f;
-        sq = fmaf(d, d, sq);
+        v[i] = c < C ? v[i] - dmean : 0.f;
+        sq = fmaf(v[i], v[i], sq);
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) sq += __shfl_xor(sq, off);
@@ -366,7 +380,7 @@ __global__ __launch_bounds__(256) void k_layernorm(const float* __restrict__ x, 
 #pragma unroll
     for (int i = 0; i < LN_MAX_PER_LANE; ++i) {
         const int c = lane + 64 * i;
-        if (c < C) orow[c] = (v[i] - mean) * rstd * gamma[c] + beta[c];
+        if (c < C) orow[c] = v[i] * rstd * gamma[c] + beta[c];
     }
 }
 

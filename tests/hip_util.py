@@ -268,3 +268,62 @@ def head_posterior(x_nhwc, gamma, beta, weight, bias, xt_idx, a, c, mode, *, sof
     hip.check(lib.ccdm_head_posterior(C.byref(h), C.byref(p), 0), "head_posterior")
     sync()
     return dict(xt_next=xt_next.cpu(), probs=probs.cpu(), onehot=onehot.cpu(), posterior=post.cpu(), logits=logits.cpu(), flag=int(flag.item()))
+
+
+def layernorm(x: torch.Tensor, gamma, beta, eps: float = 1e-6, guard_rows: int = 1):
+    """ccdm_layernorm of x [rows, C] (cpu fp32) -> cpu [rows, C].  The output buffer has `guard_rows` extra rows of NaN behind it, which
+    must come back untouched."""
+    lib = hip.load()
+    rows, Cc = x.shape
+    xd = x.contiguous().to(DEV)
+    g, b = torch.as_tensor(gamma, dtype=torch.float32).to(DEV), torch.as_tensor(beta, dtype=torch.float32).to(DEV)
+    out = torch.full((rows + guard_rows, Cc), float("nan"), device=DEV)
+    hip.check(lib.ccdm_layernorm(xd.data_ptr(), g.data_ptr(), b.data_ptr(), eps, rows, Cc, out.data_ptr(), 0), "layernorm")
+    sync()
+    out = out.cpu()
+    assert torch.isnan(out[rows:]).all(), "ccdm_layernorm wrote behind its last row"
+    return out[:rows]
+
+
+def gelu(x: torch.Tensor, guard: int = 64):
+    """ccdm_gelu of a flat cpu fp32 tensor -> cpu; `guard` NaN elements behind the output must come back untouched."""
+    lib = hip.load()
+    n = x.numel()
+    xd = x.contiguous().to(DEV)
+    out = torch.full((n + guard,), float("nan"), device=DEV)
+    hip.check(lib.ccdm_gelu(xd.data_ptr(), n, out.data_ptr(), 0), "gelu")
+    sync()
+    out = out.cpu()
+    assert torch.isnan(out[n:]).all(), "ccdm_gelu wrote behind its last element"
+    return out[:n]
+
+
+def token_linear(x: torch.Tensor, weight, bias=None, resid=None, diag: int = 0, packed=None):
+    """A ViT linear layer the way dino.ViTExtractor._linear runs it: x [N, rows, Cin] (rows % 16 == 0) as a [N, rows/16, 16, Cin] token
+    image through ccdm_conv2d, ksize 1, PREC_F16X3, no statistics; weight [Cout, Cin] numpy, bias [Cout] or None (a NULL pointer),
+    resid [N, rows, Cout] cuda or None.  diag: hip.DIAG_* bits.  packed: a device buffer of hip.pack_conv_weight to reuse.
+    Returns out [N, rows, Cout] cuda."""
+    lib = hip.load()
+    N, rows, Cin = x.shape
+    assert rows % 16 == 0
+    w = np.ascontiguousarray(weight, dtype=np.float32)
+    cout = w.shape[0]
+    assert w.shape == (cout, Cin)
+    wdev = packed if packed is not None else torch.from_numpy(hip.pack_conv_weight(w.reshape(cout, Cin, 1, 1), 1, hip.PREC_F16X3)).to(DEV)
+    bdev = torch.as_tensor(np.asarray(bias, dtype=np.float32)).to(DEV) if bias is not None else None
+    xd = x.contiguous().to(DEV)
+    out = torch.full((N, rows, cout), float("nan"), device=DEV)
+    a = hip.ConvArgs()
+    a.in0, a.C0 = xd.data_ptr(), Cin
+    a.eps, a.act = 1e-5, hip.ACT_NONE
+    a.N, a.Hin, a.Win, a.Hout, a.Wout = N, rows // 16, 16, rows // 16, 16
+    a.ksize, a.stride, a.up = 1, 1, 0
+    a.w, a.bias, a.Cout, a.prec = wdev.data_ptr(), (bdev.data_ptr() if bdev is not None else None), cout, hip.PREC_F16X3 | int(diag)
+    a.emb_off = -1
+    if resid is not None:
+        assert resid.is_cuda and tuple(resid.shape) == (N, rows, cout) and resid.is_contiguous()
+        a.resid = resid.data_ptr()
+    a.out = out.data_ptr()
+    hip.check(lib.ccdm_conv2d(C.byref(a), 0), "token linear")
+    sync()
+    return out
