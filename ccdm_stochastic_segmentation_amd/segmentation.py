@@ -16,6 +16,10 @@ against the original full-resolution labels — the reference's `evaluation/eval
                                                  pixels or as a ratio of the image diagonal, from the counts of one HIP kernel pair
                                                  (ccdm_segboundary) on the class map ccdm_segexport writes; boundary_from_counts is
                                                  the host formula, resolve_boundary_widths the width rule
+    SegmentationUncertainty(num_classes, ...)    does the spread of a multi-sample prediction mark its wrong pixels (beyond the
+                                                 reference): error-detection AUROC / AUPR, sparsification (AUSE, AURG) and PAvPU of
+                                                 the entropy and mutual-information maps, from the counts of one HIP kernel
+                                                 (ccdm_uncscore) on the same walk; uncertainty_from_counts is the host formula
     PredictionWriter(directory, split)           writes them as PNGs under outputs/<split>/{submit,debug,label}
     eval_segmentation(params, ...)               the evaluation loop (no ignite), built like evaluation.eval_lidc_uncertainty; with
                                                  evaluation.cityscapes_script also the official script's scores
@@ -472,6 +476,176 @@ class SegmentationBoundary:
                 "by_width": {str(e): boundary_from_counts(bc[i], tm[i], class_names) for i, e in enumerate(self.widths)}}
 
 
+# ------------------------------------------------------------------------------------------------ uncertainty quality
+UNCERTAINTY_MEASURES = ("entropy", "mutual_info")       # the per-pixel maps of DenoisingModel.predict_multiple that are scored
+UNCERTAINTY_PATCHES = (2, 4, 8, 16)                     # the patch sizes ccdm_uncscore takes
+UNCERTAINTY_MAX_BINS = 512
+
+
+def check_uncertainty_settings(bins, patch, measures, key: str = "") -> Tuple[int, int, Tuple[str, ...]]:
+    """(bins, patch, measures) of the uncertainty scores, checked on the host; `key` prefixes the name a ValueError gives."""
+    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not 2 <= int(bins) <= UNCERTAINTY_MAX_BINS:
+        raise ValueError(f"{key}bins: {bins!r} (the kernel takes 2..{UNCERTAINTY_MAX_BINS} uncertainty bins)")
+    if isinstance(patch, bool) or not isinstance(patch, (int, np.integer)) or int(patch) not in UNCERTAINTY_PATCHES:
+        raise ValueError(f"{key}patch: {patch!r} is not in {list(UNCERTAINTY_PATCHES)}")
+    if isinstance(measures, str) or not isinstance(measures, (list, tuple)) or not measures or len(set(measures)) != len(measures) \
+            or any(m not in UNCERTAINTY_MEASURES for m in measures):
+        raise ValueError(f"{key}measures: {measures!r} (expected a non-empty list without repeats from {list(UNCERTAINTY_MEASURES)})")
+    return int(bins), int(patch), tuple(measures)
+
+
+def uncertainty_from_counts(pix, patch) -> Dict[str, object]:
+    """The uncertainty-quality scores of one measure behind the counts of ccdm_uncscore, in float64 numpy (no GPU):
+      pix    [M,2] by uncertainty bin (bin b holds the values in [b/M, (b+1)/M) of the scale): {pixels, wrong pixels};
+      patch  [M,2] by bin of the patch's mean uncertainty: {patches, inaccurate patches}.
+    Returns a dict of plain Python values (JSON as it stands); with e the error rate:
+      pixels, bins, error_rate;
+      auroc_error_detection  the uncertainty as the detector of wrong pixels: P(u of a wrong pixel > u of a right one) +
+                             P(same bin) / 2, the trapezoid over the bins = the Mann-Whitney statistic of the binned values; None
+                             without a wrong or without a right pixel;
+      aupr_error             the wrong pixels as positives: the step-wise average precision, sum of (recall step) * precision
+                             over the non-empty bins from the most to the least uncertain; None without a wrong pixel;
+      sparsification         {"fraction_removed", "error", "ideal"} at the M + 1 bin edges: entry k removes the k most uncertain
+                             bins; error = wrong / kept among the kept pixels, ideal = max(e - f, 0) / (1 - f) at the removed
+                             fraction f (the wrong pixels removed first; formed as max(wrong - removed, 0) / kept from the
+                             integers); None where nothing is kept;
+      ause                   the area between error / e and ideal / e, trapezoids over fraction_removed on the entries that keep
+                             a pixel (the curve ends where only the lowest non-empty bin is left: a bin cannot be split);
+      aurg                   the area between the random baseline (constant e) and the curve, (1 - error / e), likewise;
+                             ause and aurg are None when e is 0;
+      patches, thresholds    the patches counted; k / M for k = 0 .. M: a patch whose bin is >= k is uncertain at threshold k / M;
+      p_accurate_given_certain, p_uncertain_given_inaccurate, pavpu   per threshold (Mukhoti & Gal 2018): n_ac / (n_ac + n_ic),
+                             n_iu / (n_ic + n_iu), (n_ac + n_iu) / patches; None on an empty denominator;
+      pavpu_max, pavpu_max_threshold, pavpu_mean   the largest pavpu, the first threshold that reaches it, the mean over the
+                             thresholds; None without patches."""
+    pix, patch = np.asarray(pix), np.asarray(patch)
+    if pix.ndim != 2 or pix.shape[1] != 2 or patch.shape != pix.shape:
+        raise ValueError(f"expected pix [M,2] and patch [M,2], got {pix.shape} and {patch.shape}")
+    M = int(pix.shape[0])
+    n, wrong = pix[:, 0].astype(np.float64), pix[:, 1].astype(np.float64)
+    right = n - wrong
+    N, n_wrong, n_right = n.sum(), wrong.sum(), right.sum()
+    res: Dict[str, object] = {"pixels": int(pix[:, 0].sum()), "bins": M, "error_rate": float(n_wrong / N) if N else None}
+
+    auroc = None
+    if n_wrong and n_right:
+        below = np.concatenate([[0.0], np.cumsum(right)[:-1]])          # right pixels in the lower bins
+        auroc = float((wrong * (below + 0.5 * right)).sum() / (n_wrong * n_right))
+    res["auroc_error_detection"] = auroc
+
+    aupr = None
+    if n_wrong:
+        has = n[::-1] > 0
+        precision = np.cumsum(wrong[::-1])[has] / np.cumsum(n[::-1])[has]
+        aupr = float((wrong[::-1][has] / n_wrong * precision).sum())
+    res["aupr_error"] = aupr
+
+    removed = np.concatenate([[0.0], np.cumsum(n[::-1])])               # entry k: the k most uncertain bins
+    kept = N - removed
+    kept_wrong = n_wrong - np.concatenate([[0.0], np.cumsum(wrong[::-1])])
+    some = kept > 0
+    error = kept_wrong[some] / kept[some]
+    ideal = np.maximum(n_wrong - removed[some], 0.0) / kept[some]
+    frac = removed[some] / N if N else removed[some]
+    pad = [None] * int((~some).sum())
+    res["sparsification"] = {"fraction_removed": [float(f) for f in removed / N] if N else [None] * (M + 1),
+                             "error": [float(v) for v in error] + pad, "ideal": [float(v) for v in ideal] + pad}
+    ause = aurg = None
+    if n_wrong:
+        e = n_wrong / N
+        step = np.diff(frac)
+
+        def area(d):
+            return float((step * 0.5 * (d[1:] + d[:-1])).sum())
+        ause, aurg = area((error - ideal) / e), area(1.0 - error / e)
+    res["ause"], res["aurg"] = ause, aurg
+
+    count, bad = patch[:, 0].astype(np.float64), patch[:, 1].astype(np.float64)
+    good = count - bad
+    total = count.sum()
+    n_ac = np.concatenate([[0.0], np.cumsum(good)])                     # entry k: the accurate patches in the bins below k
+    n_ic = np.concatenate([[0.0], np.cumsum(bad)])
+    n_iu = bad.sum() - n_ic
+
+    def ratio(a, b):
+        return [float(x / y) if y else None for x, y in zip(a, b)]
+    res["patches"] = int(patch[:, 0].sum())
+    res["thresholds"] = [k / M for k in range(M + 1)]
+    res["p_accurate_given_certain"] = ratio(n_ac, n_ac + n_ic)
+    res["p_uncertain_given_inaccurate"] = ratio(n_iu, n_ic + n_iu)
+    res["pavpu"] = pavpu = ratio(n_ac + n_iu, np.full(M + 1, total))
+    if total:
+        best = int(np.argmax(pavpu))
+        res.update(pavpu_max=pavpu[best], pavpu_max_threshold=best / M, pavpu_mean=float(np.mean(pavpu)))
+    else:
+        res.update(pavpu_max=None, pavpu_max_threshold=None, pavpu_mean=None)
+    return res
+
+
+class SegmentationUncertainty:
+    """Does the uncertainty of a multi-sample prediction mark the pixels it gets wrong?  (Beyond the reference, which never scores
+    its samples' spread.)  Over the pixels SegmentationConfusion counts, with the class it counts, every measure of `measures` —
+    the per-pixel maps of DenoisingModel.predict_multiple, at the prediction's resolution — is upsampled as the prediction is,
+    put on the scale [0, ln K] and counted into `bins` equal-width bins, per pixel and per aligned `patch` x `patch` patch, split
+    by wrong / right: one HIP kernel (ccdm_uncscore) without a full-resolution tensor.  The scale: both measures are at most
+    the entropy of the mean over the K channels, which is at most ln K; ranges[m] = float32(ln K) for both, and a value beyond
+    it lands in the last bin.
+      pix_count, patch_count   int64 [len(measures), bins, 2]: {pixels, wrong pixels}, {patches, inaccurate patches}, accumulated
+                               on the device.
+    update(prediction, maps, labels): prediction and labels as SegmentationConfusion.update takes them, maps a dict with an fp32
+    [B,h,w] tensor per measure.  result(names) is {"pixels", "bins", "patch", "range", "measures": {name:
+    uncertainty_from_counts(...)}} for the measures `names` (default: all)."""
+
+    def __init__(self, num_classes: int, device=None, bins: int = 256, patch: int = 8, measures: Sequence[str] = UNCERTAINTY_MEASURES):
+        self.num_classes = _check_num_classes(num_classes)
+        self.bins, self.patch, self.measures = check_uncertainty_settings(bins, patch, measures)
+        self.C = self.num_classes - 1
+        self.range = float(np.float32(np.log(self.num_classes)))
+        self.device = _cuda_device(device, "SegmentationUncertainty")
+        self._pix = torch.zeros((len(self.measures), self.bins, 2), dtype=torch.int64, device=self.device)
+        self._patch = torch.zeros((len(self.measures), self.bins, 2), dtype=torch.int64, device=self.device)
+
+    @property
+    def pix_count(self) -> torch.Tensor:
+        return self._pix.cpu()
+
+    @property
+    def patch_count(self) -> torch.Tensor:
+        return self._patch.cpu()
+
+    @torch.no_grad()
+    def update(self, prediction: torch.Tensor, maps: Dict[str, torch.Tensor], labels: torch.Tensor) -> None:
+        import ctypes
+        if labels.ndim != 3 or labels.shape[0] != prediction.shape[0]:
+            raise ValueError(f"labels: expected [B,H,W] with B = {prediction.shape[0]}, got {tuple(labels.shape)}")
+        missing = [m for m in self.measures if m not in maps]
+        if missing:
+            raise ValueError(f"maps: no map for {missing} (got {sorted(maps)})")
+        probs, ps, cls, h, w = prediction_form(prediction, self.num_classes, self.device)
+        lab = _labels_u8(labels, self.device)
+        B, H, W = (int(s) for s in lab.shape)
+        for m in self.measures:
+            if tuple(maps[m].shape) != (B, h, w):
+                raise ValueError(f"maps[{m!r}]: expected {(B, h, w)} = [B,h,w] of the prediction, got {tuple(maps[m].shape)}")
+        if B == 0:
+            return
+        stack = torch.stack([maps[m].to(self.device, torch.float32) for m in self.measures]).contiguous()
+        U = len(self.measures)
+        ranges = (ctypes.c_float * U)(*([self.range] * U))
+        hip.check(hip.load().ccdm_uncscore(*prediction_args(probs, ps, cls), lab.data_ptr(), stack.data_ptr(), ranges, B, h, w, H, W,
+                                           self.num_classes, U, self.bins, self.patch, self._pix.data_ptr(), self._patch.data_ptr(),
+                                           None, 0, torch.cuda.current_stream(self.device).cuda_stream), "uncscore")
+
+    def result(self, names: Optional[Sequence[str]] = None) -> Dict[str, object]:
+        names = self.measures if names is None else tuple(names)
+        unknown = [m for m in names if m not in self.measures]
+        if unknown:
+            raise ValueError(f"names: {unknown} not among the measures {list(self.measures)}")
+        pix, patch = self.pix_count.numpy(), self.patch_count.numpy()
+        scores = {m: uncertainty_from_counts(pix[self.measures.index(m)], patch[self.measures.index(m)]) for m in names}
+        return {"pixels": int(pix[0, :, 0].sum()), "bins": self.bins, "patch": self.patch, "range": self.range, "measures": scores}
+
+
 # ------------------------------------------------------------------------------------------------ prediction export
 EXPORT_OUTPUTS = ("train_id", "label_id", "color")
 
@@ -768,6 +942,13 @@ def eval_segmentation(params: dict, dataset=None, device=None, model=None, synth
     `evaluation.boundary_widths` (default ["ratio:0.02"]) lists the band widths, each an int (pixels, 1..64) or "ratio:R" (R times
     the diagonal of the scored size); a bad list raises before anything is sampled.  The result then holds "boundary"
     (SegmentationBoundary.result: Boundary IoU and trimap IoU per width), also written to <output_path>/boundary.json.
+    `evaluation.uncertainty` (default off): also score whether the samples' spread marks the wrong pixels (SegmentationUncertainty,
+    one more HIP launch per batch).  Needs `evaluations` >= 2: the batch's prediction then comes from model.predict_multiple with
+    maps ("mean", "entropy", "mutual_info") — the same passes, mean and Philox calls as without the key — and "mean" feeds every
+    other scorer.  `evaluation.uncertainty_bins` (default 256, 2..512), `evaluation.uncertainty_patch` (default 8; 2, 4, 8 or 16)
+    and `evaluation.uncertainty_measures` (default both maps); a bad value, or one evaluation, raises before anything is sampled.
+    Under the majority vote mutual_info equals entropy by construction, so only entropy is scored there.  The result then holds
+    "uncertainty" (SegmentationUncertainty.result), also written to <output_path>/uncertainty.json.
     `model`: a ready DenoisingModel-like callable (tests inject one); default: built from `params`."""
     from . import evaluation as E
     world = int(os.environ.get("WORLD_SIZE", "1") or 1)
@@ -787,6 +968,21 @@ def eval_segmentation(params: dict, dataset=None, device=None, model=None, synth
     if section.get("boundary", False):
         boundary_widths = section.get("boundary_widths", list(BOUNDARY_DEFAULT_WIDTHS))
         resolve_boundary_widths(boundary_widths)
+    unc_settings = None
+    if section.get("uncertainty", False):
+        unc_settings = check_uncertainty_settings(section.get("uncertainty_bins", 256), section.get("uncertainty_patch", 8),
+                                                  section.get("uncertainty_measures", list(UNCERTAINTY_MEASURES)), "evaluation.uncertainty_")
+        n_eval, strategy = E.vote_settings(params)
+        if n_eval < 2:
+            raise ValueError(f"evaluation.uncertainty needs evaluation.evaluations >= 2 (got {n_eval}): a single pass has no sample spread")
+        if strategy == "majority":      # one-hot passes: every H(p_s) is 0, mutual_info is the entropy map again
+            scored = tuple(m for m in unc_settings[2] if m != "mutual_info")
+            if not scored:
+                raise ValueError("evaluation.uncertainty_measures: under evaluation_vote_strategy majority mutual_info equals entropy "
+                                 "by construction and only entropy is scored; list entropy")
+            if scored != unc_settings[2]:
+                LOGGER.info("uncertainty: under the majority vote mutual_info equals entropy by construction; only entropy is scored")
+            unc_settings = unc_settings[:2] + (scored,)
     dataset = dataset if dataset is not None else make_segmentation_dataset(params)
     LOGGER.info("%d images in validation dataset '%s'", len(dataset), params["dataset_file"])
     if resolution not in RESOLUTIONS:
@@ -817,14 +1013,22 @@ def eval_segmentation(params: dict, dataset=None, device=None, model=None, synth
         scores = CityscapesScores(num_classes, device)
     calib = SegmentationCalibration(num_classes, device, int(section.get("calibration_bins", 15))) if section.get("calibration", False) else None
     boundary = SegmentationBoundary(num_classes, device, boundary_widths) if boundary_widths is not None else None
+    unc = SegmentationUncertainty(num_classes, device, *unc_settings) if unc_settings is not None else None
     n_img = 0
     for image, labels, labels_orig, *rest in loader:
         image = image.to(device)
         feature_condition = encoder(image) if encoder is not None else None
-        prediction = E.predict_multiple(model, image, params, feature_condition)
+        if unc is None:
+            prediction = E.predict_multiple(model, image, params, feature_condition)
+        else:           # the same passes as E.predict_multiple (evaluations >= 2), with the two uncertainty maps folded alongside the mean
+            multi = model.predict_multiple(image, feature_condition, num_evaluations=evaluations, voting=vote,
+                                           maps=("mean", "entropy", "mutual_info"))
+            prediction = multi["mean"]
         target = labels_orig if resolution == "original" else labels.argmax(dim=1)
         target = target.to(device)
         conf.update(prediction, target)
+        if unc is not None:
+            unc.update(prediction, multi, target)
         if calib is not None:
             calib.update(prediction, target)
         if boundary is not None:
@@ -868,6 +1072,13 @@ def eval_segmentation(params: dict, dataset=None, device=None, model=None, synth
             LOGGER.info("boundary width %s (%s px): Boundary mIoU %s  trimap mIoU %.4f over %d pixels (%s)", w["entry"],
                         ", ".join(str(p) for p in w["pixels"]), "n/a" if s["mean_boundary_iou"] is None else f"{s['mean_boundary_iou']:.4f}",
                         s["trimap_miou"], s["trimap_pixels"], path)
+    if unc is not None:
+        res["uncertainty"] = u = unc.result()
+        path = _write_json(E.expanduservars(params["output_path"]), "uncertainty", u)
+        for m, s in u["measures"].items():
+            LOGGER.info("uncertainty %s over %d pixels, %d bins, %d x %d patches: AUROC (error detection) %s  AUSE %s  PAvPU max %s (%s)", m,
+                        s["pixels"], u["bins"], u["patch"], u["patch"],
+                        *("n/a" if s[k] is None else f"{s[k]:.4f}" for k in ("auroc_error_detection", "ause", "pavpu_max")), path)
     LOGGER.info("mIoU %.4f  soft mIoU %.4f over %d images (resolution %s, %d evaluation(s), %s)", res["mIoU"], res["mIoU_soft"], n_img,
                 resolution, evaluations, vote)
     return res

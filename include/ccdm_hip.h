@@ -562,6 +562,40 @@ int ccdm_segboundary(const uint8_t* pred /*dev [B,H,W] train ids*/, const uint8_
                      size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Uncertainty-quality counts of a multi-sample prediction, device part (beyond the reference, which never scores its samples'
+ * spread): the histograms behind the error-detection AUROC / AUPR, the sparsification curve and PAvPU (Mukhoti & Gal 2018), in
+ * one pass over the output pixels of [B,H,W], without a full-resolution tensor.  The prediction (probs XOR cls), the labels, the
+ * counted pixels (label < C, C = K-1), the bilinear sample and the argmax `pred` are those of ccdm_seg_confusion above, through
+ * the same device code: the class judged here is the class counted there and the byte ccdm_segexport writes as train_id with
+ * scored = K-1, bit for bit.  wrong = (pred != label).
+ *   maps    fp32 [U][B,h,w] (device): U per-pixel uncertainty maps at the prediction's resolution (the entropy / mutual_info
+ *           maps of ccdm_vote_finalize);  ranges  fp32 [U] (HOST), each > 0: the value of map m that fills the scale.
+ * Per counted pixel and map m:
+ *   u       the bilinear sample of maps[m] at the output pixel by the formula of ccdm_seg_confusion with the same i0, i1, l0, l1
+ *           as the probabilities: u = lh0 * (lw0 * u00 + lw1 * u01) + lh1 * (lw0 * u10 + lw1 * u11) in fp32; (H,W) == (h,w)
+ *           reads the pixel itself;
+ *   t       u / ranges[m] (IEEE fp32 division); a t that is not > 0 (NaN included) becomes 0, t >= 1 becomes 1;
+ *   q       (int)(t * 65536.0f), so 0 <= q <= 65536.  Everything after this line is integer arithmetic.
+ * Outputs (device):
+ *   pix     int64 [U][M][2]: pix[m][bin] += {1, wrong} with bin = min((q*M) >> 16, M-1).  ACCUMULATED across calls;
+ *   patch   int64 [U][M][2]: the image is cut into aligned, non-overlapping P x P patches from pixel (0,0), truncated at the right
+ *           and bottom edges.  For a patch with n >= 1 counted pixels, Q = the sum of their q, e = the number of wrong ones; the
+ *           patch is inaccurate iff 2*e >= n; patch[m][bin] += {1, inaccurate} with bin = min((Q*M) / (n*65536), M-1) in 64-bit
+ *           integer division.  Patches with n = 0 are not counted.  ACCUMULATED across calls.
+ * K in [2,32], U in [1,4], M in [2,512], P in {2,4,8,16}: each limit is checked before anything is launched and each refusal
+ * names the argument; a refused call writes nothing.  ccdm_uncscore_workspace_bytes is 0 (the per-block tables live on chip);
+ * workspace may be NULL.  Integer atomics only, after a per-block count in LDS: every count is exact in any order, two identical
+ * calls are bit-identical.  B = 0 returns 0 without a launch and leaves the outputs as they are.
+ * (Named without the ccdm_seg prefixes: the evaluator's tests pin the sets of ccdm_seg_*, ccdm_segcalib* and ccdm_segboundary*
+ * symbols.)
+ * ------------------------------------------------------------------------------------------------- */
+size_t ccdm_uncscore_workspace_bytes(int B, int H, int W, int K, int U, int M);
+int ccdm_uncscore(const float* probs /*dev or NULL*/, int64_t pixel_stride, const uint8_t* cls /*dev [B,h,w] or NULL*/,
+                  const uint8_t* labels /*dev [B,H,W]*/, const float* maps /*dev [U][B,h,w]*/, const float* ranges /*HOST [U], > 0*/,
+                  int B, int h, int w, int H, int W, int K, int U, int M, int P, int64_t* pix /*dev [U][M][2]*/,
+                  int64_t* patch /*dev [U][M][2]*/, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Multi-sample prediction (DenoisingModel.predict_multiple): S sampling passes of the same B images folded into one
  * mean map, a per-pixel vote and two uncertainty maps.  The reference's Evaluator.predict_multiple
  * (evaluation/eval_cdm.py:176-193) accumulates `total += prediction_i * (1 / S)` on the host; these read a pass
