@@ -9,7 +9,8 @@
 // Users: ccdm_segeval.hip (k_seg_confusion), ccdm_segexport.hip (k_seg_export), ccdm_csscore.hip (k_csscore; k_csscore_ids takes
 // the tiles only), ccdm_segcalib.hip (k_seg_calib).  Every one of them classifies a pixel through these and nothing else, so
 // the class one counts is the class the others count, bin and write, bit for bit.  ccdm_segboundary.hip reads the class map the
-// export kernel wrote; its row pass (k_segboundary_rows) takes the tiles and a wave helper.
+// export kernel wrote; its row pass (k_segboundary_rows) takes the tiles and a wave helper.  ccdm_contourf.hip reads that class
+// map too; both of its passes take the tiles, the match pass also the loop over groups of lanes with equal key.
 #pragma once
 #include <type_traits>
 

@@ -16,6 +16,11 @@ against the original full-resolution labels — the reference's `evaluation/eval
                                                  pixels or as a ratio of the image diagonal, from the counts of one HIP kernel pair
                                                  (ccdm_segboundary) on the class map ccdm_segexport writes; boundary_from_counts is
                                                  the host formula, resolve_boundary_widths the width rule
+    SegmentationContourF(num_classes, ...)       the boundary F-score (BF score, beyond the reference) per class and image at
+                                                 tolerances in pixels or as a ratio of the image diagonal, from the counts of one
+                                                 HIP kernel pair (ccdm_contourf: a disc search around every contour pixel) on the
+                                                 class map ccdm_segexport writes; contour_f_from_counts is the host formula,
+                                                 resolve_contour_tolerances the tolerance rule
     SegmentationUncertainty(num_classes, ...)    does the spread of a multi-sample prediction mark its wrong pixels (beyond the
                                                  reference): error-detection AUROC / AUPR, sparsification (AUSE, AURG) and PAvPU of
                                                  the entropy and mutual-information maps, from the counts of one HIP kernel
@@ -341,11 +346,11 @@ BOUNDARY_MAX_WIDTH = 64             # the widest band ccdm_segboundary takes, in
 BOUNDARY_DEFAULT_WIDTHS = ("ratio:0.02",)       # the Boundary IoU paper's 2 % of the image diagonal: 46 px at 1024 x 2048
 
 
-def _width_entry(entry):
-    """One entry of a width list -> ("px", int) or ("ratio", float); ValueError for anything else."""
+def _px_entry(entry, what: str, limit: int):
+    """One entry of a list of pixel sizes -> ("px", int) or ("ratio", float); ValueError for anything else."""
     if isinstance(entry, (int, np.integer)) and not isinstance(entry, bool):
-        if not 1 <= int(entry) <= BOUNDARY_MAX_WIDTH:
-            raise ValueError(f"boundary width {entry!r}: a width in pixels lies in [1, {BOUNDARY_MAX_WIDTH}]")
+        if not 1 <= int(entry) <= limit:
+            raise ValueError(f"{what} {entry!r}: a value in pixels lies in [1, {limit}]")
         return "px", int(entry)
     if isinstance(entry, str) and entry.startswith("ratio:"):
         try:
@@ -353,9 +358,32 @@ def _width_entry(entry):
         except ValueError:
             ratio = float("nan")
         if not (0.0 < ratio < float("inf")):
-            raise ValueError(f"boundary width {entry!r}: expected 'ratio:R' with a number R > 0")
+            raise ValueError(f"{what} {entry!r}: expected 'ratio:R' with a number R > 0")
         return "ratio", ratio
-    raise ValueError(f"boundary width {entry!r}: expected an int in [1, {BOUNDARY_MAX_WIDTH}] (pixels) or the string 'ratio:R'")
+    raise ValueError(f"{what} {entry!r}: expected an int in [1, {limit}] (pixels) or the string 'ratio:R'")
+
+
+def _resolve_px_list(entries, size: Optional[Sequence[int]], what: str, limit: int) -> List[int]:
+    """The rule the boundary widths and the contour tolerances share: a non-empty list without repeats of ints in [1, limit]
+    (pixels) and "ratio:R" strings, which stand for max(1, round(R * sqrt(H^2 + W^2))) pixels at size = (H, W) and must not exceed
+    `limit` there.  Without `size` the entries are only checked and a ratio entry gives 0."""
+    if isinstance(entries, (str, bytes)) or not isinstance(entries, (list, tuple)) or len(entries) == 0:
+        raise ValueError(f"{what}s {entries!r}: expected a non-empty list of ints (pixels) and 'ratio:R' strings")
+    if len({str(e) for e in entries}) != len(entries):
+        raise ValueError(f"{what}s {list(entries)!r}: an entry is repeated")
+    out = []
+    for entry in entries:
+        kind, v = _px_entry(entry, what, limit)
+        if kind == "ratio":
+            if size is None:
+                v = 0
+            else:
+                H, W = int(size[0]), int(size[1])
+                v = max(1, int(round(v * float(np.sqrt(float(H * H + W * W))))))
+                if v > limit:
+                    raise ValueError(f"{what} {entry!r} is {v} pixels at {H} x {W}: the limit is {limit} pixels")
+        out.append(v)
+    return out
 
 
 def resolve_boundary_widths(widths, size: Optional[Sequence[int]] = None) -> List[int]:
@@ -363,23 +391,7 @@ def resolve_boundary_widths(widths, size: Optional[Sequence[int]] = None) -> Lis
     the string "ratio:R", which stands for max(1, round(R * sqrt(H^2 + W^2))) pixels at the scored size (H, W) (Python's round, as
     the published Boundary IoU code).  Returns the widths in pixels, one per entry; without `size` the entries are only checked
     and a ratio entry gives 0.  An entry that is neither, or a width outside [1, 64], is a ValueError that names the limit."""
-    if isinstance(widths, (str, bytes)) or not isinstance(widths, (list, tuple)) or len(widths) == 0:
-        raise ValueError(f"boundary widths {widths!r}: expected a non-empty list of ints (pixels) and 'ratio:R' strings")
-    if len({str(e) for e in widths}) != len(widths):
-        raise ValueError(f"boundary widths {list(widths)!r}: an entry is repeated")
-    out = []
-    for entry in widths:
-        kind, v = _width_entry(entry)
-        if kind == "ratio":
-            if size is None:
-                v = 0
-            else:
-                H, W = int(size[0]), int(size[1])
-                v = max(1, int(round(v * float(np.sqrt(float(H * H + W * W))))))
-                if v > BOUNDARY_MAX_WIDTH:
-                    raise ValueError(f"boundary width {entry!r} is {v} pixels at {H} x {W}: the widest band is {BOUNDARY_MAX_WIDTH} pixels")
-        out.append(v)
-    return out
+    return _resolve_px_list(widths, size, "boundary width", BOUNDARY_MAX_WIDTH)
 
 
 def boundary_from_counts(bcounts, trimap, class_names: Optional[Sequence[str]] = None) -> Dict[str, object]:
@@ -474,6 +486,126 @@ class SegmentationBoundary:
         bc, tm = self.bcounts.numpy(), self.trimap.numpy()
         return {"widths": [{"entry": e, "pixels": list(p)} for e, p in zip(self.widths, self.pixels)],
                 "by_width": {str(e): boundary_from_counts(bc[i], tm[i], class_names) for i, e in enumerate(self.widths)}}
+
+
+# ------------------------------------------------------------------------------------------------ boundary F-score
+CONTOUR_MAX_TOLERANCE = 32          # the widest disc ccdm_contourf searches, in pixels
+CONTOUR_DEFAULT_TOLERANCES = ("ratio:0.0075",)      # bfscore's 0.75 % of the image diagonal: 17 px at 1024 x 2048
+
+
+def resolve_contour_tolerances(tolerances, size: Optional[Sequence[int]] = None) -> List[int]:
+    """The tolerance rule of the boundary F-score: the rule of resolve_boundary_widths (a non-empty list without repeats of ints,
+    pixels, and "ratio:R" strings, R times the diagonal of the scored size (H, W), rounded, at least 1) with the limit
+    [1, 32].  Returns the tolerances in pixels, one per entry; without `size` the entries are only checked and a ratio entry
+    gives 0.  A bad entry, or a ratio beyond 32 pixels at `size`, is a ValueError that names the limit."""
+    return _resolve_px_list(tolerances, size, "contour tolerance", CONTOUR_MAX_TOLERANCE)
+
+
+def contour_f_from_counts(counts, class_names: Optional[Sequence[str]] = None) -> Dict[str, object]:
+    """The boundary F-scores behind the counts of ccdm_contourf at one tolerance, in float64 on the host (no GPU):
+      counts  [N,C,4] per image and class {nP, mP, nG, mG}: the contour pixels of the prediction, those of them matched in the
+              labels, the contour pixels of the labels, those of them matched in the prediction.
+    A cell (image, class) is scored when nG > 0: precision = mP / nP (0 when nP = 0), recall = mG / nG, F = 2PR / (P + R) (0 when
+    P + R = 0).  Returns a dict of plain Python values (JSON as it stands); per class a list, or a dict keyed by class_names:
+      bf_score, precision, recall   the mean over the class's scored images, None when it has none;
+      images      the scored cells of the class;  pred_only: its cells with nG = 0 < nP, reported and not averaged;
+      mean_bf_score   the mean of bf_score over the classes that have a value, None when there is none;
+      pooled      {"bf_score", "precision", "recall"} per class from the sums of the four counts over all images (None for a
+                  class whose summed nG is 0), with their class means "mean_bf_score", "mean_precision", "mean_recall";
+      counts      those sums, [C][4]."""
+    ct = np.asarray(counts)
+    if ct.ndim != 3 or ct.shape[2] != 4:
+        raise ValueError(f"expected counts [N,C,4], got {ct.shape}")
+    ct = ct.astype(np.int64)
+    N, C = ct.shape[:2]
+    if class_names is not None and len(class_names) != C:
+        raise ValueError(f"class_names: {len(class_names)} names for {C} classes")
+
+    def prf(nP, mP, nG, mG):
+        """(precision, recall, F) of a scored cell, nG > 0"""
+        P = float(mP) / float(nP) if nP > 0 else 0.0
+        R = float(mG) / float(nG)
+        return P, R, (2.0 * P * R / (P + R) if P + R > 0 else 0.0)
+
+    def mean(values):
+        have = [v for v in values if v is not None]
+        return float(np.mean(have)) if have else None
+    named = (lambda v: list(v)) if class_names is None else (lambda v: dict(zip(class_names, v)))
+    per_image = [[prf(*ct[n, c]) for n in range(N) if ct[n, c, 2] > 0] for c in range(C)]
+    col = lambda k: [float(np.mean([t[k] for t in cells])) if cells else None for cells in per_image]
+    total = ct.sum(axis=0)
+    pooled = [prf(*total[c]) if total[c, 2] > 0 else (None, None, None) for c in range(C)]
+    pcol = lambda k: [t[k] for t in pooled]
+    return {"bf_score": named(col(2)), "precision": named(col(0)), "recall": named(col(1)),
+            "images": named([len(cells) for cells in per_image]),
+            "pred_only": named([int(((ct[:, c, 2] == 0) & (ct[:, c, 0] > 0)).sum()) for c in range(C)]),
+            "mean_bf_score": mean(col(2)),
+            "pooled": {"bf_score": named(pcol(2)), "precision": named(pcol(0)), "recall": named(pcol(1)),
+                       "mean_bf_score": mean(pcol(2)), "mean_precision": mean(pcol(0)), "mean_recall": mean(pcol(1))},
+            "counts": total.tolist()}
+
+
+class SegmentationContourF:
+    """The boundary F-score of a segmentation prediction against the labels (beyond the reference; Csurka et al.'s BF score,
+    MATLAB's bfscore, the DAVIS F-measure): how much of the predicted contour of a class lies within a tolerance of the true
+    one, and how much of the true contour was found, per class and per image, at every tolerance of `tolerances`
+    (resolve_contour_tolerances; default bfscore's 0.75 % of the image diagonal), over the pixels SegmentationConfusion counts,
+    with the class it counts.  update(prediction, labels) takes what SegmentationConfusion.update takes: one ccdm_segexport launch
+    turns the prediction into the class map at the labels' size, then one ccdm_contourf launch per tolerance counts
+      counts  int64 [tolerances, images, C, 4]: {nP, mP, nG, mG} per image and class (the contract of include/ccdm_hip.h); the
+              tables of the updates are kept on the device and concatenated.
+    A ratio entry is resolved again at every update, at that update's (H, W); `pixels` keeps, per entry, the distinct pixel
+    tolerances used so far.  result() is contour_f_from_counts per entry."""
+
+    def __init__(self, num_classes: int, device=None, tolerances: Sequence = CONTOUR_DEFAULT_TOLERANCES):
+        self.num_classes = _check_num_classes(num_classes)
+        self.tolerances = list(tolerances) if isinstance(tolerances, (list, tuple)) else tolerances
+        resolve_contour_tolerances(self.tolerances)
+        self.tolerances = [e if isinstance(e, str) else int(e) for e in self.tolerances]
+        self.C = self.num_classes - 1
+        self.device = _cuda_device(device, "SegmentationContourF")
+        self._tables: List[torch.Tensor] = []               # one [tolerances, B, C, 4] per update
+        self.pixels: List[List[int]] = [[] for _ in self.tolerances]
+        # ccdm_segexport wants both tables although only train_id is written
+        self._export_tables = torch.zeros(4 * self.num_classes, dtype=torch.uint8, device=self.device)
+        self._ws: Optional[torch.Tensor] = None
+
+    @property
+    def counts(self) -> torch.Tensor:
+        if not self._tables:
+            return torch.zeros((len(self.tolerances), 0, self.C, 4), dtype=torch.int64)
+        return torch.cat(self._tables, dim=1).cpu()
+
+    @torch.no_grad()
+    def update(self, prediction: torch.Tensor, labels: torch.Tensor) -> None:
+        if labels.ndim != 3 or labels.shape[0] != prediction.shape[0]:
+            raise ValueError(f"labels: expected [B,H,W] with B = {prediction.shape[0]}, got {tuple(labels.shape)}")
+        probs, ps, cls, h, w = prediction_form(prediction, self.num_classes, self.device)
+        lab = _labels_u8(labels, self.device)
+        B, H, W = (int(s) for s in lab.shape)
+        px = resolve_contour_tolerances(self.tolerances, (H, W))
+        if B == 0:
+            return
+        lib = hip.load()
+        K, stream = self.num_classes, torch.cuda.current_stream(self.device).cuda_stream
+        train_id = torch.empty((B, H, W), dtype=torch.uint8, device=self.device)
+        hip.check(lib.ccdm_segexport(*prediction_args(probs, ps, cls), B, h, w, H, W, K, K - 1, self._export_tables.data_ptr(),
+                                     self._export_tables.data_ptr() + K, train_id.data_ptr(), None, None, stream), "segexport")
+        need = int(lib.ccdm_contourf_workspace_bytes(B, H, W))
+        self._ws = _grown(self._ws, need, self.device)
+        table = torch.zeros((len(px), B, self.C, 4), dtype=torch.int64, device=self.device)
+        for i, theta in enumerate(px):
+            hip.check(lib.ccdm_contourf(train_id.data_ptr(), lab.data_ptr(), B, H, W, K, theta, table[i].data_ptr(), self._ws.data_ptr(), need,
+                                        stream), "contourf")
+            if theta not in self.pixels[i]:
+                self.pixels[i].append(theta)
+        self._tables.append(table)
+
+    def result(self, class_names: Optional[Sequence[str]] = None) -> Dict[str, object]:
+        """{"tolerances": [{"entry", "pixels"} per entry], "by_tolerance": {str(entry): contour_f_from_counts(...)}}"""
+        ct = self.counts.numpy()
+        return {"tolerances": [{"entry": e, "pixels": list(p)} for e, p in zip(self.tolerances, self.pixels)],
+                "by_tolerance": {str(e): contour_f_from_counts(ct[i], class_names) for i, e in enumerate(self.tolerances)}}
 
 
 # ------------------------------------------------------------------------------------------------ uncertainty quality
@@ -942,6 +1074,12 @@ def eval_segmentation(params: dict, dataset=None, device=None, model=None, synth
     `evaluation.boundary_widths` (default ["ratio:0.02"]) lists the band widths, each an int (pixels, 1..64) or "ratio:R" (R times
     the diagonal of the scored size); a bad list raises before anything is sampled.  The result then holds "boundary"
     (SegmentationBoundary.result: Boundary IoU and trimap IoU per width), also written to <output_path>/boundary.json.
+    `evaluation.contour_f` (default off): also score the boundary F-score (SegmentationContourF: one ccdm_segexport launch and one
+    ccdm_contourf launch per tolerance per batch, on the tensor and labels the confusion matrices get).
+    `evaluation.contour_tolerances` (default ["ratio:0.0075"]) lists the tolerances, each an int (pixels, 1..32) or "ratio:R" (R
+    times the diagonal of the scored size); a bad list raises before anything is sampled.  The result then holds "contour_f"
+    (SegmentationContourF.result: the BF score per class, per image and pooled, per tolerance), also written to
+    <output_path>/contour_f.json.
     `evaluation.uncertainty` (default off): also score whether the samples' spread marks the wrong pixels (SegmentationUncertainty,
     one more HIP launch per batch).  Needs `evaluations` >= 2: the batch's prediction then comes from model.predict_multiple with
     maps ("mean", "entropy", "mutual_info") — the same passes, mean and Philox calls as without the key — and "mean" feeds every
@@ -968,6 +1106,10 @@ def eval_segmentation(params: dict, dataset=None, device=None, model=None, synth
     if section.get("boundary", False):
         boundary_widths = section.get("boundary_widths", list(BOUNDARY_DEFAULT_WIDTHS))
         resolve_boundary_widths(boundary_widths)
+    contour_tolerances = None
+    if section.get("contour_f", False):
+        contour_tolerances = section.get("contour_tolerances", list(CONTOUR_DEFAULT_TOLERANCES))
+        resolve_contour_tolerances(contour_tolerances)
     unc_settings = None
     if section.get("uncertainty", False):
         unc_settings = check_uncertainty_settings(section.get("uncertainty_bins", 256), section.get("uncertainty_patch", 8),
@@ -996,6 +1138,8 @@ def eval_segmentation(params: dict, dataset=None, device=None, model=None, synth
     num_classes = input_shapes[1][0]
     if boundary_widths is not None:            # a ratio that is too wide at the scored size, before anything is sampled
         resolve_boundary_widths(boundary_widths, dataset[0][2].shape[-2:] if resolution == "original" else labels0.shape[-2:])
+    if contour_tolerances is not None:
+        resolve_contour_tolerances(contour_tolerances, dataset[0][2].shape[-2:] if resolution == "original" else labels0.shape[-2:])
     encoder = _feature_encoder(params, synthetic_weights_seed, device)
     if model is None:
         model = E.build_from_params(params, input_shapes, device)
@@ -1013,6 +1157,7 @@ def eval_segmentation(params: dict, dataset=None, device=None, model=None, synth
         scores = CityscapesScores(num_classes, device)
     calib = SegmentationCalibration(num_classes, device, int(section.get("calibration_bins", 15))) if section.get("calibration", False) else None
     boundary = SegmentationBoundary(num_classes, device, boundary_widths) if boundary_widths is not None else None
+    contour = SegmentationContourF(num_classes, device, contour_tolerances) if contour_tolerances is not None else None
     unc = SegmentationUncertainty(num_classes, device, *unc_settings) if unc_settings is not None else None
     n_img = 0
     for image, labels, labels_orig, *rest in loader:
@@ -1033,6 +1178,8 @@ def eval_segmentation(params: dict, dataset=None, device=None, model=None, synth
             calib.update(prediction, target)
         if boundary is not None:
             boundary.update(prediction, target)
+        if contour is not None:
+            contour.update(prediction, target)
         if writer is not None:
             writer.write(prediction, target, tuple(target.shape[1:]))
         if scores is not None:
@@ -1072,6 +1219,15 @@ def eval_segmentation(params: dict, dataset=None, device=None, model=None, synth
             LOGGER.info("boundary width %s (%s px): Boundary mIoU %s  trimap mIoU %.4f over %d pixels (%s)", w["entry"],
                         ", ".join(str(p) for p in w["pixels"]), "n/a" if s["mean_boundary_iou"] is None else f"{s['mean_boundary_iou']:.4f}",
                         s["trimap_miou"], s["trimap_pixels"], path)
+    if contour is not None:
+        res["contour_f"] = ctf = contour.result(names)
+        path = _write_json(E.expanduservars(params["output_path"]), "contour_f", ctf)
+        for t in ctf["tolerances"]:
+            s = ctf["by_tolerance"][str(t["entry"])]
+            LOGGER.info("contour tolerance %s (%s px): mean BF score %s  pooled %s over %d scored cells (%s)", t["entry"],
+                        ", ".join(str(p) for p in t["pixels"]),
+                        *("n/a" if v is None else f"{v:.4f}" for v in (s["mean_bf_score"], s["pooled"]["mean_bf_score"])),
+                        sum(s["images"].values()), path)
     if unc is not None:
         res["uncertainty"] = u = unc.result()
         path = _write_json(E.expanduservars(params["output_path"]), "uncertainty", u)

