@@ -573,6 +573,22 @@ class SamplerEngine:
         hip.check(self.lib.ccdm_engine_run(self._handle, first_row, n_steps, int(with_epilogue), int(use_graph),
                                            self._stream()), "engine_run")
 
+    def clamp_known_labels(self, known: torch.Tensor, cumalpha_tm1: float, mode: int, step_row: int, *, philox_seed: int = 0,
+                           sample_offset: int = 0) -> None:
+        """Overwrite the known pixels of the state the last `run` left (ccdm_known_labels_step, asynchronous on the engine's stream).
+        known: uint8 [N,H*W] on the engine's device, class < K = known, 255 = free; cumalpha_tm1 / mode: columns 1 and 2 of the
+        table row `step_row` that run executed.  The two probabilities are formed in float64 and rounded to fp32 once."""
+        assert known.dtype == torch.uint8 and known.is_cuda and known.is_contiguous() and tuple(known.shape) == (self.N, self.H * self.W)
+        c = float(cumalpha_tm1)
+        p_miss = (1.0 - c) / self.K
+        last = mode != hip.STEP_SAMPLE
+        hip.check(self.lib.ccdm_known_labels_step(
+            known.data_ptr(), self.N, self.H * self.W, self.K, float(np.float32(c + p_miss)), float(np.float32(p_miss)), int(mode),
+            int(step_row), int(philox_seed) & (2 ** 64 - 1), int(sample_offset), self.xt.data_ptr(),
+            None if self.stem_onehot_on_load else self.xin.ptr, self.Cs,
+            self.out_probs.data_ptr() if last else None, self.out_onehot.data_ptr() if last else None, self._stream()), "known_labels_step")
+        self._known_keepalive = known
+
     def ce_logits(self) -> Optional[torch.Tensor]:
         """[N,K-1,H,W] logits of the optional ce head after the last run (BCHW view of channels-last memory), else None."""
         if self.head_ce is None:

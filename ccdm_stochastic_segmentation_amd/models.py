@@ -277,7 +277,21 @@ class DenoisingModel(nn.Module):
     product, with the exact-fp32 kernel taking over any layer whose raw input leaves the split's range) or
     hip.PREC_F32 (exact fp32 MFMA everywhere, the validation mode).  hip.PREC_F16 is the OPT-IN single-pass fast mode (every conv on the
     general kernel with one fp16 MFMA per product; attention cores keep the split): narrower arithmetic than the reference's, outside the
-    parity contract, never a default."""
+    parity contract, never a default.
+    `known_labels` (keyword of `forward`, `forward_denoising`, `predict_multiple`): sample segmentations that agree with labels already at
+    hand — an integer map [N,H,W] holding a class in [0,K) where the label is known and 255 where the pixel is free.  The replacement
+    method of RePaint (Lugmayr et al. 2022) for categorical diffusion, no retraining: after every reverse step each known pixel is
+    overwritten with a draw from the forward process at that step's noise level, q(x_{t-1} | x_0 = y) = Cat(cumalpha_{t-1} onehot(y) +
+    (1 - cumalpha_{t-1}) / K) (ccdm_known_labels_step, one launch per step and sub-batch), so the network sees known pixels that carry the
+    right amount of noise and denoises the free ones in agreement with them.  x_T is left as given (at t = T the forward process is
+    uniform to within cumalpha_T); the state a walk returns carries the labels themselves: its last row is clamped with cumalpha = 1, at
+    t = 1 (where cumalpha_0 = 1 anyway) and on a walk that stops above it.  The draw is keyed by (pixel, global sample index, step row)
+    under the call's Philox key on counters the epilogue never uses: results do not depend on `substreams`, `use_graph` or how the
+    batch is sharded (a caller that shards passes its shard's slice of the map).  A conditioned call walks every engine one step at a
+    time and takes the static execution-mode rule (no `calibrate_mode` measurement); rng = "torch_cpu" has no reference stream for this
+    draw and is refused.  Without the keyword nothing changes: no extra launch, no per-step stepping."""
+
+    KNOWN_FREE = 255        # the value of a free pixel in `known_labels`
 
     def __init__(self, diffusion: DiffusionModel, unet: UNetModel, dataset_file: str, step_T_sample: str = "majority"):
         super().__init__()
@@ -343,7 +357,10 @@ class DenoisingModel(nn.Module):
 
     # ------------------------------------------------------------------ reference API
     def forward(self, x: Tensor, condition: Tensor, feature_condition: Tensor = None, t: Optional[Tensor] = None,
-                label_ref_logits: Optional[Tensor] = None, validation: bool = False) -> Union[Tensor, dict]:
+                label_ref_logits: Optional[Tensor] = None, validation: bool = False, *,
+                known_labels: Optional[Tensor] = None) -> Union[Tensor, dict]:
+        if known_labels is not None and (self.training or validation):
+            raise ValueError("known_labels: only a sampling call (eval mode, validation=False) takes known labels")
         if self.training:
             if not isinstance(t, Tensor):
                 raise ValueError("'t' needs to be a Tensor at training time")
@@ -353,8 +370,8 @@ class DenoisingModel(nn.Module):
         if validation:
             return self.forward_step(x, condition, feature_condition, t)
         if t is None:
-            return self.forward_denoising(x, condition, feature_condition, label_ref_logits=label_ref_logits)
-        return self.forward_denoising(x, condition, feature_condition, cast(int, t.item()), label_ref_logits)
+            return self.forward_denoising(x, condition, feature_condition, label_ref_logits=label_ref_logits, known_labels=known_labels)
+        return self.forward_denoising(x, condition, feature_condition, cast(int, t.item()), label_ref_logits, known_labels=known_labels)
 
     # ------------------------------------------------------------------ engine plumbing
     def _weights_key(self) -> Tuple[int, int]:
@@ -535,11 +552,37 @@ class DenoisingModel(nn.Module):
 
     def forward_denoising(self, x: Optional[Tensor], condition: Tensor, feature_condition: Tensor,
                           init_t: Optional[int] = None, label_ref_logits: Optional[Tensor] = None, *,
-                          consume: Optional[Callable[[SamplerEngine, int, int], None]] = None) -> dict:
+                          consume: Optional[Callable[[SamplerEngine, int, int], None]] = None,
+                          known_labels: Optional[Tensor] = None) -> dict:
         """`consume` (predict_multiple): instead of returning the call's output, hand every sub-batch engine (eng, lo, hi) to
-        consume(eng, lo, hi) once the call has succeeded, with the engine's stream current; the result is then {}."""
+        consume(eng, lo, hi) once the call has succeeded, with the engine's stream current; the result is then {}.
+        `known_labels`: integer [N,H,W], a class where the label is known, 255 where the pixel is free (see the class docstring)."""
+        known = None if known_labels is None else self._check_known_labels(known_labels, (x.shape[0], x.shape[2], x.shape[3]), x.shape[1])
+        return self._sample(x, condition, feature_condition, init_t, label_ref_logits, consume, known)
+
+    def _check_known_labels(self, known_labels: Tensor, shape: Tuple[int, int, int], K: int) -> Tensor:
+        """The one host-side check of a call's `known_labels` (before anything runs): the map as uint8 [N,H*W] on the model's device."""
+        if self.rng == "torch_cpu":
+            raise ValueError("known_labels: not available with rng = 'torch_cpu' (the host-noise parity mode has no reference stream for "
+                             "the draw at the known pixels); use rng = 'philox'")
+        if not isinstance(known_labels, Tensor) or known_labels.dtype in (torch.bool,) or known_labels.dtype.is_floating_point \
+                or known_labels.dtype.is_complex:
+            raise ValueError(f"known_labels: expected an integer tensor (a class in [0,{K}) where the label is known, {self.KNOWN_FREE} where the "
+                             f"pixel is free), got {getattr(known_labels, 'dtype', type(known_labels).__name__)}")
+        shape = tuple(int(v) for v in shape)
+        if tuple(known_labels.shape) != shape:
+            raise ValueError(f"known_labels: expected shape {shape} = [N,H,W], got {tuple(known_labels.shape)}")
+        host = known_labels.detach().cpu()
+        bad = ((host < 0) | (host >= K)) & (host != self.KNOWN_FREE)
+        if bool(bad.any()):
+            raise ValueError(f"known_labels: values must be classes in [0,{K}) or {self.KNOWN_FREE} (free); found {int(host[bad][0])}")
+        return host.to(torch.uint8).reshape(shape[0], shape[1] * shape[2]).contiguous().to(next(self.unet.parameters()).device)
+
+    def _sample(self, x: Optional[Tensor], condition: Tensor, feature_condition: Tensor, init_t: Optional[int],
+                label_ref_logits: Optional[Tensor], consume, known: Optional[Tensor]) -> dict:
+        """One sampling call; `known`: what _check_known_labels returned, or None."""
         out = self._with_range_fallback(lambda: self._forward_denoising(x, condition, feature_condition, init_t, label_ref_logits,
-                                                                        consume))
+                                                                        consume, known_labels=known))
         if self.philox_advance:
             self.philox_call += 1           # the next call draws from a fresh stream (a range-error re-run above replayed this one)
         return out
@@ -550,7 +593,8 @@ class DenoisingModel(nn.Module):
     @torch.no_grad()
     def predict_multiple(self, condition: Tensor, feature_condition: Optional[Tensor] = None, *, num_evaluations: int,
                          voting: Optional[str] = None, x: Optional[Tensor] = None, t: Optional[Tensor] = None, batched: bool = False,
-                         maps: Sequence[str] = ("mean", "vote", "entropy", "mutual_info")) -> Dict[str, Tensor]:
+                         maps: Sequence[str] = ("mean", "vote", "entropy", "mutual_info"),
+                         known_labels: Optional[Tensor] = None) -> Dict[str, Tensor]:
         """S = `num_evaluations` samples of every image of `condition` [B,C,H,W], combined on the device into one prediction and
         per-pixel uncertainty maps — the reference's Evaluator.predict_multiple (evaluation/eval_cdm.py:176-193), which sums S
         `predict_single` outputs as `total += prediction_i * (1 / S)`.
@@ -564,6 +608,8 @@ class DenoisingModel(nn.Module):
         majority passes every H(p_s) is 0, so it equals `entropy`).
         x: optional one-hot x_T [S,B,K,H,W]; default: drawn per pass as predict_single does (uniform one-hot on condition's device).
         t: as in forward (e.g. 10000 + steps for a strided walk).
+        known_labels: integer [B,H,W] (a class where the label is known, 255 where the pixel is free): every pass is conditioned on it
+          (class docstring), so `vote` equals the label and `entropy` is 0 at the known pixels.
         batched=False: S sampling calls of B samples, each advancing `philox_call` exactly like S calls of model(x_i, condition);
           after each call the pass is folded into device accumulators straight from the engine (ccdm_vote_accumulate), so memory
           is one pass plus the accumulators.  The range-error fallback and the execution-mode choice apply per pass.
@@ -590,6 +636,7 @@ class DenoisingModel(nn.Module):
         if x is not None and tuple(x.shape) != (S, B, K, H, W):
             raise ValueError(f"x: expected one-hot x_T of shape {(S, B, K, H, W)} = [S,B,K,H,W], got {tuple(x.shape)}")
         init_t = None if t is None else int(t.item() if isinstance(t, Tensor) else t)
+        known = None if known_labels is None else self._check_known_labels(known_labels, (B, H, W), K)
         dev = next(self.unet.parameters()).device
         lib = hip.load()
         majority = voting == "majority"
@@ -619,7 +666,7 @@ class DenoisingModel(nn.Module):
                                                        ptr(counts, lo * HW * K), ptr(ent_sum, lo * HW), stream()), "vote_accumulate")
 
                 for i in range(S):
-                    self.forward_denoising(x[i] if x is not None else draw(B), condition, feature_condition, init_t, consume=consume)
+                    self._sample(x[i] if x is not None else draw(B), condition, feature_condition, init_t, None, consume, known)
             else:
                 xr = x.transpose(0, 1).reshape(B * S, K, H, W) if x is not None else draw(B * S)
                 cond = condition.repeat_interleave(S, dim=0)
@@ -630,7 +677,7 @@ class DenoisingModel(nn.Module):
                 def consume(eng, lo: int, hi: int) -> None:
                     buf[lo:hi].copy_(eng.xt if majority else eng.out_probs.reshape(hi - lo, HW, K))
 
-                self.forward_denoising(xr, cond, fc, init_t, consume=consume)
+                self._sample(xr, cond, fc, init_t, None, consume, None if known is None else known.repeat_interleave(S, dim=0))
                 if majority:
                     vote8 = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
                     mean = torch.empty((B, H, W, K), dtype=torch.float32, device=dev) if "mean" in maps else None
@@ -687,7 +734,10 @@ class DenoisingModel(nn.Module):
         return {"diffusion_out": out, "logits": logits}
 
     def _forward_denoising(self, x: Optional[Tensor], condition: Tensor, feature_condition: Tensor,
-                           init_t: Optional[int] = None, label_ref_logits: Optional[Tensor] = None, consume=None) -> dict:
+                           init_t: Optional[int] = None, label_ref_logits: Optional[Tensor] = None, consume=None, *,
+                           known_labels: Optional[Tensor] = None) -> dict:
+        """`known_labels`: None, or the checked map (_check_known_labels: uint8 [N,H*W] on the model's device)."""
+        known = known_labels
         if label_ref_logits is not None:
             # the reference's guidance branch reads attributes that do not exist (guidance_scale_weights,
             # diffusion_denoising.py:172-174): it raises AttributeError there too.
@@ -706,6 +756,10 @@ class DenoisingModel(nn.Module):
         if self.rng not in ("philox", "torch_cpu"):
             raise ValueError(f"unknown rng mode {self.rng!r}")
         host_rng = self.rng == "torch_cpu"
+        if known is not None and host_rng:
+            raise ValueError("known_labels: not available with rng = 'torch_cpu'")
+        # known labels: cumalpha of the state each row produces; the last row returns the labels themselves (class docstring)
+        clamp_c = [1.0 if j == S - 1 else c_ for j, (a_, c_, m_) in enumerate(coeffs)]
         key = self._philox_key()
         gN, first = self.noise_slice if (host_rng and self.noise_slice is not None) else (N, 0)
         # Samples are independent through all T steps: the batch may be walked as several contiguous
@@ -729,7 +783,7 @@ class DenoisingModel(nn.Module):
             return parts_
 
         def run_steps(parts_, s0_: int, s1_: int, noises_, noise_row0_: int, graph_: bool):
-            if len(parts_) == 1:
+            if len(parts_) == 1 and known is None:
                 parts_[0][0].run(s1_ - s0_, first_row=s0_, noise=noises_[0], noise_row0=noise_row0_, philox_seed=key,
                                  sample_offset=self.sample_offset, use_graph=graph_)
             else:
@@ -737,12 +791,15 @@ class DenoisingModel(nn.Module):
                     for j, (eng, lo, hi) in enumerate(parts_):
                         eng.run(1, first_row=s, noise=noises_[j], noise_row0=noise_row0_, philox_seed=key,
                                 sample_offset=self.sample_offset + lo, use_graph=graph_)
+                        if known is not None:          # on the engine's stream, behind the step: the next step reads the clamped state
+                            eng.clamp_known_labels(known[lo:hi], clamp_c[s], coeffs[s][2], s, philox_seed=key,
+                                                   sample_offset=self.sample_offset + lo)
 
         nsub = int(self.substreams) if int(self.substreams) > 0 else auto_substreams(N, H, W)
         nsub = max(1, min(nsub, N))
         use_graph = bool(self.use_graph)
         if (int(self.substreams) <= 0 and self.calibrate_mode and not host_rng and self._range_probe is None and nsub > 1
-                and S >= self.CALIBRATION_MIN_STEPS):
+                and S >= self.CALIBRATION_MIN_STEPS and known is None):
             nsub, use_graph = self._calibrate_mode(x, condition, feature_condition, prepare, run_steps, nsub, use_graph, S)
         self.last_mode = (nsub, use_graph)
         parts = prepare(nsub)

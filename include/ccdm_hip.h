@@ -306,6 +306,27 @@ size_t ccdm_pack_head_weight(const float* oihw, int K, int Cin, void* out);     
 int ccdm_head_posterior(const ccdm_head_args* a, const ccdm_post_args* post, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Sampling with known pixel labels (DenoisingModel(..., known_labels=)): the replacement method of RePaint (Lugmayr et al. 2022) for
+ * categorical diffusion.  Launched after a denoise step has left x_{t-1} in `xt`: every pixel whose `known` byte is a class y < K is
+ * overwritten with a draw from the forward process at that step's noise level,
+ *     q(x_{t-1} | x_0 = y) = Cat(c * onehot(y) + (1 - c) / K),   c = cumalpha_{t-1} (column 1 of the step's table row);
+ * a pixel whose byte is >= K (255 = free; any other byte that is no class too) is not touched in any buffer.  One thread per pixel.
+ *   mode == CCDM_STEP_SAMPLE: p_k = (k == y) ? p_hit : p_miss, x = argmax_k p_k / E_k (fp32 IEEE division, first maximum wins: the
+ *     epilogue's Exp(1) race) with E_k = -log(U) of word k % 4 of Philox4x32-10(counter = (pixel, sample_offset + n, step_row,
+ *     0x80000000 | k / 4), key = philox_seed) — the epilogue's own blocks have a fourth counter word < 64, so the two draws of a pixel
+ *     and step never share a block.  The host forms p_miss = (1 - c) / K and p_hit = c + (1 - c) / K in float64 and rounds each to
+ *     fp32 once.  Writes xt[i] = x and, if xin != NULL, the one-hot into xin[i * xin_stride + 0 .. K) (channels >= K: the image, untouched).
+ *   the three last-step modes (c = 1, nothing is drawn): xt[i] = y; one-hot of y into out_probs (fp32) / out_onehot (int64) / xin,
+ *     each if non-NULL.
+ * K in [1, CCDM_MAX_CLASSES]; xin_stride >= K where xin is given.  Results depend on (pixel, global sample index, step row, key) only.
+ * ------------------------------------------------------------------------------------------------- */
+int ccdm_known_labels_step(const uint8_t* known /*dev [N,HW]: class < K = known, 255 = free*/, int N, int HW, int K,
+                           float p_hit, float p_miss, int mode /*CCDM_STEP_SAMPLE | _LAST_CONFIDENCE | _LAST_MAJORITY | _LAST_KEEP*/,
+                           int step_row, uint64_t philox_seed, uint32_t sample_offset,
+                           uint8_t* xt /*dev [N,HW]*/, float* xin /*dev [N,HW,xin_stride] or NULL*/, int xin_stride,
+                           float* out_probs /*[N,HW,K] or NULL*/, int64_t* out_onehot /*[N,HW,K] or NULL*/, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * LIDC metrics, device part: for every image and every pair (i, j) of class-index maps
  * a[img][i], b[img][j], the per-class pixel counts out[img][i][j][k] = {|a==k & b==k|, |a==k | b==k|}.
  * Replaces the [B,S,S',HW,K] boolean broadcast of `batched_distance` / `iou`
