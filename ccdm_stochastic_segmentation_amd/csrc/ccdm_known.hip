@@ -4,6 +4,12 @@
 // step epilogue (argmax_k p_k / E_k, first maximum wins) on a Philox counter range of its own.  The last step has c = 1: the label.
 // One thread per pixel, free pixels leave at once; HBM-bound: reads 1 byte per pixel, writes 1 byte (+ K floats of the stem's input)
 // per KNOWN pixel.
+//
+// Resampling jumps (RePaint's harmonisation): ccdm_renoise_step takes the whole state back up the chain, x_t ~ q(x_t | x_{t-j}) =
+// Cat(r * onehot(x_{t-j}) + (1 - r) / K) with r the ratio of the two levels' cumalphas — j forward steps in ONE draw, because uniform
+// transition kernels compose in closed form.  Every pixel, known or free; the same race on a third counter range (0x40000000 | kq).
+// Reads 1 byte and writes 1 byte per pixel (+ K floats where the stem reads its one-hot from memory).  Measured, these bytes are 4 %
+// (64 x 128x128, K = 2) and 11 % (4 x 128x256, K = 20 with xin) of the HBM rate at the launch's time: DESIGN.md section 4.
 #include "ccdm_common.h"
 #include "ccdm_sampler_common.h"
 
@@ -20,20 +26,7 @@ __global__ __launch_bounds__(256) void k_known_labels_step(const uint8_t* __rest
     int x = y;
     if (mode == CCDM_STEP_SAMPLE) {
         const uint32_t pix = (uint32_t)(i % HW), smp = (uint32_t)(i / HW) + sample_offset;
-        float best = -INFINITY;
-        x = 0;
-        for (int kq = 0; kq * 4 < K; ++kq) {
-            uint32_t w[4];
-            Philox::run(pix, smp, step_row, 0x80000000u | (uint32_t)kq, k0, k1, w);      // (the epilogue's blocks have kq < 64)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int k = kq * 4 + j;
-                if (k < K) {
-                    const float qv = (k == y ? p_hit : p_miss) / u32_to_exp1(w[j]);
-                    if (qv > best) { best = qv; x = k; }
-                }
-            }
-        }
+        x = race_hit_miss(K, y, p_hit, p_miss, pix, smp, step_row, 0x80000000u, k0, k1);      // (the epilogue's blocks have kq < 64)
     } else {
         if (out_probs) for (int k = 0; k < K; ++k) out_probs[i * K + k] = (k == x) ? 1.0f : 0.0f;
         if (out_onehot) for (int k = 0; k < K; ++k) out_onehot[i * K + k] = (k == x) ? 1 : 0;
@@ -42,6 +35,47 @@ __global__ __launch_bounds__(256) void k_known_labels_step(const uint8_t* __rest
     if (xin) {
         float* d = xin + i * xin_stride;
         for (int k = 0; k < K; ++k) d[k] = (k == x) ? 1.0f : 0.0f;
+    }
+}
+
+// one thread per pixel; a byte >= K on entry (never produced by the host) counts as class K - 1
+__global__ __launch_bounds__(256) void k_renoise_step(size_t npix, int HW, int K, float p_stay, float p_move, uint32_t step_row, uint32_t k0,
+                                                      uint32_t k1, uint32_t sample_offset, uint8_t* __restrict__ xt, float* __restrict__ xin,
+                                                      int xin_stride) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npix) return;
+    const int own = min((int)xt[i], K - 1);
+    const int x = race_hit_miss(K, own, p_stay, p_move, (uint32_t)(i % HW), (uint32_t)(i / HW) + sample_offset, step_row, 0x40000000u, k0, k1);
+    xt[i] = (uint8_t)x;
+    if (xin) {
+        float* d = xin + i * xin_stride;
+        for (int k = 0; k < K; ++k) d[k] = (k == x) ? 1.0f : 0.0f;
+    }
+}
+
+// no xin (the stem builds its one-hot from xt): a thread takes 4 consecutive pixels of the flat [N*HW] map with one 32-bit load and
+// store (xt 4-byte aligned: the launcher checks); the pixels of a group may belong to two samples; the last npix % 4 bytes go one by one
+__global__ __launch_bounds__(256) void k_renoise_step_x4(size_t npix, int HW, int K, float p_stay, float p_move, uint32_t step_row, uint32_t k0,
+                                                         uint32_t k1, uint32_t sample_offset, uint8_t* __restrict__ xt) {
+    const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t i0 = q * 4;
+    if (i0 >= npix) return;
+    if (i0 + 4 <= npix) {
+        const uint32_t in = *reinterpret_cast<const uint32_t*>(xt + i0);
+        uint32_t out = 0;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const size_t i = i0 + b;
+            const int own = min((int)((in >> (8 * b)) & 0xFFu), K - 1);
+            const int x = race_hit_miss(K, own, p_stay, p_move, (uint32_t)(i % HW), (uint32_t)(i / HW) + sample_offset, step_row, 0x40000000u, k0, k1);
+            out |= (uint32_t)x << (8 * b);
+        }
+        *reinterpret_cast<uint32_t*>(xt + i0) = out;
+    } else {
+        for (size_t i = i0; i < npix; ++i) {
+            const int own = min((int)xt[i], K - 1);
+            xt[i] = (uint8_t)race_hit_miss(K, own, p_stay, p_move, (uint32_t)(i % HW), (uint32_t)(i / HW) + sample_offset, step_row, 0x40000000u, k0, k1);
+        }
     }
 }
 
@@ -65,5 +99,27 @@ extern "C" int ccdm_known_labels_step(const uint8_t* known, int N, int HW, int K
                        p_hit, p_miss, mode, (uint32_t)step_row, (uint32_t)philox_seed, (uint32_t)(philox_seed >> 32), sample_offset, xt, xin,
                        xin_stride, out_probs, out_onehot);
     CCDM_CHECK_LAUNCH("known_labels_step");
+    return 0;
+}
+
+extern "C" int ccdm_renoise_step(int N, int HW, int K, float p_stay, float p_move, int step_row, uint64_t philox_seed, uint32_t sample_offset,
+                                 uint8_t* xt, float* xin, int xin_stride, void* stream) {
+    CCDM_REQUIRE(xt, "renoise_step: null pointer");
+    CCDM_REQUIRE(N >= 1 && HW >= 1, "renoise_step: bad shape N=%d HW=%d", N, HW);
+    CCDM_REQUIRE(K >= 1 && K <= CCDM_MAX_CLASSES, "renoise_step: K=%d outside [1,%d]", K, CCDM_MAX_CLASSES);
+    CCDM_REQUIRE(!xin || xin_stride >= K, "renoise_step: xin_stride %d < K %d", xin_stride, K);
+    CCDM_REQUIRE(step_row >= 0, "renoise_step: step_row %d", step_row);
+    const size_t npix = (size_t)N * HW;
+    CCDM_REQUIRE((npix + 255) / 256 <= 0x7FFFFFFFull, "renoise_step: too many pixels");
+    const uint32_t k0 = (uint32_t)philox_seed, k1 = (uint32_t)(philox_seed >> 32);
+    if (!xin && ((uintptr_t)xt & 3) == 0) {
+        const size_t groups = (npix + 3) / 4;
+        hipLaunchKernelGGL(k_renoise_step_x4, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, (hipStream_t)stream, npix, HW, K, p_stay,
+                           p_move, (uint32_t)step_row, k0, k1, sample_offset, xt);
+    } else {
+        hipLaunchKernelGGL(k_renoise_step, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, (hipStream_t)stream, npix, HW, K, p_stay,
+                           p_move, (uint32_t)step_row, k0, k1, sample_offset, xt, xin, xin_stride);
+    }
+    CCDM_CHECK_LAUNCH("renoise_step");
     return 0;
 }

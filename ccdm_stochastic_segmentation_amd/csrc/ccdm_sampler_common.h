@@ -26,6 +26,28 @@ __device__ __forceinline__ float u32_to_exp1(uint32_t bits) {
     return -logf(u);
 }
 
+// The Exp(1) race over a two-valued categorical: p_k = p_hit for k == own, p_miss otherwise; argmax_k p_k / E_k, first maximum wins,
+// E_k from word k % 4 of the Philox block with fourth counter word `tag | k / 4`.  Shared by the clamp at the known pixels (own = the
+// label, tag 0x80000000) and the renoise of a resampling jump (own = x_t, tag 0x40000000): ccdm_known.hip.
+__device__ __forceinline__ int race_hit_miss(const int K, const int own, const float p_hit, const float p_miss, const uint32_t pix, const uint32_t smp,
+                                             const uint32_t step_row, const uint32_t tag, const uint32_t k0, const uint32_t k1) {
+    float best = -INFINITY;
+    int x = 0;
+    for (int kq = 0; kq * 4 < K; ++kq) {
+        uint32_t w[4];
+        Philox::run(pix, smp, step_row, tag | (uint32_t)kq, k0, k1, w);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int k = kq * 4 + j;
+            if (k < K) {
+                const float qv = (k == own ? p_hit : p_miss) / u32_to_exp1(w[j]);
+                if (qv > best) { best = qv; x = k; }
+            }
+        }
+    }
+    return x;
+}
+
 // per-run fields of the epilogue: from the device-resident block when there is one (uniform scalar loads), else the arguments themselves
 __device__ __forceinline__ ccdm_post_args post_resolve_run(const ccdm_post_args& a_in) {
     ccdm_post_args a = a_in;

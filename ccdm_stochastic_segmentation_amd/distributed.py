@@ -165,7 +165,8 @@ def _check_same_host_rng(world: int, device) -> None:
 
 
 def sample_sharded(model, x: torch.Tensor, condition: torch.Tensor, feature_condition: Optional[torch.Tensor] = None,
-                   t: Optional[torch.Tensor] = None, gather=True, *, known_labels: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   t: Optional[torch.Tensor] = None, gather=True, *, known_labels: Optional[torch.Tensor] = None,
+                   resample: Optional[Tuple[int, int]] = None) -> torch.Tensor:
     """Run `model` (a DenoisingModel-like callable) on this rank's shard of the global batch and return the
     full [N,K,H,W] prediction on every rank, or only the local shard (gather=False).
     gather=True: fp32 probabilities travel as they are; int64 one-hot ("majority") predictions travel as their uint8 argmax map
@@ -173,7 +174,8 @@ def sample_sharded(model, x: torch.Tensor, condition: torch.Tensor, feature_cond
     gather="index": force the index form for any output (fp32 one-hot of a shortened walk).
     known_labels: handed to the model as it is — x, condition and feature_condition are sliced here, this map is NOT: the caller passes
     the slice [lo:hi] = shard_range(N, rank, world) of its global map (the draw at the known pixels is keyed by the global sample index,
-    so the shards reproduce the single-process samples)."""
+    so the shards reproduce the single-process samples).
+    resample: (jump_length, resamples), handed to the model as it is (the renoising draws are keyed by the global sample index too)."""
     world = dist.get_world_size() if dist.is_initialized() else 1
     rank = dist.get_rank() if dist.is_initialized() else 0
     n = x.shape[0]
@@ -186,6 +188,8 @@ def sample_sharded(model, x: torch.Tensor, condition: torch.Tensor, feature_cond
         kw = {} if t is None else {"t": t}
         if known_labels is not None:
             kw["known_labels"] = known_labels
+        if resample is not None:
+            kw["resample"] = resample
         fc = feature_condition[lo:hi] if feature_condition is not None else None
         out = model(x[lo:hi], condition[lo:hi], fc, **kw)["diffusion_out"].contiguous()
     finally:

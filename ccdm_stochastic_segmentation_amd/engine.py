@@ -589,6 +589,14 @@ class SamplerEngine:
             self.out_probs.data_ptr() if last else None, self.out_onehot.data_ptr() if last else None, self._stream()), "known_labels_step")
         self._known_keepalive = known
 
+    def renoise(self, p_stay: float, p_move: float, step_row: int, *, philox_seed: int = 0, sample_offset: int = 0) -> None:
+        """Redraw every pixel of the state from the forward process between two levels of the chain (ccdm_renoise_step, asynchronous on
+        the engine's stream): a resampling jump back up to table row `step_row`, which the next `run` executes.  p_stay / p_move: the
+        fp32 pair the caller formed from the two levels' cumalphas."""
+        hip.check(self.lib.ccdm_renoise_step(
+            self.N, self.H * self.W, self.K, float(p_stay), float(p_move), int(step_row), int(philox_seed) & (2 ** 64 - 1), int(sample_offset),
+            self.xt.data_ptr(), None if self.stem_onehot_on_load else self.xin.ptr, self.Cs, self._stream()), "renoise_step")
+
     def ce_logits(self) -> Optional[torch.Tensor]:
         """[N,K-1,H,W] logits of the optional ce head after the last run (BCHW view of channels-last memory), else None."""
         if self.head_ce is None:

@@ -27,7 +27,7 @@ from .unet_spec import UNetSpec, make_unet_spec
 LOGGER = logging.getLogger(__name__)
 
 __all__ = ["build_model", "DiffusionModel", "DenoisingModel", "UNetModel", "OneHotCategoricalBCHW",
-           "linear_schedule", "cosine_schedule", "step_values"]
+           "linear_schedule", "cosine_schedule", "step_values", "resample_walk", "pass_key"]
 
 
 # --------------------------------------------------------------------------------------------------
@@ -66,6 +66,46 @@ def step_values(time_steps: int, init_t: Optional[int]) -> List[int]:
         LOGGER.warning(f"Override default {time_steps} time steps with {len(vals)}.")
         return vals
     return list(range(init_t, 0, -1))
+
+
+def resample_walk(S: int, jump_length: int, resamples: int) -> List[Tuple[int, int, Optional[int]]]:
+    """The order in which a walk of S table rows with RePaint's resampling jumps (Lugmayr et al. 2022) visits its rows: a list of
+    (row, pass, renoise_from).  Level L is the state before row L, R = S - L rows remain below it.  Jump points are the levels with
+    R in {j, 2j, 3j, ...} and R < S - j (j = jump_length): the walk never jumps back to the pure-noise level (RePaint's rule).  Each
+    jump point has `resamples` - 1 jumps; walking down, a level that has jumps left uses one: the state is renoised from level L to
+    level L - j and the walk continues at row L - j.  `pass` counts the earlier visits of the row (it selects the noise key of the
+    visit, see pass_key); `renoise_from` is the level the state is renoised from before this row runs, or None.
+    A deviation from RePaint: no jump starts at R = 0.  The last row returns an argmax or a probability map, not a draw of the chain,
+    so there is nothing to renoise.  resamples = 1 or jump_length = 0 gives the plain walk; so does a jump_length with no jump point.
+    The length is S + (resamples - 1) * j * #{m >= 1 : m * j < S - j}."""
+    S, j, r = int(S), int(jump_length), int(resamples)
+    left = {R: r - 1 for R in range(j, S - j, j)} if (j > 0 and r > 1) else {}
+    visits = [0] * S
+    walk: List[Tuple[int, int, Optional[int]]] = []
+    L, renoise_from = 0, None
+    while L < S:
+        walk.append((L, visits[L], renoise_from))
+        visits[L] += 1
+        renoise_from = None
+        L += 1
+        if left.get(S - L, 0) > 0:
+            left[S - L] -= 1
+            renoise_from = L
+            L -= j
+    return walk
+
+
+def pass_key(key: int, p: int) -> int:
+    """Philox key of pass `p` of a table row (p = the number of earlier visits of the row in a resampled walk): the call's key itself
+    for p = 0, else the splitmix64 finaliser of key + 0x9E3779B97F4A7C15 * p — the mixing DenoisingModel._philox_key applies to
+    (philox_seed, philox_call).  A revisit must not replay the first visit's noise: the epilogue keys its draws by the table row."""
+    key = int(key) & 0xFFFFFFFFFFFFFFFF
+    if int(p) == 0:
+        return key
+    z = (key + 0x9E3779B97F4A7C15 * int(p)) & 0xFFFFFFFFFFFFFFFF
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & 0xFFFFFFFFFFFFFFFF
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & 0xFFFFFFFFFFFFFFFF
+    return z ^ (z >> 31)
 
 
 class OneHotCategoricalBCHW:
@@ -289,7 +329,16 @@ class DenoisingModel(nn.Module):
     under the call's Philox key on counters the epilogue never uses: results do not depend on `substreams`, `use_graph` or how the
     batch is sharded (a caller that shards passes its shard's slice of the map).  A conditioned call walks every engine one step at a
     time and takes the static execution-mode rule (no `calibrate_mode` measurement); rng = "torch_cpu" has no reference stream for this
-    draw and is refused.  Without the keyword nothing changes: no extra launch, no per-step stepping."""
+    draw and is refused.  Without the keyword nothing changes: no extra launch, no per-step stepping.
+    `resample` = (jump_length, resamples) (keyword next to `known_labels`, which it needs): RePaint's resampling jumps.  With the
+    clamp alone the free pixels get one reverse step per noise level to agree with known pixels that were drawn independently of them.
+    A resampled walk goes back up the chain by `jump_length` levels at every jump point and walks down again, `resamples` times per
+    band (`resample_walk` is the order of the rows), so the free pixels are denoised again with the known ones in view.  Going up is
+    one launch of ccdm_renoise_step whatever the jump length: every pixel is redrawn from q(x_t | x_{t-j}) = Cat(r onehot(x_{t-j}) +
+    (1 - r) / K), r = cumalpha_t / cumalpha_{t-j}.  Pass p of a row draws under pass_key(key, p), so a revisit sees fresh noise and the
+    walk up to the first jump is the plain conditioned walk bit for bit.  The step tables, the captured graphs and the independence of
+    `substreams`, `use_graph` and sharding are those of a conditioned call.  None, (j, 1), (0, r) and a jump_length without a jump
+    point change nothing."""
 
     KNOWN_FREE = 255        # the value of a free pixel in `known_labels`
 
@@ -358,9 +407,11 @@ class DenoisingModel(nn.Module):
     # ------------------------------------------------------------------ reference API
     def forward(self, x: Tensor, condition: Tensor, feature_condition: Tensor = None, t: Optional[Tensor] = None,
                 label_ref_logits: Optional[Tensor] = None, validation: bool = False, *,
-                known_labels: Optional[Tensor] = None) -> Union[Tensor, dict]:
+                known_labels: Optional[Tensor] = None, resample: Optional[Tuple[int, int]] = None) -> Union[Tensor, dict]:
         if known_labels is not None and (self.training or validation):
             raise ValueError("known_labels: only a sampling call (eval mode, validation=False) takes known labels")
+        if resample is not None and (self.training or validation):
+            raise ValueError("resample: only a sampling call (eval mode, validation=False) has a walk to resample")
         if self.training:
             if not isinstance(t, Tensor):
                 raise ValueError("'t' needs to be a Tensor at training time")
@@ -370,8 +421,10 @@ class DenoisingModel(nn.Module):
         if validation:
             return self.forward_step(x, condition, feature_condition, t)
         if t is None:
-            return self.forward_denoising(x, condition, feature_condition, label_ref_logits=label_ref_logits, known_labels=known_labels)
-        return self.forward_denoising(x, condition, feature_condition, cast(int, t.item()), label_ref_logits, known_labels=known_labels)
+            return self.forward_denoising(x, condition, feature_condition, label_ref_logits=label_ref_logits, known_labels=known_labels,
+                                          resample=resample)
+        return self.forward_denoising(x, condition, feature_condition, cast(int, t.item()), label_ref_logits, known_labels=known_labels,
+                                      resample=resample)
 
     # ------------------------------------------------------------------ engine plumbing
     def _weights_key(self) -> Tuple[int, int]:
@@ -553,12 +606,32 @@ class DenoisingModel(nn.Module):
     def forward_denoising(self, x: Optional[Tensor], condition: Tensor, feature_condition: Tensor,
                           init_t: Optional[int] = None, label_ref_logits: Optional[Tensor] = None, *,
                           consume: Optional[Callable[[SamplerEngine, int, int], None]] = None,
-                          known_labels: Optional[Tensor] = None) -> dict:
+                          known_labels: Optional[Tensor] = None, resample: Optional[Tuple[int, int]] = None) -> dict:
         """`consume` (predict_multiple): instead of returning the call's output, hand every sub-batch engine (eng, lo, hi) to
         consume(eng, lo, hi) once the call has succeeded, with the engine's stream current; the result is then {}.
-        `known_labels`: integer [N,H,W], a class where the label is known, 255 where the pixel is free (see the class docstring)."""
+        `known_labels`: integer [N,H,W], a class where the label is known, 255 where the pixel is free (see the class docstring).
+        `resample`: (jump_length, resamples), RePaint's resampling jumps of a walk with known labels (class docstring)."""
+        jumps = self._check_resample(resample, known_labels)
         known = None if known_labels is None else self._check_known_labels(known_labels, (x.shape[0], x.shape[2], x.shape[3]), x.shape[1])
-        return self._sample(x, condition, feature_condition, init_t, label_ref_logits, consume, known)
+        return self._sample(x, condition, feature_condition, init_t, label_ref_logits, consume, known, jumps)
+
+    def _check_resample(self, resample, known_labels) -> Optional[Tuple[int, int]]:
+        """The one host-side check of a call's `resample` (before anything runs): (jump_length, resamples) as two ints, or None where
+        the pair asks for no jump."""
+        if resample is None:
+            return None
+        if known_labels is None:
+            raise ValueError("resample: needs known_labels (the jumps harmonise the free pixels with the known ones; without any there "
+                             "is nothing to harmonise)")
+        if self.rng == "torch_cpu":
+            raise ValueError("resample: not available with rng = 'torch_cpu' (the host-noise parity mode has no reference stream for the "
+                             "renoising draws); use rng = 'philox'")
+        ok = isinstance(resample, (tuple, list)) and len(resample) == 2 and all(
+            isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) for v in resample)
+        if not ok or int(resample[0]) < 0 or int(resample[1]) < 1:
+            raise ValueError(f"resample: expected (jump_length, resamples), two integers with jump_length >= 0 and resamples >= 1, got {resample!r}")
+        j, r = int(resample[0]), int(resample[1])
+        return None if (j == 0 or r == 1) else (j, r)
 
     def _check_known_labels(self, known_labels: Tensor, shape: Tuple[int, int, int], K: int) -> Tensor:
         """The one host-side check of a call's `known_labels` (before anything runs): the map as uint8 [N,H*W] on the model's device."""
@@ -579,10 +652,10 @@ class DenoisingModel(nn.Module):
         return host.to(torch.uint8).reshape(shape[0], shape[1] * shape[2]).contiguous().to(next(self.unet.parameters()).device)
 
     def _sample(self, x: Optional[Tensor], condition: Tensor, feature_condition: Tensor, init_t: Optional[int],
-                label_ref_logits: Optional[Tensor], consume, known: Optional[Tensor]) -> dict:
-        """One sampling call; `known`: what _check_known_labels returned, or None."""
+                label_ref_logits: Optional[Tensor], consume, known: Optional[Tensor], jumps: Optional[Tuple[int, int]] = None) -> dict:
+        """One sampling call; `known`: what _check_known_labels returned, or None; `jumps`: what _check_resample returned."""
         out = self._with_range_fallback(lambda: self._forward_denoising(x, condition, feature_condition, init_t, label_ref_logits,
-                                                                        consume, known_labels=known))
+                                                                        consume, known_labels=known, resample=jumps))
         if self.philox_advance:
             self.philox_call += 1           # the next call draws from a fresh stream (a range-error re-run above replayed this one)
         return out
@@ -594,7 +667,7 @@ class DenoisingModel(nn.Module):
     def predict_multiple(self, condition: Tensor, feature_condition: Optional[Tensor] = None, *, num_evaluations: int,
                          voting: Optional[str] = None, x: Optional[Tensor] = None, t: Optional[Tensor] = None, batched: bool = False,
                          maps: Sequence[str] = ("mean", "vote", "entropy", "mutual_info"),
-                         known_labels: Optional[Tensor] = None) -> Dict[str, Tensor]:
+                         known_labels: Optional[Tensor] = None, resample: Optional[Tuple[int, int]] = None) -> Dict[str, Tensor]:
         """S = `num_evaluations` samples of every image of `condition` [B,C,H,W], combined on the device into one prediction and
         per-pixel uncertainty maps — the reference's Evaluator.predict_multiple (evaluation/eval_cdm.py:176-193), which sums S
         `predict_single` outputs as `total += prediction_i * (1 / S)`.
@@ -610,6 +683,7 @@ class DenoisingModel(nn.Module):
         t: as in forward (e.g. 10000 + steps for a strided walk).
         known_labels: integer [B,H,W] (a class where the label is known, 255 where the pixel is free): every pass is conditioned on it
           (class docstring), so `vote` equals the label and `entropy` is 0 at the known pixels.
+        resample: (jump_length, resamples): every pass walks with RePaint's resampling jumps (class docstring); needs known_labels.
         batched=False: S sampling calls of B samples, each advancing `philox_call` exactly like S calls of model(x_i, condition);
           after each call the pass is folded into device accumulators straight from the engine (ccdm_vote_accumulate), so memory
           is one pass plus the accumulators.  The range-error fallback and the execution-mode choice apply per pass.
@@ -636,6 +710,7 @@ class DenoisingModel(nn.Module):
         if x is not None and tuple(x.shape) != (S, B, K, H, W):
             raise ValueError(f"x: expected one-hot x_T of shape {(S, B, K, H, W)} = [S,B,K,H,W], got {tuple(x.shape)}")
         init_t = None if t is None else int(t.item() if isinstance(t, Tensor) else t)
+        jumps = self._check_resample(resample, known_labels)
         known = None if known_labels is None else self._check_known_labels(known_labels, (B, H, W), K)
         dev = next(self.unet.parameters()).device
         lib = hip.load()
@@ -666,7 +741,7 @@ class DenoisingModel(nn.Module):
                                                        ptr(counts, lo * HW * K), ptr(ent_sum, lo * HW), stream()), "vote_accumulate")
 
                 for i in range(S):
-                    self._sample(x[i] if x is not None else draw(B), condition, feature_condition, init_t, None, consume, known)
+                    self._sample(x[i] if x is not None else draw(B), condition, feature_condition, init_t, None, consume, known, jumps)
             else:
                 xr = x.transpose(0, 1).reshape(B * S, K, H, W) if x is not None else draw(B * S)
                 cond = condition.repeat_interleave(S, dim=0)
@@ -677,7 +752,7 @@ class DenoisingModel(nn.Module):
                 def consume(eng, lo: int, hi: int) -> None:
                     buf[lo:hi].copy_(eng.xt if majority else eng.out_probs.reshape(hi - lo, HW, K))
 
-                self._sample(xr, cond, fc, init_t, None, consume, None if known is None else known.repeat_interleave(S, dim=0))
+                self._sample(xr, cond, fc, init_t, None, consume, None if known is None else known.repeat_interleave(S, dim=0), jumps)
                 if majority:
                     vote8 = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
                     mean = torch.empty((B, H, W, K), dtype=torch.float32, device=dev) if "mean" in maps else None
@@ -735,8 +810,9 @@ class DenoisingModel(nn.Module):
 
     def _forward_denoising(self, x: Optional[Tensor], condition: Tensor, feature_condition: Tensor,
                            init_t: Optional[int] = None, label_ref_logits: Optional[Tensor] = None, consume=None, *,
-                           known_labels: Optional[Tensor] = None) -> dict:
-        """`known_labels`: None, or the checked map (_check_known_labels: uint8 [N,H*W] on the model's device)."""
+                           known_labels: Optional[Tensor] = None, resample: Optional[Tuple[int, int]] = None) -> dict:
+        """`known_labels`: None, or the checked map (_check_known_labels: uint8 [N,H*W] on the model's device); `resample`: None, or the
+        checked pair (_check_resample)."""
         known = known_labels
         if label_ref_logits is not None:
             # the reference's guidance branch reads attributes that do not exist (guidance_scale_weights,
@@ -761,6 +837,21 @@ class DenoisingModel(nn.Module):
         # known labels: cumalpha of the state each row produces; the last row returns the labels themselves (class docstring)
         clamp_c = [1.0 if j == S - 1 else c_ for j, (a_, c_, m_) in enumerate(coeffs)]
         key = self._philox_key()
+        # resampling jumps: the rows in the order the walk visits them, and per entry the renoising pair (p_stay, p_move) of the jump
+        # that precedes it.  From level L to level M = L - j (the state before row M): r = cumalpha_{t_M} / cumalpha_{t_L} in float64,
+        # each probability rounded to fp32 once.  A walk without a jump point is the plain conditioned walk: nothing below changes.
+        walk = None
+        if resample is not None:
+            walk = resample_walk(S, *resample)
+            if len(walk) == S:
+                walk = None
+        renoise_p: Dict[int, Tuple[float, float]] = {}
+        cum = self.diffusion.cumalphas.detach().cpu().double() if walk is not None else None         # (cumalpha_t = cum[t - 1])
+        for e, (row, _, src) in enumerate(walk or []):
+            if src is not None:
+                r_ = float(cum[t_values[row] - 1]) / float(cum[t_values[src] - 1])
+                p_move = (1.0 - r_) / K
+                renoise_p[e] = (float(np.float32(r_ + p_move)), float(np.float32(p_move)))
         gN, first = self.noise_slice if (host_rng and self.noise_slice is not None) else (N, 0)
         # Samples are independent through all T steps: the batch may be walked as several contiguous
         # sub-batches, each with its own step executor on its own HIP stream.  The kernels of the low-resolution stages
@@ -783,7 +874,17 @@ class DenoisingModel(nn.Module):
             return parts_
 
         def run_steps(parts_, s0_: int, s1_: int, noises_, noise_row0_: int, graph_: bool):
-            if len(parts_) == 1 and known is None:
+            if walk is not None:                       # s0_, s1_ count the walk's entries, not table rows
+                for e in range(s0_, s1_):
+                    row, p, src = walk[e]
+                    kp = pass_key(key, p)
+                    for j, (eng, lo, hi) in enumerate(parts_):
+                        if src is not None:            # back up the chain to the state before `row`, on the engine's stream
+                            eng.renoise(*renoise_p[e], row, philox_seed=kp, sample_offset=self.sample_offset + lo)
+                        eng.run(1, first_row=row, philox_seed=kp, sample_offset=self.sample_offset + lo, use_graph=graph_)
+                        eng.clamp_known_labels(known[lo:hi], clamp_c[row], coeffs[row][2], row, philox_seed=kp,
+                                               sample_offset=self.sample_offset + lo)
+            elif len(parts_) == 1 and known is None:
                 parts_[0][0].run(s1_ - s0_, first_row=s0_, noise=noises_[0], noise_row0=noise_row0_, philox_seed=key,
                                  sample_offset=self.sample_offset, use_graph=graph_)
             else:
@@ -811,9 +912,9 @@ class DenoisingModel(nn.Module):
             blk = max(1, HOST_NOISE_BLOCK_BYTES // max(per_step, 1))
             blocks = [(s0, min(s0 + blk, S)) for s0 in range(0, S, blk)]
         else:
-            blocks = [(0, S)]
+            blocks = [(0, S if walk is None else len(walk))]
         if self._range_probe is not None:      # diagnosing fp32 re-run: one step per block, every step's activations are probed
-            blocks = [(s, s + 1) for s in range(S)]
+            blocks = [(s, s + 1) for s in range(S if walk is None else len(walk))]
         for s0, s1 in blocks:
             noises: List[Optional[Tensor]] = [None] * nsub
             if host_rng:

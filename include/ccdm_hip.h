@@ -327,6 +327,30 @@ int ccdm_known_labels_step(const uint8_t* known /*dev [N,HW]: class < K = known,
                            float* out_probs /*[N,HW,K] or NULL*/, int64_t* out_onehot /*[N,HW,K] or NULL*/, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Resampling jumps of a walk with known labels (DenoisingModel(..., known_labels=, resample=(jump_length, resamples))): RePaint's
+ * harmonisation.  The walk goes back up the chain by `jump_length` levels and down again, so that the free pixels are denoised once
+ * more with the known ones in view.  Going up is this kernel: EVERY pixel of `xt`, known or free (a known pixel's state is a sample of
+ * q(x_t | x_0 = y), and renoising it keeps it one), is redrawn from the forward process between the two levels,
+ *     x_new ~ Cat(p_k),  p_k = p_stay for k == xt[i], p_move otherwise,
+ *     p_move = (1 - r) / K,  p_stay = r + p_move,  r = cumalpha_{t of the level reached} / cumalpha_{t of the level left}
+ * (formed by the host in float64, each rounded to fp32 once): uniform transition kernels compose in closed form, so a jump of any
+ * length is ONE launch.  The draw is the epilogue's Exp(1) race, x_new = argmax_k p_k / E_k (fp32 IEEE division, first maximum wins)
+ * with E_k = -log(U) of word k % 4 of Philox4x32-10(counter = (pixel, sample_offset + n, step_row, 0x40000000 | k / 4), key =
+ * philox_seed): a counter range of its own (the epilogue's fourth word is < 64, the clamp's has bit 31 set).  step_row = the table row
+ * the walk continues at.  Writes xt[i] = x_new and, if xin != NULL, the one-hot into xin[i * xin_stride + 0 .. K) (channels >= K: the
+ * image, untouched).  A byte xt[i] >= K on entry is a caller's error the host never makes; it is treated as class K - 1.
+ * Keying of a revisit: the epilogue keys its noise by the table row, so a row that is walked again must not see the same key.  Every
+ * launch of pass p of a row (the denoise step, its clamp, and the renoise that precedes it) runs under pass_key(key, p): the call's key
+ * itself for p = 0, and for p >= 1 the splitmix64 finaliser of key + 0x9E3779B97F4A7C15 * p (mod 2^64) — the mixing that derives a
+ * call's key from (philox_seed, philox_call).
+ * One thread per pixel; without xin one thread per 4 consecutive pixels of the flat map (one 32-bit load and store, where xt is 4-byte
+ * aligned; the last N*HW % 4 bytes one by one).  K in [1, CCDM_MAX_CLASSES]; xin_stride >= K where xin is given.  Results depend on
+ * (pixel, global sample index, step row, key) only.
+ * ------------------------------------------------------------------------------------------------- */
+int ccdm_renoise_step(int N, int HW, int K, float p_stay, float p_move, int step_row, uint64_t philox_seed, uint32_t sample_offset,
+                      uint8_t* xt /*dev [N,HW]*/, float* xin /*dev [N,HW,xin_stride] or NULL*/, int xin_stride, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * LIDC metrics, device part: for every image and every pair (i, j) of class-index maps
  * a[img][i], b[img][j], the per-class pixel counts out[img][i][j][k] = {|a==k & b==k|, |a==k | b==k|}.
  * Replaces the [B,S,S',HW,K] boolean broadcast of `batched_distance` / `iou`

@@ -1,0 +1,512 @@
+"""RePaint's resampling jumps of a walk with known labels: DenoisingModel(..., known_labels=, resample=(jump_length, resamples)), the
+order of the rows (models.resample_walk), the per-pass Philox key (models.pass_key) and the renoising kernel ccdm_renoise_step
+(include/ccdm_hip.h).  The kernel is checked for equality against a numpy restatement built on the oracle's Philox4x32-10; the sampler
+for what must not change without a jump, for the constraint, for independence of the execution shape, and step by step against the
+conditioned loop restated from the oracle's public step functions, extended with the renoise restatement and the pass keys."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import ccdm_oracle as O
+from ccdm_stochastic_segmentation_amd import build_model, hip, make_synthetic_state_dict
+from ccdm_stochastic_segmentation_amd.models import pass_key, resample_walk, step_values
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FREE = 255
+SYMBOL = "ccdm_renoise_step"
+CLAMP = "ccdm_known_labels_step"
+TAG_RENOISE, TAG_CLAMP = 0x40000000, 0x80000000
+# the 32x32 two-level network of test_known_labels, T = 6: t = None walks its 6 rows, t = 10004 walks it strided, t = 6, 4, 3, 1
+SMALL_BP = dict(base_channels=32, channel_mult=(1, 2), attention_resolutions=[2], num_heads=1, num_head_channels=32, softmax_output=True)
+SMALL_CFG = dict(num_heads=1, num_head_channels=32)
+T_SMALL, H, W = 6, 32, 32
+T_STRIDED = torch.as_tensor(10004)
+
+
+def small_model(K, vote="majority", seed=3):
+    m = build_model(T_SMALL, "cosine", {"s": 0.008}, [(1, H, W), (K, H, W)], (1, H, W), "unet_openai", SMALL_BP, "datasets.lidc", vote, None)
+    sd = {k: torch.from_numpy(v) for k, v in make_synthetic_state_dict(m.unet.spec, seed).items()}
+    m.unet.load_state_dict(sd, strict=True)
+    return m, sd
+
+
+def probabilities(c, K):
+    """(p_hit, p_miss) = (p_stay, p_move) as the host forms them: in float64, each rounded to fp32 once"""
+    p_miss = (1.0 - float(c)) / K
+    return np.float32(float(c) + p_miss), np.float32(p_miss)
+
+
+def race_restatement(own, K, c, step_row, seed, sample0, tag):
+    """argmax_k p_k / E_k with p_k = p_hit for k == own[n, pixel], p_miss otherwise, following oracle.philox_exponential: the same
+    bits -> uniform -> -log map in fp32, counter word 3 = tag | k // 4, the division in fp32, the first maximum wins.
+    own: [N,HW] integer array of classes < K."""
+    N, HW = own.shape
+    p_hit, p_miss = probabilities(c, K)
+    pix = np.arange(HW, dtype=np.uint32)[None, :, None]
+    smp = (np.arange(N, dtype=np.uint32) + np.uint32(sample0))[:, None, None]
+    kq = (np.uint32(tag) | (np.arange(K, dtype=np.uint32) // 4))[None, None, :]
+    ctr = np.stack(np.broadcast_arrays(pix, smp, np.uint32(step_row), kq), axis=-1).astype(np.uint32)
+    key = np.array([seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF], dtype=np.uint32)
+    blk = O.philox4x32_10(ctr, key)
+    word = np.take_along_axis(blk, np.broadcast_to((np.arange(K) % 4)[None, None, :, None], (N, HW, K, 1)).astype(np.int64), axis=-1)[..., 0]
+    u = ((word >> np.uint32(8)).astype(np.float32) + np.float32(0.5)) * np.float32(2.0 ** -24)
+    e = (-np.log(u.astype(np.float32))).astype(np.float32)
+    p = np.where(np.arange(K)[None, None, :] == own[..., None], p_hit, p_miss).astype(np.float32)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        q = (p / e).astype(np.float32)
+    q = np.where(np.isnan(q), -np.inf, q)                  # `qv > best` is false for a NaN (0 / 0): it never wins
+    return np.argmax(q, axis=-1).astype(np.int64)
+
+
+def renoise_restatement(xt, K, r, step_row, seed, sample0):
+    """What ccdm_renoise_step leaves in xt: every pixel redrawn, own class = xt."""
+    return race_restatement(xt, K, r, step_row, seed, sample0, TAG_RENOISE)
+
+
+def clamp_restatement(known, xt, K, c, step_row, seed, sample0):
+    """What ccdm_known_labels_step leaves in xt in mode STEP_SAMPLE (test_known_labels.clamp_restatement)."""
+    draw = race_restatement(np.where(known < K, known, 0), K, c, step_row, seed, sample0, TAG_CLAMP)
+    return np.where(known < K, draw, xt).astype(np.int64)
+
+
+# ------------------------------------------------------------------------------------------------ CPU
+def test_resample_walk_tables():
+    """The tabled walks entry for entry, the length formula, and the invariants of every walk for S <= 12, j <= 6, r <= 4."""
+    def cols(S, j, r):
+        w = resample_walk(S, j, r)
+        return [e[0] for e in w], [e[1] for e in w], {i: e[2] for i, e in enumerate(w) if e[2] is not None}
+    assert cols(6, 2, 2) == ([0, 1, 2, 3, 2, 3, 4, 5], [0, 0, 0, 0, 1, 1, 0, 0], {4: 4})
+    assert cols(6, 2, 3)[0] == [0, 1, 2, 3, 2, 3, 2, 3, 4, 5]
+    assert cols(7, 2, 2)[0] == [0, 1, 2, 1, 2, 3, 4, 3, 4, 5, 6] and cols(7, 2, 2)[2] == {3: 3, 7: 5}
+    assert cols(4, 1, 3)[0] == [0, 1, 1, 1, 2, 2, 2, 3]
+    for S, j, r in ((6, 3, 2), (6, 4, 5), (6, 2, 1), (6, 0, 3)):
+        assert resample_walk(S, j, r) == [(row, 0, None) for row in range(S)], (S, j, r)
+    assert len(resample_walk(250, 10, 10)) == 2320
+    assert len(resample_walk(len(step_values(6, 10004)), 1, 2)) == 6 and cols(4, 1, 2)[0] == [0, 1, 1, 2, 2, 3]
+    for S in range(1, 13):
+        for j in range(0, 7):
+            for r in range(1, 5):
+                w = resample_walk(S, j, r)
+                points = len([m for m in range(1, S + 1) if m * j < S - j]) if j > 0 else 0
+                assert len(w) == S + (r - 1) * j * points, (S, j, r)
+                assert w[0] == (0, 0, None) and w[-1] == (S - 1, 0, None)
+                seen = {}
+                for i, (row, p, src) in enumerate(w):
+                    assert 0 <= row < S and p == seen.get(row, 0), (S, j, r, i)        # `pass` counts the earlier visits
+                    seen[row] = p + 1
+                    if src is None:
+                        assert i == 0 or row == w[i - 1][0] + 1
+                    else:
+                        assert src - row == j and src == w[i - 1][0] + 1              # renoised from the level just reached, j levels up
+                        assert src < S and row > 0                                    # never from the final state, never to pure noise
+                        assert (S - src) % j == 0 and S - src < S - j
+                assert all(seen[row] >= 1 for row in range(S))
+
+
+def test_pass_key():
+    for key in (0, 99, 0xFEEDFACE12345678, 2 ** 64 - 1):
+        keys = [pass_key(key, p) for p in range(10)]
+        assert keys[0] == key and len(set(keys)) == 10 and all(0 <= k < 2 ** 64 for k in keys)
+    # the mixing _philox_key applies to (seed, call)
+    m, _ = small_model(2)
+    m.philox_seed, m.philox_call = 1234, 7
+    assert pass_key(1234, 7) == m._philox_key()
+
+
+CTYPE_OF = {"int": C.c_int, "float": C.c_float, "uint64_t": C.c_uint64, "uint32_t": C.c_uint32}
+
+
+def test_renoise_symbol_declared_bound_and_built():
+    """hip.py binds the symbol with argtypes that match the header's declaration, the library built from ccdm_known.hip exports it,
+    and the ABI number is unchanged (the refusal of bad arguments is checked where there is a device: the GPU tests below)."""
+    hdr = open(os.path.join(ROOT, "include", "ccdm_hip.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    m = re.search(r"\bint\s+" + SYMBOL + r"\s*\(([^;]*)\)\s*;", hdr)
+    assert m, "not declared in include/ccdm_hip.h"
+    want = []
+    for arg in m.group(1).split(","):
+        words = arg.replace("*", " * ").split()
+        want.append(C.c_void_p if "*" in words else CTYPE_OF[[w for w in words if w != "const"][0]])
+    res, args = hip.SIGNATURES[SYMBOL]
+    assert res is C.c_int and args == want and len(args) == 12
+    assert SYMBOL in open(os.path.join(hip.CSRC, "ccdm_known.hip")).read()
+    assert hip.ABI_VERSION == 11
+    import __graft_entry__ as g
+    g.build()
+    lib = hip.load()
+    assert hasattr(lib, SYMBOL) and lib.ccdm_version() == 11
+
+
+def test_resample_argument_validation():
+    """resample without known_labels, with rng = 'torch_cpu', bad pairs and a training / validation call raise ValueError naming the
+    reason before anything runs (a model that was never moved to a GPU: nothing can run)."""
+    m, _ = small_model(3)
+    m.eval()
+    N, K = 2, 3
+    x = torch.nn.functional.one_hot(torch.zeros((N, H, W), dtype=torch.int64), K).permute(0, 3, 1, 2).float()
+    cond = torch.zeros(N, 1, H, W)
+    ok = torch.full((N, H, W), FREE, dtype=torch.int64)
+    calls = (lambda **kw: m(x, cond, t=T_STRIDED, **kw), lambda **kw: m.forward_denoising(x, cond, None, 10004, **kw),
+             lambda **kw: m.predict_multiple(cond, num_evaluations=2, voting="majority", t=T_STRIDED, **kw))
+    for call in calls:
+        with pytest.raises(ValueError, match="resample.*known_labels"):
+            call(resample=(2, 2))
+        for bad in ((2,), (2, 2, 2), (2.0, 2), (2, 2.5), ("2", 2), (-1, 2), (2, 0), (2, -3), 2, (True, 2), "ab"):
+            with pytest.raises(ValueError, match="resample.*jump_length"):
+                call(known_labels=ok, resample=bad)
+    m.rng = "torch_cpu"
+    for call in calls:
+        with pytest.raises(ValueError, match="resample.*torch_cpu"):
+            call(known_labels=ok, resample=(2, 2))
+    m.rng = "philox"
+    with pytest.raises(ValueError, match="resample.*sampling call"):
+        m(x, cond, t=torch.full((N,), 3.0), validation=True, resample=(2, 2))
+    m.train()
+    with pytest.raises(ValueError, match="resample.*sampling call"):
+        m(x, cond, t=torch.full((N,), 3.0), resample=(2, 2))
+    m.eval()
+    assert m.philox_call == 0 and m._engines == {}          # nothing ran
+    # the accepted forms; a pair that asks for no jump is no pair
+    assert m._check_resample((2, 3), ok) == (2, 3) and m._check_resample([np.int64(1), 2], ok) == (1, 2)
+    assert m._check_resample((2, 1), ok) is None and m._check_resample((0, 4), ok) is None and m._check_resample(None, None) is None
+
+
+def test_sample_sharded_hands_resample_through():
+    from ccdm_stochastic_segmentation_amd.distributed import sample_sharded
+    seen = {}
+
+    class Stub:
+        rng, sample_offset, noise_slice = "philox", 0, None
+
+        def __call__(self, x, cond, fc, **kw):
+            seen.update(kw)
+            return {"diffusion_out": x}
+    x = torch.zeros(3, 2, 4, 4)
+    kl = torch.full((3, 4, 4), FREE)
+    sample_sharded(Stub(), x, torch.zeros(3, 1, 4, 4), known_labels=kl, resample=(2, 3))
+    assert seen["known_labels"] is kl and seen["resample"] == (2, 3)
+    seen.clear()
+    sample_sharded(Stub(), x, torch.zeros(3, 1, 4, 4), known_labels=kl)
+    assert "resample" not in seen
+
+
+# ------------------------------------------------------------------------------------------------ GPU: the kernel alone
+DEV = torch.device("cuda:0")
+SEED = 0xFEEDFACE12345678
+
+
+@pytest.fixture(scope="module")
+def lib():
+    if not torch.cuda.is_available():
+        pytest.fail("-m gpu tests need a GPU")
+    return hip.load()
+
+
+def run_renoise(lib, xt, K, r, *, step_row=0, seed=SEED, sample_offset=0, xin=None, misalign=False):
+    """xt: integer array [N,HW]; xin: fp32 array [N,HW,stride] or None.  Returns (xt, xin) after the launch as numpy arrays.
+    misalign: xt starts one byte into its allocation (the per-byte kernel instead of the 4-pixel one)."""
+    N, HW = xt.shape
+    buf = torch.zeros(N * HW + 4, dtype=torch.uint8, device=DEV)
+    o = 1 if misalign else 0
+    buf[o:o + N * HW] = torch.from_numpy(xt.astype(np.uint8)).reshape(-1).to(DEV)
+    dxin = None if xin is None else torch.from_numpy(xin).contiguous().to(DEV)
+    p_stay, p_move = probabilities(r, K)
+    hip.check(getattr(lib, SYMBOL)(N, HW, K, float(p_stay), float(p_move), step_row, seed, sample_offset, buf.data_ptr() + o,
+                                   None if dxin is None else dxin.data_ptr(), 0 if xin is None else xin.shape[2], 0), SYMBOL)
+    torch.cuda.synchronize()
+    assert bool((buf[:o] == 0).all()) and bool((buf[o + N * HW:] == 0).all()), "a byte outside the map was written"
+    return buf[o:o + N * HW].cpu().numpy().reshape(N, HW).astype(np.int64), (None if dxin is None else dxin.cpu().numpy())
+
+
+def run_clamp(lib, known, xt, K, c, *, step_row, seed=SEED, sample_offset=0):
+    N, HW = known.shape
+    dk, dx = (torch.from_numpy(a.astype(np.uint8)).contiguous().to(DEV) for a in (known, xt))
+    p_hit, p_miss = probabilities(c, K)
+    hip.check(getattr(lib, CLAMP)(dk.data_ptr(), N, HW, K, float(p_hit), float(p_miss), hip.STEP_SAMPLE, step_row, seed, sample_offset,
+                                  dx.data_ptr(), None, 0, None, None, 0), CLAMP)
+    torch.cuda.synchronize()
+    return dx.cpu().numpy().astype(np.int64)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("N,HW,K", [(3, 63, 2), (2, 256, 3), (2, 256, 5), (2, 64, 20), (1, 64, 255)])
+def test_renoise_kernel_equals_the_restatement(lib, N, HW, K):
+    """xt and the one-hot channels equal the numpy restatement at every pixel; the image channels >= K survive; r = 1 returns the input,
+    r = 0 does not depend on it; the draw moves with the sample offset, the step row and the seed, and is not the clamp's."""
+    rng = np.random.default_rng(3000 + K)
+    stride = (K + 4) // 4 * 4 + 1                     # > K, and no multiple of 4
+    xt0 = rng.integers(0, K, (N, HW))
+    xin0 = rng.standard_normal((N, HW, stride)).astype(np.float32)
+    draws = {}
+    for r in (0.0, 0.37, 1.0):
+        for off, row, with_xin in ((0, 0, True), (0, 0, False), (5, 3, False), (5, 3, True), (0, 3, False)):
+            got, xin = run_renoise(lib, xt0, K, r, step_row=row, sample_offset=off, xin=xin0 if with_xin else None)
+            want = renoise_restatement(xt0, K, r, row, SEED, off)
+            what = f"r={r} off={off} row={row} xin={with_xin}"
+            assert np.array_equal(got, want), what + f": {int((got != want).sum())} pixels differ from the restatement"
+            if r == 1.0:
+                assert np.array_equal(got, xt0), what
+            if with_xin:
+                assert np.array_equal(xin[..., K:].view(np.uint32), xin0[..., K:].view(np.uint32)), what + ": an image channel changed"
+                assert np.array_equal(xin[..., :K], (np.arange(K)[None, None, :] == want[..., None]).astype(np.float32)), what
+            draws[(r, off, row)] = got
+    # r = 0: uniform whatever the input
+    other, _ = run_renoise(lib, (xt0 + 1) % K, K, 0.0, step_row=3, sample_offset=5)
+    assert np.array_equal(other, draws[(0.0, 5, 3)])
+    # the 4-pixel kernel and the per-byte kernel (xt not 4-byte aligned) draw the same
+    byte, _ = run_renoise(lib, xt0, K, 0.37, step_row=3, sample_offset=5, misalign=True)
+    assert np.array_equal(byte, draws[(0.37, 5, 3)])
+    # r = 0.37: a fair share of the pixels leave their class, and which ones depends on the counters and the key
+    base = draws[(0.37, 0, 3)]
+    assert not np.array_equal(base, draws[(0.37, 5, 3)]) and not np.array_equal(base, draws[(0.37, 0, 0)])
+    assert not np.array_equal(base, run_renoise(lib, xt0, K, 0.37, step_row=3, seed=SEED + 1)[0])
+    # the clamp's draw at the same counters over an all-known map equal to xt: another counter range
+    clamp = run_clamp(lib, xt0, xt0, K, 0.37, step_row=3)
+    assert np.array_equal(clamp, clamp_restatement(xt0, xt0, K, 0.37, 3, SEED, 0)) and not np.array_equal(clamp, base)
+    if N * HW >= 128:
+        # P(x != own) = (1 - r)(K - 1)/K <= 0.63; >= 128 draws: a standard deviation <= sqrt(0.25 / 128) = 0.044
+        left = (draws[(0.37, 0, 0)] != xt0).mean()
+        assert abs(left - 0.63 * (K - 1) / K) < 0.2, left
+    # sharding: samples 1.. of a batch at offset 5 are samples 0.. of a batch at offset 6
+    if N > 1:
+        a, _ = run_renoise(lib, xt0, K, 0.37, step_row=2, sample_offset=5)
+        b, _ = run_renoise(lib, xt0[1:], K, 0.37, step_row=2, sample_offset=6)
+        assert np.array_equal(a[1:], b)
+
+
+@pytest.mark.gpu
+def test_renoise_kernel_refuses_bad_arguments(lib):
+    N, HW, K = 2, 64, 3
+    xt = torch.full((N, HW), 2, dtype=torch.uint8, device=DEV)
+    xin = torch.full((N, HW, 4), 7.5, device=DEV)
+    good = dict(N=N, HW=HW, K=K, p_stay=1.0, p_move=0.0, step_row=0, seed=0, off=0, xt=xt.data_ptr(), xin=xin.data_ptr(), stride=4, stream=0)
+    for change, text in ((dict(N=0), "N=0"), (dict(N=-1), "N=-1"), (dict(HW=0), "HW=0"), (dict(K=0), "K=0"), (dict(K=256), "K=256"),
+                         (dict(xt=None), "null"), (dict(stride=2), "xin_stride"), (dict(step_row=-1), "step_row")):
+        assert getattr(lib, SYMBOL)(*dict(good, **change).values()) < 0, change
+        assert "renoise_step" in hip.last_error() and text in hip.last_error(), (change, hip.last_error())
+    torch.cuda.synchronize()
+    assert bool((xt == 2).all()) and bool((xin == 7.5).all())           # nothing was launched
+    assert getattr(lib, SYMBOL)(*good.values()) == 0                     # p_stay = 1: the state stays, its one-hot is written
+    torch.cuda.synchronize()
+    assert bool((xt == 2).all()) and bool((xin[..., :K].cpu() == torch.tensor([0.0, 0.0, 1.0])).all()) and bool((xin[..., K:] == 7.5).all())
+
+
+# ------------------------------------------------------------------------------------------------ GPU: the sampler
+@pytest.fixture(scope="module", params=[2, 5], ids=["K2-fused-head", "K5-epilogue-xin"])
+def sampler(request):
+    """K = 2: stem conv and fused head-and-posterior launch (x_t travels as the uint8 index only); K = 5: the general epilogue, which
+    writes the one-hot into the stem's input."""
+    if not torch.cuda.is_available():
+        pytest.fail("-m gpu tests need a GPU")
+    K = request.param
+    model, sd = small_model(K)
+    model = model.to(DEV).eval()
+    model.rng, model.philox_seed, model.philox_advance = "philox", 99, False          # every call replays call 0's stream
+    rng = np.random.default_rng(40 + K)
+    N = 4
+    image = torch.from_numpy(rng.uniform(-1, 1, (N, 1, H, W)).astype(np.float32))
+    x = O.one_hot_bchw(torch.from_numpy(rng.integers(0, K, (N, H, W))), K)
+    labels = torch.from_numpy(rng.integers(0, K, (N, H, W)))
+    known = torch.where(torch.from_numpy(rng.random((N, H, W)) < 0.3), labels, torch.full_like(labels, FREE))
+    eng = model._engine(x.to(DEV), image.to(DEV), None)
+    assert eng.head_fused == (K == 2) and eng.stem_onehot_on_load == (K == 2)
+    return dict(model=model, sd=sd, K=K, N=N, image=image.to(DEV), x=x.to(DEV), labels=labels, known=known, image_cpu=image, x_cpu=x)
+
+
+def settings(model, **kw):
+    for k, v in kw.items():
+        setattr(model, k, v)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("vote", ["majority", "confidence"])
+def test_without_a_jump_nothing_changes(sampler, vote):
+    """S = 6: resample = None, (0, 3), (2, 1) and (3, 2) (no jump point) are bit-identical to the conditioned call without the keyword,
+    and launch no renoise."""
+    s, model = sampler, sampler["model"]
+    settings(model, step_T_sample=vote, substreams=0, use_graph=True)
+    known = s["known"].to(DEV)
+    lib = hip.load()
+    real, calls = getattr(lib, SYMBOL), []
+    try:
+        setattr(lib, SYMBOL, lambda *a: calls.append(a) or real(*a))
+        plain = model(s["x"], s["image"], known_labels=known)["diffusion_out"].clone()
+        assert plain.dtype == (torch.int64 if vote == "majority" else torch.float32)
+        for pair in (None, (0, 3), (2, 1), (3, 2)):
+            out = model(s["x"], s["image"], known_labels=known, resample=pair)["diffusion_out"]
+            assert torch.equal(out, plain) and out.dtype == plain.dtype and out.stride() == plain.stride(), pair
+        assert calls == []
+    finally:
+        setattr(lib, SYMBOL, real)
+        settings(model, step_T_sample="majority")
+
+
+def oracle_resampled_walk(sd, K, x, image, known, t_values, key, walk):
+    """The conditioned loop restated from the oracle's step functions (test_known_labels.oracle_conditioned_walk), walking the rows in
+    the order of `walk`: pass p of a row draws under pass_key(key, p); before an entry with a jump the state is renoised from the level
+    left to the row's level.  Returns [(kind, row, class map [N,H,W])] in launch order, kind = 'renoise' | 'clamp'."""
+    _, alphas, cum = O.make_schedule("cosine", T_SMALL, {"s": 0.008})
+    N = x.shape[0]
+    kn = known.reshape(N, H * W).numpy()
+    xt, events = x, []
+    S = len(t_values)
+    for row, p, src in walk:
+        kp = pass_key(key, p)
+        t = t_values[row]
+        if src is not None:
+            r = float(cum[t_values[row] - 1].double()) / float(cum[t_values[src] - 1].double())
+            idx = renoise_restatement(xt.argmax(dim=1).reshape(N, H * W).numpy(), K, r, row, kp, 0)
+            idx = torch.from_numpy(idx).reshape(N, H, W)
+            events.append(("renoise", row, idx))
+            xt = O.one_hot_bchw(idx, K)
+        x0pred = O.unet_forward(sd, SMALL_CFG, xt, image, None, torch.full((N,), float(t)))["diffusion_out"]
+        a, c = O.posterior_coeffs(alphas, cum, t)
+        p_hat = O.normalise_probs(torch.clamp(O.theta_post_prob_ref(xt, x0pred, a, c), min=1e-12), "cascade")
+        if t > 1:
+            e = torch.from_numpy(O.philox_exponential(kp, row, 0, N, H * W, K)).reshape(N, H, W, K)
+            idx = O.sample_index(p_hat, e)
+        else:
+            idx = p_hat.argmax(dim=-1)
+        idx = clamp_restatement(kn, idx.reshape(N, H * W).numpy(), K, 1.0 if row == S - 1 else c, row, kp, 0)
+        idx = torch.from_numpy(idx).reshape(N, H, W)
+        events.append(("clamp", row, idx))
+        xt = O.one_hot_bchw(idx, K)
+    return events
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("t,pair,rows", [(None, (2, 2), [0, 1, 2, 3, 2, 3, 4, 5]), (T_STRIDED, (1, 2), [0, 1, 1, 2, 2, 3])],
+                         ids=["S6-jump2", "S4-strided-jump1"])
+def test_resampled_walk_against_the_oracle_step_by_step(sampler, monkeypatch, t, pair, rows):
+    """Seeded, 30 % of the pixels known, default precision, free-running: the launches follow resample_walk (rows, pass keys, the
+    renoising pair), and the class map after every clamp and after every renoise equals the oracle restatement's (mismatch 0, the
+    assertion of the seeded free-running walks of test_hip_parity)."""
+    s, model = sampler, sampler["model"]
+    K, N = s["K"], 2
+    lib = hip.load()
+    real_clamp, real_renoise = getattr(lib, CLAMP), getattr(lib, SYMBOL)
+    settings(model, substreams=1, use_graph=True, step_T_sample="majority")
+    eng = model._engine(s["x"][:N], s["image"][:N], None)
+    seen = []
+
+    def snap():
+        with torch.cuda.stream(eng.stream):
+            return eng.xt.clone()
+
+    def spy_clamp(*args):
+        rc = real_clamp(*args)
+        assert args[10] == eng.xt.data_ptr()
+        seen.append(("clamp", args[7], args[8], None, snap()))
+        return rc
+
+    def spy_renoise(*args):
+        rc = real_renoise(*args)
+        assert args[8] == eng.xt.data_ptr() and (args[9] is None) == (K == 2) and args[7] == 0
+        seen.append(("renoise", args[5], args[6], (args[3], args[4]), snap()))
+        return rc
+    monkeypatch.setattr(lib, CLAMP, spy_clamp)
+    monkeypatch.setattr(lib, SYMBOL, spy_renoise)
+    kw = {} if t is None else {"t": t}
+    out = model(s["x"][:N], s["image"][:N], known_labels=s["known"][:N], resample=pair, **kw)["diffusion_out"].cpu()
+    monkeypatch.undo()
+    t_values = step_values(T_SMALL, None if t is None else int(t))
+    walk = resample_walk(len(t_values), *pair)
+    assert [e[0] for e in walk] == rows
+    key = model._philox_key()
+    want_launches, cum = [], model.diffusion.cumalphas.cpu().double()
+    for row, p, src in walk:
+        if src is not None:
+            r = float(cum[t_values[row] - 1]) / float(cum[t_values[src] - 1])
+            want_launches.append(("renoise", row, pass_key(key, p), tuple(float(v) for v in probabilities(r, K))))
+        want_launches.append(("clamp", row, pass_key(key, p), None))
+    assert [v[:4] for v in seen] == want_launches
+    ref = oracle_resampled_walk(s["sd"], K, s["x_cpu"][:N], s["image_cpu"][:N], s["known"][:N], t_values, key, walk)
+    assert [(k, r) for k, r, _ in ref] == [(k, r) for k, r, _, _, _ in seen]
+    for j, ((kind, row, want), got) in enumerate(zip(ref, seen)):
+        got = got[4].cpu().reshape(N, H, W).long()
+        mism = (got != want).float().mean().item()
+        print(f"resampled walk K={K} launch {j} ({kind}, row {row}, t={t_values[row]}): class mismatch {mism:.2e}")
+        assert mism == 0.0, (j, kind, row, mism)
+    assert torch.equal(out, O.one_hot_bchw(ref[-1][2], K, torch.int64))
+
+
+@pytest.mark.gpu
+def test_resampled_samples_keep_the_constraint_and_the_execution_shape_does_not_matter(sampler):
+    """resample = (2, 2) at S = 6: known pixels come back as their labels in every step_T_sample mode, a fully known map returns the
+    labels; bit-identical across substreams 1 / 2, graph on / off and two half-batches at sample_offset 0 / 2; no graph capture is
+    added by the jumps; the free pixels differ from the un-resampled call's while the known pixels agree."""
+    s, model = sampler, sampler["model"]
+    K, known, labels = s["K"], s["known"], s["labels"]
+    is_known = known < K
+    dknown = known.to(DEV)
+    try:
+        for vote, dtype in (("majority", torch.int64), ("confidence", torch.float32), (None, torch.int64), ("keep", torch.float32)):
+            settings(model, step_T_sample=vote, substreams=0, use_graph=True)
+            out = model(s["x"], s["image"], known_labels=dknown, resample=(2, 2))["diffusion_out"].cpu()
+            assert out.dtype == dtype and tuple(out.shape) == (s["N"], K, H, W), vote
+            want = O.one_hot_bchw(torch.where(is_known, known, torch.zeros_like(known)), K, dtype)
+            mask = is_known[:, None].expand_as(out)
+            assert torch.equal(out[mask], want[mask]), vote
+            full = model(s["x"], s["image"], known_labels=labels, resample=(2, 2))["diffusion_out"].cpu()
+            assert torch.equal(full, O.one_hot_bchw(labels, K, dtype)), vote
+        settings(model, step_T_sample="majority")
+        modes = ((1, True), (2, True), (1, False), (2, False))
+
+        def captures():
+            return {k: e.graph_captures() for k, (_, e) in model._engines.items()}
+        for sub, graph in modes:                   # the plain conditioned call in every mode: whatever it captures is captured now
+            settings(model, substreams=sub, use_graph=graph)
+            unresampled = model(s["x"], s["image"], known_labels=dknown)["diffusion_out"].clone()
+        before = captures()
+        outs = {}
+        for sub, graph in modes:
+            settings(model, substreams=sub, use_graph=graph)
+            outs[(sub, graph)] = model(s["x"], s["image"], known_labels=dknown, resample=(2, 2))["diffusion_out"].clone()
+            assert model.last_mode == (sub, graph)
+        assert captures() == before and sum(before.values()) >= 1
+        ref = outs[(1, True)]
+        assert all(torch.equal(ref, v) for v in outs.values())
+        halves = []
+        for lo in (0, 2):
+            settings(model, substreams=1, use_graph=True, sample_offset=lo)
+            halves.append(model(s["x"][lo:lo + 2], s["image"][lo:lo + 2], known_labels=dknown[lo:lo + 2], resample=(2, 2))["diffusion_out"].clone())
+        settings(model, sample_offset=0)
+        assert torch.equal(torch.cat(halves, 0), ref)
+        free = (~is_known)[:, None].expand_as(ref).to(DEV)
+        assert not torch.equal(ref[free], unresampled[free]) and torch.equal(ref[~free], unresampled[~free])
+    finally:
+        settings(model, step_T_sample="majority", substreams=0, use_graph=True, sample_offset=0)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("batched", [False, True], ids=["sequential", "batched"])
+@pytest.mark.parametrize("voting", ["majority", "confidence"])
+def test_predict_multiple_resamples_every_pass(sampler, voting, batched):
+    """S = 3 passes, resample = (2, 2) at 6 rows (one jump): one renoise launch per sampling call, jump and sub-batch; `vote` equals the
+    label and `entropy` is exactly 0 at the known pixels; the free pixels are still sampled."""
+    s, model = sampler, sampler["model"]
+    K, B = s["K"], 2
+    known = s["known"][:B]
+    is_known = known < K
+    settings(model, substreams=0, use_graph=True, philox_advance=True, philox_call=0)
+    lib = hip.load()
+    real, calls = getattr(lib, SYMBOL), []
+    try:
+        setattr(lib, SYMBOL, lambda *a: calls.append(a) or real(*a))
+        out = model.predict_multiple(s["image"][:B], num_evaluations=3, voting=voting, batched=batched, known_labels=known, resample=(2, 2),
+                                     maps=("mean", "vote", "entropy"))
+        sampling_calls = 1 if batched else 3
+        assert model.philox_call == sampling_calls
+        assert len(calls) == sampling_calls * 1 * model.last_mode[0]
+        vote, ent, mean = out["vote"].cpu(), out["entropy"].cpu(), out["mean"].cpu()
+        assert torch.equal(vote[is_known], known[is_known])
+        assert bool((ent[is_known] == 0).all())
+        assert torch.equal(mean.permute(0, 2, 3, 1)[is_known], torch.nn.functional.one_hot(known[is_known], K).float())
+        assert bool((ent[~is_known] > 0).any())
+    finally:
+        setattr(lib, SYMBOL, real)
+        settings(model, philox_advance=False, philox_call=0)
