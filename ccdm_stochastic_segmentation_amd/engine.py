@@ -597,6 +597,21 @@ class SamplerEngine:
             self.N, self.H * self.W, self.K, float(p_stay), float(p_move), int(step_row), int(philox_seed) & (2 ** 64 - 1), int(sample_offset),
             self.xt.data_ptr(), None if self.stem_onehot_on_load else self.xin.ptr, self.Cs, self._stream()), "renoise_step")
 
+    def evidence_step(self, evidence: torch.Tensor, alpha_t: float, cumalpha_tm1: float, mode: int, step_row: int, *, philox_seed: int = 0,
+                      sample_offset: int = 0) -> None:
+        """The reverse step under per-pixel soft evidence (ccdm_evidence_step, asynchronous on the engine's stream), behind a `run` of a
+        table row whose mode is STEP_SOFTMAX_ONLY: that run left the network's x0 in out_probs and x_t in xt; this multiplies x0 by the
+        weights and does the step of (alpha_t, cumalpha_tm1, mode) — the real columns of row `step_row` — with the Philox counters the
+        unguided step of that row uses.  evidence: fp32 [N,H*W,K] on the engine's device, weights in [0,1]."""
+        assert evidence.dtype == torch.float32 and evidence.is_cuda and evidence.is_contiguous() \
+            and tuple(evidence.shape) == (self.N, self.H * self.W, self.K)
+        hip.check(self.lib.ccdm_evidence_step(
+            self.out_probs.data_ptr(), evidence.data_ptr(), self.N, self.H * self.W, self.K, float(alpha_t), float(cumalpha_tm1), int(mode),
+            int(step_row), int(philox_seed) & (2 ** 64 - 1), int(sample_offset), self.xt.data_ptr(),
+            None if self.stem_onehot_on_load else self.xin.ptr, self.Cs, self.out_probs.data_ptr(), self.out_onehot.data_ptr(),
+            self._stream()), "evidence_step")
+        self._evidence_keepalive = evidence
+
     def ce_logits(self) -> Optional[torch.Tensor]:
         """[N,K-1,H,W] logits of the optional ce head after the last run (BCHW view of channels-last memory), else None."""
         if self.head_ce is None:

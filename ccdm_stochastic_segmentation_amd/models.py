@@ -338,7 +338,19 @@ class DenoisingModel(nn.Module):
     (1 - r) / K), r = cumalpha_t / cumalpha_{t-j}.  Pass p of a row draws under pass_key(key, p), so a revisit sees fresh noise and the
     walk up to the first jump is the plain conditioned walk bit for bit.  The step tables, the captured graphs and the independence of
     `substreams`, `use_graph` and sharding are those of a conditioned call.  None, (j, 1), (0, r) and a jump_length without a jump
-    point change nothing."""
+    point change nothing.
+    `evidence` (keyword next to `known_labels`): sample under per-pixel SOFT evidence — a float map [N,K,H,W] of class weights in
+    [0,1], w_k proportional to the likelihood p(e | x_0 = k) of independent evidence e at that pixel: a scribble the annotator is fairly
+    sure of (0.9 on its class, 0.1 elsewhere), another model's or rater's probability map, classes that are impossible in a region
+    (weight 0), a per-class re-weighting for prior shift; all-ones is no evidence.  Exact for categorical diffusion, no gradient, no
+    scale, no retraining: the network predicts x0 = p(x_0 | x_t), Bayes gives p(x_0 | x_t, e) proportional to x0_k w_k, and the
+    reverse step's posterior is linear in that vector up to its normalisation — so every row's network pass stops at x0
+    (STEP_SOFTMAX_ONLY) and ccdm_evidence_step multiplies it by w and does the row's step with the counters of the unguided draw
+    (all-ones evidence reproduces the unguided call bit for bit).  The call walks like one with known labels: one step at a time, the
+    static execution-mode rule, results independent of `substreams`, `use_graph` and sharding (a caller that shards passes its shard's
+    slice).  Per walk entry: renoise (if a jump precedes), the network, the evidence step, the clamp — `evidence` composes with
+    `known_labels` and `resample`, whose rules do not change.  A pixel whose weights are all 0, a value outside [0,1], rng =
+    "torch_cpu" and a model with `softmax_output: no` (its x0 holds logits) are refused."""
 
     KNOWN_FREE = 255        # the value of a free pixel in `known_labels`
 
@@ -407,7 +419,10 @@ class DenoisingModel(nn.Module):
     # ------------------------------------------------------------------ reference API
     def forward(self, x: Tensor, condition: Tensor, feature_condition: Tensor = None, t: Optional[Tensor] = None,
                 label_ref_logits: Optional[Tensor] = None, validation: bool = False, *,
-                known_labels: Optional[Tensor] = None, resample: Optional[Tuple[int, int]] = None) -> Union[Tensor, dict]:
+                known_labels: Optional[Tensor] = None, resample: Optional[Tuple[int, int]] = None,
+                evidence: Optional[Tensor] = None) -> Union[Tensor, dict]:
+        if evidence is not None and (self.training or validation):
+            self._check_evidence(evidence, None, sampling=False)
         if known_labels is not None and (self.training or validation):
             raise ValueError("known_labels: only a sampling call (eval mode, validation=False) takes known labels")
         if resample is not None and (self.training or validation):
@@ -422,9 +437,9 @@ class DenoisingModel(nn.Module):
             return self.forward_step(x, condition, feature_condition, t)
         if t is None:
             return self.forward_denoising(x, condition, feature_condition, label_ref_logits=label_ref_logits, known_labels=known_labels,
-                                          resample=resample)
+                                          resample=resample, evidence=evidence)
         return self.forward_denoising(x, condition, feature_condition, cast(int, t.item()), label_ref_logits, known_labels=known_labels,
-                                      resample=resample)
+                                      resample=resample, evidence=evidence)
 
     # ------------------------------------------------------------------ engine plumbing
     def _weights_key(self) -> Tuple[int, int]:
@@ -606,14 +621,46 @@ class DenoisingModel(nn.Module):
     def forward_denoising(self, x: Optional[Tensor], condition: Tensor, feature_condition: Tensor,
                           init_t: Optional[int] = None, label_ref_logits: Optional[Tensor] = None, *,
                           consume: Optional[Callable[[SamplerEngine, int, int], None]] = None,
-                          known_labels: Optional[Tensor] = None, resample: Optional[Tuple[int, int]] = None) -> dict:
+                          known_labels: Optional[Tensor] = None, resample: Optional[Tuple[int, int]] = None,
+                          evidence: Optional[Tensor] = None) -> dict:
         """`consume` (predict_multiple): instead of returning the call's output, hand every sub-batch engine (eng, lo, hi) to
         consume(eng, lo, hi) once the call has succeeded, with the engine's stream current; the result is then {}.
         `known_labels`: integer [N,H,W], a class where the label is known, 255 where the pixel is free (see the class docstring).
-        `resample`: (jump_length, resamples), RePaint's resampling jumps of a walk with known labels (class docstring)."""
+        `resample`: (jump_length, resamples), RePaint's resampling jumps of a walk with known labels (class docstring).
+        `evidence`: float [N,K,H,W], per-pixel class weights in [0,1] (class docstring)."""
+        ev = None if evidence is None else self._check_evidence(evidence, tuple(x.shape))
         jumps = self._check_resample(resample, known_labels)
         known = None if known_labels is None else self._check_known_labels(known_labels, (x.shape[0], x.shape[2], x.shape[3]), x.shape[1])
-        return self._sample(x, condition, feature_condition, init_t, label_ref_logits, consume, known, jumps)
+        return self._sample(x, condition, feature_condition, init_t, label_ref_logits, consume, known, jumps, ev)
+
+    def _check_evidence(self, evidence: Tensor, shape: Optional[Tuple[int, int, int, int]], sampling: bool = True) -> Tensor:
+        """The one host-side check of a call's `evidence` (before anything runs): the map as contiguous fp32 [N,H*W,K] on the model's
+        device.  shape: the call's (N,K,H,W)."""
+        if not sampling or self.training:
+            raise ValueError("evidence: only a sampling call (eval mode, validation=False) takes evidence")
+        if self.rng == "torch_cpu":
+            raise ValueError("evidence: not available with rng = 'torch_cpu' (the host-noise parity mode replays the reference's draws, and the "
+                             "reference has no guided step to be in parity with); "
+                             "use rng = 'philox'")
+        if not self.unet.spec.softmax_output:
+            raise ValueError("evidence: needs a model whose output is a probability vector; with `softmax_output: no` x0 holds logits, "
+                             "which weights cannot multiply")
+        if not isinstance(evidence, Tensor) or not evidence.dtype.is_floating_point:
+            raise ValueError(f"evidence: expected a floating-point tensor of class weights in [0,1], got "
+                             f"{getattr(evidence, 'dtype', type(evidence).__name__)}")
+        shape = tuple(int(v) for v in cast(tuple, shape))
+        if tuple(evidence.shape) != shape:
+            raise ValueError(f"evidence: expected shape {shape} = [N,K,H,W], got {tuple(evidence.shape)}")
+        host = evidence.detach().to(torch.float32).cpu()
+        if not bool(torch.isfinite(host).all()):
+            raise ValueError("evidence: values must be finite weights in [0,1]; found NaN or infinity")
+        if bool((host < 0).any()) or bool((host > 1).any()):
+            bad = host[(host < 0) | (host > 1)][0]
+            raise ValueError(f"evidence: values must be weights in [0,1]; found {float(bad)}")
+        if bool((host.max(dim=1).values <= 0).any()):
+            raise ValueError("evidence: a pixel whose K weights are all 0 rules out every class there")
+        N, K, H, W = shape
+        return host.permute(0, 2, 3, 1).reshape(N, H * W, K).contiguous().to(next(self.unet.parameters()).device)
 
     def _check_resample(self, resample, known_labels) -> Optional[Tuple[int, int]]:
         """The one host-side check of a call's `resample` (before anything runs): (jump_length, resamples) as two ints, or None where
@@ -652,10 +699,12 @@ class DenoisingModel(nn.Module):
         return host.to(torch.uint8).reshape(shape[0], shape[1] * shape[2]).contiguous().to(next(self.unet.parameters()).device)
 
     def _sample(self, x: Optional[Tensor], condition: Tensor, feature_condition: Tensor, init_t: Optional[int],
-                label_ref_logits: Optional[Tensor], consume, known: Optional[Tensor], jumps: Optional[Tuple[int, int]] = None) -> dict:
-        """One sampling call; `known`: what _check_known_labels returned, or None; `jumps`: what _check_resample returned."""
+                label_ref_logits: Optional[Tensor], consume, known: Optional[Tensor], jumps: Optional[Tuple[int, int]] = None,
+                evidence: Optional[Tensor] = None) -> dict:
+        """One sampling call; `known`: what _check_known_labels returned, or None; `jumps`: what _check_resample returned; `evidence`:
+        what _check_evidence returned, or None."""
         out = self._with_range_fallback(lambda: self._forward_denoising(x, condition, feature_condition, init_t, label_ref_logits,
-                                                                        consume, known_labels=known, resample=jumps))
+                                                                        consume, known_labels=known, resample=jumps, evidence=evidence))
         if self.philox_advance:
             self.philox_call += 1           # the next call draws from a fresh stream (a range-error re-run above replayed this one)
         return out
@@ -667,7 +716,8 @@ class DenoisingModel(nn.Module):
     def predict_multiple(self, condition: Tensor, feature_condition: Optional[Tensor] = None, *, num_evaluations: int,
                          voting: Optional[str] = None, x: Optional[Tensor] = None, t: Optional[Tensor] = None, batched: bool = False,
                          maps: Sequence[str] = ("mean", "vote", "entropy", "mutual_info"),
-                         known_labels: Optional[Tensor] = None, resample: Optional[Tuple[int, int]] = None) -> Dict[str, Tensor]:
+                         known_labels: Optional[Tensor] = None, resample: Optional[Tuple[int, int]] = None,
+                         evidence: Optional[Tensor] = None) -> Dict[str, Tensor]:
         """S = `num_evaluations` samples of every image of `condition` [B,C,H,W], combined on the device into one prediction and
         per-pixel uncertainty maps — the reference's Evaluator.predict_multiple (evaluation/eval_cdm.py:176-193), which sums S
         `predict_single` outputs as `total += prediction_i * (1 / S)`.
@@ -684,6 +734,7 @@ class DenoisingModel(nn.Module):
         known_labels: integer [B,H,W] (a class where the label is known, 255 where the pixel is free): every pass is conditioned on it
           (class docstring), so `vote` equals the label and `entropy` is 0 at the known pixels.
         resample: (jump_length, resamples): every pass walks with RePaint's resampling jumps (class docstring); needs known_labels.
+        evidence: float [B,K,H,W] per-pixel class weights in [0,1] (class docstring): every pass is sampled under it.
         batched=False: S sampling calls of B samples, each advancing `philox_call` exactly like S calls of model(x_i, condition);
           after each call the pass is folded into device accumulators straight from the engine (ccdm_vote_accumulate), so memory
           is one pass plus the accumulators.  The range-error fallback and the execution-mode choice apply per pass.
@@ -710,6 +761,7 @@ class DenoisingModel(nn.Module):
         if x is not None and tuple(x.shape) != (S, B, K, H, W):
             raise ValueError(f"x: expected one-hot x_T of shape {(S, B, K, H, W)} = [S,B,K,H,W], got {tuple(x.shape)}")
         init_t = None if t is None else int(t.item() if isinstance(t, Tensor) else t)
+        ev = None if evidence is None else self._check_evidence(evidence, (B, K, H, W))
         jumps = self._check_resample(resample, known_labels)
         known = None if known_labels is None else self._check_known_labels(known_labels, (B, H, W), K)
         dev = next(self.unet.parameters()).device
@@ -741,7 +793,7 @@ class DenoisingModel(nn.Module):
                                                        ptr(counts, lo * HW * K), ptr(ent_sum, lo * HW), stream()), "vote_accumulate")
 
                 for i in range(S):
-                    self._sample(x[i] if x is not None else draw(B), condition, feature_condition, init_t, None, consume, known, jumps)
+                    self._sample(x[i] if x is not None else draw(B), condition, feature_condition, init_t, None, consume, known, jumps, ev)
             else:
                 xr = x.transpose(0, 1).reshape(B * S, K, H, W) if x is not None else draw(B * S)
                 cond = condition.repeat_interleave(S, dim=0)
@@ -752,7 +804,8 @@ class DenoisingModel(nn.Module):
                 def consume(eng, lo: int, hi: int) -> None:
                     buf[lo:hi].copy_(eng.xt if majority else eng.out_probs.reshape(hi - lo, HW, K))
 
-                self._sample(xr, cond, fc, init_t, None, consume, None if known is None else known.repeat_interleave(S, dim=0), jumps)
+                self._sample(xr, cond, fc, init_t, None, consume, None if known is None else known.repeat_interleave(S, dim=0), jumps,
+                             None if ev is None else ev.repeat_interleave(S, dim=0))
                 if majority:
                     vote8 = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
                     mean = torch.empty((B, H, W, K), dtype=torch.float32, device=dev) if "mean" in maps else None
@@ -810,9 +863,10 @@ class DenoisingModel(nn.Module):
 
     def _forward_denoising(self, x: Optional[Tensor], condition: Tensor, feature_condition: Tensor,
                            init_t: Optional[int] = None, label_ref_logits: Optional[Tensor] = None, consume=None, *,
-                           known_labels: Optional[Tensor] = None, resample: Optional[Tuple[int, int]] = None) -> dict:
+                           known_labels: Optional[Tensor] = None, resample: Optional[Tuple[int, int]] = None,
+                           evidence: Optional[Tensor] = None) -> dict:
         """`known_labels`: None, or the checked map (_check_known_labels: uint8 [N,H*W] on the model's device); `resample`: None, or the
-        checked pair (_check_resample)."""
+        checked pair (_check_resample); `evidence`: None, or the checked map (_check_evidence: fp32 [N,H*W,K] on the model's device)."""
         known = known_labels
         if label_ref_logits is not None:
             # the reference's guidance branch reads attributes that do not exist (guidance_scale_weights,
@@ -834,6 +888,10 @@ class DenoisingModel(nn.Module):
         host_rng = self.rng == "torch_cpu"
         if known is not None and host_rng:
             raise ValueError("known_labels: not available with rng = 'torch_cpu'")
+        if evidence is not None and host_rng:
+            raise ValueError("evidence: not available with rng = 'torch_cpu'")
+        # evidence: the network pass of every row stops at x0 (out_probs; x_t untouched), the row's real step follows in evidence_step
+        table = coeffs if evidence is None else [(a_, c_, hip.STEP_SOFTMAX_ONLY) for a_, c_, m_ in coeffs]
         # known labels: cumalpha of the state each row produces; the last row returns the labels themselves (class docstring)
         clamp_c = [1.0 if j == S - 1 else c_ for j, (a_, c_, m_) in enumerate(coeffs)]
         key = self._philox_key()
@@ -869,7 +927,7 @@ class DenoisingModel(nn.Module):
                 eng = self._engine(x[lo:hi], condition[lo:hi], fc, slot=j)
                 with eng.enter():
                     eng.set_inputs(self._to_index(x[lo:hi], eng.device), condition[lo:hi].to(eng.device), fc)
-                    eng.set_tables([float(t) for t in t_values], coeffs)
+                    eng.set_tables([float(t) for t in t_values], table)
                 parts_.append((eng, lo, hi))
             return parts_
 
@@ -882,9 +940,11 @@ class DenoisingModel(nn.Module):
                         if src is not None:            # back up the chain to the state before `row`, on the engine's stream
                             eng.renoise(*renoise_p[e], row, philox_seed=kp, sample_offset=self.sample_offset + lo)
                         eng.run(1, first_row=row, philox_seed=kp, sample_offset=self.sample_offset + lo, use_graph=graph_)
+                        if evidence is not None:
+                            eng.evidence_step(evidence[lo:hi], *coeffs[row], row, philox_seed=kp, sample_offset=self.sample_offset + lo)
                         eng.clamp_known_labels(known[lo:hi], clamp_c[row], coeffs[row][2], row, philox_seed=kp,
                                                sample_offset=self.sample_offset + lo)
-            elif len(parts_) == 1 and known is None:
+            elif len(parts_) == 1 and known is None and evidence is None:
                 parts_[0][0].run(s1_ - s0_, first_row=s0_, noise=noises_[0], noise_row0=noise_row0_, philox_seed=key,
                                  sample_offset=self.sample_offset, use_graph=graph_)
             else:
@@ -892,6 +952,8 @@ class DenoisingModel(nn.Module):
                     for j, (eng, lo, hi) in enumerate(parts_):
                         eng.run(1, first_row=s, noise=noises_[j], noise_row0=noise_row0_, philox_seed=key,
                                 sample_offset=self.sample_offset + lo, use_graph=graph_)
+                        if evidence is not None:       # on the engine's stream, behind the network pass that stopped at x0
+                            eng.evidence_step(evidence[lo:hi], *coeffs[s], s, philox_seed=key, sample_offset=self.sample_offset + lo)
                         if known is not None:          # on the engine's stream, behind the step: the next step reads the clamped state
                             eng.clamp_known_labels(known[lo:hi], clamp_c[s], coeffs[s][2], s, philox_seed=key,
                                                    sample_offset=self.sample_offset + lo)
@@ -900,7 +962,7 @@ class DenoisingModel(nn.Module):
         nsub = max(1, min(nsub, N))
         use_graph = bool(self.use_graph)
         if (int(self.substreams) <= 0 and self.calibrate_mode and not host_rng and self._range_probe is None and nsub > 1
-                and S >= self.CALIBRATION_MIN_STEPS and known is None):
+                and S >= self.CALIBRATION_MIN_STEPS and known is None and evidence is None):
             nsub, use_graph = self._calibrate_mode(x, condition, feature_condition, prepare, run_steps, nsub, use_graph, S)
         self.last_mode = (nsub, use_graph)
         parts = prepare(nsub)

@@ -351,6 +351,32 @@ int ccdm_renoise_step(int N, int HW, int K, float p_stay, float p_move, int step
                       uint8_t* xt /*dev [N,HW]*/, float* xin /*dev [N,HW,xin_stride] or NULL*/, int xin_stride, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Sampling under per-pixel soft evidence (DenoisingModel(..., evidence=)).  The network's x0 = p(x_0 | x_t) of a pixel and independent
+ * evidence e with likelihood p(e | x_0 = k) proportional to w_k give p(x_0 | x_t, e) proportional to x0_k * w_k (Bayes); the reverse
+ * step's posterior is linear in that vector up to its final normalisation, so the guided step is the unguided one on x0 * w.
+ * Launched after a denoise step whose table row has mode CCDM_STEP_SOFTMAX_ONLY has left x0 in out_probs (and x_t untouched in `xt`).
+ * Per pixel:
+ *   x0'_k = x0_k * evidence_k      one fp32 multiply, no renormalisation (the scale cancels in the step's own normalisation);
+ *   then ccdm_posterior_sample's arithmetic with softmax = 0 on x0' (the same device function: posterior in the documented op order
+ *   with alpha_t / cumalpha_tm1 as given, clamp at 1e-12, cascade normalisation), and by `mode`
+ *   CCDM_STEP_SAMPLE:          the Exp(1) race with the counters of the unguided step of that row, Philox4x32-10(counter = (pixel,
+ *                              sample_offset + n, step_row, k / 4), key = philox_seed); writes xt[i] and, if xin != NULL, the one-hot
+ *                              into xin[i * xin_stride + 0 .. K) (channels >= K: the image, untouched);
+ *   CCDM_STEP_LAST_CONFIDENCE: the probabilities into out_probs (if non-NULL);
+ *   CCDM_STEP_LAST_MAJORITY:   the argmax one-hot into out_onehot (if non-NULL), its index into xt;
+ *   CCDM_STEP_LAST_KEEP:       nothing.
+ * x0 and out_probs may be the same buffer: a pixel's K values are read completely before any of them is written.  All-ones evidence
+ * gives the bits of the unguided step.  K in [1, CCDM_MAX_CLASSES]; xin_stride >= K where xin is given; CCDM_STEP_SOFTMAX_ONLY is
+ * refused.  K <= 4: one thread per pixel; above, a block's pixels are staged through LDS so that global loads and the one-hot stores
+ * are contiguous.  Results depend on (pixel, global sample index, step row, key) only.
+ * ------------------------------------------------------------------------------------------------- */
+int ccdm_evidence_step(const float* x0 /*dev [N,HW,K]*/, const float* evidence /*dev [N,HW,K], weights in [0,1]*/, int N, int HW, int K,
+                       float alpha_t, float cumalpha_tm1, int mode /*CCDM_STEP_SAMPLE | _LAST_CONFIDENCE | _LAST_MAJORITY | _LAST_KEEP*/,
+                       int step_row, uint64_t philox_seed, uint32_t sample_offset,
+                       uint8_t* xt /*dev [N,HW]: x_t in, x_{t-1} out*/, float* xin /*dev [N,HW,xin_stride] or NULL*/, int xin_stride,
+                       float* out_probs /*[N,HW,K] or NULL*/, int64_t* out_onehot /*[N,HW,K] or NULL*/, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * LIDC metrics, device part: for every image and every pair (i, j) of class-index maps
  * a[img][i], b[img][j], the per-class pixel counts out[img][i][j][k] = {|a==k & b==k|, |a==k | b==k|}.
  * Replaces the [B,S,S',HW,K] boolean broadcast of `batched_distance` / `iou`
