@@ -11,9 +11,10 @@
 // arithmetic on the vector pipe (three IEEE divisions, a logarithm and a quarter Philox block per class), as for the unguided draw
 // kernel, which reads half the floats in 0.96x / 0.88x of the time: DESIGN.md section 4.
 //   K <= 4   one thread per pixel; the pixel's K values of x0 and of the evidence are one 8- or 16-byte load each where K is 2 or 4.
-//   K <= 32  a block's 256 pixels move as what they are, one contiguous run of 256 K floats per operand: 16-byte requests in lane
-//            order, multiplied on the way into LDS rows of an odd pitch (conflict-free per-thread reads); the one-hot channels of xin
-//            leave the same way (k_posterior_staged's scheme).  (K | 1) * 1 KiB of LDS per block: 4 blocks per CU at K = 32.
+//   K <= 32  a block's 256 pixels move as what they are, one contiguous run of 256 K floats per operand, multiplied on the way into
+//            LDS rows, and the one-hot channels of xin leave the same way: k_posterior_staged's scheme, and its two passes
+//            (stage_class_rows with the multiply, store_onehot_rows: ccdm_sampler_common.h).  (K | 1) * 1 KiB of LDS per block: 4
+//            blocks per CU at K = 32.
 //   K <= 255 the same with 64 pixels per block (at most 65 536 bytes of LDS); the pixel's classes no longer fit the register file and
 //            the core's arrays spill — no dataset has that many classes, and the arithmetic is not written a second time for them.
 // x0 and out_probs may be the same buffer (in the engine they are): a pixel's K values are in registers (one thread per pixel) or the
@@ -27,14 +28,6 @@
 namespace ccdm {
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// idx / d for the flat index of a block's [pixel][channel] run: (idx * ceil(2^20 / d)) >> 20 where d <= 64 (idx < 256 * d: error
-// < idx / 2^20 < 1 / d), a plain division above
-struct RowDiv {
-    unsigned d, m;
-    __device__ explicit RowDiv(unsigned d_) : d(d_), m(d_ <= 64u ? ((1u << 20) + d_ - 1u) / d_ : 0u) {}
-    __device__ __forceinline__ unsigned operator()(unsigned idx) const { return m ? (idx * m) >> 20 : idx / d; }
-};
 
 // `a`: head = x0 (softmax = 0, head_stride = K), xt_next = xt, no table, no noise buffer, no run block: filled by the launcher below
 template <int KP>
@@ -72,27 +65,7 @@ __global__ __launch_bounds__(BLK) void k_evidence_staged(const ccdm_post_args a,
     const int tid = threadIdx.x;
     const int nvalid = (int)std::min<size_t>(BLK, npix - i0);
     const int K = a.K;
-    {
-        const RowDiv row((unsigned)K);
-        const float* src = a.head + i0 * K;
-        const float* wsrc = ev + i0 * K;
-        const int total = nvalid * K;
-        if ((total & 3) == 0 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(wsrc)) & 15) == 0) {
-            for (int q = tid; q < total / 4; q += BLK) {
-                const f32x4 v = reinterpret_cast<const f32x4*>(src)[q], w = reinterpret_cast<const f32x4*>(wsrc)[q];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const unsigned idx = 4u * (unsigned)q + (unsigned)e, p = row(idx), k = idx - p * (unsigned)K;
-                    sx[p * PITCH + k] = v[e] * w[e];
-                }
-            }
-        } else {
-            for (int idx = tid; idx < total; idx += BLK) {
-                const unsigned p = row((unsigned)idx), k = (unsigned)idx - p * (unsigned)K;
-                sx[p * PITCH + k] = src[idx] * wsrc[idx];
-            }
-        }
-    }
+    stage_class_rows<BLK, PITCH, true>(sx, a.head + i0 * K, ev + i0 * K, nvalid, (unsigned)K, tid);
     __syncthreads();
     const bool onehot = mode == CCDM_STEP_SAMPLE && a.xin;               // uniform
     int bi = 0;
@@ -105,36 +78,8 @@ __global__ __launch_bounds__(BLK) void k_evidence_staged(const ccdm_post_args a,
     if (!onehot) return;
     sb[tid] = bi;
     __syncthreads();
-    {
-        const unsigned stride = (unsigned)a.xin_stride;
-        const RowDiv row(stride);
-        float* dst = a.xin + i0 * stride;
-        const int total = nvalid * (int)stride;
-        if ((total & 3) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
-            for (int q = tid; q < total / 4; q += BLK) {
-                f32x4 v;
-                bool all = true;
-                bool oh[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const unsigned idx = 4u * (unsigned)q + (unsigned)e, p = row(idx), c = idx - p * stride;
-                    oh[e] = c < (unsigned)K;
-                    all = all && oh[e];
-                    v[e] = (int)c == sb[p] ? 1.0f : 0.0f;
-                }
-                if (all) reinterpret_cast<f32x4*>(dst)[q] = v;
-                else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) if (oh[e]) dst[4 * q + e] = v[e];
-                }
-            }
-        } else {
-            for (int idx = tid; idx < total; idx += BLK) {
-                const unsigned p = row((unsigned)idx), c = (unsigned)idx - p * stride;
-                if (c < (unsigned)K) dst[idx] = (int)c == sb[p] ? 1.0f : 0.0f;
-            }
-        }
-    }
+    const unsigned stride = (unsigned)a.xin_stride;
+    store_onehot_rows<BLK>(a.xin + i0 * stride, sb, nvalid, stride, K, tid);
 }
 
 }  // namespace ccdm
@@ -144,16 +89,9 @@ using namespace ccdm;
 extern "C" int ccdm_evidence_step(const float* x0, const float* evidence, int N, int HW, int K, float alpha_t, float cumalpha_tm1, int mode,
                                   int step_row, uint64_t philox_seed, uint32_t sample_offset, uint8_t* xt, float* xin, int xin_stride,
                                   float* out_probs, int64_t* out_onehot, void* stream) {
-    CCDM_REQUIRE(x0 && evidence && xt, "evidence_step: null pointer");
-    CCDM_REQUIRE(N >= 1 && HW >= 1, "evidence_step: bad shape N=%d HW=%d", N, HW);
-    CCDM_REQUIRE(K >= 1 && K <= CCDM_MAX_CLASSES, "evidence_step: K=%d outside [1,%d]", K, CCDM_MAX_CLASSES);
-    CCDM_REQUIRE(!xin || xin_stride >= K, "evidence_step: xin_stride %d < K %d", xin_stride, K);
-    CCDM_REQUIRE(mode == CCDM_STEP_SAMPLE || mode == CCDM_STEP_LAST_CONFIDENCE || mode == CCDM_STEP_LAST_MAJORITY || mode == CCDM_STEP_LAST_KEEP,
-                 "evidence_step: mode %d", mode);
-    CCDM_REQUIRE(step_row >= 0, "evidence_step: step_row %d", step_row);
-    const size_t npix = (size_t)N * HW;
     const int blk = K <= 32 ? 256 : 64;
-    CCDM_REQUIRE((npix + blk - 1) / blk <= 0x7FFFFFFFull, "evidence_step: too many pixels");
+    if (const int rc = check_step_args("evidence_step", x0 && evidence && xt, N, HW, K, xin, xin_stride, mode, step_row, blk)) return rc;
+    const size_t npix = (size_t)N * HW;
     ccdm_post_args a = {};
     a.head = x0; a.softmax = 0; a.head_stride = K;
     a.xt = xt; a.xt_next = xt;
@@ -164,20 +102,16 @@ extern "C" int ccdm_evidence_step(const float* x0, const float* evidence, int N,
     const dim3 grid((unsigned)((npix + blk - 1) / blk)), block(blk);
     hipStream_t s = (hipStream_t)stream;
     const float al = alpha_t, cu = cumalpha_tm1;
-    if (K <= 4) {
-        const uintptr_t both = reinterpret_cast<uintptr_t>(x0) | reinterpret_cast<uintptr_t>(evidence);
-        const int vec = (K == 2 && (both & 7) == 0) || (K == 4 && (both & 15) == 0);
-        if (K <= 2) hipLaunchKernelGGL(k_evidence<2>, grid, block, 0, s, a, evidence, al, cu, mode, step_row, vec);
-        else hipLaunchKernelGGL(k_evidence<4>, grid, block, 0, s, a, evidence, al, cu, mode, step_row, vec);
-    }
-    else if (K <= 8) hipLaunchKernelGGL((k_evidence_staged<8, 256>), grid, block, 0, s, a, evidence, al, cu, mode, step_row);
-    else if (K <= 16) hipLaunchKernelGGL((k_evidence_staged<16, 256>), grid, block, 0, s, a, evidence, al, cu, mode, step_row);
-    else if (K <= 20) hipLaunchKernelGGL((k_evidence_staged<20, 256>), grid, block, 0, s, a, evidence, al, cu, mode, step_row);
-    else if (K <= 24) hipLaunchKernelGGL((k_evidence_staged<24, 256>), grid, block, 0, s, a, evidence, al, cu, mode, step_row);
-    else if (K <= 32) hipLaunchKernelGGL((k_evidence_staged<32, 256>), grid, block, 0, s, a, evidence, al, cu, mode, step_row);
-    else if (K <= 64) hipLaunchKernelGGL((k_evidence_staged<64, 64>), grid, block, 0, s, a, evidence, al, cu, mode, step_row);
-    else if (K <= 128) hipLaunchKernelGGL((k_evidence_staged<128, 64>), grid, block, 0, s, a, evidence, al, cu, mode, step_row);
-    else hipLaunchKernelGGL((k_evidence_staged<256, 64>), grid, block, 0, s, a, evidence, al, cu, mode, step_row);
+    dispatch_kp<256>(K, [&](auto c) {
+        constexpr int KP = decltype(c)::value;
+        if constexpr (KP <= 4) {
+            const uintptr_t both = reinterpret_cast<uintptr_t>(x0) | reinterpret_cast<uintptr_t>(evidence);
+            const int vec = (K == 2 && (both & 7) == 0) || (K == 4 && (both & 15) == 0);
+            hipLaunchKernelGGL(k_evidence<KP>, grid, block, 0, s, a, evidence, al, cu, mode, step_row, vec);
+        } else {
+            hipLaunchKernelGGL((k_evidence_staged<KP, (KP <= 32 ? 256 : 64)>), grid, block, 0, s, a, evidence, al, cu, mode, step_row);
+        }
+    });
     CCDM_CHECK_LAUNCH("evidence_step");
     return 0;
 }

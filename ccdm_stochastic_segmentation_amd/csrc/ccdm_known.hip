@@ -10,6 +10,8 @@
 // transition kernels compose in closed form.  Every pixel, known or free; the same race on a third counter range (0x40000000 | kq).
 // Reads 1 byte and writes 1 byte per pixel (+ K floats where the stem reads its one-hot from memory).  Measured, these bytes are 4 %
 // (64 x 128x128, K = 2) and 11 % (4 x 128x256, K = 20 with xin) of the HBM rate at the launch's time: DESIGN.md section 4.
+// The race (race_hit_miss), the one-hot store (write_onehot) and the entry points' argument checks (check_step_args) are
+// ccdm_sampler_common.h's, shared with the epilogue and the evidence step.
 #include "ccdm_common.h"
 #include "ccdm_sampler_common.h"
 
@@ -28,14 +30,11 @@ __global__ __launch_bounds__(256) void k_known_labels_step(const uint8_t* __rest
         const uint32_t pix = (uint32_t)(i % HW), smp = (uint32_t)(i / HW) + sample_offset;
         x = race_hit_miss(K, y, p_hit, p_miss, pix, smp, step_row, 0x80000000u, k0, k1);      // (the epilogue's blocks have kq < 64)
     } else {
-        if (out_probs) for (int k = 0; k < K; ++k) out_probs[i * K + k] = (k == x) ? 1.0f : 0.0f;
+        if (out_probs) write_onehot(out_probs + i * K, K, x);
         if (out_onehot) for (int k = 0; k < K; ++k) out_onehot[i * K + k] = (k == x) ? 1 : 0;
     }
     xt[i] = (uint8_t)x;
-    if (xin) {
-        float* d = xin + i * xin_stride;
-        for (int k = 0; k < K; ++k) d[k] = (k == x) ? 1.0f : 0.0f;
-    }
+    if (xin) write_onehot(xin + i * xin_stride, K, x);
 }
 
 // one thread per pixel; a byte >= K on entry (never produced by the host) counts as class K - 1
@@ -47,10 +46,7 @@ __global__ __launch_bounds__(256) void k_renoise_step(size_t npix, int HW, int K
     const int own = min((int)xt[i], K - 1);
     const int x = race_hit_miss(K, own, p_stay, p_move, (uint32_t)(i % HW), (uint32_t)(i / HW) + sample_offset, step_row, 0x40000000u, k0, k1);
     xt[i] = (uint8_t)x;
-    if (xin) {
-        float* d = xin + i * xin_stride;
-        for (int k = 0; k < K; ++k) d[k] = (k == x) ? 1.0f : 0.0f;
-    }
+    if (xin) write_onehot(xin + i * xin_stride, K, x);
 }
 
 // no xin (the stem builds its one-hot from xt): a thread takes 4 consecutive pixels of the flat [N*HW] map with one 32-bit load and
@@ -86,15 +82,8 @@ using namespace ccdm;
 extern "C" int ccdm_known_labels_step(const uint8_t* known, int N, int HW, int K, float p_hit, float p_miss, int mode, int step_row,
                                       uint64_t philox_seed, uint32_t sample_offset, uint8_t* xt, float* xin, int xin_stride,
                                       float* out_probs, int64_t* out_onehot, void* stream) {
-    CCDM_REQUIRE(known && xt, "known_labels_step: null pointer");
-    CCDM_REQUIRE(N >= 1 && HW >= 1, "known_labels_step: bad shape N=%d HW=%d", N, HW);
-    CCDM_REQUIRE(K >= 1 && K <= CCDM_MAX_CLASSES, "known_labels_step: K=%d outside [1,%d]", K, CCDM_MAX_CLASSES);
-    CCDM_REQUIRE(!xin || xin_stride >= K, "known_labels_step: xin_stride %d < K %d", xin_stride, K);
-    CCDM_REQUIRE(mode == CCDM_STEP_SAMPLE || mode == CCDM_STEP_LAST_CONFIDENCE || mode == CCDM_STEP_LAST_MAJORITY || mode == CCDM_STEP_LAST_KEEP,
-                 "known_labels_step: mode %d", mode);
-    CCDM_REQUIRE(step_row >= 0, "known_labels_step: step_row %d", step_row);
+    if (const int rc = check_step_args("known_labels_step", known && xt, N, HW, K, xin, xin_stride, mode, step_row, 256)) return rc;
     const size_t npix = (size_t)N * HW;
-    CCDM_REQUIRE((npix + 255) / 256 <= 0x7FFFFFFFull, "known_labels_step: too many pixels");
     hipLaunchKernelGGL(k_known_labels_step, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, (hipStream_t)stream, known, npix, HW, K,
                        p_hit, p_miss, mode, (uint32_t)step_row, (uint32_t)philox_seed, (uint32_t)(philox_seed >> 32), sample_offset, xt, xin,
                        xin_stride, out_probs, out_onehot);
@@ -104,13 +93,9 @@ extern "C" int ccdm_known_labels_step(const uint8_t* known, int N, int HW, int K
 
 extern "C" int ccdm_renoise_step(int N, int HW, int K, float p_stay, float p_move, int step_row, uint64_t philox_seed, uint32_t sample_offset,
                                  uint8_t* xt, float* xin, int xin_stride, void* stream) {
-    CCDM_REQUIRE(xt, "renoise_step: null pointer");
-    CCDM_REQUIRE(N >= 1 && HW >= 1, "renoise_step: bad shape N=%d HW=%d", N, HW);
-    CCDM_REQUIRE(K >= 1 && K <= CCDM_MAX_CLASSES, "renoise_step: K=%d outside [1,%d]", K, CCDM_MAX_CLASSES);
-    CCDM_REQUIRE(!xin || xin_stride >= K, "renoise_step: xin_stride %d < K %d", xin_stride, K);
-    CCDM_REQUIRE(step_row >= 0, "renoise_step: step_row %d", step_row);
+    // (no mode argument: a renoise is always a draw)
+    if (const int rc = check_step_args("renoise_step", xt != nullptr, N, HW, K, xin, xin_stride, CCDM_STEP_SAMPLE, step_row, 256)) return rc;
     const size_t npix = (size_t)N * HW;
-    CCDM_REQUIRE((npix + 255) / 256 <= 0x7FFFFFFFull, "renoise_step: too many pixels");
     const uint32_t k0 = (uint32_t)philox_seed, k1 = (uint32_t)(philox_seed >> 32);
     if (!xin && ((uintptr_t)xt & 3) == 0) {
         const size_t groups = (npix + 3) / 4;

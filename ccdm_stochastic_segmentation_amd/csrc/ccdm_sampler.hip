@@ -9,6 +9,9 @@
 //   P_k   = max(P_k, 1e-12)                                                         diffusion_denoising.py:204
 //   Phat  = P_k / sum_K P   (cascade order: blocks of 16 sequential, tail first)    torch Categorical normalisation
 //   idx   = argmax_k Phat_k / E_k, first maximum wins                               torch.multinomial(n=1)
+// That arithmetic, the LDS staging of the many-class kernel and the K -> KP ladder of the launcher are defined once, in
+// ccdm_sampler_common.h (posterior_pixel_core, stage_class_rows / store_onehot_rows, dispatch_kp), for this file, ccdm_head.hip and
+// ccdm_evidence.hip.
 #include "ccdm_common.h"
 #include "ccdm_sampler_common.h"
 
@@ -33,11 +36,9 @@ __global__ __launch_bounds__(256) void k_posterior(const ccdm_post_args a_in) {
 
 // Many classes (K > 4): a thread's K head values are K * 4 bytes apart from its neighbour's, and so are the one-hot channels it writes into
 // the stem's input — as per-thread accesses that is K load and K store instructions per wave touching 64 different lines each (K = 20,
-// 16 x 256x512: 289 us, a quarter of the HBM rate, half of it waiting on the memory front end).  Here the block's 256 pixels move as what
-// they are, one contiguous run of 256 * K floats in and 256 * xin_stride floats out: 16-byte requests in lane order, exchanged through LDS
-// (rows padded to an odd pitch: conflict-free per-thread reads).  The stem input's image channels (positions K.. of each pixel) are not
-// touched: a 16-byte piece that lies wholly inside one-hot channels is one store, a piece that straddles image channels is written
-// element by element.  Same arithmetic (posterior_pixel), same bits.
+// 16 x 256x512: 289 us, a quarter of the HBM rate, half of it waiting on the memory front end).  Here the block's 256 pixels move as
+// contiguous runs through LDS (stage_class_rows / store_onehot_rows, ccdm_sampler_common.h: the one definition of the scheme).
+// Same arithmetic (posterior_pixel), same bits.
 template <int KP>
 __global__ __launch_bounds__(256) void k_posterior_staged(const ccdm_post_args a_in) {
     constexpr int PITCH = KP | 1;
@@ -50,28 +51,8 @@ __global__ __launch_bounds__(256) void k_posterior_staged(const ccdm_post_args a
     const int nvalid = (int)std::min<size_t>(256, npix - i0);
     const int K = a.K;
     const int step = a.step_ptr ? *a.step_ptr : 0;
-    // idx / d for idx < 256 * 64, d in [5, 64]: (idx * ceil(2^20 / d)) >> 20 (error < idx / 2^20 < 1 / d)
-    const unsigned hs = (unsigned)a.head_stride;                       // K <= hs <= KP (launch_posterior)
-    const unsigned MK = ((1u << 20) + hs - 1u) / hs;
-    {
-        const float* src = a.head + i0 * hs;
-        const int total = nvalid * (int)hs;
-        if ((total & 3) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
-            for (int q = tid; q < total / 4; q += 256) {
-                const f32x4 v = reinterpret_cast<const f32x4*>(src)[q];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const unsigned idx = 4u * (unsigned)q + (unsigned)e, p = (idx * MK) >> 20, k = idx - p * hs;
-                    sx[p * PITCH + k] = v[e];
-                }
-            }
-        } else {
-            for (int idx = tid; idx < total; idx += 256) {
-                const unsigned p = ((unsigned)idx * MK) >> 20, k = (unsigned)idx - p * hs;
-                sx[p * PITCH + k] = src[idx];
-            }
-        }
-    }
+    const unsigned hs = (unsigned)a.head_stride;                       // K <= hs <= KP (posterior_staged_ok)
+    stage_class_rows<256, PITCH, false, KP>(sx, a.head + i0 * hs, nullptr, nvalid, hs, tid);
     __syncthreads();
     int bi = 0;
     if (tid < nvalid) {
@@ -84,36 +65,8 @@ __global__ __launch_bounds__(256) void k_posterior_staged(const ccdm_post_args a
     if (mode != CCDM_STEP_SAMPLE || !a.xin) return;
     sb[tid] = bi;
     __syncthreads();
-    {
-        const unsigned stride = (unsigned)a.xin_stride;
-        const unsigned MS = ((1u << 20) + stride - 1u) / stride;
-        float* dst = a.xin + i0 * stride;
-        const int total = nvalid * (int)stride;
-        if ((total & 3) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
-            for (int q = tid; q < total / 4; q += 256) {
-                f32x4 v;
-                bool all = true;
-                bool oh[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const unsigned idx = 4u * (unsigned)q + (unsigned)e, p = (idx * MS) >> 20, c = idx - p * stride;
-                    oh[e] = c < (unsigned)K;
-                    all = all && oh[e];
-                    v[e] = (int)c == sb[p] ? 1.0f : 0.0f;
-                }
-                if (all) reinterpret_cast<f32x4*>(dst)[q] = v;
-                else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) if (oh[e]) dst[4 * q + e] = v[e];
-                }
-            }
-        } else {
-            for (int idx = tid; idx < total; idx += 256) {
-                const unsigned p = ((unsigned)idx * MS) >> 20, c = (unsigned)idx - p * stride;
-                if (c < (unsigned)K) dst[idx] = (int)c == sb[p] ? 1.0f : 0.0f;
-            }
-        }
-    }
+    const unsigned stride = (unsigned)a.xin_stride;                    // K <= stride <= 64 (posterior_staged_ok)
+    store_onehot_rows<256, 64>(a.xin + i0 * stride, sb, nvalid, stride, K, tid);
 }
 
 // More than 32 classes (round 5; no reference dataset has them — builder.py:36-45 accepts any label shape): a pixel's K values live in
@@ -234,7 +187,11 @@ __global__ __launch_bounds__(128) void k_posterior_many(const ccdm_post_args a_i
 }
 
 // the staged form needs contiguous head rows and strides its index arithmetic covers
-static int posterior_kp(int K) { return K <= 2 ? 2 : K <= 4 ? 4 : K <= 8 ? 8 : K <= 16 ? 16 : K <= 20 ? 20 : K <= 24 ? 24 : 32; }
+static int posterior_kp(int K) {
+    int kp = 0;
+    dispatch_kp(K, [&](auto c) { kp = c; });
+    return kp;
+}
 static bool posterior_staged_ok(const ccdm_post_args& a) {
     return a.K > 4 && a.head_stride <= posterior_kp(a.K) && (!a.xin || (a.xin_stride >= a.K && a.xin_stride <= 64));
 }
@@ -257,25 +214,18 @@ int launch_posterior(const ccdm_post_args& a, hipStream_t s) {
         CCDM_CHECK_LAUNCH("posterior(many classes)");
         return 0;
     }
-    dim3 grid((unsigned)((npix + 255) / 256)), block(256);
-    if (posterior_staged_ok(a)) {
-        if (a.K <= 8) hipLaunchKernelGGL(k_posterior_staged<8>, grid, block, 0, s, a);
-        else if (a.K <= 16) hipLaunchKernelGGL(k_posterior_staged<16>, grid, block, 0, s, a);
-        else if (a.K <= 20) hipLaunchKernelGGL(k_posterior_staged<20>, grid, block, 0, s, a);
-        else if (a.K <= 24) hipLaunchKernelGGL(k_posterior_staged<24>, grid, block, 0, s, a);
-        else hipLaunchKernelGGL(k_posterior_staged<32>, grid, block, 0, s, a);
-        CCDM_CHECK_LAUNCH("posterior");
-        return 0;
-    }
-    if (a.K <= 2) hipLaunchKernelGGL(k_posterior<2>, grid, block, 0, s, a);
-    else if (a.K <= 4) hipLaunchKernelGGL(k_posterior<4>, grid, block, 0, s, a);
-    else if (a.K <= 8) hipLaunchKernelGGL(k_posterior<8>, grid, block, 0, s, a);
-    else if (a.K <= 16) hipLaunchKernelGGL(k_posterior<16>, grid, block, 0, s, a);
-    // (the per-class work — four IEEE divisions, an exponential, a quarter Philox block — is predicated, not skipped, beyond K: Cityscapes'
-    //  K = 20 on the 32-wide instantiation did 60 % more arithmetic than it needed)
-    else if (a.K <= 20) hipLaunchKernelGGL(k_posterior<20>, grid, block, 0, s, a);
-    else if (a.K <= 24) hipLaunchKernelGGL(k_posterior<24>, grid, block, 0, s, a);
-    else hipLaunchKernelGGL(k_posterior<32>, grid, block, 0, s, a);
+    const dim3 grid((unsigned)((npix + 255) / 256)), block(256);
+    const bool staged = posterior_staged_ok(a);
+    dispatch_kp(a.K, [&](auto c) {
+        constexpr int KP = decltype(c)::value;
+        if constexpr (KP > 4) {                            // (staged implies K > 4)
+            if (staged) {
+                hipLaunchKernelGGL(k_posterior_staged<KP>, grid, block, 0, s, a);
+                return;
+            }
+        }
+        hipLaunchKernelGGL(k_posterior<KP>, grid, block, 0, s, a);
+    });
     CCDM_CHECK_LAUNCH("posterior");
     return 0;
 }

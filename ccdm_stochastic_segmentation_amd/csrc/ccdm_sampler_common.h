@@ -1,8 +1,14 @@
 // The per-pixel arithmetic of the step epilogue — softmax_K -> categorical posterior -> clamp -> normalise -> Exp(1)-race argmax (or the
-// last-step outputs) — shared by the stand-alone epilogue kernel (ccdm_sampler.hip) and the head kernel that ends in it
-// (ccdm_head.hip): ONE definition, so both produce the same bits from the same logits.  See ccdm_sampler.hip for the arithmetic order.
+// last-step outputs) — shared by the stand-alone epilogue kernel (ccdm_sampler.hip), the head kernel that ends in it (ccdm_head.hip)
+// and the evidence step (ccdm_evidence.hip): ONE definition, so all produce the same bits from the same values.  See ccdm_sampler.hip
+// for the arithmetic order.  Also here, once each: the two LDS passes of the staged kernels (stage_class_rows, store_onehot_rows), the
+// per-thread one-hot store (write_onehot), the K -> KP ladder of the launchers (dispatch_kp) and the argument checks the step entry
+// points share (check_step_args).
 #pragma once
 #include "ccdm_common.h"
+
+#include <type_traits>
+#include <utility>
 
 namespace ccdm {
 
@@ -212,6 +218,122 @@ __device__ __forceinline__ void posterior_pixel(const ccdm_post_args& a, const s
     const int mode = (int)row[2];
     const int xt = mode == CCDM_STEP_SOFTMAX_ONLY ? 0 : (int)a.xt[i];
     posterior_pixel_core<KP>(a, i, x0, step, al, cu, mode, xt, chosen);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The staged kernels (k_posterior_staged, k_evidence_staged): a block's BLK pixels move as what they are, one contiguous run of
+// [pixel][class] floats in and [pixel][xin_stride] floats out: 16-byte requests in lane order, exchanged through LDS rows padded to an
+// odd pitch (conflict-free per-thread reads), element by element where the run is not a whole number of aligned 16-byte pieces.
+
+// idx / d for the flat index of a block's [pixel][channel] run: (idx * ceil(2^20 / d)) >> 20 where d <= 64 (idx < 256 * d: error
+// < idx / 2^20 < 1 / d), a plain division above
+// (MAXD: the caller's bound on d; where it is at most 64, the choice is made at compile time)
+template <unsigned MAXD>
+struct RowDiv {
+    unsigned d, m;
+    __device__ explicit RowDiv(unsigned d_) : d(d_), m(MAXD <= 64u || d_ <= 64u ? ((1u << 20) + d_ - 1u) / d_ : 0u) {}
+    __device__ __forceinline__ unsigned operator()(unsigned idx) const { return MAXD <= 64u || m ? (idx * m) >> 20 : idx / d; }
+};
+
+// stage-in: sx[p * PITCH + k] = src[p * row_len + k] (WEIGHTED: * wsrc[the same]) for the block's nvalid pixels, k < row_len <= PITCH
+// (MAXLEN: the caller's bound on row_len, if it has one)
+template <int BLK, int PITCH, bool WEIGHTED, unsigned MAXLEN = ~0u>
+__device__ __forceinline__ void stage_class_rows(float* const sx, const float* const src, const float* const wsrc, const int nvalid,
+                                                 const unsigned row_len, const int tid) {
+    const RowDiv<MAXLEN> row(row_len);
+    const int total = nvalid * (int)row_len;
+    uintptr_t addr = reinterpret_cast<uintptr_t>(src);
+    if constexpr (WEIGHTED) addr |= reinterpret_cast<uintptr_t>(wsrc);
+    if ((total & 3) == 0 && (addr & 15) == 0) {
+        for (int q = tid; q < total / 4; q += BLK) {
+            f32x4 v = reinterpret_cast<const f32x4*>(src)[q];
+            if constexpr (WEIGHTED) {
+                const f32x4 w = reinterpret_cast<const f32x4*>(wsrc)[q];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = v[e] * w[e];
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const unsigned idx = 4u * (unsigned)q + (unsigned)e, p = row(idx), k = idx - p * row_len;
+                sx[p * PITCH + k] = v[e];
+            }
+        }
+    } else {
+        for (int idx = tid; idx < total; idx += BLK) {
+            const unsigned p = row((unsigned)idx), k = (unsigned)idx - p * row_len;
+            if constexpr (WEIGHTED) sx[p * PITCH + k] = src[idx] * wsrc[idx];
+            else sx[p * PITCH + k] = src[idx];
+        }
+    }
+}
+
+// write-out: channel c < K of pixel p gets c == sb[p] ? 1 : 0; the image channels (c >= K of each `stride`-float pixel) are not touched:
+// a 16-byte piece that lies wholly inside one-hot channels is one store, a piece that straddles image channels goes element by element
+// (MAXSTRIDE: the caller's bound on stride, if it has one)
+template <int BLK, unsigned MAXSTRIDE = ~0u>
+__device__ __forceinline__ void store_onehot_rows(float* const dst, const int* const sb, const int nvalid, const unsigned stride, const int K,
+                                                  const int tid) {
+    const RowDiv<MAXSTRIDE> row(stride);
+    const int total = nvalid * (int)stride;
+    if ((total & 3) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
+        for (int q = tid; q < total / 4; q += BLK) {
+            f32x4 v;
+            bool all = true;
+            bool oh[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const unsigned idx = 4u * (unsigned)q + (unsigned)e, p = row(idx), c = idx - p * stride;
+                oh[e] = c < (unsigned)K;
+                all = all && oh[e];
+                v[e] = (int)c == sb[p] ? 1.0f : 0.0f;
+            }
+            if (all) reinterpret_cast<f32x4*>(dst)[q] = v;
+            else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) if (oh[e]) dst[4 * q + e] = v[e];
+            }
+        }
+    } else {
+        for (int idx = tid; idx < total; idx += BLK) {
+            const unsigned p = row((unsigned)idx), c = (unsigned)idx - p * stride;
+            if (c < (unsigned)K) dst[idx] = (int)c == sb[p] ? 1.0f : 0.0f;
+        }
+    }
+}
+
+// the per-thread form: the K one-hot channels of one pixel
+__device__ __forceinline__ void write_onehot(float* const d, const int K, const int x) {
+    for (int k = 0; k < K; ++k) d[k] = (k == x) ? 1.0f : 0.0f;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Host side.  The ladder from K to the padded class count KP a kernel is instantiated for: f(std::integral_constant<int, KP>{}) for the
+// first rung >= K, the rung MAX for everything above the one below it.  (The per-class work — four IEEE divisions, an exponential, a
+// quarter Philox block — is predicated, not skipped, beyond K: Cityscapes' K = 20 on the 32-wide instantiation did 60 % more arithmetic
+// than it needed, hence 20 and 24.)  The register kernels end at 32; the rungs above are the evidence kernel's.
+constexpr int KP_LADDER[] = {2, 4, 8, 16, 20, 24, 32, 64, 128, 256};
+
+template <int MAX = 32, int I = 0, class F>
+inline void dispatch_kp(const int K, F&& f) {
+    constexpr int KP = KP_LADDER[I];
+    if constexpr (KP >= MAX) f(std::integral_constant<int, KP>{});
+    else if (K <= KP) f(std::integral_constant<int, KP>{});
+    else dispatch_kp<MAX, I + 1>(K, std::forward<F>(f));
+}
+
+// What ccdm_known_labels_step, ccdm_renoise_step and ccdm_evidence_step check alike (`name`: the entry's, without the prefix; `pointers`:
+// the entry's required pointers are all there; `blk`: pixels per block of the launch).  0, or fail()'s code.
+inline int check_step_args(const char* name, const bool pointers, const int N, const int HW, const int K, const float* xin, const int xin_stride,
+                           const int mode, const int step_row, const int blk) {
+    CCDM_REQUIRE(pointers, "%s: null pointer", name);
+    CCDM_REQUIRE(N >= 1 && HW >= 1, "%s: bad shape N=%d HW=%d", name, N, HW);
+    CCDM_REQUIRE(K >= 1 && K <= CCDM_MAX_CLASSES, "%s: K=%d outside [1,%d]", name, K, CCDM_MAX_CLASSES);
+    CCDM_REQUIRE(!xin || xin_stride >= K, "%s: xin_stride %d < K %d", name, xin_stride, K);
+    CCDM_REQUIRE(mode == CCDM_STEP_SAMPLE || mode == CCDM_STEP_LAST_CONFIDENCE || mode == CCDM_STEP_LAST_MAJORITY || mode == CCDM_STEP_LAST_KEEP,
+                 "%s: mode %d", name, mode);
+    CCDM_REQUIRE(step_row >= 0, "%s: step_row %d", name, step_row);
+    CCDM_REQUIRE(((size_t)N * HW + blk - 1) / blk <= 0x7FFFFFFFull, "%s: too many pixels", name);
+    return 0;
 }
 
 }  // namespace ccdm

@@ -573,6 +573,12 @@ class SamplerEngine:
         hip.check(self.lib.ccdm_engine_run(self._handle, first_row, n_steps, int(with_epilogue), int(use_graph),
                                            self._stream()), "engine_run")
 
+    def _step_state_args(self, philox_seed: int, sample_offset: int) -> tuple:
+        """What the three step calls below take alike: the Philox key, the sample offset, x_t, the stem's input where it reads its
+        one-hot from memory (else None), and that buffer's pixel stride."""
+        return (int(philox_seed) & (2 ** 64 - 1), int(sample_offset), self.xt.data_ptr(),
+                None if self.stem_onehot_on_load else self.xin.ptr, self.Cs)
+
     def clamp_known_labels(self, known: torch.Tensor, cumalpha_tm1: float, mode: int, step_row: int, *, philox_seed: int = 0,
                            sample_offset: int = 0) -> None:
         """Overwrite the known pixels of the state the last `run` left (ccdm_known_labels_step, asynchronous on the engine's stream).
@@ -584,9 +590,8 @@ class SamplerEngine:
         last = mode != hip.STEP_SAMPLE
         hip.check(self.lib.ccdm_known_labels_step(
             known.data_ptr(), self.N, self.H * self.W, self.K, float(np.float32(c + p_miss)), float(np.float32(p_miss)), int(mode),
-            int(step_row), int(philox_seed) & (2 ** 64 - 1), int(sample_offset), self.xt.data_ptr(),
-            None if self.stem_onehot_on_load else self.xin.ptr, self.Cs,
-            self.out_probs.data_ptr() if last else None, self.out_onehot.data_ptr() if last else None, self._stream()), "known_labels_step")
+            int(step_row), *self._step_state_args(philox_seed, sample_offset), self.out_probs.data_ptr() if last else None,
+            self.out_onehot.data_ptr() if last else None, self._stream()), "known_labels_step")
         self._known_keepalive = known
 
     def renoise(self, p_stay: float, p_move: float, step_row: int, *, philox_seed: int = 0, sample_offset: int = 0) -> None:
@@ -594,8 +599,8 @@ class SamplerEngine:
         the engine's stream): a resampling jump back up to table row `step_row`, which the next `run` executes.  p_stay / p_move: the
         fp32 pair the caller formed from the two levels' cumalphas."""
         hip.check(self.lib.ccdm_renoise_step(
-            self.N, self.H * self.W, self.K, float(p_stay), float(p_move), int(step_row), int(philox_seed) & (2 ** 64 - 1), int(sample_offset),
-            self.xt.data_ptr(), None if self.stem_onehot_on_load else self.xin.ptr, self.Cs, self._stream()), "renoise_step")
+            self.N, self.H * self.W, self.K, float(p_stay), float(p_move), int(step_row), *self._step_state_args(philox_seed, sample_offset),
+            self._stream()), "renoise_step")
 
     def evidence_step(self, evidence: torch.Tensor, alpha_t: float, cumalpha_tm1: float, mode: int, step_row: int, *, philox_seed: int = 0,
                       sample_offset: int = 0) -> None:
@@ -607,8 +612,7 @@ class SamplerEngine:
             and tuple(evidence.shape) == (self.N, self.H * self.W, self.K)
         hip.check(self.lib.ccdm_evidence_step(
             self.out_probs.data_ptr(), evidence.data_ptr(), self.N, self.H * self.W, self.K, float(alpha_t), float(cumalpha_tm1), int(mode),
-            int(step_row), int(philox_seed) & (2 ** 64 - 1), int(sample_offset), self.xt.data_ptr(),
-            None if self.stem_onehot_on_load else self.xin.ptr, self.Cs, self.out_probs.data_ptr(), self.out_onehot.data_ptr(),
+            int(step_row), *self._step_state_args(philox_seed, sample_offset), self.out_probs.data_ptr(), self.out_onehot.data_ptr(),
             self._stream()), "evidence_step")
         self._evidence_keepalive = evidence
 

@@ -12,6 +12,7 @@ Inference only: there is no autograd through the HIP kernels.
 """
 from __future__ import annotations
 
+import dataclasses
 import logging
 import math
 from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple, Union, cast
@@ -106,6 +107,27 @@ def pass_key(key: int, p: int) -> int:
     z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & 0xFFFFFFFFFFFFFFFF
     z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & 0xFFFFFFFFFFFFFFFF
     return z ^ (z >> 31)
+
+
+@dataclasses.dataclass(frozen=True)
+class Guidance:
+    """What guides one sampling call, as DenoisingModel._check_guidance returns it: `known` uint8 [N,H*W] (_check_known_labels), `jumps`
+    (jump_length, resamples) (_check_resample), `evidence` fp32 [N,H*W,K] (_check_evidence); None each where the call has none."""
+    known: Optional[Tensor] = None
+    jumps: Optional[Tuple[int, int]] = None
+    evidence: Optional[Tensor] = None
+
+    def __bool__(self) -> bool:
+        """The walk has something to do between the network's steps (jumps need known labels)."""
+        return self.known is not None or self.evidence is not None
+
+    def walk(self, S: int) -> List[Tuple[int, int, Optional[int]]]:
+        """The (row, pass, renoise_from) entries of a walk of S table rows: resample_walk's; [(s, 0, None) ...] without jumps."""
+        return resample_walk(S, *(self.jumps or (0, 1)))
+
+    def repeat_interleave(self, S: int) -> "Guidance":
+        """For a batch in which every sample is repeated S times (predict_multiple(batched=True))."""
+        return Guidance(*(v.repeat_interleave(S, dim=0) if isinstance(v, Tensor) else v for v in (self.known, self.jumps, self.evidence)))
 
 
 class OneHotCategoricalBCHW:
@@ -628,10 +650,15 @@ class DenoisingModel(nn.Module):
         `known_labels`: integer [N,H,W], a class where the label is known, 255 where the pixel is free (see the class docstring).
         `resample`: (jump_length, resamples), RePaint's resampling jumps of a walk with known labels (class docstring).
         `evidence`: float [N,K,H,W], per-pixel class weights in [0,1] (class docstring)."""
-        ev = None if evidence is None else self._check_evidence(evidence, tuple(x.shape))
+        guide = self._check_guidance(known_labels, resample, evidence, None if x is None else tuple(x.shape))
+        return self._sample(x, condition, feature_condition, init_t, label_ref_logits, consume, guide)
+
+    def _check_guidance(self, known_labels, resample, evidence, shape: Optional[Tuple[int, int, int, int]]) -> Guidance:
+        """The host-side checks of a call's three guidance keywords (before anything runs), in this order; shape: the call's (N,K,H,W)."""
+        ev = None if evidence is None else self._check_evidence(evidence, shape)
         jumps = self._check_resample(resample, known_labels)
-        known = None if known_labels is None else self._check_known_labels(known_labels, (x.shape[0], x.shape[2], x.shape[3]), x.shape[1])
-        return self._sample(x, condition, feature_condition, init_t, label_ref_logits, consume, known, jumps, ev)
+        known = None if known_labels is None else self._check_known_labels(known_labels, (shape[0], shape[2], shape[3]), shape[1])
+        return Guidance(known, jumps, ev)
 
     def _check_evidence(self, evidence: Tensor, shape: Optional[Tuple[int, int, int, int]], sampling: bool = True) -> Tensor:
         """The one host-side check of a call's `evidence` (before anything runs): the map as contiguous fp32 [N,H*W,K] on the model's
@@ -699,12 +726,10 @@ class DenoisingModel(nn.Module):
         return host.to(torch.uint8).reshape(shape[0], shape[1] * shape[2]).contiguous().to(next(self.unet.parameters()).device)
 
     def _sample(self, x: Optional[Tensor], condition: Tensor, feature_condition: Tensor, init_t: Optional[int],
-                label_ref_logits: Optional[Tensor], consume, known: Optional[Tensor], jumps: Optional[Tuple[int, int]] = None,
-                evidence: Optional[Tensor] = None) -> dict:
-        """One sampling call; `known`: what _check_known_labels returned, or None; `jumps`: what _check_resample returned; `evidence`:
-        what _check_evidence returned, or None."""
+                label_ref_logits: Optional[Tensor], consume, guide: Guidance) -> dict:
+        """One sampling call; `guide`: what _check_guidance returned."""
         out = self._with_range_fallback(lambda: self._forward_denoising(x, condition, feature_condition, init_t, label_ref_logits,
-                                                                        consume, known_labels=known, resample=jumps, evidence=evidence))
+                                                                        consume, guide))
         if self.philox_advance:
             self.philox_call += 1           # the next call draws from a fresh stream (a range-error re-run above replayed this one)
         return out
@@ -761,9 +786,7 @@ class DenoisingModel(nn.Module):
         if x is not None and tuple(x.shape) != (S, B, K, H, W):
             raise ValueError(f"x: expected one-hot x_T of shape {(S, B, K, H, W)} = [S,B,K,H,W], got {tuple(x.shape)}")
         init_t = None if t is None else int(t.item() if isinstance(t, Tensor) else t)
-        ev = None if evidence is None else self._check_evidence(evidence, (B, K, H, W))
-        jumps = self._check_resample(resample, known_labels)
-        known = None if known_labels is None else self._check_known_labels(known_labels, (B, H, W), K)
+        guide = self._check_guidance(known_labels, resample, evidence, (B, K, H, W))
         dev = next(self.unet.parameters()).device
         lib = hip.load()
         majority = voting == "majority"
@@ -793,7 +816,7 @@ class DenoisingModel(nn.Module):
                                                        ptr(counts, lo * HW * K), ptr(ent_sum, lo * HW), stream()), "vote_accumulate")
 
                 for i in range(S):
-                    self._sample(x[i] if x is not None else draw(B), condition, feature_condition, init_t, None, consume, known, jumps, ev)
+                    self._sample(x[i] if x is not None else draw(B), condition, feature_condition, init_t, None, consume, guide)
             else:
                 xr = x.transpose(0, 1).reshape(B * S, K, H, W) if x is not None else draw(B * S)
                 cond = condition.repeat_interleave(S, dim=0)
@@ -804,8 +827,7 @@ class DenoisingModel(nn.Module):
                 def consume(eng, lo: int, hi: int) -> None:
                     buf[lo:hi].copy_(eng.xt if majority else eng.out_probs.reshape(hi - lo, HW, K))
 
-                self._sample(xr, cond, fc, init_t, None, consume, None if known is None else known.repeat_interleave(S, dim=0), jumps,
-                             None if ev is None else ev.repeat_interleave(S, dim=0))
+                self._sample(xr, cond, fc, init_t, None, consume, guide.repeat_interleave(S))
                 if majority:
                     vote8 = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
                     mean = torch.empty((B, H, W, K), dtype=torch.float32, device=dev) if "mean" in maps else None
@@ -862,12 +884,10 @@ class DenoisingModel(nn.Module):
         return {"diffusion_out": out, "logits": logits}
 
     def _forward_denoising(self, x: Optional[Tensor], condition: Tensor, feature_condition: Tensor,
-                           init_t: Optional[int] = None, label_ref_logits: Optional[Tensor] = None, consume=None, *,
-                           known_labels: Optional[Tensor] = None, resample: Optional[Tuple[int, int]] = None,
-                           evidence: Optional[Tensor] = None) -> dict:
-        """`known_labels`: None, or the checked map (_check_known_labels: uint8 [N,H*W] on the model's device); `resample`: None, or the
-        checked pair (_check_resample); `evidence`: None, or the checked map (_check_evidence: fp32 [N,H*W,K] on the model's device)."""
-        known = known_labels
+                           init_t: Optional[int] = None, label_ref_logits: Optional[Tensor] = None, consume=None,
+                           guide: Guidance = Guidance()) -> dict:
+        """`guide`: the call's checked guidance (_check_guidance), on the model's device."""
+        known, evidence = guide.known, guide.evidence
         if label_ref_logits is not None:
             # the reference's guidance branch reads attributes that do not exist (guidance_scale_weights,
             # diffusion_denoising.py:172-174): it raises AttributeError there too.
@@ -886,26 +906,18 @@ class DenoisingModel(nn.Module):
         if self.rng not in ("philox", "torch_cpu"):
             raise ValueError(f"unknown rng mode {self.rng!r}")
         host_rng = self.rng == "torch_cpu"
-        if known is not None and host_rng:
-            raise ValueError("known_labels: not available with rng = 'torch_cpu'")
-        if evidence is not None and host_rng:
-            raise ValueError("evidence: not available with rng = 'torch_cpu'")
         # evidence: the network pass of every row stops at x0 (out_probs; x_t untouched), the row's real step follows in evidence_step
         table = coeffs if evidence is None else [(a_, c_, hip.STEP_SOFTMAX_ONLY) for a_, c_, m_ in coeffs]
         # known labels: cumalpha of the state each row produces; the last row returns the labels themselves (class docstring)
         clamp_c = [1.0 if j == S - 1 else c_ for j, (a_, c_, m_) in enumerate(coeffs)]
         key = self._philox_key()
-        # resampling jumps: the rows in the order the walk visits them, and per entry the renoising pair (p_stay, p_move) of the jump
-        # that precedes it.  From level L to level M = L - j (the state before row M): r = cumalpha_{t_M} / cumalpha_{t_L} in float64,
-        # each probability rounded to fp32 once.  A walk without a jump point is the plain conditioned walk: nothing below changes.
-        walk = None
-        if resample is not None:
-            walk = resample_walk(S, *resample)
-            if len(walk) == S:
-                walk = None
+        # The rows in the order the walk visits them — (row, 0, None) for row 0 .. S - 1 unless resampling jumps are taken — and per entry
+        # the renoising pair (p_stay, p_move) of the jump that precedes it.  From level L to level M = L - j (the state before row M):
+        # r = cumalpha_{t_M} / cumalpha_{t_L} in float64, each probability rounded to fp32 once.
+        walk = guide.walk(S)
         renoise_p: Dict[int, Tuple[float, float]] = {}
-        cum = self.diffusion.cumalphas.detach().cpu().double() if walk is not None else None         # (cumalpha_t = cum[t - 1])
-        for e, (row, _, src) in enumerate(walk or []):
+        cum = self.diffusion.cumalphas.detach().cpu().double() if len(walk) > S else None           # (cumalpha_t = cum[t - 1])
+        for e, (row, _, src) in enumerate(walk):
             if src is not None:
                 r_ = float(cum[t_values[row] - 1]) / float(cum[t_values[src] - 1])
                 p_move = (1.0 - r_) / K
@@ -931,38 +943,34 @@ class DenoisingModel(nn.Module):
                 parts_.append((eng, lo, hi))
             return parts_
 
-        def run_steps(parts_, s0_: int, s1_: int, noises_, noise_row0_: int, graph_: bool):
-            if walk is not None:                       # s0_, s1_ count the walk's entries, not table rows
-                for e in range(s0_, s1_):
-                    row, p, src = walk[e]
-                    kp = pass_key(key, p)
-                    for j, (eng, lo, hi) in enumerate(parts_):
-                        if src is not None:            # back up the chain to the state before `row`, on the engine's stream
-                            eng.renoise(*renoise_p[e], row, philox_seed=kp, sample_offset=self.sample_offset + lo)
-                        eng.run(1, first_row=row, philox_seed=kp, sample_offset=self.sample_offset + lo, use_graph=graph_)
-                        if evidence is not None:
-                            eng.evidence_step(evidence[lo:hi], *coeffs[row], row, philox_seed=kp, sample_offset=self.sample_offset + lo)
-                        eng.clamp_known_labels(known[lo:hi], clamp_c[row], coeffs[row][2], row, philox_seed=kp,
-                                               sample_offset=self.sample_offset + lo)
-            elif len(parts_) == 1 and known is None and evidence is None:
+        def run_row(eng, lo: int, hi: int, row: int, kp: int, renoise, noise, noise_row0_: int, graph_: bool):
+            """One walk entry of one sub-batch, all on the engine's stream: the renoise back up the chain to the state before `row` (if a
+            jump precedes the entry), the network's step, the evidence step behind a network pass that stopped at x0, the clamp (the
+            next step reads the clamped state).  kp: the Philox key of this pass of the row."""
+            off = self.sample_offset + lo
+            if renoise is not None:
+                eng.renoise(*renoise, row, philox_seed=kp, sample_offset=off)
+            eng.run(1, first_row=row, noise=noise, noise_row0=noise_row0_, philox_seed=kp, sample_offset=off, use_graph=graph_)
+            if evidence is not None:
+                eng.evidence_step(evidence[lo:hi], *coeffs[row], row, philox_seed=kp, sample_offset=off)
+            if known is not None:
+                eng.clamp_known_labels(known[lo:hi], clamp_c[row], coeffs[row][2], row, philox_seed=kp, sample_offset=off)
+
+        def run_steps(parts_, s0_: int, s1_: int, noises_, noise_row0_: int, graph_: bool):       # s0_, s1_ count the walk's entries
+            if len(parts_) == 1 and not guide:
                 parts_[0][0].run(s1_ - s0_, first_row=s0_, noise=noises_[0], noise_row0=noise_row0_, philox_seed=key,
                                  sample_offset=self.sample_offset, use_graph=graph_)
-            else:
-                for s in range(s0_, s1_):              # one step of every sub-batch in turn: the streams advance side by side
-                    for j, (eng, lo, hi) in enumerate(parts_):
-                        eng.run(1, first_row=s, noise=noises_[j], noise_row0=noise_row0_, philox_seed=key,
-                                sample_offset=self.sample_offset + lo, use_graph=graph_)
-                        if evidence is not None:       # on the engine's stream, behind the network pass that stopped at x0
-                            eng.evidence_step(evidence[lo:hi], *coeffs[s], s, philox_seed=key, sample_offset=self.sample_offset + lo)
-                        if known is not None:          # on the engine's stream, behind the step: the next step reads the clamped state
-                            eng.clamp_known_labels(known[lo:hi], clamp_c[s], coeffs[s][2], s, philox_seed=key,
-                                                   sample_offset=self.sample_offset + lo)
+                return
+            for e in range(s0_, s1_):                  # one entry of every sub-batch in turn: the streams advance side by side
+                row, p, _ = walk[e]
+                for j, (eng, lo, hi) in enumerate(parts_):
+                    run_row(eng, lo, hi, row, pass_key(key, p), renoise_p.get(e), noises_[j], noise_row0_, graph_)
 
         nsub = int(self.substreams) if int(self.substreams) > 0 else auto_substreams(N, H, W)
         nsub = max(1, min(nsub, N))
         use_graph = bool(self.use_graph)
         if (int(self.substreams) <= 0 and self.calibrate_mode and not host_rng and self._range_probe is None and nsub > 1
-                and S >= self.CALIBRATION_MIN_STEPS and known is None and evidence is None):
+                and S >= self.CALIBRATION_MIN_STEPS and not guide):
             nsub, use_graph = self._calibrate_mode(x, condition, feature_condition, prepare, run_steps, nsub, use_graph, S)
         self.last_mode = (nsub, use_graph)
         parts = prepare(nsub)
@@ -974,9 +982,9 @@ class DenoisingModel(nn.Module):
             blk = max(1, HOST_NOISE_BLOCK_BYTES // max(per_step, 1))
             blocks = [(s0, min(s0 + blk, S)) for s0 in range(0, S, blk)]
         else:
-            blocks = [(0, S if walk is None else len(walk))]
+            blocks = [(0, len(walk))]
         if self._range_probe is not None:      # diagnosing fp32 re-run: one step per block, every step's activations are probed
-            blocks = [(s, s + 1) for s in range(S if walk is None else len(walk))]
+            blocks = [(s, s + 1) for s in range(len(walk))]
         for s0, s1 in blocks:
             noises: List[Optional[Tensor]] = [None] * nsub
             if host_rng:

@@ -4,33 +4,18 @@ normalise_probs in cascade order, sample_index on philox_exponential's noise); i
 the kernel is held bit for bit against it, and the sampler is checked launch by launch on the device's own inputs, free-running
 against the oracle's loop, for what must not change without the keyword, and for independence of the execution shape."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 from oracle import ccdm_oracle as O
-from ccdm_stochastic_segmentation_amd import build_model, hip, make_synthetic_state_dict
+from ccdm_stochastic_segmentation_amd import hip
+from tests.sampler_util import (DEV, FREE, H, SEED, SMALL_CFG, T_SMALL, T_STRIDED, W, assert_symbol_declared_bound_and_built, load_lib,
+                                make_sampler, onehot_np, sample_sharded_keywords, settings, small_model)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FREE = 255
 SYMBOL = "ccdm_evidence_step"
-# the 32x32 two-level network of test_known_labels, T = 6: t = 10004 walks it strided, t = 6, 4, 3, 1
-SMALL_BP = dict(base_channels=32, channel_mult=(1, 2), attention_resolutions=[2], num_heads=1, num_head_channels=32, softmax_output=True)
-SMALL_CFG = dict(num_heads=1, num_head_channels=32)
-T_SMALL, H, W = 6, 32, 32
-T_STRIDED = torch.as_tensor(10004)
-T_VALUES = [6, 4, 3, 1]
-
-
-def small_model(K, vote="majority", seed=3, **bp):
-    m = build_model(T_SMALL, "cosine", {"s": 0.008}, [(1, H, W), (K, H, W)], (1, H, W), "unet_openai", dict(SMALL_BP, **bp), "datasets.lidc",
-                    vote, None)
-    sd = {k: torch.from_numpy(v) for k, v in make_synthetic_state_dict(m.unet.spec, seed).items()}
-    m.unet.load_state_dict(sd, strict=True)
-    return m, sd
+T_VALUES = [6, 4, 3, 1]          # t = 10004 walks the small model strided
 
 
 def evidence_restatement(x0, ev, xt, a, c, mode, step_row, seed, sample0):
@@ -65,10 +50,6 @@ def random_inputs(rng, N, HW, K):
     return x0, ev, xt
 
 
-def onehot_np(idx, K):
-    return np.arange(K)[None, None, :] == idx[..., None]
-
-
 def sampler_evidence(rng, N, K, onehot_share=0.0):
     """[N,K,H,W] fp32: a soft map (weights in [0.05,1]), and on a share of the pixels a one-hot on a random class"""
     ev = rng.uniform(0.05, 1.0, (N, K, H, W)).astype(np.float32)
@@ -79,29 +60,11 @@ def sampler_evidence(rng, N, K, onehot_share=0.0):
 
 
 # ------------------------------------------------------------------------------------------------ CPU
-CTYPE_OF = {"int": C.c_int, "float": C.c_float, "uint64_t": C.c_uint64, "uint32_t": C.c_uint32}
-
-
 def test_evidence_symbol_declared_bound_and_built():
     """hip.py binds the symbol with argtypes that match the header's declaration (17 arguments), the source is in the build list, the
     library cross-built from it exports it under the unchanged ABI number, and every bad argument is refused before anything is launched
     (host pointers: a launch would fault) with the expected word in the error string."""
-    hdr = open(os.path.join(ROOT, "include", "ccdm_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    m = re.search(r"\bint\s+" + SYMBOL + r"\s*\(([^;]*)\)\s*;", hdr)
-    assert m, "not declared in include/ccdm_hip.h"
-    want = []
-    for arg in m.group(1).split(","):
-        words = arg.replace("*", " * ").split()
-        want.append(C.c_void_p if "*" in words else CTYPE_OF[[w for w in words if w != "const"][0]])
-    res, args = hip.SIGNATURES[SYMBOL]
-    assert res is C.c_int and args == want and len(args) == 17
-    assert "ccdm_evidence.hip" in hip.SOURCES and os.path.exists(os.path.join(hip.CSRC, "ccdm_evidence.hip"))
-    assert hip.ABI_VERSION == 11 and hip.MAX_CLASSES == 255
-    import __graft_entry__ as g
-    g.build()
-    lib = hip.load()
-    assert hasattr(lib, SYMBOL) and lib.ccdm_version() == 11
+    lib = assert_symbol_declared_bound_and_built(SYMBOL, 17, "ccdm_evidence.hip")
     buf = np.zeros(256, dtype=np.float32)
     p = buf.ctypes.data
     good = dict(x0=p, ev=p, N=1, HW=8, K=2, a=0.5, c=0.5, mode=hip.STEP_SAMPLE, step_row=0, seed=0, off=0, xt=p, xin=None, stride=4,
@@ -211,39 +174,22 @@ def test_the_restatement_is_bayes_rule(K):
 
 def test_sample_sharded_hands_the_callers_evidence_through():
     """distributed.sample_sharded slices x and the conditions, not evidence: the caller passes its shard's slice."""
-    from ccdm_stochastic_segmentation_amd.distributed import sample_sharded
-    seen = {}
-
-    class Stub:
-        rng, sample_offset, noise_slice = "philox", 0, None
-
-        def __call__(self, x, cond, fc, **kw):
-            seen.update(kw)
-            return {"diffusion_out": x}
-    x = torch.zeros(3, 2, 4, 4)
     ev = torch.ones(3, 2, 4, 4)
     kl = torch.full((3, 4, 4), FREE)
-    sample_sharded(Stub(), x, torch.zeros(3, 1, 4, 4), evidence=ev)
+    seen = sample_sharded_keywords(evidence=ev)
     assert seen["evidence"] is ev and "known_labels" not in seen
-    seen.clear()
-    sample_sharded(Stub(), x, torch.zeros(3, 1, 4, 4), known_labels=kl, resample=(2, 3), evidence=ev)
+    seen = sample_sharded_keywords(known_labels=kl, resample=(2, 3), evidence=ev)
     assert seen["evidence"] is ev and seen["known_labels"] is kl and seen["resample"] == (2, 3)
-    seen.clear()
-    sample_sharded(Stub(), x, torch.zeros(3, 1, 4, 4))
-    assert "evidence" not in seen
+    assert "evidence" not in sample_sharded_keywords()
 
 
 # ------------------------------------------------------------------------------------------------ GPU: the kernel alone
-DEV = torch.device("cuda:0")
-SEED = 0xFEEDFACE12345678
 SHAPES = [(3, 63, 2), (2, 300, 5), (2, 64, 20), (1, 64, 255)]       # a partial block; a block boundary inside a sample; staged; the largest K
 
 
 @pytest.fixture(scope="module")
 def lib():
-    if not torch.cuda.is_available():
-        pytest.fail("-m gpu tests need a GPU")
-    return hip.load()
+    return load_lib()
 
 
 def coefficients(t, T=250):
@@ -384,30 +330,12 @@ def test_evidence_kernel_refuses_bad_arguments(lib):
 def sampler(request):
     """K = 2: stem conv and fused head-and-posterior launch (x_t travels as the uint8 index only); K = 5: the general epilogue, and the
     stem reads its one-hot from xin, which the evidence step writes."""
-    if not torch.cuda.is_available():
-        pytest.fail("-m gpu tests need a GPU")
-    K = request.param
-    model, sd = small_model(K)
-    model = model.to(DEV).eval()
-    model.rng, model.philox_seed, model.philox_advance = "philox", 99, False          # every call replays call 0's stream
-    rng = np.random.default_rng(40 + K)
-    N = 4
-    image = torch.from_numpy(rng.uniform(-1, 1, (N, 1, H, W)).astype(np.float32))
-    x = O.one_hot_bchw(torch.from_numpy(rng.integers(0, K, (N, H, W))), K)
-    labels = torch.from_numpy(rng.integers(0, K, (N, H, W)))
-    known = torch.where(torch.from_numpy(rng.random((N, H, W)) < 0.3), labels, torch.full_like(labels, FREE))
-    ev, _, _ = sampler_evidence(np.random.default_rng(EVIDENCE_SEED + K), N, K)
-    eng = model._engine(x.to(DEV), image.to(DEV), None)
-    assert eng.head_fused == (K == 2) and eng.stem_onehot_on_load == (K == 2)
-    return dict(model=model, sd=sd, K=K, N=N, image=image.to(DEV), x=x.to(DEV), labels=labels, known=known, image_cpu=image, x_cpu=x, ev=ev)
+    s = make_sampler(request.param)
+    s["ev"], _, _ = sampler_evidence(np.random.default_rng(EVIDENCE_SEED + s["K"]), s["N"], s["K"])
+    return s
 
 
 EVIDENCE_SEED = 70
-
-
-def settings(model, **kw):
-    for k, v in kw.items():
-        setattr(model, k, v)
 
 
 class Spy:

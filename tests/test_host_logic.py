@@ -619,3 +619,24 @@ def test_host_noise_is_drawn_in_bounded_blocks(monkeypatch):
     torch.manual_seed(5)
     ref = torch.stack([torch.empty(3 * 64, 2).exponential_(1).reshape(3, 128) for _ in range(4)])
     assert torch.equal(whole[:4], ref)
+
+
+def test_a_walk_without_jumps_is_the_plain_walk():
+    """The sampling loop walks Guidance.walk(S) and draws pass p of a row under pass_key(key, p): without jumps (none asked for, a pair
+    that asks for none, a jump length with no jump point) the entries are (s, 0, None) in row order and pass 0 keeps the call's key,
+    so the one loop issues for a plain walk what the plain loop issued.  Also the bundle's truth value and its batched form."""
+    from ccdm_stochastic_segmentation_amd.models import Guidance
+    known, ev = torch.zeros(2, 16, dtype=torch.uint8), torch.ones(2, 16, 3)
+    for S in (1, 4, 6, 250):
+        plain = [(s, 0, None) for s in range(S)]
+        for g in (Guidance(), Guidance(known=known), Guidance(evidence=ev), Guidance(known, None, ev), Guidance(known, (S, 2)), Guidance(known, (3, 2))):
+            if g.jumps != (3, 2) or S <= 6:
+                assert g.walk(S) == plain, (S, g.jumps)
+    jumped = Guidance(known, (2, 2)).walk(6)
+    assert jumped == models.resample_walk(6, 2, 2) and [e[0] for e in jumped] == [0, 1, 2, 3, 2, 3, 4, 5]
+    for key in (0, 99, 0xFEEDFACE12345678, 2 ** 64 - 1):
+        assert models.pass_key(key, 0) == key
+    assert not Guidance() and Guidance(known=known) and Guidance(evidence=ev)
+    r = Guidance(known, (2, 2), ev).repeat_interleave(3)
+    assert r.jumps == (2, 2) and torch.equal(r.known, known.repeat_interleave(3, dim=0)) and torch.equal(r.evidence, ev.repeat_interleave(3, dim=0))
+    assert Guidance().repeat_interleave(3) == Guidance()

@@ -2,87 +2,24 @@
 (include/ccdm_hip.h).  The kernel is checked for equality against a numpy restatement built on the oracle's Philox4x32-10; the
 sampler for the constraint itself, for what must not change without the keyword, for independence of the execution shape, and step
 by step against the conditioned loop restated from the oracle's public step functions."""
-import ctypes as C
-import os
-import re
-
 import numpy as np
 import pytest
 import torch
 
 from oracle import ccdm_oracle as O
-from ccdm_stochastic_segmentation_amd import build_model, hip, make_synthetic_state_dict
+from ccdm_stochastic_segmentation_amd import hip
+from tests.sampler_util import (DEV, FREE, H, SEED, SMALL_CFG, T_SMALL, T_STRIDED, W, assert_symbol_declared_bound_and_built, clamp_restatement,
+                                load_lib, make_sampler, onehot_np, probabilities, sample_sharded_keywords, settings, small_model)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FREE = 255
 SYMBOL = "ccdm_known_labels_step"
-# the 32x32 two-level network of the sub-batch parity test (test_hip_parity.test_substreams_do_not_change_the_samples), T = 6:
-# t = 10004 walks it strided, t = 6, 4, 3, 1
-SMALL_BP = dict(base_channels=32, channel_mult=(1, 2), attention_resolutions=[2], num_heads=1, num_head_channels=32, softmax_output=True)
-SMALL_CFG = dict(num_heads=1, num_head_channels=32)
-T_SMALL, H, W = 6, 32, 32
-T_STRIDED = torch.as_tensor(10004)
 T_ONE_STEP = torch.as_tensor(10001)          # one step at t = T: the walk stops above t = 1 and returns the kept index
 
 
-def small_model(K, vote="majority", seed=3):
-    m = build_model(T_SMALL, "cosine", {"s": 0.008}, [(1, H, W), (K, H, W)], (1, H, W), "unet_openai", SMALL_BP, "datasets.lidc", vote, None)
-    sd = {k: torch.from_numpy(v) for k, v in make_synthetic_state_dict(m.unet.spec, seed).items()}
-    m.unet.load_state_dict(sd, strict=True)
-    return m, sd
-
-
-def probabilities(c, K):
-    """(p_hit, p_miss) as the host forms them: in float64, each rounded to fp32 once"""
-    p_miss = (1.0 - float(c)) / K
-    return np.float32(float(c) + p_miss), np.float32(p_miss)
-
-
-def clamp_restatement(known, xt, K, c, step_row, seed, sample0):
-    """What ccdm_known_labels_step leaves in xt in mode STEP_SAMPLE, following oracle.philox_exponential: the same bits -> uniform ->
-    -log map in fp32, counter word 3 = 0x80000000 | k // 4, the division p_k / E_k in fp32, the first maximum wins.
-    known, xt: [N,HW] integer arrays."""
-    N, HW = known.shape
-    p_hit, p_miss = probabilities(c, K)
-    pix = np.arange(HW, dtype=np.uint32)[None, :, None]
-    smp = (np.arange(N, dtype=np.uint32) + np.uint32(sample0))[:, None, None]
-    kq = (np.uint32(0x80000000) | (np.arange(K, dtype=np.uint32) // 4))[None, None, :]
-    ctr = np.stack(np.broadcast_arrays(pix, smp, np.uint32(step_row), kq), axis=-1).astype(np.uint32)
-    key = np.array([seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF], dtype=np.uint32)
-    blk = O.philox4x32_10(ctr, key)
-    word = np.take_along_axis(blk, np.broadcast_to((np.arange(K) % 4)[None, None, :, None], (N, HW, K, 1)).astype(np.int64), axis=-1)[..., 0]
-    u = ((word >> np.uint32(8)).astype(np.float32) + np.float32(0.5)) * np.float32(2.0 ** -24)
-    e = (-np.log(u.astype(np.float32))).astype(np.float32)
-    p = np.where(np.arange(K)[None, None, :] == known[..., None], p_hit, p_miss).astype(np.float32)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        q = (p / e).astype(np.float32)
-    q = np.where(np.isnan(q), -np.inf, q)                  # `qv > best` is false for a NaN (0 / 0): it never wins
-    return np.where(known < K, np.argmax(q, axis=-1), xt).astype(np.int64)
-
-
 # ------------------------------------------------------------------------------------------------ CPU
-CTYPE_OF = {"int": C.c_int, "float": C.c_float, "uint64_t": C.c_uint64, "uint32_t": C.c_uint32}
-
-
 def test_known_labels_symbol_declared_bound_and_built():
     """hip.py binds the symbol with argtypes that match the header's declaration, the source is in the build list, the library built
     from it (cross-compiled for gfx950 by build()) exports it, and bad arguments are refused before anything is launched."""
-    hdr = open(os.path.join(ROOT, "include", "ccdm_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    m = re.search(r"\bint\s+" + SYMBOL + r"\s*\(([^;]*)\)\s*;", hdr)
-    assert m, "not declared in include/ccdm_hip.h"
-    want = []
-    for arg in m.group(1).split(","):
-        words = arg.replace("*", " * ").split()
-        want.append(C.c_void_p if "*" in words else CTYPE_OF[[w for w in words if w != "const"][0]])
-    res, args = hip.SIGNATURES[SYMBOL]
-    assert res is C.c_int and args == want and len(args) == 16
-    assert "ccdm_known.hip" in hip.SOURCES and os.path.exists(os.path.join(hip.CSRC, "ccdm_known.hip"))
-    assert hip.ABI_VERSION == 11 and hip.MAX_CLASSES == 255
-    import __graft_entry__ as g
-    g.build()
-    lib = hip.load()
-    assert hasattr(lib, SYMBOL) and lib.ccdm_version() == 11
+    lib = assert_symbol_declared_bound_and_built(SYMBOL, 16, "ccdm_known.hip")
     buf = np.zeros(64, dtype=np.uint8)           # (host memory: the refused calls below never reach a launch)
     p = buf.ctypes.data
     good = dict(known=p, N=1, HW=8, K=2, p_hit=1.0, p_miss=0.0, mode=hip.STEP_SAMPLE, step_row=0, seed=0, off=0, xt=p, xin=None, stride=4,
@@ -130,34 +67,15 @@ def test_known_labels_argument_validation():
 
 def test_sample_sharded_hands_the_callers_slice_through():
     """distributed.sample_sharded slices x and the conditions, not known_labels: the caller passes its shard's slice."""
-    from ccdm_stochastic_segmentation_amd.distributed import sample_sharded
-    seen = {}
-
-    class Stub:
-        rng, sample_offset, noise_slice = "philox", 0, None
-
-        def __call__(self, x, cond, fc, **kw):
-            seen.update(kw)
-            return {"diffusion_out": x}
-    x = torch.zeros(3, 2, 4, 4)
     kl = torch.full((3, 4, 4), FREE)
-    sample_sharded(Stub(), x, torch.zeros(3, 1, 4, 4), known_labels=kl)
-    assert seen["known_labels"] is kl
-    seen.clear()
-    sample_sharded(Stub(), x, torch.zeros(3, 1, 4, 4))
-    assert "known_labels" not in seen
+    assert sample_sharded_keywords(known_labels=kl)["known_labels"] is kl
+    assert "known_labels" not in sample_sharded_keywords()
 
 
 # ------------------------------------------------------------------------------------------------ GPU: the kernel alone
-DEV = torch.device("cuda:0")
-SEED = 0xFEEDFACE12345678
-
-
 @pytest.fixture(scope="module")
 def lib():
-    if not torch.cuda.is_available():
-        pytest.fail("-m gpu tests need a GPU")
-    return hip.load()
+    return load_lib()
 
 
 def run_kernel(lib, known, xt, K, c, mode, *, step_row=0, seed=SEED, sample_offset=0, xin=None, probs=None, onehot=None):
@@ -183,10 +101,6 @@ def masks(rng, N, HW, K):
         stray = rng.random((N, HW)) < 0.1
         half = np.where(stray, rng.integers(K, FREE, (N, HW)), half)
     return {"free": np.full((N, HW), FREE), "all": labels, "half": half}
-
-
-def onehot_np(idx, K):
-    return (np.arange(K)[None, None, :] == idx[..., None])
 
 
 @pytest.mark.gpu
@@ -296,26 +210,7 @@ def test_clamp_kernel_refuses_bad_arguments(lib):
 def sampler(request):
     """K = 2: stem conv and fused head-and-posterior launch (x_t travels as the uint8 index only); K = 5: the general epilogue, which
     writes the one-hot into the stem's input."""
-    if not torch.cuda.is_available():
-        pytest.fail("-m gpu tests need a GPU")
-    K = request.param
-    model, sd = small_model(K)
-    model = model.to(DEV).eval()
-    model.rng, model.philox_seed, model.philox_advance = "philox", 99, False          # every call replays call 0's stream
-    rng = np.random.default_rng(40 + K)
-    N = 4
-    image = torch.from_numpy(rng.uniform(-1, 1, (N, 1, H, W)).astype(np.float32))
-    x = O.one_hot_bchw(torch.from_numpy(rng.integers(0, K, (N, H, W))), K)
-    labels = torch.from_numpy(rng.integers(0, K, (N, H, W)))
-    known = torch.where(torch.from_numpy(rng.random((N, H, W)) < 0.3), labels, torch.full_like(labels, FREE))
-    eng = model._engine(x.to(DEV), image.to(DEV), None)
-    assert eng.head_fused == (K == 2) and eng.stem_onehot_on_load == (K == 2)
-    return dict(model=model, sd=sd, K=K, N=N, image=image.to(DEV), x=x.to(DEV), labels=labels, known=known, image_cpu=image, x_cpu=x)
-
-
-def settings(model, **kw):
-    for k, v in kw.items():
-        setattr(model, k, v)
+    return make_sampler(request.param)
 
 
 @pytest.mark.gpu
