@@ -616,6 +616,22 @@ class SamplerEngine:
             self._stream()), "evidence_step")
         self._evidence_keepalive = evidence
 
+    def shaped_step(self, evidence: Optional[torch.Tensor], inv_temperature: float, top_r: float, alpha_t: float, cumalpha_tm1: float,
+                    mode: int, step_row: int, *, philox_seed: int = 0, sample_offset: int = 0) -> None:
+        """The reverse step on a tempered and truncated x0 (ccdm_shaped_step, asynchronous on the engine's stream), behind a `run` of a
+        table row whose mode is STEP_SOFTMAX_ONLY, as `evidence_step`: x0 (times the evidence's weights, where there are any) is
+        tempered with exponent inv_temperature, cut to the smallest set of classes whose mass reaches top_r (include/ccdm_hip.h has the
+        definition), and the step of (alpha_t, cumalpha_tm1, mode) — the real columns of row `step_row` — follows with the Philox
+        counters the unguided step of that row uses.  evidence: None, or fp32 [N,H*W,K] on the engine's device, weights in [0,1]."""
+        assert evidence is None or (evidence.dtype == torch.float32 and evidence.is_cuda and evidence.is_contiguous()
+                                    and tuple(evidence.shape) == (self.N, self.H * self.W, self.K))
+        hip.check(self.lib.ccdm_shaped_step(
+            self.out_probs.data_ptr(), None if evidence is None else evidence.data_ptr(), self.N, self.H * self.W, self.K,
+            float(inv_temperature), float(top_r), float(alpha_t), float(cumalpha_tm1), int(mode), int(step_row),
+            *self._step_state_args(philox_seed, sample_offset), self.out_probs.data_ptr(), self.out_onehot.data_ptr(), self._stream()),
+            "shaped_step")
+        self._evidence_keepalive = evidence
+
     def ce_logits(self) -> Optional[torch.Tensor]:
         """[N,K-1,H,W] logits of the optional ce head after the last run (BCHW view of channels-last memory), else None."""
         if self.head_ce is None:

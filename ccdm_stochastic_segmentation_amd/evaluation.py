@@ -165,6 +165,24 @@ def apply_sampler_options(model, params: dict) -> None:
     model._fine_slices(1)                                         # validates the value
 
 
+SAMPLING_KEYS = ("temperature", "truncation")
+
+
+def sampling_keywords(params: dict) -> dict:
+    """The keywords the params key `sampling: {temperature: ..., truncation: ...}` (each optional) adds to every sampling call and to
+    predict_multiple (DenoisingModel's keywords of those names, which check the values); {} without the key.  An unknown key under
+    `sampling:` raises."""
+    section = params.get("sampling")
+    if section is None:
+        return {}
+    if not isinstance(section, dict):
+        raise ValueError(f"sampling: expected a mapping with keys from {list(SAMPLING_KEYS)}, got {section!r}")
+    unknown = [k for k in section if k not in SAMPLING_KEYS]
+    if unknown:
+        raise ValueError(f"sampling: unknown key(s) {unknown} (expected keys from {list(SAMPLING_KEYS)})")
+    return {k: section[k] for k in SAMPLING_KEYS if section.get(k) is not None}
+
+
 def _as_list(v) -> List[int]:
     return [int(x) for x in v] if isinstance(v, (list, tuple)) else [int(v)]
 
@@ -209,6 +227,8 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
     shard of the B_img*S flattened batch (distributed.sample_sharded: no collective inside the T loop, one gather of the
     predictions per batch); the metrics are then computed identically on every rank.
     `model`: a ready DenoisingModel-like callable (tests inject fixed predictions); default: built from `params`.
+    The params key `sampling: {temperature: ..., truncation: ...}` (sampling_keywords; each optional) is handed to every sampling call
+    and echoed as "sampling" in the result; without the key nothing changes.
 
     Build-owned keys of the `evaluation` section (absent: the returned dict and everything else is as without them):
          soft_labels: yes   the result gains "soft_labels": one dict per entry of `evaluations` with the scores of the first s
@@ -261,6 +281,7 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
     nonzero_total, n_img = 0, 0
     majority = getattr(model, "step_T_sample", None) in (None, "majority")
     section = params.get("evaluation") or {}
+    sampling = sampling_keywords(params)
     soft = [([], []) for _ in evaluations] if section.get("soft_labels", False) else None       # per entry: (joint, moments) of every batch
     surf = [[] for _ in evaluations] if section.get("surface_distances", False) else None        # per entry: the stats of every batch
     if surf is not None:
@@ -293,9 +314,9 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
         t = None if init_t is None else torch.as_tensor(init_t)
         if world > 1:
             # one-hot ("majority") predictions travel as uint8 class maps, probabilities as fp32
-            prediction = D.sample_sharded(model, x, image, t=t, gather="index" if majority else True)
+            prediction = D.sample_sharded(model, x, image, t=t, gather="index" if majority else True, **sampling)
         else:
-            prediction = model(x, image, **({} if t is None else {"t": t}))["diffusion_out"]
+            prediction = model(x, image, **({} if t is None else {"t": t}), **sampling)["diffusion_out"]
         prediction = prediction.reshape(labels.shape[0], -1, *labels.shape[2:])
         lab_idx = labels.to(device).argmax(dim=2)
         pred_idx = prediction.argmax(dim=2)
@@ -333,6 +354,8 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
     res = {"evaluations": evaluations, "GED": (geds / n_img).tolist(), "diversity_samples": (div_s / n_img).tolist(),
            "diversity_experts": float(div_e[0] / n_img), "HM_IoU": (hm / n_img).tolist(), "IoU": iou.tolist(), "mIoU": float(iou.mean()),
            "Dice": dice.tolist(), "nonzero": nonzero_total / (n_img * 4), "images": n_img, "world_size": world}
+    if params.get("sampling") is not None:
+        res["sampling"] = dict(sampling)
     for i, s in enumerate(evaluations):
         LOGGER.info("GED (%d): %.4g  diversity samples: %.4g  HM IoU: %.4g", s, res["GED"][i], res["diversity_samples"][i], res["HM_IoU"][i])
     if soft is not None:
@@ -419,10 +442,11 @@ def predict_multiple(model, image: torch.Tensor, params: dict, feature_condition
     (`predict_single`, :160-165) when `evaluations` is 1, else the mean of `evaluations` samples voted with
     `evaluation_vote_strategy` (`predict_multiple`, :176-193) — computed on the device by DenoisingModel.predict_multiple.
     "confidence" gives the reference's `prediction_onehot_total` bit for bit; "majority" (NotImplementedError in the reference)
-    gives the class frequencies.  Returns [B,K,H,W]."""
+    gives the class frequencies.  The params key `sampling:` (sampling_keywords) is handed to either call.  Returns [B,K,H,W]."""
     n, strategy = vote_settings(params)
+    sampling = sampling_keywords(params)
     if n == 1:
         K = model.diffusion.num_classes
         x = OneHotCategoricalBCHW(logits=torch.zeros((image.shape[0], K, *image.shape[2:]), device=image.device)).sample()
-        return model(x, image, feature_condition)["diffusion_out"]
-    return model.predict_multiple(image, feature_condition, num_evaluations=n, voting=strategy, maps=("mean",))["mean"]
+        return model(x, image, feature_condition, **sampling)["diffusion_out"]
+    return model.predict_multiple(image, feature_condition, num_evaluations=n, voting=strategy, maps=("mean",), **sampling)["mean"]

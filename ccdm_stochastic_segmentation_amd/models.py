@@ -112,14 +112,16 @@ def pass_key(key: int, p: int) -> int:
 @dataclasses.dataclass(frozen=True)
 class Guidance:
     """What guides one sampling call, as DenoisingModel._check_guidance returns it: `known` uint8 [N,H*W] (_check_known_labels), `jumps`
-    (jump_length, resamples) (_check_resample), `evidence` fp32 [N,H*W,K] (_check_evidence); None each where the call has none."""
+    (jump_length, resamples) (_check_resample), `evidence` fp32 [N,H*W,K] (_check_evidence), `shaping` (inv_temperature, top_r)
+    (_check_shaping); None each where the call has none."""
     known: Optional[Tensor] = None
     jumps: Optional[Tuple[int, int]] = None
     evidence: Optional[Tensor] = None
+    shaping: Optional[Tuple[float, float]] = None
 
     def __bool__(self) -> bool:
         """The walk has something to do between the network's steps (jumps need known labels)."""
-        return self.known is not None or self.evidence is not None
+        return self.known is not None or self.evidence is not None or self.shaping is not None
 
     def walk(self, S: int) -> List[Tuple[int, int, Optional[int]]]:
         """The (row, pass, renoise_from) entries of a walk of S table rows: resample_walk's; [(s, 0, None) ...] without jumps."""
@@ -127,7 +129,8 @@ class Guidance:
 
     def repeat_interleave(self, S: int) -> "Guidance":
         """For a batch in which every sample is repeated S times (predict_multiple(batched=True))."""
-        return Guidance(*(v.repeat_interleave(S, dim=0) if isinstance(v, Tensor) else v for v in (self.known, self.jumps, self.evidence)))
+        return Guidance(*(v.repeat_interleave(S, dim=0) if isinstance(v, Tensor) else v
+                          for v in (self.known, self.jumps, self.evidence, self.shaping)))
 
 
 class OneHotCategoricalBCHW:
@@ -372,7 +375,19 @@ class DenoisingModel(nn.Module):
     static execution-mode rule, results independent of `substreams`, `use_graph` and sharding (a caller that shards passes its shard's
     slice).  Per walk entry: renoise (if a jump precedes), the network, the evidence step, the clamp — `evidence` composes with
     `known_labels` and `resample`, whose rules do not change.  A pixel whose weights are all 0, a value outside [0,1], rng =
-    "torch_cpu" and a model with `softmax_output: no` (its x0 holds logits) are refused."""
+    "torch_cpu" and a model with `softmax_output: no` (its x0 holds logits) are refused.
+    `temperature`, `truncation` (keywords next to `known_labels`): the two controls of a generative sampler, applied per pixel to the
+    network's x0 before the reverse step (ccdm_shaped_step; include/ccdm_hip.h has the definition).  temperature tau in [0.05, 20]
+    raises x0, relative to the pixel's largest value, to the power 1 / tau: below 1 the samples get less diverse and individually more
+    accurate, above 1 the reverse.  truncation r in (0, 1] ("top-r", the truncation sampling of Improved VQ-Diffusion, Tang et al.
+    2022) keeps the smallest set of classes whose mass reaches r and drops the rest, so a draw never picks a class the network gives
+    1 % to; it matters most on short strided walks.  Temper first, then truncate; nothing is renormalised, because the step posterior
+    is linear in x0 up to its own normalisation.  The last row's vote sees the shaped x0 too.  A shaped call walks like one with
+    evidence (every row's network pass stops at x0, one ccdm_shaped_step launch per walk entry, which also applies the evidence where
+    the call has some: no ccdm_evidence_step launch then), takes the static execution-mode rule and composes with `known_labels`,
+    `resample` and `evidence`.  A set keyword runs this path even at the neutral value 1.0, which reproduces the plain call bit for
+    bit; None for both changes nothing.  One (tau, r) per call: every row and every pass of predict_multiple uses it.  A training or
+    validation call, rng = "torch_cpu" and a model with `softmax_output: no` are refused."""
 
     KNOWN_FREE = 255        # the value of a free pixel in `known_labels`
 
@@ -442,9 +457,12 @@ class DenoisingModel(nn.Module):
     def forward(self, x: Tensor, condition: Tensor, feature_condition: Tensor = None, t: Optional[Tensor] = None,
                 label_ref_logits: Optional[Tensor] = None, validation: bool = False, *,
                 known_labels: Optional[Tensor] = None, resample: Optional[Tuple[int, int]] = None,
-                evidence: Optional[Tensor] = None) -> Union[Tensor, dict]:
+                evidence: Optional[Tensor] = None, temperature: Optional[float] = None,
+                truncation: Optional[float] = None) -> Union[Tensor, dict]:
         if evidence is not None and (self.training or validation):
             self._check_evidence(evidence, None, sampling=False)
+        if self.training or validation:
+            self._check_shaping(temperature, truncation, sampling=False)
         if known_labels is not None and (self.training or validation):
             raise ValueError("known_labels: only a sampling call (eval mode, validation=False) takes known labels")
         if resample is not None and (self.training or validation):
@@ -459,9 +477,9 @@ class DenoisingModel(nn.Module):
             return self.forward_step(x, condition, feature_condition, t)
         if t is None:
             return self.forward_denoising(x, condition, feature_condition, label_ref_logits=label_ref_logits, known_labels=known_labels,
-                                          resample=resample, evidence=evidence)
+                                          resample=resample, evidence=evidence, temperature=temperature, truncation=truncation)
         return self.forward_denoising(x, condition, feature_condition, cast(int, t.item()), label_ref_logits, known_labels=known_labels,
-                                      resample=resample, evidence=evidence)
+                                      resample=resample, evidence=evidence, temperature=temperature, truncation=truncation)
 
     # ------------------------------------------------------------------ engine plumbing
     def _weights_key(self) -> Tuple[int, int]:
@@ -644,21 +662,50 @@ class DenoisingModel(nn.Module):
                           init_t: Optional[int] = None, label_ref_logits: Optional[Tensor] = None, *,
                           consume: Optional[Callable[[SamplerEngine, int, int], None]] = None,
                           known_labels: Optional[Tensor] = None, resample: Optional[Tuple[int, int]] = None,
-                          evidence: Optional[Tensor] = None) -> dict:
+                          evidence: Optional[Tensor] = None, temperature: Optional[float] = None,
+                          truncation: Optional[float] = None) -> dict:
         """`consume` (predict_multiple): instead of returning the call's output, hand every sub-batch engine (eng, lo, hi) to
         consume(eng, lo, hi) once the call has succeeded, with the engine's stream current; the result is then {}.
         `known_labels`: integer [N,H,W], a class where the label is known, 255 where the pixel is free (see the class docstring).
         `resample`: (jump_length, resamples), RePaint's resampling jumps of a walk with known labels (class docstring).
-        `evidence`: float [N,K,H,W], per-pixel class weights in [0,1] (class docstring)."""
-        guide = self._check_guidance(known_labels, resample, evidence, None if x is None else tuple(x.shape))
+        `evidence`: float [N,K,H,W], per-pixel class weights in [0,1] (class docstring).
+        `temperature` in [0.05, 20], `truncation` in (0, 1]: temper and truncate x0 before every reverse step (class docstring)."""
+        guide = self._check_guidance(known_labels, resample, evidence, None if x is None else tuple(x.shape), temperature, truncation)
         return self._sample(x, condition, feature_condition, init_t, label_ref_logits, consume, guide)
 
-    def _check_guidance(self, known_labels, resample, evidence, shape: Optional[Tuple[int, int, int, int]]) -> Guidance:
-        """The host-side checks of a call's three guidance keywords (before anything runs), in this order; shape: the call's (N,K,H,W)."""
+    def _check_guidance(self, known_labels, resample, evidence, shape: Optional[Tuple[int, int, int, int]], temperature=None,
+                        truncation=None) -> Guidance:
+        """The host-side checks of a call's guidance keywords (before anything runs), in this order; shape: the call's (N,K,H,W)."""
+        shaping = self._check_shaping(temperature, truncation)
         ev = None if evidence is None else self._check_evidence(evidence, shape)
         jumps = self._check_resample(resample, known_labels)
         known = None if known_labels is None else self._check_known_labels(known_labels, (shape[0], shape[2], shape[3]), shape[1])
-        return Guidance(known, jumps, ev)
+        return Guidance(known, jumps, ev, shaping)
+
+    def _check_shaping(self, temperature, truncation, sampling: bool = True) -> Optional[Tuple[float, float]]:
+        """The one host-side check of a call's `temperature` and `truncation` (before anything runs): (inv_temperature, top_r) as
+        ccdm_shaped_step takes them — inv_temperature = 1 / temperature in float64, rounded to fp32 once — or None where neither
+        keyword is set.  A keyword that is not set counts as 1.0."""
+        if temperature is None and truncation is None:
+            return None
+        name = "temperature" if temperature is not None else "truncation"
+
+        def real(v) -> bool:
+            return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+        if temperature is not None and not (real(temperature) and 0.05 <= float(temperature) <= 20.0):          # (a NaN fails both)
+            raise ValueError(f"temperature: expected a real number in [0.05, 20], got {temperature!r}")
+        if truncation is not None and not (real(truncation) and 0.0 < float(truncation) <= 1.0):
+            raise ValueError(f"truncation: expected a real number in (0, 1], got {truncation!r}")
+        if not sampling or self.training:
+            raise ValueError(f"{name}: only a sampling call (eval mode, validation=False) has a draw to shape")
+        if self.rng == "torch_cpu":
+            raise ValueError(f"{name}: not available with rng = 'torch_cpu' (the host-noise parity mode replays the reference's draws, and the "
+                             "reference has no shaped step to be in parity with); use rng = 'philox'")
+        if not self.unet.spec.softmax_output:
+            raise ValueError(f"{name}: needs a model whose output is a probability vector; with `softmax_output: no` x0 holds logits, "
+                             "which cannot be tempered or truncated as probabilities")
+        inv_temperature = 1.0 if temperature is None else float(np.float32(1.0 / float(temperature)))
+        return inv_temperature, (1.0 if truncation is None else float(np.float32(float(truncation))))
 
     def _check_evidence(self, evidence: Tensor, shape: Optional[Tuple[int, int, int, int]], sampling: bool = True) -> Tensor:
         """The one host-side check of a call's `evidence` (before anything runs): the map as contiguous fp32 [N,H*W,K] on the model's
@@ -742,7 +789,8 @@ class DenoisingModel(nn.Module):
                          voting: Optional[str] = None, x: Optional[Tensor] = None, t: Optional[Tensor] = None, batched: bool = False,
                          maps: Sequence[str] = ("mean", "vote", "entropy", "mutual_info"),
                          known_labels: Optional[Tensor] = None, resample: Optional[Tuple[int, int]] = None,
-                         evidence: Optional[Tensor] = None) -> Dict[str, Tensor]:
+                         evidence: Optional[Tensor] = None, temperature: Optional[float] = None,
+                         truncation: Optional[float] = None) -> Dict[str, Tensor]:
         """S = `num_evaluations` samples of every image of `condition` [B,C,H,W], combined on the device into one prediction and
         per-pixel uncertainty maps — the reference's Evaluator.predict_multiple (evaluation/eval_cdm.py:176-193), which sums S
         `predict_single` outputs as `total += prediction_i * (1 / S)`.
@@ -760,6 +808,7 @@ class DenoisingModel(nn.Module):
           (class docstring), so `vote` equals the label and `entropy` is 0 at the known pixels.
         resample: (jump_length, resamples): every pass walks with RePaint's resampling jumps (class docstring); needs known_labels.
         evidence: float [B,K,H,W] per-pixel class weights in [0,1] (class docstring): every pass is sampled under it.
+        temperature, truncation: every pass tempers and truncates x0 before every reverse step (class docstring), all with the same pair.
         batched=False: S sampling calls of B samples, each advancing `philox_call` exactly like S calls of model(x_i, condition);
           after each call the pass is folded into device accumulators straight from the engine (ccdm_vote_accumulate), so memory
           is one pass plus the accumulators.  The range-error fallback and the execution-mode choice apply per pass.
@@ -786,7 +835,7 @@ class DenoisingModel(nn.Module):
         if x is not None and tuple(x.shape) != (S, B, K, H, W):
             raise ValueError(f"x: expected one-hot x_T of shape {(S, B, K, H, W)} = [S,B,K,H,W], got {tuple(x.shape)}")
         init_t = None if t is None else int(t.item() if isinstance(t, Tensor) else t)
-        guide = self._check_guidance(known_labels, resample, evidence, (B, K, H, W))
+        guide = self._check_guidance(known_labels, resample, evidence, (B, K, H, W), temperature, truncation)
         dev = next(self.unet.parameters()).device
         lib = hip.load()
         majority = voting == "majority"
@@ -887,7 +936,7 @@ class DenoisingModel(nn.Module):
                            init_t: Optional[int] = None, label_ref_logits: Optional[Tensor] = None, consume=None,
                            guide: Guidance = Guidance()) -> dict:
         """`guide`: the call's checked guidance (_check_guidance), on the model's device."""
-        known, evidence = guide.known, guide.evidence
+        known, evidence, shaping = guide.known, guide.evidence, guide.shaping
         if label_ref_logits is not None:
             # the reference's guidance branch reads attributes that do not exist (guidance_scale_weights,
             # diffusion_denoising.py:172-174): it raises AttributeError there too.
@@ -906,8 +955,9 @@ class DenoisingModel(nn.Module):
         if self.rng not in ("philox", "torch_cpu"):
             raise ValueError(f"unknown rng mode {self.rng!r}")
         host_rng = self.rng == "torch_cpu"
-        # evidence: the network pass of every row stops at x0 (out_probs; x_t untouched), the row's real step follows in evidence_step
-        table = coeffs if evidence is None else [(a_, c_, hip.STEP_SOFTMAX_ONLY) for a_, c_, m_ in coeffs]
+        # evidence, shaping: the network pass of every row stops at x0 (out_probs; x_t untouched), the row's real step follows in
+        # evidence_step / shaped_step
+        table = coeffs if evidence is None and shaping is None else [(a_, c_, hip.STEP_SOFTMAX_ONLY) for a_, c_, m_ in coeffs]
         # known labels: cumalpha of the state each row produces; the last row returns the labels themselves (class docstring)
         clamp_c = [1.0 if j == S - 1 else c_ for j, (a_, c_, m_) in enumerate(coeffs)]
         key = self._philox_key()
@@ -945,13 +995,16 @@ class DenoisingModel(nn.Module):
 
         def run_row(eng, lo: int, hi: int, row: int, kp: int, renoise, noise, noise_row0_: int, graph_: bool):
             """One walk entry of one sub-batch, all on the engine's stream: the renoise back up the chain to the state before `row` (if a
-            jump precedes the entry), the network's step, the evidence step behind a network pass that stopped at x0, the clamp (the
-            next step reads the clamped state).  kp: the Philox key of this pass of the row."""
+            jump precedes the entry), the network's step, the shaped or the evidence step behind a network pass that stopped at x0 (one
+            launch: the shaped step applies the evidence too), the clamp (the next step reads the clamped state).  kp: the Philox key
+            of this pass of the row."""
             off = self.sample_offset + lo
             if renoise is not None:
                 eng.renoise(*renoise, row, philox_seed=kp, sample_offset=off)
             eng.run(1, first_row=row, noise=noise, noise_row0=noise_row0_, philox_seed=kp, sample_offset=off, use_graph=graph_)
-            if evidence is not None:
+            if shaping is not None:
+                eng.shaped_step(None if evidence is None else evidence[lo:hi], *shaping, *coeffs[row], row, philox_seed=kp, sample_offset=off)
+            elif evidence is not None:
                 eng.evidence_step(evidence[lo:hi], *coeffs[row], row, philox_seed=kp, sample_offset=off)
             if known is not None:
                 eng.clamp_known_labels(known[lo:hi], clamp_c[row], coeffs[row][2], row, philox_seed=kp, sample_offset=off)

@@ -1087,6 +1087,9 @@ def eval_segmentation(params: dict, dataset=None, device=None, model=None, synth
     and `evaluation.uncertainty_measures` (default both maps); a bad value, or one evaluation, raises before anything is sampled.
     Under the majority vote mutual_info equals entropy by construction, so only entropy is scored there.  The result then holds
     "uncertainty" (SegmentationUncertainty.result), also written to <output_path>/uncertainty.json.
+    The params key `sampling: {temperature: ..., truncation: ...}` (evaluation.sampling_keywords; each optional) is handed to every
+    sampling call and to predict_multiple and echoed as "sampling" in the result; an unknown key under it raises before anything is
+    sampled; without the key nothing changes.
     `model`: a ready DenoisingModel-like callable (tests inject one); default: built from `params`."""
     from . import evaluation as E
     world = int(os.environ.get("WORLD_SIZE", "1") or 1)
@@ -1096,6 +1099,7 @@ def eval_segmentation(params: dict, dataset=None, device=None, model=None, synth
     device = torch.device(device if device is not None else "cuda")
     section = params.get("evaluation") or {}
     resolution = section.get("resolution", "dataloader")
+    sampling = E.sampling_keywords(params)
     script, script_instances = bool(section.get("cityscapes_script", False)), bool(section.get("cityscapes_script_instances", False))
     if script_instances and not script:
         raise ValueError("evaluation.cityscapes_script_instances needs evaluation.cityscapes_script")
@@ -1167,7 +1171,7 @@ def eval_segmentation(params: dict, dataset=None, device=None, model=None, synth
             prediction = E.predict_multiple(model, image, params, feature_condition)
         else:           # the same passes as E.predict_multiple (evaluations >= 2), with the two uncertainty maps folded alongside the mean
             multi = model.predict_multiple(image, feature_condition, num_evaluations=evaluations, voting=vote,
-                                           maps=("mean", "entropy", "mutual_info"))
+                                           maps=("mean", "entropy", "mutual_info"), **sampling)
             prediction = multi["mean"]
         target = labels_orig if resolution == "original" else labels.argmax(dim=1)
         target = target.to(device)
@@ -1193,6 +1197,8 @@ def eval_segmentation(params: dict, dataset=None, device=None, model=None, synth
         LOGGER.info("IoU %-14s %.4f  (soft %.4f)", name, a, b)
     res = {"mIoU": float(iou.mean()), "IoU": iou.tolist(), "mIoU_soft": float(iou_soft.mean()), "IoU_soft": iou_soft.tolist(),
            "confusion": conf.confusion.tolist(), "images": n_img, "resolution": resolution, "evaluations": evaluations, "vote": vote}
+    if params.get("sampling") is not None:
+        res["sampling"] = dict(sampling)
     if writer is not None:
         res["pred_list"], res["label_list"] = list(writer.pred_list), list(writer.label_list)
         LOGGER.info("%d predictions written under %s", len(writer.pred_list), os.path.dirname(writer.path_submit))

@@ -6,7 +6,9 @@
 `dataset_file` in the YAML selects the evaluator: "...lidc_sampling_speed" -> the T-sweep timing run,
 "...lidc" -> GED / HM-IoU over the LIDC test split, "...cityscapes_miou" -> mIoU over the Cityscapes validation split
 ("datasets.cityscapes_miou": the data at dataset_path; "synthetic.cityscapes_miou": a stand-in).  Everything runs through
-the MI355X sampler; the result dictionary is also printed as one JSON line so scripts can pick it up."""
+the MI355X sampler; the result dictionary is also printed as one JSON line so scripts can pick it up.
+The optional key `sampling: {temperature: ..., truncation: ...}` tempers and truncates every sampling call of either evaluator
+(evaluation.sampling_keywords) and is echoed as "sampling" in the result."""
 import json
 import logging
 import os

@@ -377,6 +377,38 @@ int ccdm_evidence_step(const float* x0 /*dev [N,HW,K]*/, const float* evidence /
                        float* out_probs /*[N,HW,K] or NULL*/, int64_t* out_onehot /*[N,HW,K] or NULL*/, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Temperature and truncation ("top-r") sampling (DenoisingModel(..., temperature=, truncation=)): the network's x0 of a pixel is
+ * reshaped before the reverse step.  The step's posterior is linear in x0 up to its final normalisation, so the reshaped row is handed
+ * to the step as it is, without renormalising.  Launched like ccdm_evidence_step, after a denoise step whose table row has mode
+ * CCDM_STEP_SOFTMAX_ONLY; where the call has evidence too, this launch replaces the evidence launch.  THE definition, per pixel, fp32:
+ *   v_k = x0_k, or x0_k * evidence_k where evidence != NULL (ccdm_evidence_step's multiply).
+ *   Temper (skipped when inv_temperature == 1.0f; inv_temperature = 1 / temperature):
+ *     m = max_k v_k; if m == 0 the row stays as it is; otherwise u_k = v_k / m (IEEE division) and
+ *     q_k = 1 where u_k == 1, 0 where u_k == 0, else u_k^inv_temperature formed as exp2f(inv_temperature * log2f(u_k)).
+ *     Tempering is relative to the pixel's largest value: the winner is exactly 1 and no row underflows to all zeros.
+ *     Without tempering q_k = v_k.
+ *   Truncate (skipped when top_r == 1.0f):
+ *     Z = q_0 + q_1 + ... + q_{K-1} summed sequentially in index order; theta = top_r * Z (one multiply);
+ *     the classes ordered by q descending, ties by index ascending: pi(0), pi(1), ...; c_0 = 0, c_{j+1} = c_j + q_pi(j);
+ *     class pi(j) is KEPT iff c_j < theta — the smallest prefix whose mass reaches top_r; the top class is always kept when Z > 0.
+ *     A dropped class becomes 0, a kept value is not changed, nothing is renormalised (the scale cancels in the step).
+ *   Step: ccdm_posterior_sample's arithmetic with softmax = 0 on the shaped row, alpha_t / cumalpha_tm1 / mode as given and the Philox
+ *     counters of the unguided step of that row — exactly as ccdm_evidence_step; the outputs per `mode` are that entry's.
+ * Consequences: (inv_temperature, top_r) = (1, 1) is the plain step bit for bit without evidence and ccdm_evidence_step bit for bit
+ * with it; a top_r small enough to keep one class makes x0 one-hot(argmax v), and the draw is ccdm_posterior_sample on that row bit
+ * for bit; the last-step modes see the shaped row too (majority: the argmax of the shaped posterior; confidence: the shaped posterior).
+ * x0 and out_probs may be the same buffer.  Refused: what ccdm_evidence_step refuses (evidence may be NULL), an inv_temperature that
+ * is not finite or outside [1/20, 20], a top_r that is not finite or outside (0, 1].  K <= 32: the shaping runs in registers; above, in
+ * the pixel's LDS row.  Results depend on (pixel, global sample index, step row, key) only.
+ * ------------------------------------------------------------------------------------------------- */
+int ccdm_shaped_step(const float* x0 /*dev [N,HW,K]*/, const float* evidence /*dev [N,HW,K], weights in [0,1], or NULL*/, int N, int HW, int K,
+                     float inv_temperature, float top_r, float alpha_t, float cumalpha_tm1,
+                     int mode /*CCDM_STEP_SAMPLE | _LAST_CONFIDENCE | _LAST_MAJORITY | _LAST_KEEP*/, int step_row, uint64_t philox_seed,
+                     uint32_t sample_offset, uint8_t* xt /*dev [N,HW]: x_t in, x_{t-1} out*/,
+                     float* xin /*dev [N,HW,xin_stride] or NULL*/, int xin_stride, float* out_probs /*[N,HW,K] or NULL*/,
+                     int64_t* out_onehot /*[N,HW,K] or NULL*/, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * LIDC metrics, device part: for every image and every pair (i, j) of class-index maps
  * a[img][i], b[img][j], the per-class pixel counts out[img][i][j][k] = {|a==k & b==k|, |a==k | b==k|}.
  * Replaces the [B,S,S',HW,K] boolean broadcast of `batched_distance` / `iou`
