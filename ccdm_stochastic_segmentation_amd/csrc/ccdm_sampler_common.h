@@ -231,7 +231,7 @@ __device__ __forceinline__ void posterior_pixel(const ccdm_post_args& a, const s
 template <unsigned MAXD>
 struct RowDiv {
     unsigned d, m;
-    __device__ explicit RowDiv(unsigned d_) : d(d_), m(MAXD <= 64u || d_ <= 64u ? ((1u << 20) + d_ - 1u) / d_ : 0u) {}
+    __device__ __forceinline__ explicit RowDiv(unsigned d_) : d(d_), m(MAXD <= 64u || d_ <= 64u ? ((1u << 20) + d_ - 1u) / d_ : 0u) {}
     __device__ __forceinline__ unsigned operator()(unsigned idx) const { return MAXD <= 64u || m ? (idx * m) >> 20 : idx / d; }
 };
 

@@ -632,6 +632,27 @@ class SamplerEngine:
             "shaped_step")
         self._evidence_keepalive = evidence
 
+    def views_step(self, flips: Sequence[int], evidence: Optional[torch.Tensor], inv_temperature: float, top_r: float, alpha_t: float,
+                   cumalpha_tm1: float, mode: int, step_row: int, *, philox_seed: int = 0, sample_offset: int = 0) -> None:
+        """The reverse step on the mean of x0 over the V = 1 + len(flips) views of every sample (ccdm_views_step, asynchronous on the
+        engine's stream), behind a `run` of a table row whose mode is STEP_SOFTMAX_ONLY, as `shaped_step` and in its place.  The
+        engine's rows are the views of N = rows / V samples, view-major: row v * N + j is view v of sample j, view 0 the identity,
+        view v >= 1 mirrored as flips[v - 1] says (bit 0 mirrors x, bit 1 mirrors y).  The mean is taken per pixel of the identity
+        view, evidence and shaping follow as in `shaped_step` (neutral: 1.0, 1.0), the draw uses the Philox counters of the unguided
+        step of sample sample_offset + j, and the drawn class goes to every view at its mirrored place; the last-step outputs are
+        the first N rows of out_probs / out_onehot (include/ccdm_hip.h has the definition).  evidence: None, or fp32 [N,H*W,K]."""
+        V = 1 + len(flips)
+        assert 1 <= V <= 4 and self.N % V == 0 and all(0 <= int(f) <= 3 for f in flips)
+        n = self.N // V
+        assert evidence is None or (evidence.dtype == torch.float32 and evidence.is_cuda and evidence.is_contiguous()
+                                    and tuple(evidence.shape) == (n, self.H * self.W, self.K))
+        hip.check(self.lib.ccdm_views_step(
+            self.out_probs.data_ptr(), None if evidence is None else evidence.data_ptr(), n, self.H, self.W, self.K, V,
+            sum(int(f) << (2 * (v + 1)) for v, f in enumerate(flips)), float(inv_temperature), float(top_r), float(alpha_t),
+            float(cumalpha_tm1), int(mode), int(step_row), *self._step_state_args(philox_seed, sample_offset), self.out_probs.data_ptr(),
+            self.out_onehot.data_ptr(), self._stream()), "views_step")
+        self._evidence_keepalive = evidence
+
     def ce_logits(self) -> Optional[torch.Tensor]:
         """[N,K-1,H,W] logits of the optional ce head after the last run (BCHW view of channels-last memory), else None."""
         if self.head_ce is None:

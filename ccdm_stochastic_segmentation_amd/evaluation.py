@@ -165,13 +165,13 @@ def apply_sampler_options(model, params: dict) -> None:
     model._fine_slices(1)                                         # validates the value
 
 
-SAMPLING_KEYS = ("temperature", "truncation")
+SAMPLING_KEYS = ("temperature", "truncation", "views")
 
 
 def sampling_keywords(params: dict) -> dict:
-    """The keywords the params key `sampling: {temperature: ..., truncation: ...}` (each optional) adds to every sampling call and to
-    predict_multiple (DenoisingModel's keywords of those names, which check the values); {} without the key.  An unknown key under
-    `sampling:` raises."""
+    """The keywords the params key `sampling: {temperature: ..., truncation: ..., views: [...]}` (each optional) adds to every sampling
+    call and to predict_multiple (DenoisingModel's keywords of those names, which check the values; `views`, a YAML list of names from
+    hflip / vflip / hvflip, travels as a tuple); {} without the key.  An unknown key under `sampling:` raises."""
     section = params.get("sampling")
     if section is None:
         return {}
@@ -180,7 +180,17 @@ def sampling_keywords(params: dict) -> dict:
     unknown = [k for k in section if k not in SAMPLING_KEYS]
     if unknown:
         raise ValueError(f"sampling: unknown key(s) {unknown} (expected keys from {list(SAMPLING_KEYS)})")
-    return {k: section[k] for k in SAMPLING_KEYS if section.get(k) is not None}
+    return {k: tuple(section[k]) if (k == "views" and isinstance(section[k], list)) else section[k]
+            for k in SAMPLING_KEYS if section.get(k) is not None}
+
+
+def view_features(encoder, image: torch.Tensor, views) -> torch.Tensor:
+    """The feature condition of a call with `views` (DenoisingModel's keyword): [V,B,Cf,h,w], view 0 the encoder's features of the
+    image, view v >= 1 those of the image mirrored as views[v - 1] says — the encoder runs once per view on the mirrored pixels, its
+    output is not flipped after the fact (a ViT's features of a mirrored image are not the mirrored features)."""
+    from .models import DenoisingModel
+    flips = [DenoisingModel.VIEW_FLIPS[v] for v in views]
+    return torch.stack([encoder(image)] + [encoder(torch.flip(image, [d for b, d in ((1, 3), (2, 2)) if f & b])) for f in flips], 0)
 
 
 def _as_list(v) -> List[int]:
@@ -227,7 +237,7 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
     shard of the B_img*S flattened batch (distributed.sample_sharded: no collective inside the T loop, one gather of the
     predictions per batch); the metrics are then computed identically on every rank.
     `model`: a ready DenoisingModel-like callable (tests inject fixed predictions); default: built from `params`.
-    The params key `sampling: {temperature: ..., truncation: ...}` (sampling_keywords; each optional) is handed to every sampling call
+    The params key `sampling: {temperature: ..., truncation: ..., views: [...]}` (sampling_keywords; each optional) is handed to every sampling call
     and echoed as "sampling" in the result; without the key nothing changes.
 
     Build-owned keys of the `evaluation` section (absent: the returned dict and everything else is as without them):

@@ -113,15 +113,17 @@ def pass_key(key: int, p: int) -> int:
 class Guidance:
     """What guides one sampling call, as DenoisingModel._check_guidance returns it: `known` uint8 [N,H*W] (_check_known_labels), `jumps`
     (jump_length, resamples) (_check_resample), `evidence` fp32 [N,H*W,K] (_check_evidence), `shaping` (inv_temperature, top_r)
-    (_check_shaping); None each where the call has none."""
+    (_check_shaping), `views` the flip codes of views 1 .. V - 1 (_check_views: bit 0 mirrors x, bit 1 mirrors y; view 0 is the identity);
+    None each where the call has none."""
     known: Optional[Tensor] = None
     jumps: Optional[Tuple[int, int]] = None
     evidence: Optional[Tensor] = None
     shaping: Optional[Tuple[float, float]] = None
+    views: Optional[Tuple[int, ...]] = None
 
     def __bool__(self) -> bool:
         """The walk has something to do between the network's steps (jumps need known labels)."""
-        return self.known is not None or self.evidence is not None or self.shaping is not None
+        return self.known is not None or self.evidence is not None or self.shaping is not None or self.views is not None
 
     def walk(self, S: int) -> List[Tuple[int, int, Optional[int]]]:
         """The (row, pass, renoise_from) entries of a walk of S table rows: resample_walk's; [(s, 0, None) ...] without jumps."""
@@ -130,7 +132,7 @@ class Guidance:
     def repeat_interleave(self, S: int) -> "Guidance":
         """For a batch in which every sample is repeated S times (predict_multiple(batched=True))."""
         return Guidance(*(v.repeat_interleave(S, dim=0) if isinstance(v, Tensor) else v
-                          for v in (self.known, self.jumps, self.evidence, self.shaping)))
+                          for v in (self.known, self.jumps, self.evidence, self.shaping, self.views)))
 
 
 class OneHotCategoricalBCHW:
@@ -387,7 +389,25 @@ class DenoisingModel(nn.Module):
     the call has some: no ccdm_evidence_step launch then), takes the static execution-mode rule and composes with `known_labels`,
     `resample` and `evidence`.  A set keyword runs this path even at the neutral value 1.0, which reproduces the plain call bit for
     bit; None for both changes nothing.  One (tau, r) per call: every row and every pass of predict_multiple uses it.  A training or
-    validation call, rng = "torch_cpu" and a model with `softmax_output: no` are refused."""
+    validation call, rng = "torch_cpu" and a model with `softmax_output: no` are refused.
+    `views` (keyword next to `known_labels`): flip test-time augmentation inside the sampler.  A tuple of distinct names from "hflip"
+    (mirrors x), "vflip" (mirrors y) and "hvflip" (both); the identity is always view 0, so V = 1 + len(views) <= 4.  At every reverse
+    step the network runs on all V mirror images of (x_t, image) and x0 is their mean, each mapped back: x0_sym = 1/V sum_g g^-1
+    x0(g x_t, g image), a denoiser that is exactly equivariant under the listed flips where the trained one is only approximately so.
+    Exact for categorical diffusion (a mean of probability vectors is one; the step posterior is linear in x0 up to its own
+    normalisation), no retraining, V network passes per step.  The V views of a sample are V rows of the engine's batch, view-major
+    (row v * n + j of a sub-batch of n samples is view v of sample j; the host mirrors x_T, the image and the features with torch.flip);
+    every row's network pass stops at x0 and ONE ccdm_views_step launch per walk entry takes the mean, applies `evidence`, `temperature`
+    and `truncation` where the call has them (it replaces those launches), draws with the counters of the plain call — keyed by the
+    identity view's pixel and the sample, never by the engine row — and writes the drawn class to every view at its mirrored place
+    (include/ccdm_hip.h has the definition).  Results are read from view 0.  A call with views takes the static execution-mode rule
+    (`auto_substreams` sees V * N samples) and does not depend on `substreams`, `use_graph` or sharding.  A model that takes a
+    `feature_condition` needs the features of every view from the caller's own encoder, [V,N,Cf,h,w] with view v computed from the
+    mirrored image.  Refused: unknown or duplicate names, a training or validation call, rng = "torch_cpu", `softmax_output: no`, and
+    `known_labels` / `resample` together with views (the clamp and the renoise draw per engine row, so the views would stop being
+    mirror images of one another: not built).  `views=()` or None is the plain call: no code path changes."""
+
+    VIEW_FLIPS = {"hflip": 1, "vflip": 2, "hvflip": 3}        # ccdm_views_step's two bits per view: bit 0 mirrors x, bit 1 mirrors y
 
     KNOWN_FREE = 255        # the value of a free pixel in `known_labels`
 
@@ -458,11 +478,12 @@ class DenoisingModel(nn.Module):
                 label_ref_logits: Optional[Tensor] = None, validation: bool = False, *,
                 known_labels: Optional[Tensor] = None, resample: Optional[Tuple[int, int]] = None,
                 evidence: Optional[Tensor] = None, temperature: Optional[float] = None,
-                truncation: Optional[float] = None) -> Union[Tensor, dict]:
+                truncation: Optional[float] = None, views: Optional[Sequence[str]] = None) -> Union[Tensor, dict]:
         if evidence is not None and (self.training or validation):
             self._check_evidence(evidence, None, sampling=False)
         if self.training or validation:
             self._check_shaping(temperature, truncation, sampling=False)
+            self._check_views(views, sampling=False)
         if known_labels is not None and (self.training or validation):
             raise ValueError("known_labels: only a sampling call (eval mode, validation=False) takes known labels")
         if resample is not None and (self.training or validation):
@@ -477,9 +498,10 @@ class DenoisingModel(nn.Module):
             return self.forward_step(x, condition, feature_condition, t)
         if t is None:
             return self.forward_denoising(x, condition, feature_condition, label_ref_logits=label_ref_logits, known_labels=known_labels,
-                                          resample=resample, evidence=evidence, temperature=temperature, truncation=truncation)
+                                          resample=resample, evidence=evidence, temperature=temperature, truncation=truncation,
+                                          views=views)
         return self.forward_denoising(x, condition, feature_condition, cast(int, t.item()), label_ref_logits, known_labels=known_labels,
-                                      resample=resample, evidence=evidence, temperature=temperature, truncation=truncation)
+                                      resample=resample, evidence=evidence, temperature=temperature, truncation=truncation, views=views)
 
     # ------------------------------------------------------------------ engine plumbing
     def _weights_key(self) -> Tuple[int, int]:
@@ -663,24 +685,64 @@ class DenoisingModel(nn.Module):
                           consume: Optional[Callable[[SamplerEngine, int, int], None]] = None,
                           known_labels: Optional[Tensor] = None, resample: Optional[Tuple[int, int]] = None,
                           evidence: Optional[Tensor] = None, temperature: Optional[float] = None,
-                          truncation: Optional[float] = None) -> dict:
+                          truncation: Optional[float] = None, views: Optional[Sequence[str]] = None) -> dict:
         """`consume` (predict_multiple): instead of returning the call's output, hand every sub-batch engine (eng, lo, hi) to
         consume(eng, lo, hi) once the call has succeeded, with the engine's stream current; the result is then {}.
         `known_labels`: integer [N,H,W], a class where the label is known, 255 where the pixel is free (see the class docstring).
         `resample`: (jump_length, resamples), RePaint's resampling jumps of a walk with known labels (class docstring).
         `evidence`: float [N,K,H,W], per-pixel class weights in [0,1] (class docstring).
-        `temperature` in [0.05, 20], `truncation` in (0, 1]: temper and truncate x0 before every reverse step (class docstring)."""
-        guide = self._check_guidance(known_labels, resample, evidence, None if x is None else tuple(x.shape), temperature, truncation)
+        `temperature` in [0.05, 20], `truncation` in (0, 1]: temper and truncate x0 before every reverse step (class docstring).
+        `views`: names from "hflip", "vflip", "hvflip": x0 is averaged over these mirror images of the input (class docstring)."""
+        guide = self._check_guidance(known_labels, resample, evidence, None if x is None else tuple(x.shape), temperature, truncation,
+                                     views, feature_condition)
         return self._sample(x, condition, feature_condition, init_t, label_ref_logits, consume, guide)
 
     def _check_guidance(self, known_labels, resample, evidence, shape: Optional[Tuple[int, int, int, int]], temperature=None,
-                        truncation=None) -> Guidance:
+                        truncation=None, views=None, feature_condition=None) -> Guidance:
         """The host-side checks of a call's guidance keywords (before anything runs), in this order; shape: the call's (N,K,H,W)."""
+        flips = self._check_views(views, known_labels=known_labels, resample=resample, feature_condition=feature_condition, shape=shape)
         shaping = self._check_shaping(temperature, truncation)
         ev = None if evidence is None else self._check_evidence(evidence, shape)
         jumps = self._check_resample(resample, known_labels)
         known = None if known_labels is None else self._check_known_labels(known_labels, (shape[0], shape[2], shape[3]), shape[1])
-        return Guidance(known, jumps, ev, shaping)
+        return Guidance(known, jumps, ev, shaping, flips)
+
+    def _check_views(self, views, sampling: bool = True, *, known_labels=None, resample=None, feature_condition=None,
+                     shape: Optional[Tuple[int, int, int, int]] = None) -> Optional[Tuple[int, ...]]:
+        """The one host-side check of a call's `views` (before anything runs): the flip codes of views 1 .. V - 1 as ccdm_views_step
+        takes them (VIEW_FLIPS), or None where the call has no views (None or an empty sequence: the plain call).  shape: the call's
+        (N,K,H,W)."""
+        if views is None:
+            return None
+        if isinstance(views, (str, bytes)) or not isinstance(views, (tuple, list)):
+            raise ValueError(f"views: expected a sequence of names from {list(self.VIEW_FLIPS)}, got {views!r}")
+        if len(views) == 0:
+            return None
+        bad = [v for v in views if not isinstance(v, str) or v not in self.VIEW_FLIPS]
+        if bad:
+            raise ValueError(f"views: unknown name(s) {bad} (expected names from {list(self.VIEW_FLIPS)}; the identity is always a view)")
+        if len(set(views)) != len(views):
+            raise ValueError(f"views: duplicate name(s) in {list(views)} (every view counts once in the mean)")
+        if not sampling or self.training:
+            raise ValueError("views: only a sampling call (eval mode, validation=False) has a denoiser to average")
+        if self.rng == "torch_cpu":
+            raise ValueError("views: not available with rng = 'torch_cpu' (the host-noise parity mode replays the reference's draws, and the "
+                             "reference has no view-averaged step to be in parity with); use rng = 'philox'")
+        if not self.unet.spec.softmax_output:
+            raise ValueError("views: needs a model whose output is a probability vector; with `softmax_output: no` x0 holds logits, "
+                             "whose mean is not the mean of the probabilities")
+        if known_labels is not None or resample is not None:
+            raise ValueError(f"views: not available together with {'known_labels' if known_labels is not None else 'resample'} (the clamp "
+                             "and the renoise draw per engine row, so the views would stop being mirror images of one another)")
+        if feature_condition is not None and self.unet.spec.feature_condition_idx:
+            V = 1 + len(views)
+            want = None if shape is None else (V, int(shape[0]))
+            if not isinstance(feature_condition, Tensor) or feature_condition.ndim != 5 or \
+                    (want is not None and tuple(feature_condition.shape[:2]) != want):
+                raise ValueError(f"views: this model takes a feature_condition, and with views it needs the features of every view, "
+                                 f"[V,N,Cf,h,w] with V = {V} (view v from the caller's encoder on the mirrored image), got "
+                                 f"{tuple(getattr(feature_condition, 'shape', ()))}")
+        return tuple(self.VIEW_FLIPS[v] for v in views)
 
     def _check_shaping(self, temperature, truncation, sampling: bool = True) -> Optional[Tuple[float, float]]:
         """The one host-side check of a call's `temperature` and `truncation` (before anything runs): (inv_temperature, top_r) as
@@ -790,7 +852,7 @@ class DenoisingModel(nn.Module):
                          maps: Sequence[str] = ("mean", "vote", "entropy", "mutual_info"),
                          known_labels: Optional[Tensor] = None, resample: Optional[Tuple[int, int]] = None,
                          evidence: Optional[Tensor] = None, temperature: Optional[float] = None,
-                         truncation: Optional[float] = None) -> Dict[str, Tensor]:
+                         truncation: Optional[float] = None, views: Optional[Sequence[str]] = None) -> Dict[str, Tensor]:
         """S = `num_evaluations` samples of every image of `condition` [B,C,H,W], combined on the device into one prediction and
         per-pixel uncertainty maps — the reference's Evaluator.predict_multiple (evaluation/eval_cdm.py:176-193), which sums S
         `predict_single` outputs as `total += prediction_i * (1 / S)`.
@@ -809,6 +871,8 @@ class DenoisingModel(nn.Module):
         resample: (jump_length, resamples): every pass walks with RePaint's resampling jumps (class docstring); needs known_labels.
         evidence: float [B,K,H,W] per-pixel class weights in [0,1] (class docstring): every pass is sampled under it.
         temperature, truncation: every pass tempers and truncates x0 before every reverse step (class docstring), all with the same pair.
+        views: every pass averages x0 over these mirror images of the input (class docstring); a model that takes a feature_condition
+          then needs [V,B,Cf,h,w].
         batched=False: S sampling calls of B samples, each advancing `philox_call` exactly like S calls of model(x_i, condition);
           after each call the pass is folded into device accumulators straight from the engine (ccdm_vote_accumulate), so memory
           is one pass plus the accumulators.  The range-error fallback and the execution-mode choice apply per pass.
@@ -835,7 +899,7 @@ class DenoisingModel(nn.Module):
         if x is not None and tuple(x.shape) != (S, B, K, H, W):
             raise ValueError(f"x: expected one-hot x_T of shape {(S, B, K, H, W)} = [S,B,K,H,W], got {tuple(x.shape)}")
         init_t = None if t is None else int(t.item() if isinstance(t, Tensor) else t)
-        guide = self._check_guidance(known_labels, resample, evidence, (B, K, H, W), temperature, truncation)
+        guide = self._check_guidance(known_labels, resample, evidence, (B, K, H, W), temperature, truncation, views, feature_condition)
         dev = next(self.unet.parameters()).device
         lib = hip.load()
         majority = voting == "majority"
@@ -869,12 +933,15 @@ class DenoisingModel(nn.Module):
             else:
                 xr = x.transpose(0, 1).reshape(B * S, K, H, W) if x is not None else draw(B * S)
                 cond = condition.repeat_interleave(S, dim=0)
-                fc = feature_condition.repeat_interleave(S, dim=0) if feature_condition is not None else None
+                # (with views on a model that takes features: [V,B,...], the samples on dim 1)
+                fc_dim = 1 if (guide.views is not None and feature_condition is not None and feature_condition.ndim == 5) else 0
+                fc = feature_condition.repeat_interleave(S, dim=fc_dim) if feature_condition is not None else None
                 # the pass outputs of all B*S samples: class maps (1 byte a pixel) or probabilities
                 buf = torch.empty((B * S, HW) if majority else (B * S, HW, K), dtype=torch.uint8 if majority else torch.float32, device=dev)
 
                 def consume(eng, lo: int, hi: int) -> None:
-                    buf[lo:hi].copy_(eng.xt if majority else eng.out_probs.reshape(hi - lo, HW, K))
+                    # (the first hi - lo rows: with views the engine holds V times as many, view 0 first)
+                    buf[lo:hi].copy_(eng.xt.reshape(-1, HW)[:hi - lo] if majority else eng.out_probs.reshape(-1, HW, K)[:hi - lo])
 
                 self._sample(xr, cond, fc, init_t, None, consume, guide.repeat_interleave(S))
                 if majority:
@@ -936,7 +1003,8 @@ class DenoisingModel(nn.Module):
                            init_t: Optional[int] = None, label_ref_logits: Optional[Tensor] = None, consume=None,
                            guide: Guidance = Guidance()) -> dict:
         """`guide`: the call's checked guidance (_check_guidance), on the model's device."""
-        known, evidence, shaping = guide.known, guide.evidence, guide.shaping
+        known, evidence, shaping, views = guide.known, guide.evidence, guide.shaping, guide.views
+        V = 1 if views is None else 1 + len(views)
         if label_ref_logits is not None:
             # the reference's guidance branch reads attributes that do not exist (guidance_scale_weights,
             # diffusion_denoising.py:172-174): it raises AttributeError there too.
@@ -955,9 +1023,10 @@ class DenoisingModel(nn.Module):
         if self.rng not in ("philox", "torch_cpu"):
             raise ValueError(f"unknown rng mode {self.rng!r}")
         host_rng = self.rng == "torch_cpu"
-        # evidence, shaping: the network pass of every row stops at x0 (out_probs; x_t untouched), the row's real step follows in
-        # evidence_step / shaped_step
-        table = coeffs if evidence is None and shaping is None else [(a_, c_, hip.STEP_SOFTMAX_ONLY) for a_, c_, m_ in coeffs]
+        # evidence, shaping, views: the network pass of every row stops at x0 (out_probs; x_t untouched), the row's real step follows in
+        # evidence_step / shaped_step / views_step
+        stop_at_x0 = evidence is not None or shaping is not None or views is not None
+        table = coeffs if not stop_at_x0 else [(a_, c_, hip.STEP_SOFTMAX_ONLY) for a_, c_, m_ in coeffs]
         # known labels: cumalpha of the state each row produces; the last row returns the labels themselves (class docstring)
         clamp_c = [1.0 if j == S - 1 else c_ for j, (a_, c_, m_) in enumerate(coeffs)]
         key = self._philox_key()
@@ -980,29 +1049,42 @@ class DenoisingModel(nn.Module):
         # by the global sample index or sliced from the full-batch host draw): the results are bit-identical.
         # automatic: two sub-batches once the batch holds as many pixels as 32 LIDC samples (N >= 32 at 128x128; the Cityscapes-shaped
         # batches of 16 x 256x512 and 4 x 512x1024 qualify: +2.3 % / +2.0 % measured), one below
+        def mirrored(a: Tensor) -> Tensor:
+            """The V views of a sub-batch's [n,C,h,w] tensor as the engine's rows, view-major: [V * n,C,h,w], view v flipped as it says."""
+            return torch.cat([a] + [torch.flip(a, [d for b, d in ((1, 3), (2, 2)) if f & b]) for f in cast(tuple, views)], 0)
+
         def prepare(nsub_: int):
             bounds = [(N * j) // nsub_ for j in range(nsub_ + 1)]
             parts_ = []
             for j in range(nsub_):
                 lo, hi = bounds[j], bounds[j + 1]
-                fc = feature_condition[lo:hi] if feature_condition is not None else None
-                eng = self._engine(x[lo:hi], condition[lo:hi], fc, slot=j)
+                if views is None:
+                    xs, cs = x[lo:hi], condition[lo:hi]
+                    fc = feature_condition[lo:hi] if feature_condition is not None else None
+                else:
+                    xs, cs, fc = mirrored(x[lo:hi]), mirrored(condition[lo:hi]), None
+                    if feature_condition is not None and self.unet.spec.feature_condition_idx:         # [V,N,...] (_check_views)
+                        fc = feature_condition[:, lo:hi].flatten(0, 1)
+                eng = self._engine(xs, cs, fc, slot=j)
                 with eng.enter():
-                    eng.set_inputs(self._to_index(x[lo:hi], eng.device), condition[lo:hi].to(eng.device), fc)
+                    eng.set_inputs(self._to_index(xs, eng.device), cs.to(eng.device), fc)
                     eng.set_tables([float(t) for t in t_values], table)
                 parts_.append((eng, lo, hi))
             return parts_
 
         def run_row(eng, lo: int, hi: int, row: int, kp: int, renoise, noise, noise_row0_: int, graph_: bool):
             """One walk entry of one sub-batch, all on the engine's stream: the renoise back up the chain to the state before `row` (if a
-            jump precedes the entry), the network's step, the shaped or the evidence step behind a network pass that stopped at x0 (one
-            launch: the shaped step applies the evidence too), the clamp (the next step reads the clamped state).  kp: the Philox key
-            of this pass of the row."""
+            jump precedes the entry), the network's step, the views, the shaped or the evidence step behind a network pass that stopped
+            at x0 (one launch: the shaped step applies the evidence too, the views step both), the clamp (the next step reads the
+            clamped state).  kp: the Philox key of this pass of the row."""
             off = self.sample_offset + lo
             if renoise is not None:
                 eng.renoise(*renoise, row, philox_seed=kp, sample_offset=off)
             eng.run(1, first_row=row, noise=noise, noise_row0=noise_row0_, philox_seed=kp, sample_offset=off, use_graph=graph_)
-            if shaping is not None:
+            if views is not None:
+                eng.views_step(views, None if evidence is None else evidence[lo:hi], *(shaping or (1.0, 1.0)), *coeffs[row], row,
+                               philox_seed=kp, sample_offset=off)
+            elif shaping is not None:
                 eng.shaped_step(None if evidence is None else evidence[lo:hi], *shaping, *coeffs[row], row, philox_seed=kp, sample_offset=off)
             elif evidence is not None:
                 eng.evidence_step(evidence[lo:hi], *coeffs[row], row, philox_seed=kp, sample_offset=off)
@@ -1019,7 +1101,7 @@ class DenoisingModel(nn.Module):
                 for j, (eng, lo, hi) in enumerate(parts_):
                     run_row(eng, lo, hi, row, pass_key(key, p), renoise_p.get(e), noises_[j], noise_row0_, graph_)
 
-        nsub = int(self.substreams) if int(self.substreams) > 0 else auto_substreams(N, H, W)
+        nsub = int(self.substreams) if int(self.substreams) > 0 else auto_substreams(V * N, H, W)
         nsub = max(1, min(nsub, N))
         use_graph = bool(self.use_graph)
         if (int(self.substreams) <= 0 and self.calibrate_mode and not host_rng and self._range_probe is None and nsub > 1
@@ -1053,13 +1135,14 @@ class DenoisingModel(nn.Module):
         outs = []
         for eng, lo, hi in (parts if consume is None else []):
             with eng.enter():
+                n_ = hi - lo                                   # (with views the engine holds V * n_ rows: view 0 is the first n_)
                 if t_values[-1] > 1 or last_mode == hip.STEP_LAST_KEEP:
-                    idx = eng.xt.reshape(hi - lo, H, W).long()
+                    idx = eng.xt.reshape(-1, H, W)[:n_].long()
                     out = torch.nn.functional.one_hot(idx, K).permute(0, 3, 1, 2).to(torch.float32)
                 elif last_mode == hip.STEP_LAST_CONFIDENCE:
-                    out = eng.out_probs.clone().permute(0, 3, 1, 2)          # BCHW view of channels-last memory, like the reference
+                    out = eng.out_probs[:n_].clone().permute(0, 3, 1, 2)     # BCHW view of channels-last memory, like the reference
                 else:
-                    out = eng.out_onehot.clone().permute(0, 3, 1, 2)
+                    out = eng.out_onehot[:n_].clone().permute(0, 3, 1, 2)
             eng.leave()
             outs.append(out)
         # read AND clear the sticky range flag of every sub-batch engine before raising: a flag left set on a cached engine would

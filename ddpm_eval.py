@@ -7,8 +7,9 @@
 "...lidc" -> GED / HM-IoU over the LIDC test split, "...cityscapes_miou" -> mIoU over the Cityscapes validation split
 ("datasets.cityscapes_miou": the data at dataset_path; "synthetic.cityscapes_miou": a stand-in).  Everything runs through
 the MI355X sampler; the result dictionary is also printed as one JSON line so scripts can pick it up.
-The optional key `sampling: {temperature: ..., truncation: ...}` tempers and truncates every sampling call of either evaluator
-(evaluation.sampling_keywords) and is echoed as "sampling" in the result."""
+The optional key `sampling: {temperature: ..., truncation: ..., views: [hflip, ...]}` tempers and truncates every sampling call of
+either evaluator and averages its denoiser over the listed mirror images of the input (evaluation.sampling_keywords); it is echoed as
+"sampling" in the result."""
 import json
 import logging
 import os

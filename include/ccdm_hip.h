@@ -409,6 +409,41 @@ int ccdm_shaped_step(const float* x0 /*dev [N,HW,K]*/, const float* evidence /*d
                      int64_t* out_onehot /*[N,HW,K] or NULL*/, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Flip-averaged sampling (DenoisingModel(..., views=)): the denoiser is averaged over V mirror images of its input, which makes it
+ * exactly equivariant under those flips.  The V views of a sample are V rows of a larger batch, view-major: row v * N + n is view v of
+ * sample n, fed x_t and the image mirrored as view v says; view 0 is the identity.  Launched like ccdm_shaped_step, after a denoise step
+ * (on all V * N rows) whose table row has mode CCDM_STEP_SOFTMAX_ONLY, and in its place: this launch applies the evidence and the
+ * shaping too.  `flips` holds 2 bits per view, view v at bits 2v and 2v + 1: fx_v = bit 0 mirrors x, fy_v = bit 1 mirrors y.
+ * THE definition, per sample n < N and pixel (y, x) of the identity view, fp32:
+ *   src_v = (fy_v ? H - 1 - y : y) * W + (fx_v ? W - 1 - x : x)                      the pixel of view v that shows (y, x); src_0 = y * W + x
+ *   m_k = (((x0[0 * N + n][src_0][k] + x0[1 * N + n][src_1][k]) + ...) * fp32(1 / V)  summed in view order, one multiply at the end
+ *   then ccdm_shaped_step's arithmetic on the row m: v_k = m_k, or m_k * evidence[n][y * W + x][k] where evidence != NULL; temper and
+ *   truncate (each skipped at its neutral value); ccdm_posterior_sample's arithmetic with softmax = 0 on the shaped row, x_t =
+ *   xt[0 * N + n][src_0], alpha_t / cumalpha_tm1 / mode as given, and the Philox counters of the unguided step of that row for pixel
+ *   y * W + x and sample sample_offset + n: the draw is keyed as a call without views keys it, never by the engine row.
+ *   Nothing is renormalised (a mean of probability vectors is one, and the scale cancels in the step anyway).
+ * Outputs.  CCDM_STEP_SAMPLE: the drawn class goes to xt[v * N + n][src_v] for every view v < V, and where xin != NULL its one-hot to
+ * channels [0, K) of xin[v * N + n][src_v]; channels >= K are not touched.  CCDM_STEP_LAST_CONFIDENCE: the posterior goes to
+ * out_probs[n][y * W + x], xt is not touched.  CCDM_STEP_LAST_MAJORITY: the one-hot of the posterior's argmax goes to
+ * out_onehot[n][y * W + x] and its index to xt[v * N + n][src_v] for every view.  CCDM_STEP_LAST_KEEP: nothing is written.
+ * out_probs and out_onehot cover the view-0 rows, [N,HW,K]; rows v * N + n, v >= 1, of a larger buffer are not touched.
+ * x0 and out_probs may be the same buffer: a pixel's V * K values are read before anything of the pixel is written, only view-0 rows are
+ * written, each by the thread that owns the pixel, and nothing else reads those rows.
+ * Consequences.  V = 1 is ccdm_shaped_step bit for bit.  V = 2 or 4 with views whose x0 are exact mirror images of view 0 is
+ * ccdm_shaped_step on view 0 bit for bit (a sum of 2 or 4 equal values times 1/2 or 1/4 is exact), and the xt rows of all views are
+ * mirror images of one another — as they are after every launch, whatever x0 holds.  V = 2: a + b is commutative, so m for a call on
+ * mirrored inputs is the mirror of m for the original call, bit for bit (V = 3, 4: the sum's order breaks that in the last bit).
+ * Refused: what ccdm_shaped_step refuses, CCDM_STEP_SOFTMAX_ONLY, V outside [1,4], non-zero bits for view 0 or bits beyond view V - 1,
+ * V * N * H * W > 2^31 - 1.  Results depend on (pixel, global sample index, step row, key) only.
+ * ------------------------------------------------------------------------------------------------- */
+int ccdm_views_step(const float* x0 /*dev [V*N,HW,K]*/, const float* evidence /*dev [N,HW,K], weights in [0,1], or NULL*/, int N, int H, int W,
+                    int K, int V, int flips, float inv_temperature, float top_r, float alpha_t, float cumalpha_tm1,
+                    int mode /*CCDM_STEP_SAMPLE | _LAST_CONFIDENCE | _LAST_MAJORITY | _LAST_KEEP*/, int step_row, uint64_t philox_seed,
+                    uint32_t sample_offset, uint8_t* xt /*dev [V*N,HW]: x_t in, x_{t-1} out*/,
+                    float* xin /*dev [V*N,HW,xin_stride] or NULL*/, int xin_stride, float* out_probs /*[N,HW,K] or NULL*/,
+                    int64_t* out_onehot /*[N,HW,K] or NULL*/, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * LIDC metrics, device part: for every image and every pair (i, j) of class-index maps
  * a[img][i], b[img][j], the per-class pixel counts out[img][i][j][k] = {|a==k & b==k|, |a==k | b==k|}.
  * Replaces the [B,S,S',HW,K] boolean broadcast of `batched_distance` / `iou`
