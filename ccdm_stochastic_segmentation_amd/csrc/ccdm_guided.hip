@@ -1,0 +1,348 @@
+// The guided steps: the one launch behind a network pass that stopped at x0 = p(x_0 | x_t) (CCDM_STEP_SOFTMAX_ONLY).  The step
+// posterior sum_d q(x_{t-1} | x_t, x_0 = d) p(x_0 = d | .) is linear in x0 up to its final normalisation, so anything that reshapes a
+// pixel's x0 row sits in front of posterior_pixel_core (softmax = 0) without renormalising: the epilogue's arithmetic and Philox
+// counters, ONE definition (ccdm_sampler_common.h), so neutral arguments reproduce the unguided step bit for bit.  In this order:
+//   views     (DenoisingModel(..., views=), ccdm_views_step) the denoiser is averaged over mirror images of its input, x0_sym = 1/V *
+//             sum_g g^-1 x0(g x_t, g img): exactly equivariant under those flips where the trained network is only approximately so.
+//             The V views of a sample are V rows of the engine's batch, view-major (row v * N + j is view v of sample j), each fed its
+//             mirrored x_t and image; per pixel of the identity view the kernel gathers the V rows at the mirrored positions, sums them
+//             in view order and multiplies once by fp32(1 / V); after the draw — keyed by the identity view's pixel and sample, never
+//             by the engine row — the class goes back to every view at its mirrored position, so the views stay mirror images.
+//   evidence  (evidence=, ccdm_evidence_step) independent evidence e with likelihood p(e | x_0 = k) ~ w_k gives p(x_0 | x_t, e) ~
+//             x0_k * w_k (Bayes): one fp32 multiply — no gradient, no scale, no retraining.
+//   shaping   (temperature=, truncation=, ccdm_shaped_step) the row is tempered relative to its largest value, then cut to the
+//             smallest set of classes whose mass reaches top_r: shape_row / shape_lds_row (ccdm_shaping.h).  (1, 1) skips both parts
+//             by uniform branches.
+// THE definitions: include/ccdm_hip.h.  ONE kernel pair in two instantiations: VIEWS = false is ccdm_shaped_step and, at (1, 1) with
+// the evidence required, ccdm_evidence_step (a kernel of its own for that was 1.003x / 1.00x of this one: DESIGN.md section 4);
+// VIEWS = true is ccdm_views_step, which cannot stand in for the other at V = 1 (1.07x / 1.14x, its extra LDS pass).
+//
+// Shaped for HBM: per pixel 4 K V + 1 bytes in (+ 4 K of evidence), V bytes out (+ 4 K V where xin, 4 K where out_probs is written);
+// measured, the launch's time is the core's arithmetic on the vector pipe, not those bytes.
+//   K <= 4   one thread per pixel; a pixel's K values of an operand are one 8- or 16-byte load where K is 2 or 4.  The views are
+//            summed in registers (an unrolled loop over the four possible views: nothing is indexed dynamically).
+//   K <= 32  a block's 256 pixels move as what they are, one contiguous run of 256 K floats per operand, through odd-pitch LDS rows,
+//            and the one-hot channels of xin leave the same way (stage_class_rows, store_onehot_rows: ccdm_sampler_common.h).
+//            (K | 1) * 1 KiB of LDS per block: 4 blocks per CU at K = 32.  The shaping runs in registers: the classes already taken
+//            are a 32-bit mask, the next class in order comes from an unrolled max scan (first maximum wins: ties go to the lower
+//            index), and a pixel leaves the loop once its cumulated mass reaches the threshold — at most K scans of K compares, one
+//            for a peaked pixel.  No private array is indexed dynamically, so nothing goes to scratch.
+//   K <= 255 the same with 64 pixels per block (at most 65 536 bytes of LDS: no room for a second row per pixel, nor for V); the
+//            pixel's classes no longer fit the register file and the core's arrays spill — no dataset has that many classes, and the
+//            arithmetic is not written a second time for them.  The shaping works on the pixel's LDS row in place: a taken class is
+//            marked in its sign bit (all values are >= 0) and the marks are resolved — kept value or 0 — before the core reads the
+//            row.  A thread walks its own row with a k that is uniform over the wave: PITCH is odd, so the lanes' addresses tid *
+//            PITCH + k fall on distinct banks; only the marking store (a per-lane k) can collide.
+//   views, staged: view 0's run is staged like any run, then every further view is added into the ONE row per pixel in a pass over
+//            the block's [pixel][class] run, the pixel's source index coming from LDS (sb, written by the pixel's thread, one view at
+//            a time).  A block's pixels are runs of image rows, and their sources in a mirrored view are the mirrored runs of the
+//            same (x mirrored) or the mirrored (y mirrored) image rows: K contiguous floats per pixel, the pixels of an image row
+//            next to one another, so a wave's 64 loads fall into the cache lines a forward run of that length covers.  The mean's
+//            multiply and the evidence multiply are one more pass (the evidence run is contiguous).  After the draw the block's LDS
+//            rows are free (every thread has its row in registers): they hold the pixels' indices in the mirrored views for the
+//            one-hot stores, which run like store_onehot_rows with the pixel order mirrored.
+// x0 and out_probs may be the same buffer (in the engine they are).  Only rows of the identity view (without views: every row) of
+// out_probs are written, each by the thread that owns the pixel, after that pixel's x0 values are in registers (one thread per pixel)
+// or the whole block's are in LDS behind a barrier (staged), and a block owns its pixels alone; rows of the other views are read by
+// whatever block the mirror map sends them to and written by nobody.  xt: a thread reads the identity view's byte of its own pixel
+// and writes that byte and its V - 1 mirror images; the mirror maps are bijections, so no byte has two writers.  The last-step modes
+// write out_probs / out_onehot from the core, one thread per pixel: once per walk.
+#include "ccdm_common.h"
+#include "ccdm_sampler_common.h"
+#include "ccdm_shaping.h"
+
+#include <algorithm>
+#include <cmath>
+
+namespace ccdm {
+
+// What a guided launch takes next to ccdm_post_args (whose N is the number of samples, not of engine rows).  !VIEWS reads ev alone.
+struct guided_args {
+    const float* ev;        // [N,HW,K] or null
+    int H, W, V, flips;     // flips: 2 bits per view, bit 0 mirrors x, bit 1 mirrors y
+    float inv_v;            // fp32(1 / V)
+};
+
+// the flat index, in a [V*N][HW] array, of the pixel of view v that shows pixel `pix` of sample n's identity view
+__device__ __forceinline__ unsigned view_index(const guided_args& g, const int N, const int v, const unsigned n, const unsigned pix) {
+    const unsigned f = ((unsigned)g.flips >> (2 * v)) & 3u;
+    unsigned y = pix / (unsigned)g.W, x = pix - y * (unsigned)g.W;
+    if (f & 1u) x = (unsigned)g.W - 1u - x;
+    if (f & 2u) y = (unsigned)g.H - 1u - y;
+    return ((unsigned)v * (unsigned)N + n) * (unsigned)(g.H * g.W) + y * (unsigned)g.W + x;
+}
+
+// p[0 .. K) = the K floats of pixel `at` of src — times those of the same pixel of wsrc, where wsrc is not null (uniform) —, p[k >= K] = 0.
+// vec: K == KP and the rows KP * 4-byte aligned (the launcher checks)
+template <int KP>
+__device__ __forceinline__ void load_pixel_row(float (&p)[KP], const float* const src, const size_t at, const float* const wsrc, const int K,
+                                               const int vec) {
+    static_assert(KP <= 4, "the one-thread-per-pixel kernels");
+    if (vec) {
+        if constexpr (KP == 2) {
+            const f32x2 t = reinterpret_cast<const f32x2*>(src)[at];
+            p[0] = t[0]; p[1] = t[1];
+            if (wsrc) {
+                const f32x2 w = reinterpret_cast<const f32x2*>(wsrc)[at];
+                p[0] = p[0] * w[0]; p[1] = p[1] * w[1];
+            }
+        } else {
+            const f32x4 t = reinterpret_cast<const f32x4*>(src)[at];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) p[k] = t[k];
+            if (wsrc) {
+                const f32x4 w = reinterpret_cast<const f32x4*>(wsrc)[at];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) p[k] = p[k] * w[k];
+            }
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < KP; ++k) p[k] = k < K ? (wsrc ? src[at * K + k] * wsrc[at * K + k] : src[at * K + k]) : 0.f;
+    }
+}
+
+// `a`: head = x0 (softmax = 0, head_stride = K), xt_next = xt, N = samples, no table, no noise buffer, no run block (launch_guided)
+template <int KP, bool VIEWS>
+__global__ __launch_bounds__(256) void k_guided(const ccdm_post_args a, const guided_args g, const float inv_t, const float top_r, const float al,
+                                                const float cu, const int mode, const int step, const int vec) {
+    const size_t npix = (size_t)a.N * a.HW;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npix) return;
+    const int K = a.K;
+    float q[KP];
+    [[maybe_unused]] unsigned at[4];
+    if constexpr (VIEWS) {
+        const unsigned n = (unsigned)(i / a.HW), pix = (unsigned)(i - (size_t)n * a.HW);
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            if (v < g.V) {                         // uniform
+                at[v] = v == 0 ? (unsigned)i : view_index(g, a.N, v, n, pix);
+                float p[KP];
+                load_pixel_row<KP>(p, a.head, at[v], nullptr, K, vec);
+#pragma unroll
+                for (int k = 0; k < KP; ++k) q[k] = v == 0 ? p[k] : q[k] + p[k];
+            } else {
+                at[v] = 0u;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < KP; ++k) q[k] = q[k] * g.inv_v;
+        if (g.ev) {                                // uniform
+            float w[KP];
+            load_pixel_row<KP>(w, g.ev, i, nullptr, K, vec);
+#pragma unroll
+            for (int k = 0; k < KP; ++k) q[k] = q[k] * w[k];
+        }
+    } else {
+        load_pixel_row<KP>(q, a.head, i, g.ev, K, vec);          // (one call: both loads issue inside the same vec branch)
+    }
+    shape_row<KP>(q, K, inv_t, top_r);
+    if constexpr (!VIEWS) {
+        posterior_pixel_core<KP>(a, i, q, step, al, cu, mode, (int)a.xt[i]);
+    } else {
+        int bi = 0;
+        posterior_pixel_core<KP>(a, i, q, step, al, cu, mode, (int)a.xt[i], &bi);
+        if (mode == CCDM_STEP_LAST_MAJORITY) bi = (int)a.xt_next[i];          // what the core has just stored: the argmax
+        else if (mode != CCDM_STEP_SAMPLE) return;
+        const bool onehot = mode == CCDM_STEP_SAMPLE && a.xin;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            if (v < g.V) {
+                if (v > 0) a.xt_next[at[v]] = (uint8_t)bi;
+                if (onehot) write_onehot(a.xin + (size_t)at[v] * a.xin_stride, K, bi);
+            }
+        }
+    }
+}
+
+template <int KP, int BLK, bool VIEWS>
+__global__ __launch_bounds__(BLK) void k_guided_staged(const ccdm_post_args a, const guided_args g, const float inv_t, const float top_r,
+                                                       const float al, const float cu, const int mode, const int step) {
+    constexpr int PITCH = (KP | 1) > CCDM_MAX_CLASSES ? CCDM_MAX_CLASSES : (KP | 1);      // odd, >= K
+    static_assert(!VIEWS || 3 * BLK <= BLK * PITCH, "the mirrored views' pixel indices reuse the rows");
+    __shared__ float sx[BLK * PITCH];
+    __shared__ int sb[BLK];
+    const size_t npix = (size_t)a.N * a.HW;
+    const size_t i0 = (size_t)blockIdx.x * BLK;
+    const int tid = threadIdx.x;
+    const int nvalid = (int)std::min<size_t>(BLK, npix - i0);
+    const int K = a.K;
+    const bool mine = tid < nvalid;
+    [[maybe_unused]] unsigned n = 0u, pix = 0u;                          // the thread's pixel in its sample's identity view
+    if constexpr (VIEWS) {
+        if (mine) { n = (unsigned)((i0 + tid) / a.HW); pix = (unsigned)(i0 + tid - (size_t)n * a.HW); }
+        stage_class_rows<BLK, PITCH, false>(sx, a.head + i0 * K, nullptr, nvalid, (unsigned)K, tid);
+        __syncthreads();
+        // the further views, added in view order into the one row per pixel; element idx of the block's run is thread idx % BLK's in
+        // every pass below, so the barriers are for sb alone
+        const RowDiv<~0u> row((unsigned)K);
+        const int total = nvalid * K;
+        for (int v = 1; v < g.V; ++v) {
+            if (mine) sb[tid] = (int)view_index(g, a.N, v, n, pix);
+            __syncthreads();
+            for (int idx = tid; idx < total; idx += BLK) {
+                const unsigned p = row((unsigned)idx), k = (unsigned)idx - p * (unsigned)K;
+                sx[p * PITCH + k] = sx[p * PITCH + k] + a.head[(size_t)(unsigned)sb[p] * K + k];
+            }
+            __syncthreads();
+        }
+        for (int idx = tid; idx < total; idx += BLK) {
+            const unsigned p = row((unsigned)idx), k = (unsigned)idx - p * (unsigned)K;
+            float m = sx[p * PITCH + k] * g.inv_v;
+            if (g.ev) m = m * g.ev[i0 * K + idx];                        // uniform
+            sx[p * PITCH + k] = m;
+        }
+    } else {
+        if (g.ev) stage_class_rows<BLK, PITCH, true>(sx, a.head + i0 * K, g.ev + i0 * K, nvalid, (unsigned)K, tid);          // uniform
+        else stage_class_rows<BLK, PITCH, false>(sx, a.head + i0 * K, nullptr, nvalid, (unsigned)K, tid);
+    }
+    __syncthreads();
+    int bi = 0;
+    if (mine) {
+        float x0[KP];
+        if constexpr (KP <= 32) {
+#pragma unroll
+            for (int k = 0; k < KP; ++k) x0[k] = k < K ? sx[tid * PITCH + k] : 0.f;
+            shape_row<KP>(x0, K, inv_t, top_r);
+        } else {
+            shape_lds_row(sx + tid * PITCH, K, inv_t, top_r);            // the thread's own row: no barrier
+#pragma unroll
+            for (int k = 0; k < KP; ++k) x0[k] = k < K ? sx[tid * PITCH + k] : 0.f;
+        }
+        // (&bi unconditionally: the core writes the one-hot itself only where xin is set, and where it is, store_onehot_rows does it below —
+        // a pointer that does not depend on `onehot` lets bi live in a register: no scratch)
+        posterior_pixel_core<KP>(a, i0 + tid, x0, step, al, cu, mode, (int)a.xt[i0 + tid], &bi);
+        if constexpr (VIEWS)
+            if (mode == CCDM_STEP_LAST_MAJORITY) bi = (int)a.xt_next[i0 + tid];          // what the core has just stored: the argmax
+    }
+    if constexpr (VIEWS)
+        if (mode != CCDM_STEP_SAMPLE && mode != CCDM_STEP_LAST_MAJORITY) return;          // uniform
+    const bool onehot = mode == CCDM_STEP_SAMPLE && a.xin;               // uniform
+    if (!onehot) {
+        if constexpr (VIEWS)
+            if (mine)
+                for (int v = 1; v < g.V; ++v) a.xt_next[view_index(g, a.N, v, n, pix)] = (uint8_t)bi;
+        return;
+    }
+    if constexpr (VIEWS) __syncthreads();                                // every thread has its row in registers: sx is free
+    [[maybe_unused]] int* const sat = reinterpret_cast<int*>(sx);        // [V - 1][BLK]: the pixels' indices in the mirrored views
+    sb[tid] = bi;
+    if constexpr (VIEWS) {
+        if (mine) {
+            for (int v = 1; v < g.V; ++v) {
+                const unsigned at = view_index(g, a.N, v, n, pix);
+                a.xt_next[at] = (uint8_t)bi;
+                sat[(v - 1) * BLK + tid] = (int)at;
+            }
+        }
+    }
+    __syncthreads();
+    const unsigned stride = (unsigned)a.xin_stride;
+    store_onehot_rows<BLK>(a.xin + i0 * stride, sb, nvalid, stride, K, tid);
+    if constexpr (VIEWS) {
+        const RowDiv<~0u> chan(stride);
+        const int span = nvalid * (int)stride;
+        for (int v = 1; v < g.V; ++v) {
+            for (int idx = tid; idx < span; idx += BLK) {
+                const unsigned p = chan((unsigned)idx), c = (unsigned)idx - p * stride;
+                if (c < (unsigned)K) a.xin[(size_t)(unsigned)sat[(v - 1) * BLK + p] * stride + c] = (int)c == sb[p] ? 1.0f : 0.0f;
+            }
+        }
+    }
+}
+
+// What the three entries hand to launch_guided
+struct guided_call {
+    const float *x0, *evidence;
+    int N, HW, K;
+    int H, W, V, flips;                     // VIEWS alone, where HW is H * W (formed here, behind the check of H and W)
+    float inv_temperature, top_r, alpha_t, cumalpha_tm1;
+    int mode, step_row;
+    uint64_t philox_seed;
+    uint32_t sample_offset;
+    uint8_t* xt;
+    float* xin;
+    int xin_stride;
+    float* out_probs;
+    int64_t* out_onehot;
+    void* stream;
+};
+
+// The one launcher.  `name`: the entry's, as its errors carry it; needs_evidence: a null evidence pointer is refused; takes_shaping:
+// (inv_temperature, top_r) are the caller's and are checked.  0, or fail()'s code.
+template <bool VIEWS>
+static int launch_guided(const char* name, const bool needs_evidence, const bool takes_shaping, const guided_call& c) {
+    const int N = c.N, K = c.K;
+    const int blk = K <= 32 ? 256 : 64;
+    int HW = c.HW;
+    if constexpr (VIEWS) {
+        CCDM_REQUIRE(c.V >= 1 && c.V <= 4, "%s: V=%d outside [1,4]", name, c.V);
+        CCDM_REQUIRE(c.flips >= 0 && c.flips < (1 << (2 * c.V)) && (c.flips & 3) == 0, "%s: flips 0x%x (view 0 is the identity, %d views)", name,
+                     c.flips, c.V);
+        CCDM_REQUIRE(c.H >= 1 && c.W >= 1 && (size_t)c.H * c.W <= 0x7FFFFFFFull, "%s: bad shape H=%d W=%d", name, c.H, c.W);
+        HW = c.H * c.W;
+    }
+    if (const int rc = check_step_args(name, c.x0 && c.xt && (c.evidence || !needs_evidence), N, HW, K, c.xin, c.xin_stride, c.mode, c.step_row, blk))
+        return rc;
+    if constexpr (VIEWS)
+        CCDM_REQUIRE((size_t)c.V * N * HW <= 0x7FFFFFFFull, "%s: too many pixels (V*N*H*W = %zu)", name, (size_t)c.V * N * HW);
+    if (takes_shaping) {
+        CCDM_REQUIRE(std::isfinite(c.inv_temperature) && c.inv_temperature >= 0.05f && c.inv_temperature <= 20.0f,
+                     "%s: inv_temperature %g outside [1/20,20]", name, (double)c.inv_temperature);
+        CCDM_REQUIRE(std::isfinite(c.top_r) && c.top_r > 0.0f && c.top_r <= 1.0f, "%s: top_r %g outside (0,1]", name, (double)c.top_r);
+    }
+    const size_t npix = (size_t)N * HW;
+    ccdm_post_args a = {};
+    a.head = c.x0; a.softmax = 0; a.head_stride = K;
+    a.xt = c.xt; a.xt_next = c.xt;
+    a.N = N; a.HW = HW; a.K = K;
+    a.philox_seed = c.philox_seed; a.sample_offset = c.sample_offset;
+    a.xin = c.xin; a.xin_stride = c.xin_stride;
+    a.out_probs = c.out_probs; a.out_onehot = c.out_onehot;
+    const guided_args g = VIEWS ? guided_args{c.evidence, c.H, c.W, c.V, c.flips, 1.0f / (float)c.V} : guided_args{c.evidence, 0, 0, 1, 0, 1.0f};
+    const dim3 grid((unsigned)((npix + blk - 1) / blk)), block(blk);
+    hipStream_t s = (hipStream_t)c.stream;
+    const float it = c.inv_temperature, tr = c.top_r, al = c.alpha_t, cu = c.cumalpha_tm1;
+    const int mode = c.mode, step_row = c.step_row;
+    dispatch_kp<256>(K, [&](auto kp) {
+        constexpr int KP = decltype(kp)::value;
+        if constexpr (KP <= 4) {
+            const uintptr_t both = reinterpret_cast<uintptr_t>(c.x0) | reinterpret_cast<uintptr_t>(c.evidence);          // (null: no bits)
+            const int vec = (K == 2 && (both & 7) == 0) || (K == 4 && (both & 15) == 0);
+            hipLaunchKernelGGL((k_guided<KP, VIEWS>), grid, block, 0, s, a, g, it, tr, al, cu, mode, step_row, vec);
+        } else {
+            hipLaunchKernelGGL((k_guided_staged<KP, (KP <= 32 ? 256 : 64), VIEWS>), grid, block, 0, s, a, g, it, tr, al, cu, mode, step_row);
+        }
+    });
+    CCDM_CHECK_LAUNCH(name);
+    return 0;
+}
+
+}  // namespace ccdm
+
+using namespace ccdm;
+
+extern "C" int ccdm_evidence_step(const float* x0, const float* evidence, int N, int HW, int K, float alpha_t, float cumalpha_tm1, int mode,
+                                  int step_row, uint64_t philox_seed, uint32_t sample_offset, uint8_t* xt, float* xin, int xin_stride,
+                                  float* out_probs, int64_t* out_onehot, void* stream) {
+    return launch_guided<false>("evidence_step", true, false,
+                                {x0, evidence, N, HW, K, 0, 0, 1, 0, 1.0f, 1.0f, alpha_t, cumalpha_tm1, mode, step_row, philox_seed, sample_offset,
+                                 xt, xin, xin_stride, out_probs, out_onehot, stream});
+}
+
+extern "C" int ccdm_shaped_step(const float* x0, const float* evidence, int N, int HW, int K, float inv_temperature, float top_r, float alpha_t,
+                                float cumalpha_tm1, int mode, int step_row, uint64_t philox_seed, uint32_t sample_offset, uint8_t* xt, float* xin,
+                                int xin_stride, float* out_probs, int64_t* out_onehot, void* stream) {
+    return launch_guided<false>("ccdm_shaped_step", false, true,
+                                {x0, evidence, N, HW, K, 0, 0, 1, 0, inv_temperature, top_r, alpha_t, cumalpha_tm1, mode, step_row, philox_seed,
+                                 sample_offset, xt, xin, xin_stride, out_probs, out_onehot, stream});
+}
+
+extern "C" int ccdm_views_step(const float* x0, const float* evidence, int N, int H, int W, int K, int V, int flips, float inv_temperature, float top_r,
+                               float alpha_t, float cumalpha_tm1, int mode, int step_row, uint64_t philox_seed, uint32_t sample_offset, uint8_t* xt,
+                               float* xin, int xin_stride, float* out_probs, int64_t* out_onehot, void* stream) {
+    return launch_guided<true>("ccdm_views_step", false, true,
+                               {x0, evidence, N, 0, K, H, W, V, flips, inv_temperature, top_r, alpha_t, cumalpha_tm1, mode, step_row, philox_seed,
+                                sample_offset, xt, xin, xin_stride, out_probs, out_onehot, stream});
+}

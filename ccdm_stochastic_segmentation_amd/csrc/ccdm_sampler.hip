@@ -11,7 +11,7 @@
 //   idx   = argmax_k Phat_k / E_k, first maximum wins                               torch.multinomial(n=1)
 // That arithmetic, the LDS staging of the many-class kernel and the K -> KP ladder of the launcher are defined once, in
 // ccdm_sampler_common.h (posterior_pixel_core, stage_class_rows / store_onehot_rows, dispatch_kp), for this file, ccdm_head.hip and
-// ccdm_evidence.hip.
+// ccdm_guided.hip.
 #include "ccdm_common.h"
 #include "ccdm_sampler_common.h"
 

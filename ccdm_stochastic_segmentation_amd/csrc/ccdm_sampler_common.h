@@ -1,6 +1,6 @@
 // The per-pixel arithmetic of the step epilogue — softmax_K -> categorical posterior -> clamp -> normalise -> Exp(1)-race argmax (or the
 // last-step outputs) — shared by the stand-alone epilogue kernel (ccdm_sampler.hip), the head kernel that ends in it (ccdm_head.hip)
-// and the evidence step (ccdm_evidence.hip): ONE definition, so all produce the same bits from the same values.  See ccdm_sampler.hip
+// and the guided steps (ccdm_guided.hip): ONE definition, so all produce the same bits from the same values.  See ccdm_sampler.hip
 // for the arithmetic order.  Also here, once each: the two LDS passes of the staged kernels (stage_class_rows, store_onehot_rows), the
 // per-thread one-hot store (write_onehot), the K -> KP ladder of the launchers (dispatch_kp) and the argument checks the step entry
 // points share (check_step_args).
@@ -221,7 +221,7 @@ __device__ __forceinline__ void posterior_pixel(const ccdm_post_args& a, const s
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// The staged kernels (k_posterior_staged, k_evidence_staged): a block's BLK pixels move as what they are, one contiguous run of
+// The staged kernels (k_posterior_staged, k_guided_staged): a block's BLK pixels move as what they are, one contiguous run of
 // [pixel][class] floats in and [pixel][xin_stride] floats out: 16-byte requests in lane order, exchanged through LDS rows padded to an
 // odd pitch (conflict-free per-thread reads), element by element where the run is not a whole number of aligned 16-byte pieces.
 
@@ -310,7 +310,7 @@ __device__ __forceinline__ void write_onehot(float* const d, const int K, const 
 // Host side.  The ladder from K to the padded class count KP a kernel is instantiated for: f(std::integral_constant<int, KP>{}) for the
 // first rung >= K, the rung MAX for everything above the one below it.  (The per-class work — four IEEE divisions, an exponential, a
 // quarter Philox block — is predicated, not skipped, beyond K: Cityscapes' K = 20 on the 32-wide instantiation did 60 % more arithmetic
-// than it needed, hence 20 and 24.)  The register kernels end at 32; the rungs above are the evidence kernel's.
+// than it needed, hence 20 and 24.)  The register kernels end at 32; the rungs above are the guided kernels'.
 constexpr int KP_LADDER[] = {2, 4, 8, 16, 20, 24, 32, 64, 128, 256};
 
 template <int MAX = 32, int I = 0, class F>
@@ -321,7 +321,7 @@ inline void dispatch_kp(const int K, F&& f) {
     else dispatch_kp<MAX, I + 1>(K, std::forward<F>(f));
 }
 
-// What ccdm_known_labels_step, ccdm_renoise_step and ccdm_evidence_step check alike (`name`: the entry's, without the prefix; `pointers`:
+// What ccdm_known_labels_step, ccdm_renoise_step and the guided steps check alike (`name`: the entry's, as its errors carry it; `pointers`:
 // the entry's required pointers are all there; `blk`: pixels per block of the launch).  0, or fail()'s code.
 inline int check_step_args(const char* name, const bool pointers, const int N, const int HW, const int K, const float* xin, const int xin_stride,
                            const int mode, const int step_row, const int blk) {

@@ -1,6 +1,6 @@
 // The shaping of a pixel's x0 row before the reverse step — temper relative to the row's largest value, then cut to the smallest set of
 // classes whose mass reaches top_r (THE definition: include/ccdm_hip.h, ccdm_shaped_step) — in its two forms, on registers and on an LDS
-// row: ONE definition for the kernels that shape a row in front of posterior_pixel_core (ccdm_shaped.hip, ccdm_views.hip).
+// row: ONE definition for the kernels that shape a row in front of posterior_pixel_core (ccdm_guided.hip).
 #pragma once
 #include "ccdm_common.h"
 

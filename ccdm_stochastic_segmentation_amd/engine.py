@@ -602,55 +602,38 @@ class SamplerEngine:
             self.N, self.H * self.W, self.K, float(p_stay), float(p_move), int(step_row), *self._step_state_args(philox_seed, sample_offset),
             self._stream()), "renoise_step")
 
-    def evidence_step(self, evidence: torch.Tensor, alpha_t: float, cumalpha_tm1: float, mode: int, step_row: int, *, philox_seed: int = 0,
-                      sample_offset: int = 0) -> None:
-        """The reverse step under per-pixel soft evidence (ccdm_evidence_step, asynchronous on the engine's stream), behind a `run` of a
-        table row whose mode is STEP_SOFTMAX_ONLY: that run left the network's x0 in out_probs and x_t in xt; this multiplies x0 by the
-        weights and does the step of (alpha_t, cumalpha_tm1, mode) — the real columns of row `step_row` — with the Philox counters the
-        unguided step of that row uses.  evidence: fp32 [N,H*W,K] on the engine's device, weights in [0,1]."""
-        assert evidence.dtype == torch.float32 and evidence.is_cuda and evidence.is_contiguous() \
-            and tuple(evidence.shape) == (self.N, self.H * self.W, self.K)
-        hip.check(self.lib.ccdm_evidence_step(
-            self.out_probs.data_ptr(), evidence.data_ptr(), self.N, self.H * self.W, self.K, float(alpha_t), float(cumalpha_tm1), int(mode),
-            int(step_row), *self._step_state_args(philox_seed, sample_offset), self.out_probs.data_ptr(), self.out_onehot.data_ptr(),
-            self._stream()), "evidence_step")
-        self._evidence_keepalive = evidence
-
-    def shaped_step(self, evidence: Optional[torch.Tensor], inv_temperature: float, top_r: float, alpha_t: float, cumalpha_tm1: float,
-                    mode: int, step_row: int, *, philox_seed: int = 0, sample_offset: int = 0) -> None:
-        """The reverse step on a tempered and truncated x0 (ccdm_shaped_step, asynchronous on the engine's stream), behind a `run` of a
-        table row whose mode is STEP_SOFTMAX_ONLY, as `evidence_step`: x0 (times the evidence's weights, where there are any) is
-        tempered with exponent inv_temperature, cut to the smallest set of classes whose mass reaches top_r (include/ccdm_hip.h has the
-        definition), and the step of (alpha_t, cumalpha_tm1, mode) — the real columns of row `step_row` — follows with the Philox
-        counters the unguided step of that row uses.  evidence: None, or fp32 [N,H*W,K] on the engine's device, weights in [0,1]."""
-        assert evidence is None or (evidence.dtype == torch.float32 and evidence.is_cuda and evidence.is_contiguous()
-                                    and tuple(evidence.shape) == (self.N, self.H * self.W, self.K))
-        hip.check(self.lib.ccdm_shaped_step(
-            self.out_probs.data_ptr(), None if evidence is None else evidence.data_ptr(), self.N, self.H * self.W, self.K,
-            float(inv_temperature), float(top_r), float(alpha_t), float(cumalpha_tm1), int(mode), int(step_row),
-            *self._step_state_args(philox_seed, sample_offset), self.out_probs.data_ptr(), self.out_onehot.data_ptr(), self._stream()),
-            "shaped_step")
-        self._evidence_keepalive = evidence
-
-    def views_step(self, flips: Sequence[int], evidence: Optional[torch.Tensor], inv_temperature: float, top_r: float, alpha_t: float,
-                   cumalpha_tm1: float, mode: int, step_row: int, *, philox_seed: int = 0, sample_offset: int = 0) -> None:
-        """The reverse step on the mean of x0 over the V = 1 + len(flips) views of every sample (ccdm_views_step, asynchronous on the
-        engine's stream), behind a `run` of a table row whose mode is STEP_SOFTMAX_ONLY, as `shaped_step` and in its place.  The
-        engine's rows are the views of N = rows / V samples, view-major: row v * N + j is view v of sample j, view 0 the identity,
-        view v >= 1 mirrored as flips[v - 1] says (bit 0 mirrors x, bit 1 mirrors y).  The mean is taken per pixel of the identity
-        view, evidence and shaping follow as in `shaped_step` (neutral: 1.0, 1.0), the draw uses the Philox counters of the unguided
-        step of sample sample_offset + j, and the drawn class goes to every view at its mirrored place; the last-step outputs are
-        the first N rows of out_probs / out_onehot (include/ccdm_hip.h has the definition).  evidence: None, or fp32 [N,H*W,K]."""
+    def guided_step(self, evidence: Optional[torch.Tensor], shaping: Optional[Tuple[float, float]], views: Optional[Sequence[int]],
+                    alpha_t: float, cumalpha_tm1: float, mode: int, step_row: int, *, philox_seed: int = 0, sample_offset: int = 0) -> None:
+        """The reverse step behind a `run` of a table row whose mode is STEP_SOFTMAX_ONLY (asynchronous on the engine's stream): that run
+        left the network's x0 in out_probs and x_t in xt; this reshapes x0 and does the step of (alpha_t, cumalpha_tm1, mode) — the real
+        columns of row `step_row` — with the Philox counters the unguided step of that row uses (include/ccdm_hip.h has the definitions).
+        views: None, or the flip codes of views 1 .. V - 1 (bit 0 mirrors x, bit 1 mirrors y): the engine's rows are the V views of
+          n = N / V samples, view-major (row v * n + j is view v of sample j, view 0 the identity); x0 becomes its mean over the views per
+          pixel of the identity view, the counters are those of sample sample_offset + j, the drawn class goes to every view at its
+          mirrored place, and the last-step outputs are the first n rows of out_probs / out_onehot.
+        evidence: None, or fp32 [n,H*W,K] on the engine's device, weights in [0,1]: x0 is multiplied by them.
+        shaping: None, or (inv_temperature, top_r): x0 is tempered with that exponent and cut to the smallest set of classes whose mass
+          reaches top_r.
+        One launch: ccdm_views_step where there are views (neutral shaping: 1.0, 1.0), else ccdm_shaped_step where there is shaping, else
+        ccdm_evidence_step."""
+        flips = () if views is None else tuple(int(f) for f in views)
         V = 1 + len(flips)
-        assert 1 <= V <= 4 and self.N % V == 0 and all(0 <= int(f) <= 3 for f in flips)
+        assert 1 <= V <= 4 and self.N % V == 0 and all(0 <= f <= 3 for f in flips)
         n = self.N // V
         assert evidence is None or (evidence.dtype == torch.float32 and evidence.is_cuda and evidence.is_contiguous()
                                     and tuple(evidence.shape) == (n, self.H * self.W, self.K))
-        hip.check(self.lib.ccdm_views_step(
-            self.out_probs.data_ptr(), None if evidence is None else evidence.data_ptr(), n, self.H, self.W, self.K, V,
-            sum(int(f) << (2 * (v + 1)) for v, f in enumerate(flips)), float(inv_temperature), float(top_r), float(alpha_t),
-            float(cumalpha_tm1), int(mode), int(step_row), *self._step_state_args(philox_seed, sample_offset), self.out_probs.data_ptr(),
-            self.out_onehot.data_ptr(), self._stream()), "views_step")
+        ev = None if evidence is None else evidence.data_ptr()
+        tail = (float(alpha_t), float(cumalpha_tm1), int(mode), int(step_row), *self._step_state_args(philox_seed, sample_offset),
+                self.out_probs.data_ptr(), self.out_onehot.data_ptr(), self._stream())
+        x0 = self.out_probs.data_ptr()
+        if views is not None:
+            inv_t, top_r = shaping or (1.0, 1.0)
+            hip.check(self.lib.ccdm_views_step(x0, ev, n, self.H, self.W, self.K, V, sum(f << (2 * (v + 1)) for v, f in enumerate(flips)),
+                                               float(inv_t), float(top_r), *tail), "views_step")
+        elif shaping is not None:
+            hip.check(self.lib.ccdm_shaped_step(x0, ev, n, self.H * self.W, self.K, float(shaping[0]), float(shaping[1]), *tail), "shaped_step")
+        else:
+            hip.check(self.lib.ccdm_evidence_step(x0, ev, n, self.H * self.W, self.K, *tail), "evidence_step")
         self._evidence_keepalive = evidence
 
     def ce_logits(self) -> Optional[torch.Tensor]:

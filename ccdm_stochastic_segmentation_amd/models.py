@@ -1024,7 +1024,7 @@ class DenoisingModel(nn.Module):
             raise ValueError(f"unknown rng mode {self.rng!r}")
         host_rng = self.rng == "torch_cpu"
         # evidence, shaping, views: the network pass of every row stops at x0 (out_probs; x_t untouched), the row's real step follows in
-        # evidence_step / shaped_step / views_step
+        # guided_step
         stop_at_x0 = evidence is not None or shaping is not None or views is not None
         table = coeffs if not stop_at_x0 else [(a_, c_, hip.STEP_SOFTMAX_ONLY) for a_, c_, m_ in coeffs]
         # known labels: cumalpha of the state each row produces; the last row returns the labels themselves (class docstring)
@@ -1074,20 +1074,14 @@ class DenoisingModel(nn.Module):
 
         def run_row(eng, lo: int, hi: int, row: int, kp: int, renoise, noise, noise_row0_: int, graph_: bool):
             """One walk entry of one sub-batch, all on the engine's stream: the renoise back up the chain to the state before `row` (if a
-            jump precedes the entry), the network's step, the views, the shaped or the evidence step behind a network pass that stopped
-            at x0 (one launch: the shaped step applies the evidence too, the views step both), the clamp (the next step reads the
-            clamped state).  kp: the Philox key of this pass of the row."""
+            jump precedes the entry), the network's step, the guided step behind a network pass that stopped at x0 (one launch: views,
+            evidence and shaping), the clamp (the next step reads the clamped state).  kp: the Philox key of this pass of the row."""
             off = self.sample_offset + lo
             if renoise is not None:
                 eng.renoise(*renoise, row, philox_seed=kp, sample_offset=off)
             eng.run(1, first_row=row, noise=noise, noise_row0=noise_row0_, philox_seed=kp, sample_offset=off, use_graph=graph_)
-            if views is not None:
-                eng.views_step(views, None if evidence is None else evidence[lo:hi], *(shaping or (1.0, 1.0)), *coeffs[row], row,
-                               philox_seed=kp, sample_offset=off)
-            elif shaping is not None:
-                eng.shaped_step(None if evidence is None else evidence[lo:hi], *shaping, *coeffs[row], row, philox_seed=kp, sample_offset=off)
-            elif evidence is not None:
-                eng.evidence_step(evidence[lo:hi], *coeffs[row], row, philox_seed=kp, sample_offset=off)
+            if stop_at_x0:
+                eng.guided_step(None if evidence is None else evidence[lo:hi], shaping, views, *coeffs[row], row, philox_seed=kp, sample_offset=off)
             if known is not None:
                 eng.clamp_known_labels(known[lo:hi], clamp_c[row], coeffs[row][2], row, philox_seed=kp, sample_offset=off)
 

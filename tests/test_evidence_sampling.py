@@ -64,7 +64,7 @@ def test_evidence_symbol_declared_bound_and_built():
     """hip.py binds the symbol with argtypes that match the header's declaration (17 arguments), the source is in the build list, the
     library cross-built from it exports it under the unchanged ABI number, and every bad argument is refused before anything is launched
     (host pointers: a launch would fault) with the expected word in the error string."""
-    lib = assert_symbol_declared_bound_and_built(SYMBOL, 17, "ccdm_evidence.hip")
+    lib = assert_symbol_declared_bound_and_built(SYMBOL, 17, "ccdm_guided.hip")
     buf = np.zeros(256, dtype=np.float32)
     p = buf.ctypes.data
     good = dict(x0=p, ev=p, N=1, HW=8, K=2, a=0.5, c=0.5, mode=hip.STEP_SAMPLE, step_row=0, seed=0, off=0, xt=p, xin=None, stride=4,

@@ -103,7 +103,7 @@ def test_shaped_symbol_declared_bound_and_built():
     """hip.py binds the symbol with argtypes that match the header's declaration (19 arguments), the source is in the build list, the
     library cross-built from it exports it under the unchanged ABI number, and every bad argument is refused before anything is launched
     (host pointers: a launch would fault) with the expected word and the entry's name in the error string."""
-    lib = assert_symbol_declared_bound_and_built(SYMBOL, 19, "ccdm_shaped.hip")
+    lib = assert_symbol_declared_bound_and_built(SYMBOL, 19, "ccdm_guided.hip")
     buf = np.zeros(256, dtype=np.float32)
     p = buf.ctypes.data
     good = dict(x0=p, ev=p, N=1, HW=8, K=2, inv=1.0, r=1.0, a=0.5, c=0.5, mode=hip.STEP_SAMPLE, step_row=0, seed=0, off=0, xt=p, xin=None,
@@ -381,7 +381,8 @@ def test_truncating_kernel_equals_the_restatement(lib, N, HW, K):
 @pytest.mark.parametrize("N,HW,K", SHAPES)
 def test_neutral_values_are_the_plain_and_the_evidence_step(lib, N, HW, K):
     """(inv_temperature, top_r) = (1, 1): without evidence the bits of ccdm_posterior_sample (softmax = 0) on the same inputs, with
-    evidence those of ccdm_evidence_step — xt, and out_probs in confidence mode with x0 aliased."""
+    evidence those of the numpy evidence restatement — xt, and out_probs in confidence mode with x0 aliased.  ccdm_evidence_step launches
+    this kernel at (1, 1), so the two entries are held to agree as well: that guards the entry's wiring, not the arithmetic."""
     rng = np.random.default_rng(6000 + K)
     x0, ev, xt = mixed_inputs(rng, N, HW, K)
     row, off = 3, 5
@@ -393,11 +394,13 @@ def test_neutral_values_are_the_plain_and_the_evidence_step(lib, N, HW, K):
         assert np.array_equal(bits(got["x0"]), bits(run_posterior_sample(lib, x0, xt, a, c, hip.STEP_LAST_CONFIDENCE, row, off)[1])), t
         assert np.array_equal(got["xt"], xt.astype(np.uint8))
         kw = dict(step_row=row, sample_offset=off)
+        probs, idx = evidence_restatement(x0, ev, xt, a, c, hip.STEP_SAMPLE, row, SEED, off)
         got = run_kernel(lib, x0, ev, xt, 1.0, 1.0, a, c, hip.STEP_SAMPLE, **kw)["xt"]
+        assert np.array_equal(got.astype(np.int64), idx), f"t={t}: {int((got != idx).sum())} of {idx.size} pixels differ"
         assert np.array_equal(got, run_kernel(lib, x0, ev, xt, 1.0, 1.0, a, c, hip.STEP_SAMPLE, symbol="ccdm_evidence_step", **kw)["xt"]), t
         got = run_kernel(lib, x0, ev, xt, 1.0, 1.0, a, c, hip.STEP_LAST_CONFIDENCE, alias=True, **kw)["x0"]
-        ref = run_kernel(lib, x0, ev, xt, 1.0, 1.0, a, c, hip.STEP_LAST_CONFIDENCE, alias=True, symbol="ccdm_evidence_step", **kw)["x0"]
-        assert np.array_equal(bits(got), bits(ref)) and not np.array_equal(bits(got), bits(x0)), t
+        assert np.array_equal(bits(got), bits(probs)), f"t={t}: {int((bits(got) != bits(probs)).sum())} probabilities differ"
+        assert not np.array_equal(bits(got), bits(x0)), t
 
 
 @pytest.mark.gpu

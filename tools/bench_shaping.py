@@ -2,12 +2,12 @@
 """Times temperature and truncation sampling (DenoisingModel(..., temperature=, truncation=)) in one run.
 
     shaped_kernel     ccdm_shaped_step alone at 64 x 128x128, K = 2 (one thread per pixel, no xin) and at 4 x 128x256, K = 20 with xin
-                      (the staged kernel), in STEP_SAMPLE, beside ccdm_evidence_step on the same inputs — the yardstick: the shaped launch
-                      moves the same bytes and adds the selection.  Device events around `--launches` back-to-back launches (so a
-                      launch's share of the queue, not a kernel trace), rounds interleaved in rotating order.  Cases, all with evidence
-                      unless named otherwise:
-                        evidence            ccdm_evidence_step
-                        neutral             (tau, r) = (1, 1): both parts skipped
+                      (the staged kernel), in STEP_SAMPLE.  The yardstick is the kernel itself at (tau, r) = (1, 1), where both parts
+                      are skipped: the same bytes moved, without the selection.  Device events around `--launches` back-to-back
+                      launches (so a launch's share of the queue, not a kernel trace), rounds interleaved in rotating order.  Cases,
+                      all with evidence unless named otherwise:
+                        evidence_entry      ccdm_evidence_step: the same kernel at (1, 1) through the entry that takes no shaping
+                        neutral             (tau, r) = (1, 1) through ccdm_shaped_step
                         truncate            r = 0.9 on flat rows (every entry within a factor 3 of the others: at K = 20 a pixel scans
                                             about 18 times before its mass reaches r)
                         truncate_peaked     r = 0.9 on rows that are softmax of 4 N(0,1) logits (one to three scans), mixed pixel by
@@ -72,7 +72,7 @@ def bench_kernel(dev, launches, rounds):
                 hip.check(lib.ccdm_shaped_step(x0p, evp, N, HW, K, inv, top_r, a, c, hip.STEP_SAMPLE, i % 250, 1, 0, xt.data_ptr(), xp, stride,
                                                None, None, stream), "shaped_step")
             return launch
-        fns = {"evidence": evidence, "neutral": shaped("flat", True, 1.0, 1.0), "truncate": shaped("flat", True, 1.0, 0.9),
+        fns = {"evidence_entry": evidence, "neutral": shaped("flat", True, 1.0, 1.0), "truncate": shaped("flat", True, 1.0, 0.9),
                "truncate_peaked": shaped("peaked", True, 1.0, 0.9), "temper": shaped("flat", True, inv_tau, 1.0),
                "temper_truncate": shaped("flat", True, inv_tau, 0.9), "truncate_no_evidence": shaped("flat", False, 1.0, 0.9)}
         us = {k: [] for k in fns}
@@ -93,7 +93,7 @@ def bench_kernel(dev, launches, rounds):
             order = order[1:] + order[:1]                    # (the first window of a round starts on an idle device)
         med = {k: float(np.median(v)) for k, v in us.items()}
         out[name] = {"us_per_launch": {k: {"median": round(med[k], 3), "min": round(min(v), 3), "max": round(max(v), 3)} for k, v in us.items()},
-                     "over_evidence": {k: round(med[k] / med["evidence"], 3) for k in fns if k != "evidence"}}
+                     "over_neutral": {k: round(med[k] / med["neutral"], 3) for k in fns if k != "neutral"}}
     return out
 
 
