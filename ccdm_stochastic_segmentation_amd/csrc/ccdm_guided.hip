@@ -13,6 +13,12 @@
 //   shaping   (temperature=, truncation=, ccdm_shaped_step) the row is tempered relative to its largest value, then cut to the
 //             smallest set of classes whose mass reaches top_r: shape_row / shape_lds_row (ccdm_shaping.h).  (1, 1) skips both parts
 //             by uniform branches.
+//   tiles     (tiles=, ccdm_tiled_step; in the views' place, never together with them) a canvas larger than the network's geometry: the
+//             engine's rows are overlapping tiles of the canvas state, tile-major, and x0 of a canvas pixel is the mean over the c >= 1
+//             tiles that cover it, summed in tile order and multiplied once by fp32(1 / c); the draw is keyed by the canvas pixel and
+//             the sample, and the class goes to the canvas state and back to every covering tile, so the tiles stay crops of one state.
+//             A kernel pair of its own (k_tiled, k_tiled_staged) below the guided pair, on the same shared pieces: the geometric map is a
+//             run-time loop over a per-pixel number of contributors where the views' is an unrolled loop over at most four.
 // THE definitions: include/ccdm_hip.h.  ONE kernel pair in two instantiations: VIEWS = false is ccdm_shaped_step and, at (1, 1) with
 // the evidence required, ccdm_evidence_step (a kernel of its own for that was 1.003x / 1.00x of this one: DESIGN.md section 4);
 // VIEWS = true is ccdm_views_step, which cannot stand in for the other at V = 1 (1.07x / 1.14x, its extra LDS pass).
@@ -252,6 +258,190 @@ __global__ __launch_bounds__(BLK) void k_guided_staged(const ccdm_post_args a, c
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Tiles (ccdm_tiled_step): the same construction as the views with translations for mirrors and a per-pixel number of contributors.
+// `a` describes the CANVAS (head = the tiles' x0, xt = xt_next = the canvas state, N = samples, HW = Hc * Wc, out_probs / out_onehot
+// the canvas's, no xin: the core draws and writes the canvas state, the kernel carries the class to the covering tiles).
+
+// What a tiled launch takes next to ccdm_post_args
+struct tiled_args {
+    const float* ev;        // canvas evidence [N,Hc*Wc,K] or null
+    uint8_t* txt;           // the tiles' xt [R*N,h*w]
+    float* txin;            // the tiles' xin [R*N,h*w,xin_stride] or null
+    int xin_stride;
+    int Hc, Wc, h, w, sy, sx, Ty, Tx;
+    int cmax;               // the largest number of covering tiles of any canvas pixel
+};
+
+// Along one axis (extent L, tile extent l, stride s, T tiles with origins min(i * s, L - l): include/ccdm_hip.h): the tiles i0 .. i1
+// that cover coordinate y.  Tile i < T - 1 starts at i * s < L - l, the last one at L - l.
+__host__ __device__ __forceinline__ void covering_tiles(const int y, const int L, const int l, const int s, const int T, int& i0, int& i1) {
+    i1 = y >= L - l ? T - 1 : y / s;
+    const int first = y < l ? 0 : (y - l) / s + 1;                       // the first i with i * s + l > y
+    i0 = first < T - 1 ? first : T - 1;
+}
+
+// a canvas pixel and the tiles i0 .. i1 x j0 .. j1 that cover it
+struct tile_cover {
+    unsigned n;
+    int y, x, i0, i1, j0, j1;
+    __device__ __forceinline__ int count() const { return (i1 - i0 + 1) * (j1 - j0 + 1); }
+};
+
+__device__ __forceinline__ tile_cover cover_of(const tiled_args& g, const size_t i) {
+    tile_cover c;
+    const unsigned hw = (unsigned)(g.Hc * g.Wc);
+    c.n = (unsigned)(i / hw);
+    const unsigned pix = (unsigned)(i - (size_t)c.n * hw);
+    c.y = (int)(pix / (unsigned)g.Wc);
+    c.x = (int)(pix - (unsigned)c.y * (unsigned)g.Wc);
+    covering_tiles(c.y, g.Hc, g.h, g.sy, g.Ty, c.i0, c.i1);
+    covering_tiles(c.x, g.Wc, g.w, g.sx, g.Tx, c.j0, c.j1);
+    return c;
+}
+
+// the flat index, in a [R*N][h*w] array, of the pixel of tile (ti, tj) of sample c.n that shows the canvas pixel c
+__device__ __forceinline__ unsigned tile_index(const tiled_args& g, const int N, const tile_cover& c, const int ti, const int tj) {
+    const int oy = min(ti * g.sy, g.Hc - g.h), ox = min(tj * g.sx, g.Wc - g.w);
+    return ((unsigned)(ti * g.Tx + tj) * (unsigned)N + c.n) * (unsigned)(g.h * g.w) + (unsigned)((c.y - oy) * g.w + (c.x - ox));
+}
+
+template <int KP>
+__global__ __launch_bounds__(256) void k_tiled(const ccdm_post_args a, const tiled_args g, const float inv_t, const float top_r, const float al,
+                                               const float cu, const int mode, const int step, const int vec) {
+    const size_t npix = (size_t)a.N * a.HW;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npix) return;
+    const int K = a.K;
+    const tile_cover c = cover_of(g, i);
+    float q[KP];
+    load_pixel_row<KP>(q, a.head, tile_index(g, a.N, c, c.i0, c.j0), nullptr, K, vec);
+    for (int ti = c.i0; ti <= c.i1; ++ti) {                              // ascending r = ti * Tx + tj
+        for (int tj = ti == c.i0 ? c.j0 + 1 : c.j0; tj <= c.j1; ++tj) {
+            float p[KP];
+            load_pixel_row<KP>(p, a.head, tile_index(g, a.N, c, ti, tj), nullptr, K, vec);
+#pragma unroll
+            for (int k = 0; k < KP; ++k) q[k] = q[k] + p[k];
+        }
+    }
+    const float inv_c = 1.0f / (float)c.count();
+#pragma unroll
+    for (int k = 0; k < KP; ++k) q[k] = q[k] * inv_c;
+    if (g.ev) {                                    // uniform
+        float w[KP];
+        load_pixel_row<KP>(w, g.ev, i, nullptr, K, vec);
+#pragma unroll
+        for (int k = 0; k < KP; ++k) q[k] = q[k] * w[k];
+    }
+    shape_row<KP>(q, K, inv_t, top_r);
+    int bi = 0;
+    posterior_pixel_core<KP>(a, i, q, step, al, cu, mode, (int)a.xt[i], &bi);
+    if (mode == CCDM_STEP_LAST_MAJORITY) bi = (int)a.xt_next[i];          // what the core has just stored: the argmax
+    else if (mode != CCDM_STEP_SAMPLE) return;
+    const bool onehot = mode == CCDM_STEP_SAMPLE && g.txin;
+    for (int ti = c.i0; ti <= c.i1; ++ti) {
+        for (int tj = c.j0; tj <= c.j1; ++tj) {
+            const unsigned at = tile_index(g, a.N, c, ti, tj);
+            g.txt[at] = (uint8_t)bi;
+            if (onehot) write_onehot(g.txin + (size_t)at * g.xin_stride, K, bi);
+        }
+    }
+}
+
+template <int KP, int BLK>
+__global__ __launch_bounds__(BLK) void k_tiled_staged(const ccdm_post_args a, const tiled_args g, const float inv_t, const float top_r,
+                                                      const float al, const float cu, const int mode, const int step) {
+    constexpr int PITCH = (KP | 1) > CCDM_MAX_CLASSES ? CCDM_MAX_CLASSES : (KP | 1);      // odd, >= K
+    static_assert(BLK <= BLK * PITCH, "the tile pixels' indices reuse the rows");
+    __shared__ float sx[BLK * PITCH];
+    __shared__ int sb[BLK];
+    const size_t npix = (size_t)a.N * a.HW;
+    const size_t i0 = (size_t)blockIdx.x * BLK;
+    const int tid = threadIdx.x;
+    const int nvalid = (int)std::min<size_t>(BLK, npix - i0);
+    const int K = a.K;
+    const bool mine = tid < nvalid;
+    tile_cover c = {};
+    int cnt = 0;
+    if (mine) { c = cover_of(g, i0 + tid); cnt = c.count(); }
+    // The covering tiles, added in ascending r into the one row per pixel, a pass over the block's [pixel][class] run per contributor
+    // rank; the pixel's source index comes from LDS (sb, written by the pixel's thread; -1: the pixel has fewer contributors and sits
+    // the pass out).  Element idx of the run is thread idx % BLK's in every pass, so the barriers are for sb alone.
+    const RowDiv<~0u> row((unsigned)K);
+    const int total = nvalid * K;
+    int ti = c.i0, tj = c.j0;
+    for (int rank = 0; rank < g.cmax; ++rank) {
+        if (mine) {
+            sb[tid] = rank < cnt ? (int)tile_index(g, a.N, c, ti, tj) : -1;
+            if (++tj > c.j1) { tj = c.j0; ++ti; }
+        }
+        __syncthreads();
+        for (int idx = tid; idx < total; idx += BLK) {
+            const unsigned p = row((unsigned)idx), k = (unsigned)idx - p * (unsigned)K;
+            const int s = sb[p];
+            if (s >= 0) {
+                const float v = a.head[(size_t)(unsigned)s * K + k];
+                sx[p * PITCH + k] = rank == 0 ? v : sx[p * PITCH + k] + v;
+            }
+        }
+        __syncthreads();
+    }
+    if (mine) sb[tid] = __float_as_int(1.0f / (float)cnt);
+    __syncthreads();
+    for (int idx = tid; idx < total; idx += BLK) {
+        const unsigned p = row((unsigned)idx), k = (unsigned)idx - p * (unsigned)K;
+        float m = sx[p * PITCH + k] * __int_as_float(sb[p]);
+        if (g.ev) m = m * g.ev[i0 * K + idx];                            // uniform
+        sx[p * PITCH + k] = m;
+    }
+    __syncthreads();
+    int bi = 0;
+    if (mine) {
+        float x0[KP];
+        if constexpr (KP <= 32) {
+#pragma unroll
+            for (int k = 0; k < KP; ++k) x0[k] = k < K ? sx[tid * PITCH + k] : 0.f;
+            shape_row<KP>(x0, K, inv_t, top_r);
+        } else {
+            shape_lds_row(sx + tid * PITCH, K, inv_t, top_r);            // the thread's own row: no barrier
+#pragma unroll
+            for (int k = 0; k < KP; ++k) x0[k] = k < K ? sx[tid * PITCH + k] : 0.f;
+        }
+        posterior_pixel_core<KP>(a, i0 + tid, x0, step, al, cu, mode, (int)a.xt[i0 + tid], &bi);
+        if (mode == CCDM_STEP_LAST_MAJORITY) bi = (int)a.xt_next[i0 + tid];          // what the core has just stored: the argmax
+    }
+    if (mode != CCDM_STEP_SAMPLE && mode != CCDM_STEP_LAST_MAJORITY) return;          // uniform
+    const bool onehot = mode == CCDM_STEP_SAMPLE && g.txin;              // uniform
+    if (!onehot) {
+        if (mine)
+            for (ti = c.i0; ti <= c.i1; ++ti)
+                for (tj = c.j0; tj <= c.j1; ++tj) g.txt[tile_index(g, a.N, c, ti, tj)] = (uint8_t)bi;
+        return;
+    }
+    __syncthreads();                                                     // every thread has its row in registers: sx and sb are free
+    int* const sat = reinterpret_cast<int*>(sx);                         // [BLK]: the pixels' indices in the tile of the current rank
+    sb[tid] = bi;
+    const unsigned stride = (unsigned)g.xin_stride;
+    const RowDiv<~0u> chan(stride);
+    const int span = nvalid * (int)stride;
+    ti = c.i0; tj = c.j0;
+    for (int rank = 0; rank < g.cmax; ++rank) {
+        if (mine) {
+            const int at = rank < cnt ? (int)tile_index(g, a.N, c, ti, tj) : -1;
+            if (at >= 0) g.txt[at] = (uint8_t)bi;
+            sat[tid] = at;
+            if (++tj > c.j1) { tj = c.j0; ++ti; }
+        }
+        __syncthreads();
+        for (int idx = tid; idx < span; idx += BLK) {
+            const unsigned p = chan((unsigned)idx), ch = (unsigned)idx - p * stride;
+            const int at = sat[p];
+            if (ch < (unsigned)K && at >= 0) g.txin[(size_t)(unsigned)at * stride + ch] = (int)ch == sb[p] ? 1.0f : 0.0f;
+        }
+        __syncthreads();
+    }
+}
+
 // What the three entries hand to launch_guided
 struct guided_call {
     const float *x0, *evidence;
@@ -319,6 +509,51 @@ static int launch_guided(const char* name, const bool needs_evidence, const bool
     return 0;
 }
 
+// What ccdm_tiled_step hands to launch_tiled: `c` with N = samples, H x W = the canvas, xt = the canvas state, out_probs / out_onehot the
+// canvas's, and xin / xin_stride the TILES' (next to their xt, tile_xt); V, flips and HW unused.
+static int launch_tiled(const char* name, const guided_call& c, const int h, const int w, const int sy, const int sx, uint8_t* const tile_xt) {
+    const int N = c.N, K = c.K, Hc = c.H, Wc = c.W;
+    const int blk = K <= 32 ? 256 : 64;
+    CCDM_REQUIRE(Hc >= 1 && Wc >= 1 && (size_t)Hc * Wc <= 0x7FFFFFFFull, "%s: bad shape Hc=%d Wc=%d", name, Hc, Wc);
+    CCDM_REQUIRE(h >= 1 && h <= Hc && w >= 1 && w <= Wc, "%s: tile h=%d w=%d outside [1,Hc=%d] x [1,Wc=%d]", name, h, w, Hc, Wc);
+    CCDM_REQUIRE(sy >= 1 && sy <= h && sx >= 1 && sx <= w, "%s: stride sy=%d sx=%d outside [1,h=%d] x [1,w=%d]", name, sy, sx, h, w);
+    const int HW = Hc * Wc;
+    if (const int rc = check_step_args(name, c.x0 && c.xt && tile_xt, N, HW, K, c.xin, c.xin_stride, c.mode, c.step_row, blk)) return rc;
+    const int Ty = 1 + (Hc - h + sy - 1) / sy, Tx = 1 + (Wc - w + sx - 1) / sx;
+    CCDM_REQUIRE((size_t)N * HW <= 0x7FFFFFFFull && (size_t)Ty * Tx * N * h * w <= 0x7FFFFFFFull,
+                 "%s: too many pixels (N*Hc*Wc = %zu, R*N*h*w = %zu)", name, (size_t)N * HW, (size_t)Ty * Tx * N * h * w);
+    CCDM_REQUIRE(std::isfinite(c.inv_temperature) && c.inv_temperature >= 0.05f && c.inv_temperature <= 20.0f,
+                 "%s: inv_temperature %g outside [1/20,20]", name, (double)c.inv_temperature);
+    CCDM_REQUIRE(std::isfinite(c.top_r) && c.top_r > 0.0f && c.top_r <= 1.0f, "%s: top_r %g outside (0,1]", name, (double)c.top_r);
+    int cy = 1, cx = 1, lo, hi;
+    for (int y = 0; y < Hc; ++y) { covering_tiles(y, Hc, h, sy, Ty, lo, hi); cy = std::max(cy, hi - lo + 1); }
+    for (int x = 0; x < Wc; ++x) { covering_tiles(x, Wc, w, sx, Tx, lo, hi); cx = std::max(cx, hi - lo + 1); }
+    const size_t npix = (size_t)N * HW;
+    ccdm_post_args a = {};
+    a.head = c.x0; a.softmax = 0; a.head_stride = K;
+    a.xt = c.xt; a.xt_next = c.xt;
+    a.N = N; a.HW = HW; a.K = K;
+    a.philox_seed = c.philox_seed; a.sample_offset = c.sample_offset;
+    a.out_probs = c.out_probs; a.out_onehot = c.out_onehot;
+    const tiled_args g = {c.evidence, tile_xt, c.xin, c.xin_stride, Hc, Wc, h, w, sy, sx, Ty, Tx, cy * cx};
+    const dim3 grid((unsigned)((npix + blk - 1) / blk)), block(blk);
+    hipStream_t s = (hipStream_t)c.stream;
+    const float it = c.inv_temperature, tr = c.top_r, al = c.alpha_t, cu = c.cumalpha_tm1;
+    const int mode = c.mode, step_row = c.step_row;
+    dispatch_kp<256>(K, [&](auto kp) {
+        constexpr int KP = decltype(kp)::value;
+        if constexpr (KP <= 4) {
+            const uintptr_t both = reinterpret_cast<uintptr_t>(c.x0) | reinterpret_cast<uintptr_t>(c.evidence);          // (null: no bits)
+            const int vec = (K == 2 && (both & 7) == 0) || (K == 4 && (both & 15) == 0);
+            hipLaunchKernelGGL((k_tiled<KP>), grid, block, 0, s, a, g, it, tr, al, cu, mode, step_row, vec);
+        } else {
+            hipLaunchKernelGGL((k_tiled_staged<KP, (KP <= 32 ? 256 : 64)>), grid, block, 0, s, a, g, it, tr, al, cu, mode, step_row);
+        }
+    });
+    CCDM_CHECK_LAUNCH(name);
+    return 0;
+}
+
 }  // namespace ccdm
 
 using namespace ccdm;
@@ -345,4 +580,13 @@ extern "C" int ccdm_views_step(const float* x0, const float* evidence, int N, in
     return launch_guided<true>("ccdm_views_step", false, true,
                                {x0, evidence, N, 0, K, H, W, V, flips, inv_temperature, top_r, alpha_t, cumalpha_tm1, mode, step_row, philox_seed,
                                 sample_offset, xt, xin, xin_stride, out_probs, out_onehot, stream});
+}
+
+extern "C" int ccdm_tiled_step(const float* x0, const float* evidence, int N, int Hc, int Wc, int h, int w, int sy, int sx, int K, float inv_temperature,
+                               float top_r, float alpha_t, float cumalpha_tm1, int mode, int step_row, uint64_t philox_seed, uint32_t sample_offset,
+                               uint8_t* canvas_xt, uint8_t* xt, float* xin, int xin_stride, float* out_probs, int64_t* out_onehot, void* stream) {
+    return launch_tiled("ccdm_tiled_step",
+                        {x0, evidence, N, 0, K, Hc, Wc, 1, 0, inv_temperature, top_r, alpha_t, cumalpha_tm1, mode, step_row, philox_seed,
+                         sample_offset, canvas_xt, xin, xin_stride, out_probs, out_onehot, stream},
+                        h, w, sy, sx, xt);
 }

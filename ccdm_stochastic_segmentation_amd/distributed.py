@@ -167,7 +167,7 @@ def _check_same_host_rng(world: int, device) -> None:
 def sample_sharded(model, x: torch.Tensor, condition: torch.Tensor, feature_condition: Optional[torch.Tensor] = None,
                    t: Optional[torch.Tensor] = None, gather=True, *, known_labels: Optional[torch.Tensor] = None,
                    resample: Optional[Tuple[int, int]] = None, evidence: Optional[torch.Tensor] = None,
-                   temperature: Optional[float] = None, truncation: Optional[float] = None, views=None) -> torch.Tensor:
+                   temperature: Optional[float] = None, truncation: Optional[float] = None, views=None, tiles=None) -> torch.Tensor:
     """Run `model` (a DenoisingModel-like callable) on this rank's shard of the global batch and return the
     full [N,K,H,W] prediction on every rank, or only the local shard (gather=False).
     gather=True: fp32 probabilities travel as they are; int64 one-hot ("majority") predictions travel as their uint8 argmax map
@@ -180,7 +180,9 @@ def sample_sharded(model, x: torch.Tensor, condition: torch.Tensor, feature_cond
     evidence: per-pixel class weights [hi - lo,K,H,W], handed to the model as it is like known_labels: the caller passes its shard's slice.
     temperature, truncation: handed to the model as they are (the shaped draw keeps the unguided draw's counters: global sample index).
     views: handed to the model as it is (the view-averaged draw is keyed by the global sample index too, never by the engine row); a
-    feature_condition [V,N,...] (DenoisingModel's `views`) is sliced along its sample axis."""
+    feature_condition [V,N,...] (DenoisingModel's `views`) is sliced along its sample axis.
+    tiles: (h, w, sy, sx), handed to the model as it is (the tiled draw is keyed by the canvas pixel and the global sample index, never by
+    the engine row or tile); a feature_condition [R,N,...] (DenoisingModel's `tiles`) is sliced along its sample axis."""
     world = dist.get_world_size() if dist.is_initialized() else 1
     rank = dist.get_rank() if dist.is_initialized() else 0
     n = x.shape[0]
@@ -203,7 +205,10 @@ def sample_sharded(model, x: torch.Tensor, condition: torch.Tensor, feature_cond
             kw["truncation"] = truncation
         if views is not None:
             kw["views"] = views
-        per_view = views is not None and len(views) > 0 and feature_condition is not None and feature_condition.ndim == 5
+        if tiles is not None:
+            kw["tiles"] = tiles
+        per_view = ((views is not None and len(views) > 0) or tiles is not None) and feature_condition is not None \
+            and feature_condition.ndim == 5
         fc = None if feature_condition is None else (feature_condition[:, lo:hi] if per_view else feature_condition[lo:hi])
         out = model(x[lo:hi], condition[lo:hi], fc, **kw)["diffusion_out"].contiguous()
     finally:

@@ -50,6 +50,19 @@ def timestep_embedding_host(timesteps: torch.Tensor, dim: int, max_period: int =
     return emb
 
 
+class TileCanvas:
+    """The canvas of a tiled sampling call (DenoisingModel(..., tiles=); ccdm_tiled_step in include/ccdm_hip.h), next to the engine
+    whose N rows are the R tiles of n samples, tile-major: the state xt uint8 [n,Hc*Wc] (x_t in, x_{t-1} out of every tiled step) and
+    the last step's out_probs fp32 / out_onehot int64 [n,Hc,Wc,K], on the engine's device; allocated with the engine's stream current
+    (SamplerEngine.tile_canvas).  It has the attributes a consumer of a pass reads from an engine."""
+
+    def __init__(self, n: int, Hc: int, Wc: int, sy: int, sx: int, K: int, device: torch.device):
+        self.n, self.Hc, self.Wc, self.sy, self.sx = int(n), int(Hc), int(Wc), int(sy), int(sx)
+        self.xt = torch.zeros((self.n, self.Hc * self.Wc), dtype=torch.uint8, device=device)
+        self.out_probs = torch.empty((self.n, self.Hc, self.Wc, K), dtype=torch.float32, device=device)
+        self.out_onehot = torch.empty((self.n, self.Hc, self.Wc, K), dtype=torch.int64, device=device)
+
+
 class SamplerEngine:
     """One engine per (weights, N, H, W).  Not thread-safe (like the reference's module)."""
 
@@ -74,6 +87,8 @@ class SamplerEngine:
         self._sd = {k: v.detach().to("cpu", torch.float32).contiguous() for k, v in state_dict.items()}
         self.feature_shape = feature_shape
         self._handle = None
+        self._tile_canvas: Optional[TileCanvas] = None          # tile_canvas(): the canvas of the tiled calls this engine's rows serve
+        self._tile_canvas_key = None
         with torch.cuda.device(device):
             # a private non-default stream: HIP graph capture is not allowed on the legacy default stream
             self.stream = torch.cuda.Stream(device=device)
@@ -602,8 +617,22 @@ class SamplerEngine:
             self.N, self.H * self.W, self.K, float(p_stay), float(p_move), int(step_row), *self._step_state_args(philox_seed, sample_offset),
             self._stream()), "renoise_step")
 
+    def tile_canvas(self, n: int, Hc: int, Wc: int, sy: int, sx: int) -> TileCanvas:
+        """The canvas holder of a tiled call whose R tiles of n samples are this engine's rows (kept: the next call of the same geometry
+        gets the same buffers).  Call with the engine's stream current."""
+        key = (int(n), int(Hc), int(Wc), int(sy), int(sx))
+        if self._tile_canvas_key != key:
+            R = (1 + -((self.H - key[1]) // key[3])) * (1 + -((self.W - key[2]) // key[4]))
+            if not (1 <= key[3] <= self.H <= key[1] and 1 <= key[4] <= self.W <= key[2]) or R * key[0] != self.N:
+                raise ValueError(f"tiles: an engine of {self.N} rows of {self.H}x{self.W} does not hold the tiles of {key[0]} canvases "
+                                 f"{key[1]}x{key[2]} at strides ({key[3]}, {key[4]})")
+            self._tile_canvas = TileCanvas(*key, self.K, self.device)
+            self._tile_canvas_key = key
+        return self._tile_canvas
+
     def guided_step(self, evidence: Optional[torch.Tensor], shaping: Optional[Tuple[float, float]], views: Optional[Sequence[int]],
-                    alpha_t: float, cumalpha_tm1: float, mode: int, step_row: int, *, philox_seed: int = 0, sample_offset: int = 0) -> None:
+                    alpha_t: float, cumalpha_tm1: float, mode: int, step_row: int, *, philox_seed: int = 0, sample_offset: int = 0,
+                    canvas: Optional[TileCanvas] = None) -> None:
         """The reverse step behind a `run` of a table row whose mode is STEP_SOFTMAX_ONLY (asynchronous on the engine's stream): that run
         left the network's x0 in out_probs and x_t in xt; this reshapes x0 and does the step of (alpha_t, cumalpha_tm1, mode) — the real
         columns of row `step_row` — with the Philox counters the unguided step of that row uses (include/ccdm_hip.h has the definitions).
@@ -614,8 +643,27 @@ class SamplerEngine:
         evidence: None, or fp32 [n,H*W,K] on the engine's device, weights in [0,1]: x0 is multiplied by them.
         shaping: None, or (inv_temperature, top_r): x0 is tempered with that exponent and cut to the smallest set of classes whose mass
           reaches top_r.
-        One launch: ccdm_views_step where there are views (neutral shaping: 1.0, 1.0), else ccdm_shaped_step where there is shaping, else
-        ccdm_evidence_step."""
+        canvas: None, or the holder of a tiled call (tile_canvas): the engine's rows are the R tiles of canvas.n samples, tile-major
+          (row r * n + j is tile r of sample j), H x W each at strides (canvas.sy, canvas.sx) on a canvas.Hc x canvas.Wc canvas; x0
+          becomes its mean over the covering tiles per canvas pixel, x_t is canvas.xt, the counters are those of the canvas pixel and
+          sample sample_offset + j, the drawn class goes to canvas.xt and to every covering tile, and the last-step outputs are the
+          canvas's.  evidence is then fp32 [n,Hc*Wc,K].  Not together with views.
+        One launch: ccdm_tiled_step where there is a canvas, else ccdm_views_step where there are views (neutral shaping: 1.0, 1.0),
+        else ccdm_shaped_step where there is shaping, else ccdm_evidence_step."""
+        if canvas is not None:
+            assert views is None and canvas is self._tile_canvas
+            n = canvas.n
+            assert evidence is None or (evidence.dtype == torch.float32 and evidence.is_cuda and evidence.is_contiguous()
+                                        and tuple(evidence.shape) == (n, canvas.Hc * canvas.Wc, self.K))
+            inv_t, top_r = shaping or (1.0, 1.0)
+            seed, off, xt, xin, stride = self._step_state_args(philox_seed, sample_offset)
+            hip.check(self.lib.ccdm_tiled_step(
+                self.out_probs.data_ptr(), None if evidence is None else evidence.data_ptr(), n, canvas.Hc, canvas.Wc, self.H, self.W,
+                canvas.sy, canvas.sx, self.K, float(inv_t), float(top_r), float(alpha_t), float(cumalpha_tm1), int(mode), int(step_row), seed,
+                off, canvas.xt.data_ptr(), xt, xin, stride, canvas.out_probs.data_ptr(), canvas.out_onehot.data_ptr(), self._stream()),
+                "tiled_step")
+            self._evidence_keepalive = evidence
+            return
         flips = () if views is None else tuple(int(f) for f in views)
         V = 1 + len(flips)
         assert 1 <= V <= 4 and self.N % V == 0 and all(0 <= f <= 3 for f in flips)

@@ -165,13 +165,14 @@ def apply_sampler_options(model, params: dict) -> None:
     model._fine_slices(1)                                         # validates the value
 
 
-SAMPLING_KEYS = ("temperature", "truncation", "views")
+SAMPLING_KEYS = ("temperature", "truncation", "views", "tiles")
 
 
 def sampling_keywords(params: dict) -> dict:
-    """The keywords the params key `sampling: {temperature: ..., truncation: ..., views: [...]}` (each optional) adds to every sampling
+    """The keywords the params key `sampling: {temperature: ..., truncation: ..., views: [...], tiles: [...]}` (each optional) adds to every sampling
     call and to predict_multiple (DenoisingModel's keywords of those names, which check the values; `views`, a YAML list of names from
-    hflip / vflip / hvflip, travels as a tuple); {} without the key.  An unknown key under `sampling:` raises."""
+    hflip / vflip / hvflip, travels as a tuple, and so does `tiles`, a YAML list of the four integers h, w, sy, sx); {} without the key.
+    An unknown key under `sampling:` raises."""
     section = params.get("sampling")
     if section is None:
         return {}
@@ -180,7 +181,7 @@ def sampling_keywords(params: dict) -> dict:
     unknown = [k for k in section if k not in SAMPLING_KEYS]
     if unknown:
         raise ValueError(f"sampling: unknown key(s) {unknown} (expected keys from {list(SAMPLING_KEYS)})")
-    return {k: tuple(section[k]) if (k == "views" and isinstance(section[k], list)) else section[k]
+    return {k: tuple(section[k]) if (k in ("views", "tiles") and isinstance(section[k], list)) else section[k]
             for k in SAMPLING_KEYS if section.get(k) is not None}
 
 
@@ -191,6 +192,16 @@ def view_features(encoder, image: torch.Tensor, views) -> torch.Tensor:
     from .models import DenoisingModel
     flips = [DenoisingModel.VIEW_FLIPS[v] for v in views]
     return torch.stack([encoder(image)] + [encoder(torch.flip(image, [d for b, d in ((1, 3), (2, 2)) if f & b])) for f in flips], 0)
+
+
+def tile_features(encoder, image: torch.Tensor, tiles) -> torch.Tensor:
+    """The feature condition of a call with `tiles` = (h, w, sy, sx) (DenoisingModel's keyword): [R,B,Cf,hf,wf], tile r the encoder's
+    features of the image cropped to tile r (models.tile_origins, r = i * Tx + j) — the encoder runs once per tile on the cropped
+    pixels, as the network does."""
+    from .models import tile_origins
+    h, w, sy, sx = (int(v) for v in tiles)
+    oys, oxs = tile_origins(int(image.shape[2]), int(image.shape[3]), h, w, sy, sx)
+    return torch.stack([encoder(image[:, :, oy:oy + h, ox:ox + w]) for oy in oys for ox in oxs], 0)
 
 
 def _as_list(v) -> List[int]:
@@ -237,7 +248,7 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
     shard of the B_img*S flattened batch (distributed.sample_sharded: no collective inside the T loop, one gather of the
     predictions per batch); the metrics are then computed identically on every rank.
     `model`: a ready DenoisingModel-like callable (tests inject fixed predictions); default: built from `params`.
-    The params key `sampling: {temperature: ..., truncation: ..., views: [...]}` (sampling_keywords; each optional) is handed to every sampling call
+    The params key `sampling: {temperature: ..., truncation: ..., views: [...], tiles: [...]}` (sampling_keywords; each optional) is handed to every sampling call
     and echoed as "sampling" in the result; without the key nothing changes.
 
     Build-owned keys of the `evaluation` section (absent: the returned dict and everything else is as without them):

@@ -22,7 +22,7 @@ import torch
 from torch import Tensor, nn
 
 from . import hip
-from .engine import SamplerEngine
+from .engine import SamplerEngine, TileCanvas
 from .unet_spec import UNetSpec, make_unet_spec
 
 LOGGER = logging.getLogger(__name__)
@@ -96,6 +96,18 @@ def resample_walk(S: int, jump_length: int, resamples: int) -> List[Tuple[int, i
     return walk
 
 
+def tile_origins(Hc: int, Wc: int, h: int, w: int, sy: int, sx: int) -> Tuple[List[int], List[int]]:
+    """The tiling of a canvas Hc x Wc by tiles h x w at strides (sy, sx), 1 <= sy <= h <= Hc and 1 <= sx <= w <= Wc, as include/ccdm_hip.h
+    defines it (ccdm_tiled_step derives the same origins): (oys, oxs) with oys[i] = min(i * sy, Hc - h) for the Ty = 1 + ceil((Hc - h) /
+    sy) tiles along y — the last tile is pushed back so that it ends at the border; the origins are distinct and leave no gap — and the
+    same along x.  Tile r = i * len(oxs) + j covers rows oys[i] .. oys[i] + h - 1 and columns oxs[j] .. oxs[j] + w - 1."""
+    Hc, Wc, h, w, sy, sx = (int(v) for v in (Hc, Wc, h, w, sy, sx))
+    if not (1 <= sy <= h <= Hc and 1 <= sx <= w <= Wc):
+        raise ValueError(f"tiles: need 1 <= sy <= h <= Hc and 1 <= sx <= w <= Wc, got canvas {Hc}x{Wc}, tile {h}x{w}, strides ({sy}, {sx})")
+    return ([min(i * sy, Hc - h) for i in range(1 + -((h - Hc) // sy))],
+            [min(j * sx, Wc - w) for j in range(1 + -((w - Wc) // sx))])
+
+
 def pass_key(key: int, p: int) -> int:
     """Philox key of pass `p` of a table row (p = the number of earlier visits of the row in a resampled walk): the call's key itself
     for p = 0, else the splitmix64 finaliser of key + 0x9E3779B97F4A7C15 * p — the mixing DenoisingModel._philox_key applies to
@@ -113,17 +125,19 @@ def pass_key(key: int, p: int) -> int:
 class Guidance:
     """What guides one sampling call, as DenoisingModel._check_guidance returns it: `known` uint8 [N,H*W] (_check_known_labels), `jumps`
     (jump_length, resamples) (_check_resample), `evidence` fp32 [N,H*W,K] (_check_evidence), `shaping` (inv_temperature, top_r)
-    (_check_shaping), `views` the flip codes of views 1 .. V - 1 (_check_views: bit 0 mirrors x, bit 1 mirrors y; view 0 is the identity);
-    None each where the call has none."""
+    (_check_shaping), `views` the flip codes of views 1 .. V - 1 (_check_views: bit 0 mirrors x, bit 1 mirrors y; view 0 is the identity),
+    `tiles` (h, w, sy, sx) (_check_tiles); None each where the call has none."""
     known: Optional[Tensor] = None
     jumps: Optional[Tuple[int, int]] = None
     evidence: Optional[Tensor] = None
     shaping: Optional[Tuple[float, float]] = None
     views: Optional[Tuple[int, ...]] = None
+    tiles: Optional[Tuple[int, int, int, int]] = None
 
     def __bool__(self) -> bool:
         """The walk has something to do between the network's steps (jumps need known labels)."""
-        return self.known is not None or self.evidence is not None or self.shaping is not None or self.views is not None
+        return self.known is not None or self.evidence is not None or self.shaping is not None or self.views is not None \
+            or self.tiles is not None
 
     def walk(self, S: int) -> List[Tuple[int, int, Optional[int]]]:
         """The (row, pass, renoise_from) entries of a walk of S table rows: resample_walk's; [(s, 0, None) ...] without jumps."""
@@ -132,7 +146,7 @@ class Guidance:
     def repeat_interleave(self, S: int) -> "Guidance":
         """For a batch in which every sample is repeated S times (predict_multiple(batched=True))."""
         return Guidance(*(v.repeat_interleave(S, dim=0) if isinstance(v, Tensor) else v
-                          for v in (self.known, self.jumps, self.evidence, self.shaping, self.views)))
+                          for v in (self.known, self.jumps, self.evidence, self.shaping, self.views, self.tiles)))
 
 
 class OneHotCategoricalBCHW:
@@ -405,7 +419,29 @@ class DenoisingModel(nn.Module):
     `feature_condition` needs the features of every view from the caller's own encoder, [V,N,Cf,h,w] with view v computed from the
     mirrored image.  Refused: unknown or duplicate names, a training or validation call, rng = "torch_cpu", `softmax_output: no`, and
     `known_labels` / `resample` together with views (the clamp and the renoise draw per engine row, so the views would stop being
-    mirror images of one another: not built).  `views=()` or None is the plain call: no code path changes."""
+    mirror images of one another: not built).  `views=()` or None is the plain call: no code path changes.
+    `tiles` = (h, w, sy, sx) (keyword next to `known_labels`): sample a canvas larger than the geometry the network was trained at — a
+    180x180 slice with a 128x128 model, a whole frame with a model trained on crops.  `x` is then the canvas x_T [N,K,Hc,Wc] and
+    `condition` the canvas image [N,C,Hc,Wc].  Windows sampled independently and pasted would disagree at the seams; this is the
+    MultiDiffusion construction (Bar-Tal et al. 2023) instead: ONE chain runs on the canvas, at every reverse step the network runs on
+    overlapping h x w tiles of the current canvas state (strides sy <= h, sx <= w; `tile_origins` has the tiling: the last tile along an
+    axis is pushed back to end at the border) and x0 of a canvas pixel is the mean over the c >= 1 tiles that cover it.  Exact for
+    categorical diffusion in the sense of `views` (a mean of probability vectors is one; the step posterior is linear in x0 up to its
+    own normalisation), no retraining, R network passes of h x w per step.  The R tiles of a sample are R rows of the engine's batch,
+    tile-major (row r * n + j of a sub-batch of n samples is tile r of sample j; the host crops x_T and the image by plain slicing);
+    every row's network pass stops at x0 and ONE ccdm_tiled_step launch per walk entry takes the per-pixel mean, applies `evidence`
+    (a canvas map [N,K,Hc,Wc]), `temperature` and `truncation` where the call has them (it replaces those launches), draws with the
+    counters of a plain call at the canvas's size — keyed by the canvas pixel and the sample, never by the engine row or tile — and
+    writes the drawn class to the canvas state and to every covering tile, so the tiles stay crops of one state (include/ccdm_hip.h
+    has the definition).  Results [N,K,Hc,Wc] are read from the canvas holder (engine.TileCanvas), which is also what `consume` gets.
+    A tiled call takes the static execution-mode rule (`auto_substreams` sees R * N samples of h x w; sub-batches split by sample, all
+    tiles of a sample in one engine) and does not depend on `substreams`, `use_graph` or sharding; one tile that is the canvas
+    reproduces the plain call bit for bit.  A model that takes a `feature_condition` needs the features of every tile from the caller's
+    own encoder, [R,N,Cf,hf,wf] (evaluation.tile_features).  Refused: anything but four integers, a stride < 1 or beyond the tile, a
+    tile larger than the canvas, a training or validation call, rng = "torch_cpu", `softmax_output: no`, and `views`, `known_labels`
+    or `resample` together with tiles (the clamp and the renoise draw per engine row, so overlapping tiles would stop being crops of
+    one state: not built).  The mean is uniform (no feathered weights) and all R * N rows run in one engine (no chunking).  None is the
+    plain call: no code path changes."""
 
     VIEW_FLIPS = {"hflip": 1, "vflip": 2, "hvflip": 3}        # ccdm_views_step's two bits per view: bit 0 mirrors x, bit 1 mirrors y
 
@@ -478,10 +514,12 @@ class DenoisingModel(nn.Module):
                 label_ref_logits: Optional[Tensor] = None, validation: bool = False, *,
                 known_labels: Optional[Tensor] = None, resample: Optional[Tuple[int, int]] = None,
                 evidence: Optional[Tensor] = None, temperature: Optional[float] = None,
-                truncation: Optional[float] = None, views: Optional[Sequence[str]] = None) -> Union[Tensor, dict]:
+                truncation: Optional[float] = None, views: Optional[Sequence[str]] = None,
+                tiles: Optional[Sequence[int]] = None) -> Union[Tensor, dict]:
         if evidence is not None and (self.training or validation):
             self._check_evidence(evidence, None, sampling=False)
         if self.training or validation:
+            self._check_tiles(tiles, sampling=False)
             self._check_shaping(temperature, truncation, sampling=False)
             self._check_views(views, sampling=False)
         if known_labels is not None and (self.training or validation):
@@ -499,9 +537,10 @@ class DenoisingModel(nn.Module):
         if t is None:
             return self.forward_denoising(x, condition, feature_condition, label_ref_logits=label_ref_logits, known_labels=known_labels,
                                           resample=resample, evidence=evidence, temperature=temperature, truncation=truncation,
-                                          views=views)
+                                          views=views, tiles=tiles)
         return self.forward_denoising(x, condition, feature_condition, cast(int, t.item()), label_ref_logits, known_labels=known_labels,
-                                      resample=resample, evidence=evidence, temperature=temperature, truncation=truncation, views=views)
+                                      resample=resample, evidence=evidence, temperature=temperature, truncation=truncation, views=views,
+                                      tiles=tiles)
 
     # ------------------------------------------------------------------ engine plumbing
     def _weights_key(self) -> Tuple[int, int]:
@@ -685,27 +724,71 @@ class DenoisingModel(nn.Module):
                           consume: Optional[Callable[[SamplerEngine, int, int], None]] = None,
                           known_labels: Optional[Tensor] = None, resample: Optional[Tuple[int, int]] = None,
                           evidence: Optional[Tensor] = None, temperature: Optional[float] = None,
-                          truncation: Optional[float] = None, views: Optional[Sequence[str]] = None) -> dict:
+                          truncation: Optional[float] = None, views: Optional[Sequence[str]] = None,
+                          tiles: Optional[Sequence[int]] = None) -> dict:
         """`consume` (predict_multiple): instead of returning the call's output, hand every sub-batch engine (eng, lo, hi) to
-        consume(eng, lo, hi) once the call has succeeded, with the engine's stream current; the result is then {}.
+        consume(eng, lo, hi) once the call has succeeded, with the engine's stream current; the result is then {}.  With `tiles` the
+        first argument is the sub-batch's canvas holder (engine.TileCanvas: the xt / out_probs / out_onehot of the canvas) instead.
         `known_labels`: integer [N,H,W], a class where the label is known, 255 where the pixel is free (see the class docstring).
         `resample`: (jump_length, resamples), RePaint's resampling jumps of a walk with known labels (class docstring).
         `evidence`: float [N,K,H,W], per-pixel class weights in [0,1] (class docstring).
         `temperature` in [0.05, 20], `truncation` in (0, 1]: temper and truncate x0 before every reverse step (class docstring).
-        `views`: names from "hflip", "vflip", "hvflip": x0 is averaged over these mirror images of the input (class docstring)."""
+        `views`: names from "hflip", "vflip", "hvflip": x0 is averaged over these mirror images of the input (class docstring).
+        `tiles`: (h, w, sy, sx): x and condition are a canvas larger than the network's geometry, sampled as ONE chain whose x0 is the
+          per-pixel mean over overlapping h x w tiles at strides (sy, sx) (class docstring)."""
         guide = self._check_guidance(known_labels, resample, evidence, None if x is None else tuple(x.shape), temperature, truncation,
-                                     views, feature_condition)
+                                     views, feature_condition, tiles)
         return self._sample(x, condition, feature_condition, init_t, label_ref_logits, consume, guide)
 
     def _check_guidance(self, known_labels, resample, evidence, shape: Optional[Tuple[int, int, int, int]], temperature=None,
-                        truncation=None, views=None, feature_condition=None) -> Guidance:
+                        truncation=None, views=None, feature_condition=None, tiles=None) -> Guidance:
         """The host-side checks of a call's guidance keywords (before anything runs), in this order; shape: the call's (N,K,H,W)."""
+        geom = self._check_tiles(tiles, views=views, known_labels=known_labels, resample=resample, feature_condition=feature_condition,
+                                 shape=shape)
         flips = self._check_views(views, known_labels=known_labels, resample=resample, feature_condition=feature_condition, shape=shape)
         shaping = self._check_shaping(temperature, truncation)
         ev = None if evidence is None else self._check_evidence(evidence, shape)
         jumps = self._check_resample(resample, known_labels)
         known = None if known_labels is None else self._check_known_labels(known_labels, (shape[0], shape[2], shape[3]), shape[1])
-        return Guidance(known, jumps, ev, shaping, flips)
+        return Guidance(known, jumps, ev, shaping, flips, geom)
+
+    def _check_tiles(self, tiles, sampling: bool = True, *, views=None, known_labels=None, resample=None, feature_condition=None,
+                     shape: Optional[Tuple[int, int, int, int]] = None) -> Optional[Tuple[int, int, int, int]]:
+        """The one host-side check of a call's `tiles` (before anything runs): (h, w, sy, sx) as four ints, or None where the call has
+        none.  shape: the call's (N,K,Hc,Wc), the canvas."""
+        if tiles is None:
+            return None
+        if isinstance(tiles, (str, bytes)) or not isinstance(tiles, (tuple, list)) or len(tiles) != 4 or not all(
+                isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) for v in tiles):
+            raise ValueError(f"tiles: expected (h, w, sy, sx), four integers (tile height and width, strides along y and x), got {tiles!r}")
+        h, w, sy, sx = (int(v) for v in tiles)
+        if not (1 <= sy <= h and 1 <= sx <= w):
+            raise ValueError(f"tiles: need 1 <= sy <= h and 1 <= sx <= w (a stride beyond the tile would leave gaps), got tile {h}x{w}, "
+                             f"strides ({sy}, {sx})")
+        if shape is not None and (h > int(shape[2]) or w > int(shape[3])):
+            raise ValueError(f"tiles: the tile {h}x{w} is larger than the canvas {int(shape[2])}x{int(shape[3])}")
+        if not sampling or self.training:
+            raise ValueError("tiles: only a sampling call (eval mode, validation=False) has a canvas to sample")
+        if self.rng == "torch_cpu":
+            raise ValueError("tiles: not available with rng = 'torch_cpu' (the host-noise parity mode replays the reference's draws, and the "
+                             "reference has no tiled step to be in parity with); use rng = 'philox'")
+        if not self.unet.spec.softmax_output:
+            raise ValueError("tiles: needs a model whose output is a probability vector; with `softmax_output: no` x0 holds logits, "
+                             "whose mean is not the mean of the probabilities")
+        if views is not None and len(views) > 0:
+            raise ValueError("tiles: not available together with views (not built)")
+        if known_labels is not None or resample is not None:
+            raise ValueError(f"tiles: not available together with {'known_labels' if known_labels is not None else 'resample'} (the clamp "
+                             "and the renoise draw per engine row, so overlapping tiles would stop being crops of one state)")
+        if feature_condition is not None and self.unet.spec.feature_condition_idx:
+            R = None if shape is None else math.prod(len(o) for o in tile_origins(int(shape[2]), int(shape[3]), h, w, sy, sx))
+            want = None if shape is None else (R, int(shape[0]))
+            if not isinstance(feature_condition, Tensor) or feature_condition.ndim != 5 or \
+                    (want is not None and tuple(feature_condition.shape[:2]) != want):
+                raise ValueError(f"tiles: this model takes a feature_condition, and with tiles it needs the features of every tile, "
+                                 f"[R,N,Cf,hf,wf]{'' if R is None else f' with R = {R}'} (tile r from the caller's encoder on the cropped "
+                                 f"image: evaluation.tile_features), got {tuple(getattr(feature_condition, 'shape', ()))}")
+        return h, w, sy, sx
 
     def _check_views(self, views, sampling: bool = True, *, known_labels=None, resample=None, feature_condition=None,
                      shape: Optional[Tuple[int, int, int, int]] = None) -> Optional[Tuple[int, ...]]:
@@ -852,7 +935,8 @@ class DenoisingModel(nn.Module):
                          maps: Sequence[str] = ("mean", "vote", "entropy", "mutual_info"),
                          known_labels: Optional[Tensor] = None, resample: Optional[Tuple[int, int]] = None,
                          evidence: Optional[Tensor] = None, temperature: Optional[float] = None,
-                         truncation: Optional[float] = None, views: Optional[Sequence[str]] = None) -> Dict[str, Tensor]:
+                         truncation: Optional[float] = None, views: Optional[Sequence[str]] = None,
+                         tiles: Optional[Sequence[int]] = None) -> Dict[str, Tensor]:
         """S = `num_evaluations` samples of every image of `condition` [B,C,H,W], combined on the device into one prediction and
         per-pixel uncertainty maps — the reference's Evaluator.predict_multiple (evaluation/eval_cdm.py:176-193), which sums S
         `predict_single` outputs as `total += prediction_i * (1 / S)`.
@@ -873,6 +957,8 @@ class DenoisingModel(nn.Module):
         temperature, truncation: every pass tempers and truncates x0 before every reverse step (class docstring), all with the same pair.
         views: every pass averages x0 over these mirror images of the input (class docstring); a model that takes a feature_condition
           then needs [V,B,Cf,h,w].
+        tiles: (h, w, sy, sx): `condition` is a canvas larger than the network's geometry and every pass samples it tiled (class
+          docstring); a model that takes a feature_condition then needs [R,B,Cf,hf,wf].  The passes are folded from the canvas.
         batched=False: S sampling calls of B samples, each advancing `philox_call` exactly like S calls of model(x_i, condition);
           after each call the pass is folded into device accumulators straight from the engine (ccdm_vote_accumulate), so memory
           is one pass plus the accumulators.  The range-error fallback and the execution-mode choice apply per pass.
@@ -899,7 +985,7 @@ class DenoisingModel(nn.Module):
         if x is not None and tuple(x.shape) != (S, B, K, H, W):
             raise ValueError(f"x: expected one-hot x_T of shape {(S, B, K, H, W)} = [S,B,K,H,W], got {tuple(x.shape)}")
         init_t = None if t is None else int(t.item() if isinstance(t, Tensor) else t)
-        guide = self._check_guidance(known_labels, resample, evidence, (B, K, H, W), temperature, truncation, views, feature_condition)
+        guide = self._check_guidance(known_labels, resample, evidence, (B, K, H, W), temperature, truncation, views, feature_condition, tiles)
         dev = next(self.unet.parameters()).device
         lib = hip.load()
         majority = voting == "majority"
@@ -933,8 +1019,9 @@ class DenoisingModel(nn.Module):
             else:
                 xr = x.transpose(0, 1).reshape(B * S, K, H, W) if x is not None else draw(B * S)
                 cond = condition.repeat_interleave(S, dim=0)
-                # (with views on a model that takes features: [V,B,...], the samples on dim 1)
-                fc_dim = 1 if (guide.views is not None and feature_condition is not None and feature_condition.ndim == 5) else 0
+                # (with views or tiles on a model that takes features: [V,B,...] / [R,B,...], the samples on dim 1)
+                fc_dim = 1 if ((guide.views is not None or guide.tiles is not None) and feature_condition is not None
+                               and feature_condition.ndim == 5) else 0
                 fc = feature_condition.repeat_interleave(S, dim=fc_dim) if feature_condition is not None else None
                 # the pass outputs of all B*S samples: class maps (1 byte a pixel) or probabilities
                 buf = torch.empty((B * S, HW) if majority else (B * S, HW, K), dtype=torch.uint8 if majority else torch.float32, device=dev)
@@ -1003,7 +1090,7 @@ class DenoisingModel(nn.Module):
                            init_t: Optional[int] = None, label_ref_logits: Optional[Tensor] = None, consume=None,
                            guide: Guidance = Guidance()) -> dict:
         """`guide`: the call's checked guidance (_check_guidance), on the model's device."""
-        known, evidence, shaping, views = guide.known, guide.evidence, guide.shaping, guide.views
+        known, evidence, shaping, views, tiles = guide.known, guide.evidence, guide.shaping, guide.views, guide.tiles
         V = 1 if views is None else 1 + len(views)
         if label_ref_logits is not None:
             # the reference's guidance branch reads attributes that do not exist (guidance_scale_weights,
@@ -1023,9 +1110,13 @@ class DenoisingModel(nn.Module):
         if self.rng not in ("philox", "torch_cpu"):
             raise ValueError(f"unknown rng mode {self.rng!r}")
         host_rng = self.rng == "torch_cpu"
-        # evidence, shaping, views: the network pass of every row stops at x0 (out_probs; x_t untouched), the row's real step follows in
-        # guided_step
-        stop_at_x0 = evidence is not None or shaping is not None or views is not None
+        # evidence, shaping, views, tiles: the network pass of every row stops at x0 (out_probs; x_t untouched), the row's real step follows
+        # in guided_step
+        stop_at_x0 = evidence is not None or shaping is not None or views is not None or tiles is not None
+        # tiles: x and condition are the canvas; the engine's rows are the R tiles of every sample, h x w each (tile_origins)
+        oys, oxs = tile_origins(H, W, *tiles) if tiles is not None else ([0], [0])
+        R = len(oys) * len(oxs)
+        canvases: Dict[int, TileCanvas] = {}                 # the canvas holder of the sub-batch that starts at sample `lo`
         table = coeffs if not stop_at_x0 else [(a_, c_, hip.STEP_SOFTMAX_ONLY) for a_, c_, m_ in coeffs]
         # known labels: cumalpha of the state each row produces; the last row returns the labels themselves (class docstring)
         clamp_c = [1.0 if j == S - 1 else c_ for j, (a_, c_, m_) in enumerate(coeffs)]
@@ -1053,12 +1144,21 @@ class DenoisingModel(nn.Module):
             """The V views of a sub-batch's [n,C,h,w] tensor as the engine's rows, view-major: [V * n,C,h,w], view v flipped as it says."""
             return torch.cat([a] + [torch.flip(a, [d for b, d in ((1, 3), (2, 2)) if f & b]) for f in cast(tuple, views)], 0)
 
+        def tiled(a: Tensor) -> Tensor:
+            """The R tiles of a sub-batch's [n,C,Hc,Wc] tensor as the engine's rows, tile-major: [R * n,C,h,w], plain crops."""
+            h_, w_ = cast(tuple, tiles)[:2]
+            return torch.cat([a[:, :, oy:oy + h_, ox:ox + w_] for oy in oys for ox in oxs], 0)
+
         def prepare(nsub_: int):
             bounds = [(N * j) // nsub_ for j in range(nsub_ + 1)]
             parts_ = []
             for j in range(nsub_):
                 lo, hi = bounds[j], bounds[j + 1]
-                if views is None:
+                if tiles is not None:
+                    xs, cs, fc = tiled(x[lo:hi]), tiled(condition[lo:hi]), None
+                    if feature_condition is not None and self.unet.spec.feature_condition_idx:         # [R,N,...] (_check_tiles)
+                        fc = feature_condition[:, lo:hi].flatten(0, 1)
+                elif views is None:
                     xs, cs = x[lo:hi], condition[lo:hi]
                     fc = feature_condition[lo:hi] if feature_condition is not None else None
                 else:
@@ -1069,6 +1169,9 @@ class DenoisingModel(nn.Module):
                 with eng.enter():
                     eng.set_inputs(self._to_index(xs, eng.device), cs.to(eng.device), fc)
                     eng.set_tables([float(t) for t in t_values], table)
+                    if tiles is not None:          # the canvas state starts as x_T's class index
+                        canvases[lo] = eng.tile_canvas(hi - lo, H, W, tiles[2], tiles[3])
+                        canvases[lo].xt.copy_(self._to_index(x[lo:hi], eng.device).reshape(hi - lo, H * W))
                 parts_.append((eng, lo, hi))
             return parts_
 
@@ -1081,7 +1184,8 @@ class DenoisingModel(nn.Module):
                 eng.renoise(*renoise, row, philox_seed=kp, sample_offset=off)
             eng.run(1, first_row=row, noise=noise, noise_row0=noise_row0_, philox_seed=kp, sample_offset=off, use_graph=graph_)
             if stop_at_x0:
-                eng.guided_step(None if evidence is None else evidence[lo:hi], shaping, views, *coeffs[row], row, philox_seed=kp, sample_offset=off)
+                eng.guided_step(None if evidence is None else evidence[lo:hi], shaping, views, *coeffs[row], row, philox_seed=kp, sample_offset=off,
+                                canvas=canvases.get(lo))
             if known is not None:
                 eng.clamp_known_labels(known[lo:hi], clamp_c[row], coeffs[row][2], row, philox_seed=kp, sample_offset=off)
 
@@ -1095,7 +1199,8 @@ class DenoisingModel(nn.Module):
                 for j, (eng, lo, hi) in enumerate(parts_):
                     run_row(eng, lo, hi, row, pass_key(key, p), renoise_p.get(e), noises_[j], noise_row0_, graph_)
 
-        nsub = int(self.substreams) if int(self.substreams) > 0 else auto_substreams(V * N, H, W)
+        nsub = int(self.substreams) if int(self.substreams) > 0 else (
+            auto_substreams(V * N, H, W) if tiles is None else auto_substreams(R * N, tiles[0], tiles[1]))
         nsub = max(1, min(nsub, N))
         use_graph = bool(self.use_graph)
         if (int(self.substreams) <= 0 and self.calibrate_mode and not host_rng and self._range_probe is None and nsub > 1
@@ -1130,13 +1235,14 @@ class DenoisingModel(nn.Module):
         for eng, lo, hi in (parts if consume is None else []):
             with eng.enter():
                 n_ = hi - lo                                   # (with views the engine holds V * n_ rows: view 0 is the first n_)
+                src = canvases.get(lo, eng)                    # (with tiles the outputs are the canvas's: n_ rows of H x W)
                 if t_values[-1] > 1 or last_mode == hip.STEP_LAST_KEEP:
-                    idx = eng.xt.reshape(-1, H, W)[:n_].long()
+                    idx = src.xt.reshape(-1, H, W)[:n_].long()
                     out = torch.nn.functional.one_hot(idx, K).permute(0, 3, 1, 2).to(torch.float32)
                 elif last_mode == hip.STEP_LAST_CONFIDENCE:
-                    out = eng.out_probs[:n_].clone().permute(0, 3, 1, 2)     # BCHW view of channels-last memory, like the reference
+                    out = src.out_probs[:n_].clone().permute(0, 3, 1, 2)     # BCHW view of channels-last memory, like the reference
                 else:
-                    out = eng.out_onehot[:n_].clone().permute(0, 3, 1, 2)
+                    out = src.out_onehot[:n_].clone().permute(0, 3, 1, 2)
             eng.leave()
             outs.append(out)
         # read AND clear the sticky range flag of every sub-batch engine before raising: a flag left set on a cached engine would
@@ -1147,7 +1253,7 @@ class DenoisingModel(nn.Module):
         if consume is not None:            # (only after the flag check: a range-error re-run must not be consumed twice)
             for eng, lo, hi in parts:
                 with eng.enter():
-                    consume(eng, lo, hi)
+                    consume(canvases.get(lo, eng), lo, hi)
                 eng.leave()
             return {}
         out = outs[0] if nsub == 1 else torch.cat(outs, 0)

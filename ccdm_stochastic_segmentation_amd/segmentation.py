@@ -1087,10 +1087,10 @@ def eval_segmentation(params: dict, dataset=None, device=None, model=None, synth
     and `evaluation.uncertainty_measures` (default both maps); a bad value, or one evaluation, raises before anything is sampled.
     Under the majority vote mutual_info equals entropy by construction, so only entropy is scored there.  The result then holds
     "uncertainty" (SegmentationUncertainty.result), also written to <output_path>/uncertainty.json.
-    The params key `sampling: {temperature: ..., truncation: ..., views: [...]}` (evaluation.sampling_keywords; each optional) is handed
+    The params key `sampling: {temperature: ..., truncation: ..., views: [...], tiles: [...]}` (evaluation.sampling_keywords; each optional) is handed
     to every sampling call and to predict_multiple and echoed as "sampling" in the result; an unknown key under it raises before
     anything is sampled; without the key nothing changes.  With `views` the feature encoder, where there is one, runs once per view on
-    the mirrored image (evaluation.view_features).
+    the mirrored image (evaluation.view_features); with `tiles`, once per tile on the cropped image (evaluation.tile_features).
     `model`: a ready DenoisingModel-like callable (tests inject one); default: built from `params`."""
     from . import evaluation as E
     world = int(os.environ.get("WORLD_SIZE", "1") or 1)
@@ -1169,6 +1169,8 @@ def eval_segmentation(params: dict, dataset=None, device=None, model=None, synth
         image = image.to(device)
         if encoder is not None and sampling.get("views"):
             feature_condition = E.view_features(encoder, image, sampling["views"])
+        elif encoder is not None and sampling.get("tiles"):
+            feature_condition = E.tile_features(encoder, image, sampling["tiles"])
         else:
             feature_condition = encoder(image) if encoder is not None else None
         if unc is None:

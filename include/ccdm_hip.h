@@ -444,6 +444,49 @@ int ccdm_views_step(const float* x0 /*dev [V*N,HW,K]*/, const float* evidence /*
                     int64_t* out_onehot /*[N,HW,K] or NULL*/, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Tiled sampling of a canvas larger than the engine's geometry (DenoisingModel(..., tiles=)), the MultiDiffusion construction (Bar-Tal
+ * et al. 2023) for categorical diffusion: ONE chain runs on the canvas, at every reverse step the denoiser is evaluated on overlapping
+ * tiles of the current canvas state, the tiles' x0 are averaged per canvas pixel and one draw is made per canvas pixel.  A mean of
+ * probability vectors is one and the step posterior is linear in x0 up to its own normalisation, so the tiled step is the step on the
+ * per-pixel mean of the covering tiles' x0.
+ * THE geometry (host: models.tile_origins; the kernel derives the same origins from the six integers).  Canvas Hc x Wc, tile h x w,
+ * strides sy, sx with 1 <= sy <= h <= Hc and 1 <= sx <= w <= Wc:
+ *   Ty = 1 + ceil((Hc - h) / sy) tiles along y with origins oy_i = min(i * sy, Hc - h): the last tile is pushed back so that it ends at
+ *   the border; the origins are distinct and leave no gap.  The same along x: Tx, ox_j = min(j * sx, Wc - w).
+ *   Tile r = i * Tx + j, R = Ty * Tx.  Tile r COVERS canvas pixel (y, x) iff oy_i <= y < oy_i + h and ox_j <= x < ox_j + w;
+ *   c(y, x) >= 1 is the number of covering tiles.
+ * The R tiles of a sample are R rows of a larger batch of h x w rows, tile-major: row r * N + n is tile r of sample n, fed the crops of
+ * the canvas state and of the image.  Launched like ccdm_views_step, after a denoise step (on all R * N rows) whose table row has mode
+ * CCDM_STEP_SOFTMAX_ONLY, and in place of the evidence / shaped launch.
+ * THE definition, per sample n < N and canvas pixel (y, x), fp32:
+ *   m_k = (sum over the covering tiles in ascending r of x0[r * N + n][(y - oy_i) * w + (x - ox_j)][k]) * fp32(1 / c(y, x))
+ *         a sequential sum, one multiply at the end (by 1.0f where c = 1);
+ *   then ccdm_shaped_step's arithmetic on the row m, as ccdm_views_step does it: v_k = m_k, or m_k * evidence[n][y * Wc + x][k] where
+ *   evidence != NULL; temper and truncate (each skipped at its neutral value); ccdm_posterior_sample's arithmetic with softmax = 0 on
+ *   the shaped row, x_t = canvas_xt[n][y * Wc + x], alpha_t / cumalpha_tm1 / mode as given, and the Philox counters of the unguided
+ *   step of that row for pixel y * Wc + x and sample sample_offset + n: the draw is keyed by the canvas pixel, never by an engine row
+ *   or tile.
+ * Outputs.  CCDM_STEP_SAMPLE: the drawn class goes to canvas_xt[n][y * Wc + x] and to xt[r * N + n][(y - oy_i) * w + (x - ox_j)] for
+ * every covering tile, and where xin != NULL its one-hot to channels [0, K) of xin at that tile pixel; channels >= K are not touched.
+ * CCDM_STEP_LAST_CONFIDENCE: the posterior goes to the canvas out_probs.  CCDM_STEP_LAST_MAJORITY: the one-hot of the posterior's
+ * argmax goes to the canvas out_onehot and its index to canvas_xt and the covering tiles' xt.  CCDM_STEP_LAST_KEEP: nothing is written.
+ * Every tile pixel maps to exactly one canvas pixel, so every byte and every one-hot row has one writer.  The tiles' x0 is only read;
+ * the canvas out_probs is another buffer.
+ * Consequences.  One tile that is the canvas (h = Hc, w = Wc) is ccdm_shaped_step bit for bit.  With sy = h / 2, sx = w / 2 and a canvas
+ * that is a multiple of the strides c is in {1, 2, 4}: tiles whose x0 are exact crops of one canvas-shaped x0 give ccdm_shaped_step on
+ * that x0 bit for bit (a sum of 2 or 4 equal values times 1/2 or 1/4 is exact).  After every launch each tile's xt is the crop of
+ * canvas_xt, whatever x0 holds.
+ * Refused: what ccdm_shaped_step refuses, CCDM_STEP_SOFTMAX_ONLY, a tile larger than the canvas, a stride < 1 or larger than the tile,
+ * N * Hc * Wc or R * N * h * w > 2^31 - 1.  Results depend on (canvas pixel, global sample index, step row, key) and the geometry only.
+ * ------------------------------------------------------------------------------------------------- */
+int ccdm_tiled_step(const float* x0 /*dev [R*N,h*w,K]*/, const float* evidence /*dev [N,Hc*Wc,K], weights in [0,1], or NULL*/, int N, int Hc,
+                    int Wc, int h, int w, int sy, int sx, int K, float inv_temperature, float top_r, float alpha_t, float cumalpha_tm1,
+                    int mode /*CCDM_STEP_SAMPLE | _LAST_CONFIDENCE | _LAST_MAJORITY | _LAST_KEEP*/, int step_row, uint64_t philox_seed,
+                    uint32_t sample_offset, uint8_t* canvas_xt /*dev [N,Hc*Wc]: x_t in, x_{t-1} out*/, uint8_t* xt /*dev [R*N,h*w]*/,
+                    float* xin /*dev [R*N,h*w,xin_stride] or NULL*/, int xin_stride, float* out_probs /*[N,Hc*Wc,K] or NULL*/,
+                    int64_t* out_onehot /*[N,Hc*Wc,K] or NULL*/, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * LIDC metrics, device part: for every image and every pair (i, j) of class-index maps
  * a[img][i], b[img][j], the per-class pixel counts out[img][i][j][k] = {|a==k & b==k|, |a==k | b==k|}.
  * Replaces the [B,S,S',HW,K] boolean broadcast of `batched_distance` / `iou`
