@@ -19,6 +19,10 @@
 //             the sample, and the class goes to the canvas state and back to every covering tile, so the tiles stay crops of one state.
 //             A kernel pair of its own (k_tiled, k_tiled_staged) below the guided pair, on the same shared pieces: the geometric map is a
 //             run-time loop over a per-pixel number of contributors where the views' is an unrolled loop over at most four.
+//   slots     (serving.SamplingQueue, ccdm_slots_step; nothing reshaped) continuous batching: every engine row is a slot that holds a
+//             sample of some request at its own place in its own walk, so what the other entries take as uniform launch arguments —
+//             coefficients, mode, step row, key, sample index — comes per row from a device table.  A kernel pair of its own (k_slots,
+//             k_slots_staged) at the end of the kernels, on the same shared pieces.
 // THE definitions: include/ccdm_hip.h.  ONE kernel pair in two instantiations: VIEWS = false is ccdm_shaped_step and, at (1, 1) with
 // the evidence required, ccdm_evidence_step (a kernel of its own for that was 1.003x / 1.00x of this one: DESIGN.md section 4);
 // VIEWS = true is ccdm_views_step, which cannot stand in for the other at V = 1 (1.07x / 1.14x, its extra LDS pass).
@@ -442,6 +446,81 @@ __global__ __launch_bounds__(BLK) void k_tiled_staged(const ccdm_post_args a, co
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Slots (ccdm_slots_step): the plain step — no evidence, no shaping, one view — with every launch argument that describes the ROW
+// coming per engine row from a device table (include/ccdm_hip.h: ccdm_slot_row).  `a` as launch_guided fills it, without key and
+// offset.  A block's pixels may belong to several slots (HW need not be a multiple of the block): the slot is found per pixel, and the
+// two LDS passes of the staged kernel run per slot segment of the block, so an idle slot is neither read nor written.
+
+// a real step mode: everything else (CCDM_SLOT_IDLE) holds nothing
+__device__ __forceinline__ bool slot_runs(const int mode) { return (unsigned)mode <= (unsigned)CCDM_STEP_LAST_KEEP; }
+
+// `a` for a pixel of slot n: the slot's key, and the offset that makes the core's sample index (n + sample_offset) the slot's `sample`
+__device__ __forceinline__ ccdm_post_args slot_post_args(const ccdm_post_args& a_in, const ccdm_slot_row& r, const unsigned n) {
+    ccdm_post_args a = a_in;
+    a.philox_seed = (uint64_t)r.key_lo | ((uint64_t)r.key_hi << 32);
+    a.sample_offset = r.sample - n;                                      // (mod 2^32, like the core's sum)
+    return a;
+}
+
+template <int KP>
+__global__ __launch_bounds__(256) void k_slots(const ccdm_post_args a_in, const ccdm_slot_row* const table, const int vec) {
+    const size_t npix = (size_t)a_in.N * a_in.HW;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npix) return;
+    const unsigned n = (unsigned)i / (unsigned)a_in.HW;                  // (N * HW < 2^31: the launcher checks)
+    const ccdm_slot_row r = table[n];                                    // a wave inside one slot: 64 loads of one address
+    if (!slot_runs(r.mode)) return;
+    const ccdm_post_args a = slot_post_args(a_in, r, n);
+    float q[KP];
+    load_pixel_row<KP>(q, a.head, i, nullptr, a.K, vec);
+    posterior_pixel_core<KP>(a, i, q, r.step_row, r.alpha_t, r.cumalpha_tm1, r.mode, (int)a.xt[i]);
+}
+
+template <int KP, int BLK>
+__global__ __launch_bounds__(BLK) void k_slots_staged(const ccdm_post_args a_in, const ccdm_slot_row* const table) {
+    constexpr int PITCH = (KP | 1) > CCDM_MAX_CLASSES ? CCDM_MAX_CLASSES : (KP | 1);      // odd, >= K
+    __shared__ float sx[BLK * PITCH];
+    __shared__ int sb[BLK];
+    const unsigned HW = (unsigned)a_in.HW;
+    const unsigned npix = (unsigned)a_in.N * HW;
+    const unsigned i0 = blockIdx.x * (unsigned)BLK;
+    const int tid = threadIdx.x;
+    const int nvalid = (int)std::min<unsigned>((unsigned)BLK, npix - i0);
+    const int K = a_in.K;
+    const bool mine = tid < nvalid;
+    // the block's slots n_lo .. n_hi; slot n holds the block's pixels [max(n * HW, i0), min((n + 1) * HW, i0 + nvalid)) — all uniform
+    const unsigned n_lo = i0 / HW, n_hi = (i0 + (unsigned)nvalid - 1u) / HW;
+    for (unsigned n = n_lo; n <= n_hi; ++n) {
+        if (!slot_runs(table[n].mode)) continue;
+        const unsigned s0 = std::max(n * HW, i0) - i0, s1 = std::min((n + 1u) * HW, i0 + (unsigned)nvalid) - i0;
+        stage_class_rows<BLK, PITCH, false>(sx + s0 * PITCH, a_in.head + (size_t)(i0 + s0) * K, nullptr, (int)(s1 - s0), (unsigned)K, tid);
+    }
+    __syncthreads();
+    int bi = 0;
+    if (mine) {
+        const unsigned n = (i0 + (unsigned)tid) / HW;
+        const ccdm_slot_row r = table[n];
+        if (slot_runs(r.mode)) {
+            const ccdm_post_args a = slot_post_args(a_in, r, n);
+            float x0[KP];
+#pragma unroll
+            for (int k = 0; k < KP; ++k) x0[k] = k < K ? sx[tid * PITCH + k] : 0.f;
+            // (&bi unconditionally, as in k_guided_staged: bi stays in a register)
+            posterior_pixel_core<KP>(a, (size_t)i0 + tid, x0, r.step_row, r.alpha_t, r.cumalpha_tm1, r.mode, (int)a.xt[i0 + tid], &bi);
+        }
+    }
+    if (!a_in.xin) return;                                               // uniform
+    sb[tid] = bi;
+    __syncthreads();
+    const unsigned stride = (unsigned)a_in.xin_stride;
+    for (unsigned n = n_lo; n <= n_hi; ++n) {
+        if (table[n].mode != CCDM_STEP_SAMPLE) continue;
+        const unsigned s0 = std::max(n * HW, i0) - i0, s1 = std::min((n + 1u) * HW, i0 + (unsigned)nvalid) - i0;
+        store_onehot_rows<BLK>(a_in.xin + (size_t)(i0 + s0) * stride, sb + s0, (int)(s1 - s0), stride, K, tid);
+    }
+}
+
 // What the three entries hand to launch_guided
 struct guided_call {
     const float *x0, *evidence;
@@ -554,9 +633,44 @@ static int launch_tiled(const char* name, const guided_call& c, const int h, con
     return 0;
 }
 
+// The slots' launcher: the shapes of launch_guided; mode and step row are the table's, on the device, so the shared check gets neutral ones.
+static int launch_slots(const char* name, const float* x0, const ccdm_slot_row* table, const int N, const int HW, const int K, uint8_t* xt, float* xin,
+                        const int xin_stride, float* out_probs, int64_t* out_onehot, void* stream) {
+    const int blk = K <= 32 ? 256 : 64;
+    if (const int rc = check_step_args(name, x0 && table && xt, N, HW, K, xin, xin_stride, CCDM_STEP_SAMPLE, 0, blk)) return rc;
+    CCDM_REQUIRE((size_t)N * HW <= 0x7FFFFFFFull, "%s: too many pixels (N*HW = %zu)", name, (size_t)N * HW);
+    CCDM_REQUIRE((reinterpret_cast<uintptr_t>(table) & 3) == 0, "%s: misaligned table", name);
+    const size_t npix = (size_t)N * HW;
+    ccdm_post_args a = {};
+    a.head = x0; a.softmax = 0; a.head_stride = K;
+    a.xt = xt; a.xt_next = xt;
+    a.N = N; a.HW = HW; a.K = K;
+    a.xin = xin; a.xin_stride = xin_stride;
+    a.out_probs = out_probs; a.out_onehot = out_onehot;
+    const dim3 grid((unsigned)((npix + blk - 1) / blk)), block(blk);
+    hipStream_t s = (hipStream_t)stream;
+    dispatch_kp<256>(K, [&](auto kp) {
+        constexpr int KP = decltype(kp)::value;
+        if constexpr (KP <= 4) {
+            const uintptr_t addr = reinterpret_cast<uintptr_t>(x0);
+            const int vec = (K == 2 && (addr & 7) == 0) || (K == 4 && (addr & 15) == 0);
+            hipLaunchKernelGGL((k_slots<KP>), grid, block, 0, s, a, table, vec);
+        } else {
+            hipLaunchKernelGGL((k_slots_staged<KP, (KP <= 32 ? 256 : 64)>), grid, block, 0, s, a, table);
+        }
+    });
+    CCDM_CHECK_LAUNCH(name);
+    return 0;
+}
+
 }  // namespace ccdm
 
 using namespace ccdm;
+
+extern "C" int ccdm_slots_step(const float* x0, const ccdm_slot_row* table, int N, int HW, int K, uint8_t* xt, float* xin, int xin_stride,
+                               float* out_probs, int64_t* out_onehot, void* stream) {
+    return launch_slots("ccdm_slots_step", x0, table, N, HW, K, xt, xin, xin_stride, out_probs, out_onehot, stream);
+}
 
 extern "C" int ccdm_evidence_step(const float* x0, const float* evidence, int N, int HW, int K, float alpha_t, float cumalpha_tm1, int mode,
                                   int step_row, uint64_t philox_seed, uint32_t sample_offset, uint8_t* xt, float* xin, int xin_stride,

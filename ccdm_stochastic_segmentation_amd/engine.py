@@ -548,6 +548,39 @@ class SamplerEngine:
             hip.check(lib.ccdm_gn_stats(f.ptr, N, f.h * f.w, f.C, 1, f.stats_ptr, s), "gn_stats(feat)")
         self._cond_keepalive = (cond, feat)
 
+    def set_slot_inputs(self, n0: int, xt_idx: torch.Tensor, cond: torch.Tensor) -> None:
+        """What set_inputs does, for the rows n0 .. n0 + n - 1 only (a sampling queue admits samples into free slots while the other
+        rows are mid-walk): xt_idx uint8 [n,H,W] and cond fp32 [n,C_img,H,W], contiguous, on the engine's device.  Asynchronous on the
+        engine's stream, which the caller has made current (enter); the caller keeps both tensors alive until the copies have run."""
+        lib, s, HW = self.lib, self._stream(), self.H * self.W
+        n = int(xt_idx.shape[0])
+        n0 = int(n0)
+        if self.feat is not None:
+            raise ValueError("set_slot_inputs: a model that takes a feature_condition is not built")
+        assert 0 <= n0 and n >= 1 and n0 + n <= self.N, (n0, n, self.N)
+        assert tuple(xt_idx.shape) == (n, self.H, self.W) and xt_idx.dtype == torch.uint8 and xt_idx.is_cuda and xt_idx.is_contiguous()
+        assert tuple(cond.shape) == (n, self.C_img, self.H, self.W) and cond.dtype == torch.float32 and cond.is_cuda and cond.is_contiguous()
+        self.xt[n0:n0 + n].copy_(xt_idx.reshape(n, HW))
+        xin = self.xin.ptr + n0 * HW * self.Cs * 4
+        hip.check(lib.ccdm_nchw_to_nhwc(cond.data_ptr(), xin, n, self.C_img, HW, self.Cs, self.K, s), "nchw_to_nhwc")
+        hip.check(lib.ccdm_onehot_to_xin(self.xt.data_ptr() + n0 * HW, xin, n, HW, self.K, self.Cs, s), "onehot_to_xin")
+
+    def set_rows(self, rows: torch.Tensor, non_blocking: bool = False) -> None:
+        """Slot n's network pass of the next `run(..., first_row=0)` reads time-embedding row rows[n]: int32 [N], copied into `rowmap`
+        on the current stream (the engine's: enter).  non_blocking: `rows` is pinned and the caller guards it until the copy has run.
+        The tables no longer describe one walk: the next set_tables rewrites them, rowmap included."""
+        assert tuple(rows.shape) == (self.N,) and rows.dtype == torch.int32
+        self.rowmap.copy_(rows, non_blocking=non_blocking)
+        self._tables_key = None
+
+    def slots_step(self, table: torch.Tensor) -> None:
+        """The reverse step of every slot behind a `run` whose table row has mode STEP_SOFTMAX_ONLY, each with its own parameters
+        (ccdm_slots_step, asynchronous on the engine's stream).  table: the N rows of hip.SlotRow on the engine's device, 32 bytes each."""
+        assert table.is_cuda and table.is_contiguous() and table.numel() * table.element_size() == self.N * C.sizeof(hip.SlotRow)
+        hip.check(self.lib.ccdm_slots_step(self.out_probs.data_ptr(), table.data_ptr(), self.N, self.H * self.W, self.K, self.xt.data_ptr(),
+                                           None if self.stem_onehot_on_load else self.xin.ptr, self.Cs, self.out_probs.data_ptr(),
+                                           self.out_onehot.data_ptr(), self._stream()), "slots_step")
+
     def set_tables(self, t_rows: Sequence[float], coeffs: Sequence[Tuple[float, float, int]], per_sample: bool = False) -> None:
         """t_rows[i] = timestep of table row i; coeffs[i] = (alpha_t, cumalpha_tm1, mode).
         per_sample=True maps sample n to row n (forward_step with a per-sample t)."""

@@ -29,6 +29,7 @@ DIAG_GENERAL_KERNEL = 2048 << 8     # CCDM_DIAG_GENERAL_KERNEL: OR into ConvArgs
 PREC_F32, PREC_F16X3 = 0, 1
 PREC_F16 = 2             # CCDM_PREC_F16: the OPT-IN single-pass fast mode (one fp16 MFMA per product, ~2^-11 per operand) — outside the parity contract
 STEP_SAMPLE, STEP_LAST_CONFIDENCE, STEP_LAST_MAJORITY, STEP_LAST_KEEP, STEP_SOFTMAX_ONLY = 0, 1, 2, 3, 4
+SLOT_IDLE = -1           # CCDM_SLOT_IDLE: SlotRow.mode of a slot that holds nothing (ccdm_slots_step)
 STATS_MAX_SLICES = 64       # CCDM_STATS_MAX_SLICES: what a GroupNorm consumer reads
 F16X3_LIMIT = 4094.0        # CCDM_F16X3_LIMIT: the fp16 split is exact for staged |a| below this
 STATS_FOLD_SLICES = 16      # CCDM_STATS_FOLD_SLICES: what the engine folds a larger slice count to
@@ -76,6 +77,16 @@ class PostArgs(C.Structure):
         ("noise_row0", C.c_int32),
         ("range_flag", C.c_void_p),
         ("run", C.c_void_p),
+    ]
+
+
+class SlotRow(C.Structure):
+    """ccdm_slot_row: one row of ccdm_slots_step's device table, the per-slot parameters of a sampling queue's reverse step."""
+    _fields_ = [
+        ("alpha_t", C.c_float), ("cumalpha_tm1", C.c_float),
+        ("mode", C.c_int32), ("step_row", C.c_int32),
+        ("key_lo", C.c_uint32), ("key_hi", C.c_uint32),
+        ("sample", C.c_uint32), ("reserved", C.c_uint32),
     ]
 
 
@@ -171,6 +182,8 @@ SIGNATURES = {
     "ccdm_tiled_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                   C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ccdm_slots_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                  C.c_void_p]),
     "ccdm_pairwise_class_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "ccdm_lidcscore": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ccdm_surfdist_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),

@@ -548,8 +548,9 @@ class DenoisingModel(nn.Module):
         (optimizer steps, Polyak averaging, p.data.copy_) bump the tensors' own version counters."""
         return self.unet._weights_version, sum(int(p._version) for p in self.unet.parameters())
 
-    def _engine(self, x: Tensor, condition: Tensor, feature_condition: Optional[Tensor], slot: int = 0) -> SamplerEngine:
-        """The step executor for this input geometry (cached).  `slot` tells apart the engines of concurrent sub-batches."""
+    def _engine(self, x: Tensor, condition: Tensor, feature_condition: Optional[Tensor], slot: Any = 0) -> SamplerEngine:
+        """The step executor for this input geometry (cached).  `slot` tells apart the engines of concurrent sub-batches (an int) and
+        the engine a sampling queue owns (a key of its own, so no plain call shares it)."""
         N, K, H, W = x.shape
         spec = self.unet.spec
         if feature_condition is not None and spec.feature_condition_unwired:
@@ -572,6 +573,12 @@ class DenoisingModel(nn.Module):
         self._engines = {k: v for k, v in self._engines.items() if v[0] == wkey}
         self._engines[key] = (wkey, eng)
         return eng
+
+    def sampling_queue(self, capacity: int, image_shape: Sequence[int]):
+        """A continuous-batching queue on this model (serving.SamplingQueue): requests of any size and walk length share one engine of
+        `capacity` rows, each reproducing its solo call bit for bit."""
+        from .serving import SamplingQueue
+        return SamplingQueue(self, capacity, image_shape)
 
     def _philox_key(self) -> int:
         """64-bit Philox key of the current sampling call: splitmix64 of (philox_seed, philox_call)."""

@@ -487,6 +487,38 @@ int ccdm_tiled_step(const float* x0 /*dev [R*N,h*w,K]*/, const float* evidence /
                     int64_t* out_onehot /*[N,Hc*Wc,K] or NULL*/, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * The reverse step of a sampling queue (serving.SamplingQueue): continuous batching.  The N rows of an engine are SLOTS; each holds
+ * one sample of some request at its own place in its own walk, or nothing.  Launched like ccdm_shaped_step, after a denoise step whose
+ * table row has mode CCDM_STEP_SOFTMAX_ONLY (the network pass of slot n ran at time-embedding row emb_row_of_sample[n]): it does the
+ * reverse step of every slot with that slot's own parameters, read from a device table of one 32-byte row per slot.
+ * THE definition.  For slot n with table[n].mode one of the four real step modes, the launch leaves in xt, in channels [0, K) of xin
+ * and in rows [n * HW, (n + 1) * HW) of out_probs / out_onehot exactly the bits that
+ *     ccdm_shaped_step(x0 + n * HW * K, NULL, 1, HW, K, 1.0f, 1.0f, alpha_t, cumalpha_tm1, mode, step_row, key_hi << 32 | key_lo,
+ *                      sample, xt + n * HW, xin + n * HW * xin_stride, xin_stride, out_probs + n * HW * K, out_onehot + n * HW * K)
+ * leaves (the same device function on the same values: posterior in the documented op order, clamp, cascade normalisation, the Exp(1)
+ * race with Philox4x32-10(counter = (pixel, sample, step_row, k / 4), key)): the draw is keyed by the slot's request, its global sample
+ * index and the row of its own walk, never by the slot.  For a slot whose mode is CCDM_SLOT_IDLE — or any value that is no real step
+ * mode — nothing of the slot is read and nothing written, in any buffer.  Channels >= K of xin are never touched.
+ * x0 and out_probs may be the same buffer (in the engine they are): a pixel's K values are in registers, or its block's in LDS behind a
+ * barrier, before its out_probs row is written.  K <= 4: one thread per pixel; K <= 32: 256 pixels per block staged through LDS;
+ * above: 64 pixels per block.  A block's pixels may belong to several slots: the slot is found per pixel, the staging passes run per
+ * slot segment of the block.  Refused: a null x0 / table / xt, N or HW < 1, N * HW > 2^31 - 1, K outside [1, CCDM_MAX_CLASSES],
+ * xin_stride < K where xin is given.  The table's contents are the caller's: they are not checked on the host.
+ * ------------------------------------------------------------------------------------------------- */
+#define CCDM_SLOT_IDLE (-1)         /* ccdm_slot_row.mode of a slot that holds nothing */
+typedef struct ccdm_slot_row {
+    float alpha_t; float cumalpha_tm1;      /* the two coefficients of the slot's current row (DiffusionModel.posterior_coeffs) */
+    int32_t mode;                           /* CCDM_STEP_SAMPLE | _LAST_CONFIDENCE | _LAST_MAJORITY | _LAST_KEEP, or CCDM_SLOT_IDLE */
+    int32_t step_row;                       /* the row index in the slot's own walk: the third Philox counter word */
+    uint32_t key_lo; uint32_t key_hi;       /* the Philox key of the slot's request */
+    uint32_t sample;                        /* the global sample index: the second Philox counter word */
+    uint32_t reserved;
+} ccdm_slot_row;
+int ccdm_slots_step(const float* x0 /*dev [N,HW,K]*/, const ccdm_slot_row* table /*dev [N]*/, int N, int HW, int K,
+                    uint8_t* xt /*dev [N,HW]: x_t in, x_{t-1} out*/, float* xin /*dev [N,HW,xin_stride] or NULL*/, int xin_stride,
+                    float* out_probs /*[N,HW,K] or NULL*/, int64_t* out_onehot /*[N,HW,K] or NULL*/, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * LIDC metrics, device part: for every image and every pair (i, j) of class-index maps
  * a[img][i], b[img][j], the per-class pixel counts out[img][i][j][k] = {|a==k & b==k|, |a==k | b==k|}.
  * Replaces the [B,S,S',HW,K] boolean broadcast of `batched_distance` / `iou`
