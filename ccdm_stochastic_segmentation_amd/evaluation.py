@@ -239,6 +239,37 @@ def lesion_min_size(value) -> int:
     return value
 
 
+def mode_count(value) -> int:
+    """`mode_count`: how many modes the mode summary looks for, 1 to 16 (metrics.MODES_MAX_MODES)."""
+    if isinstance(value, bool) or not isinstance(value, int) or not 1 <= value <= M.MODES_MAX_MODES:
+        raise ValueError(f"mode_count: {value!r} (expected a whole number in [1, {M.MODES_MAX_MODES}])")
+    return value
+
+
+def mode_max_swaps(value) -> int:
+    """`mode_max_swaps`: the most swaps the clustering applies after its greedy start, at least 0."""
+    if isinstance(value, bool) or not isinstance(value, int) or value < 0:
+        raise ValueError(f"mode_max_swaps: {value!r} (expected a whole number, at least 0)")
+    return value
+
+
+def mode_summary_scores(pred_idx: torch.Tensor, lab_idx: torch.Tensor, num_classes: int, count: int, max_swaps: int) -> Dict[str, np.ndarray]:
+    """Per image of pred_idx [B,S,H,W] against the raters lab_idx [B,L,H,W], float64 [B] each: `found` (the modes metrics.sample_modes
+    finds among `count`), `largest_share`, `ged_summary` (the GED between the raters and the medoids weighted by their shares,
+    2 sum_m w_m mean_l d(m,l) - sum_{m,m'} w_m w_m' d(m,m') - mean_{l,l'} d(l,l'), d = metrics.batched_distance) and `coverage` (the
+    mean over the raters of the distance to the nearest medoid); `converged` as the clustering reports it."""
+    modes = M.sample_modes(pred_idx, num_classes, count, max_swaps=max_swaps, maps=())
+    used = (modes["medoid"] >= 0).cpu().numpy()                                  # [B,M]
+    w = modes["size"].cpu().numpy().astype(np.float64) / float(pred_idx.shape[1])     # (size / S in float64, as a mean over samples weighs)
+    to_raters = M.batched_distance(modes["mode_map"], lab_idx, num_classes)          # [B,M,L]; an unused mode weighs 0
+    among = M.batched_distance(modes["mode_map"], modes["mode_map"], num_classes)    # [B,M,M]
+    raters = M.batched_distance(lab_idx, lab_idx, num_classes)                       # [B,L,L]
+    ged = 2.0 * (w * to_raters.mean(axis=2)).sum(axis=1) - (w[:, :, None] * w[:, None, :] * among).sum(axis=(1, 2)) - raters.mean(axis=(1, 2))
+    nearest = np.where(used[:, :, None], to_raters, np.inf).min(axis=1)              # [B,L]
+    return {"found": used.sum(axis=1).astype(np.float64), "largest_share": w[:, 0], "ged_summary": ged, "coverage": nearest.mean(axis=1),
+            "converged": modes["converged"].cpu().numpy().astype(np.float64)}
+
+
 @torch.no_grad()
 def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optional[int] = None, synthetic_weights_seed: Optional[int] = None,
                           model=None) -> Dict[str, object]:
@@ -275,7 +306,14 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
                             ccdm_lesion_match call per batch and entry, kept per image and scored after the last batch); with
                             `output_path` set, also written as lidc_lesion_matching.json
          lesion_match_ious ([0.5, 0.75]): the IoUs a pair has to exceed, in [0.5, 1), each read as the decimal it is written as;
-                            lesion_min_size (1): lesions of fewer pixels are dropped; lesion_connectivity as above"""
+                            lesion_min_size (1): lesions of fewer pixels are dropped; lesion_connectivity as above
+         modes: yes         the result gains "modes": one dict per entry of `evaluations` with the mode summary of the first s
+                            samples (metrics.sample_modes: k-medoids under the GED's own distance, on the device): the mean number
+                            of modes found, the mean share of the largest, `ged_summary` (the GED between the raters and the medoids
+                            weighted by their shares) and `coverage` (the mean over raters of the distance to the nearest medoid),
+                            each a mean over the images (mode_summary_scores); with `output_path` set, also written as
+                            lidc_modes.json
+         mode_count (4): the modes looked for, 1 to 16;  mode_max_swaps (64): the most swaps of the clustering"""
     from . import distributed as D
     rank, local_rank, world = D.init_from_env()
     if device is None:
@@ -328,6 +366,10 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
         match_conn = lesion_connectivity(section)
         match_thresholds = lesion_match_thresholds(section.get("lesion_match_ious", [0.5, 0.75]))
         match_min_size = lesion_min_size(section.get("lesion_min_size", 1))
+    modes = [[] for _ in evaluations] if section.get("modes", False) else None                   # per entry: the scores of every batch
+    if modes is not None:
+        modes_count = mode_count(section.get("mode_count", 4))
+        modes_swaps = mode_max_swaps(section.get("mode_max_swaps", 64))
     for image, labels, _ in loader:                                              # Tester.test_step, :89-136
         image = image.to(device).repeat_interleave(S, dim=0)
         # x_T: uniform one-hot from the CPU generator, full batch on every rank (same seed => same draw)
@@ -357,6 +399,8 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
             if match is not None:
                 match[i].append(M.lesion_match_stats(pred_idx[:, :s], lab_idx, num_classes, connectivity=match_conn,
                                                      thresholds=match_thresholds, min_size=match_min_size))
+            if modes is not None:
+                modes[i].append(mode_summary_scores(pred_idx[:, :s], lab_idx, num_classes, modes_count, modes_swaps))
         # log-mean vote exactly as the reference takes it (:125): log(0) = -inf stays -inf (one-hot "majority" predictions:
         # a class any sample rejects is out; where every class is rejected by someone argmax falls to class 0)
         mean_pred = torch.log(prediction).mean(dim=1).argmax(dim=1)
@@ -425,6 +469,23 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
             os.makedirs(out_dir, exist_ok=True)
             with open(os.path.join(out_dir, "lidc_lesion_matching.json"), "w") as f:
                 json.dump(res["lesion_matching"], f, indent=1)
+    if modes is not None:
+        res["modes"] = []
+        for s, parts in zip(evaluations, modes):
+            per_image = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
+            res["modes"].append({"samples": int(s), "images": int(per_image["found"].size), "mode_count": modes_count, "max_swaps": modes_swaps,
+                                 "modes_found": float(per_image["found"].mean()), "largest_share": float(per_image["largest_share"].mean()),
+                                 "ged_summary": float(per_image["ged_summary"].sum() / n_img), "coverage": float(per_image["coverage"].mean()),
+                                 "converged": float(per_image["converged"].mean())})
+            r = res["modes"][-1]
+            LOGGER.info("modes (%d): %.3g of %d found  largest share %.3g  GED of the summary %.4g  coverage %.4g", s, r["modes_found"],
+                        modes_count, r["largest_share"], r["ged_summary"], r["coverage"])
+        if params.get("output_path") and rank == 0:
+            import json
+            out_dir = expanduservars(params["output_path"])
+            os.makedirs(out_dir, exist_ok=True)
+            with open(os.path.join(out_dir, "lidc_modes.json"), "w") as f:
+                json.dump(res["modes"], f, indent=1)
     return res
 
 

@@ -20,7 +20,11 @@ And the lesion-level scores: `lesion_stats` (HIP kernel ccdm_lesions: connected-
 `lesion_scores_from_stats` derives lesion-wise recall, precision, F1 and the agreement on the number of lesions on the host.
 `lesion_match_stats` pairs the lesions of the two maps one to one by IoU (HIP kernel ccdm_lesion_match on the same workspace: matched
 pairs and the fixed-point sum of their IoUs per threshold), `lesion_match_scores_from_stats` derives panoptic, segmentation and
-recognition quality on the host."""
+recognition quality on the host.
+
+And the mode summary of the samples themselves: `sample_modes` (HIP kernels ccdm_modes_distance, ccdm_modes_pam, ccdm_modes_maps:
+the pairwise fixed-point distance among the S samples of an image, k-medoids on it, per-mode vote and entropy maps) says which
+distinct segmentations the samples propose and which share of the samples each holds; everything stays on the device."""
 from __future__ import annotations
 
 import math
@@ -502,3 +506,90 @@ def lesion_match_scores_from_stats(stats: Dict[str, object], *, class_names: Opt
     if class_names is not None:
         res["class_names"] = [str(c) for c in class_names]
     return res
+
+
+# ------------------------------------------------------------------------------------------------ mode summary
+MODE_MAPS = ("vote", "entropy", "counts")
+MODES_MAX_CLASSES, MODES_MAX_SAMPLES, MODES_MAX_MODES = 32, 256, 16
+MODE_DISTANCE_ONE = 1 << 20               # Q counts the Jaccard distance of a class in units of 2^-20
+MODE_UNUSED = 255                         # mode_map / mode_vote of a mode that does not exist
+
+
+def whole_number(value, name: str, lo: int, hi: Optional[int], what: str) -> int:
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or value < lo or (hi is not None and value > hi):
+        raise ValueError(f"{name}: {value!r} ({what})")
+    return int(value)
+
+
+def sample_modes(samples_idx: torch.Tensor, num_classes: int, modes: int, max_swaps: int = 64, maps: Sequence[str] = ("vote", "entropy"),
+                 return_distance: bool = False) -> Dict[str, torch.Tensor]:
+    """The modes of S samples per image: samples_idx [B,S,H,W] integer class maps on the GPU -> k-medoids (PAM: BUILD, then
+    best-improvement SWAP) with M = `modes` clusters per image under the distance of the LIDC scores, 1 - mean foreground IoU, held as
+    the int32 fixed-point Q = sum over the classes 1..K-1 of the Jaccard distance in units of 2^-20 (include/ccdm_hip.h has the
+    definition, with every tie rule; all sums are integers, so the result does not depend on a reduction order).  2 <= num_classes
+    <= 32, 1 <= S <= 256, 1 <= modes <= 16.  Modes are ordered by size, the largest first; when the samples hold fewer than M distinct
+    foreground maps the remaining modes are unused.  Device tensors, nothing is copied to the host:
+      medoid     int32 [B,M]   the sample that stands for the mode; -1: unused
+      assign     int32 [B,S]   the mode of every sample
+      size       int32 [B,M];  share fp32 [B,M] = size / S: how likely the mode is under the samples
+      spread     int64 [B,M]   the sum of Q from the medoid to the mode's members (divide by size * (K-1) * 2^20 for the mean distance)
+      cost       int64 [B]     the sum of the spreads;  swaps int32 [B]: swaps applied (at most max_swaps);  converged int32 [B]: 1 when
+                               no single swap lowers the cost any further
+      mode_map   uint8 [B,M,H,W]   the medoid sample itself; 255 where the mode is unused
+      mode_vote  uint8 [B,M,H,W]   ("vote" in maps) the majority class over the mode's members, lowest class on ties; 255: unused
+      mode_entropy fp32 [B,M,H,W]  ("entropy") the entropy in nats of the members' class frequencies: where the mode is unsure; 0: unused
+      mode_counts int32 [B,M,H,W,K]  ("counts") the members saying each class
+      distance   int32 [B,S,S]     (return_distance) Q; Q / ((K-1) * 2^20) is within 2^-21 of `batched_distance`."""
+    if not isinstance(samples_idx, torch.Tensor) or samples_idx.dim() != 4 or samples_idx.dtype.is_floating_point or samples_idx.dtype.is_complex \
+            or samples_idx.dtype == torch.bool:
+        raise ValueError(f"samples_idx: expected integer class maps [B,S,H,W], got {getattr(samples_idx, 'dtype', type(samples_idx).__name__)} "
+                         f"{tuple(getattr(samples_idx, 'shape', ()))}")
+    K = whole_number(num_classes, "num_classes", 2, MODES_MAX_CLASSES, f"expected a whole number in [2, {MODES_MAX_CLASSES}]")
+    M = whole_number(modes, "modes", 1, MODES_MAX_MODES, f"expected a whole number in [1, {MODES_MAX_MODES}]")
+    max_swaps = whole_number(max_swaps, "max_swaps", 0, 2 ** 31 - 1, "expected a whole number, at least 0")
+    B, S, H, W = (int(v) for v in samples_idx.shape)
+    if not 1 <= S <= MODES_MAX_SAMPLES:
+        raise ValueError(f"samples_idx: S={S} samples per image (expected 1 to {MODES_MAX_SAMPLES})")
+    if H * W < 1:
+        raise ValueError(f"samples_idx: empty maps {H}x{W}")
+    maps = tuple(maps)
+    bad = [m for m in maps if m not in MODE_MAPS]
+    if bad:
+        raise ValueError(f"maps: {bad} not available (choose from {MODE_MAPS})")
+    if samples_idx.device.type != "cuda":
+        raise hip.CcdmHipError("sample_modes needs GPU tensors (no CPU path)")
+    lib = hip.load()
+    dev, HW = samples_idx.device, H * W
+    a8 = samples_idx.reshape(B, S, HW).to(torch.uint8).contiguous()
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    ws = torch.empty((B, S, S, K), dtype=torch.int32, device=dev)
+    Q = torch.empty((B, S, S), dtype=torch.int32, device=dev)
+    hip.check(lib.ccdm_modes_distance(a8.data_ptr(), B, S, HW, K, ws.data_ptr(), Q.data_ptr(), stream), "modes_distance")
+    out = {"medoid": torch.empty((B, M), dtype=torch.int32, device=dev), "assign": torch.empty((B, S), dtype=torch.int32, device=dev),
+           "size": torch.empty((B, M), dtype=torch.int32, device=dev), "spread": torch.empty((B, M), dtype=torch.int64, device=dev),
+           "cost": torch.empty((B,), dtype=torch.int64, device=dev), "swaps": torch.empty((B,), dtype=torch.int32, device=dev),
+           "converged": torch.empty((B,), dtype=torch.int32, device=dev)}
+    hip.check(lib.ccdm_modes_pam(Q.data_ptr(), B, S, M, max_swaps, out["medoid"].data_ptr(), out["assign"].data_ptr(), out["size"].data_ptr(),
+                                 out["spread"].data_ptr(), out["cost"].data_ptr(), out["swaps"].data_ptr(), out["converged"].data_ptr(),
+                                 stream), "modes_pam")
+    # (through float64: the device divides by a scalar as a multiplication by its reciprocal, which in fp32 is not the rounded quotient)
+    out["share"] = (out["size"].to(torch.float64) / float(S)).to(torch.float32)
+    used = out["medoid"] >= 0                                                                     # [B,M]
+    picked = torch.gather(a8, 1, out["medoid"].clamp(min=0).long()[:, :, None].expand(B, M, HW))     # the medoid samples themselves
+    out["mode_map"] = torch.where(used[:, :, None], picked, torch.full_like(picked, MODE_UNUSED)).reshape(B, M, H, W)
+    if maps:
+        vote = torch.empty((B, M, HW), dtype=torch.uint8, device=dev)
+        counts = torch.empty((B, M, HW, K), dtype=torch.int32, device=dev) if "counts" in maps else None
+        entropy = torch.empty((B, M, HW), dtype=torch.float32, device=dev) if "entropy" in maps else None
+        hip.check(lib.ccdm_modes_maps(a8.data_ptr(), out["assign"].data_ptr(), out["size"].data_ptr(), B, S, M, HW, K, vote.data_ptr(),
+                                      None if counts is None else counts.data_ptr(), None if entropy is None else entropy.data_ptr(),
+                                      stream), "modes_maps")
+        if "vote" in maps:
+            out["mode_vote"] = vote.reshape(B, M, H, W)
+        if counts is not None:
+            out["mode_counts"] = counts.reshape(B, M, H, W, K)
+        if entropy is not None:
+            out["mode_entropy"] = entropy.reshape(B, M, H, W)
+    if return_distance:
+        out["distance"] = Q
+    return out

@@ -1073,6 +1073,75 @@ class DenoisingModel(nn.Module):
                 out[m] = cast(Tensor, got[m])
         return out
 
+    @torch.no_grad()
+    def predict_modes(self, condition: Tensor, feature_condition: Optional[Tensor] = None, *, num_evaluations: int, modes: int,
+                      x: Optional[Tensor] = None, t: Optional[Tensor] = None, max_swaps: int = 64,
+                      maps: Sequence[str] = ("vote", "entropy"),
+                      known_labels: Optional[Tensor] = None, resample: Optional[Tuple[int, int]] = None,
+                      evidence: Optional[Tensor] = None, temperature: Optional[float] = None,
+                      truncation: Optional[float] = None, views: Optional[Sequence[str]] = None,
+                      tiles: Optional[Sequence[int]] = None) -> Dict[str, Tensor]:
+        """S = `num_evaluations` samples of every image of `condition` [B,C,H,W], summarised on the device as M = `modes` distinct
+        segmentations with the share of the samples behind each: "three hypotheses: no nodule 55 %, small nodule 30 %, large nodule
+        15 %", where predict_multiple folds the samples per pixel and loses which segmentations they were.
+
+        One sampling call of B*S samples laid out as predict_multiple(batched=True) lays them out (condition repeat-interleaved,
+        sample b*S + s = sample s of image b), every pass ending in its argmax class ("majority"); the class maps are read straight
+        from the engine into a uint8 stack and clustered by metrics.sample_modes: k-medoids (PAM) under the distance of the LIDC
+        scores, 1 - mean foreground IoU, in exact integers (include/ccdm_hip.h has the definition).  `philox_call` advances as for
+        one call.  2 <= K <= 32, 1 <= S <= 256, 1 <= modes <= 16.
+        x: optional one-hot x_T [S,B,K,H,W]; default: drawn as predict_multiple draws it.  t: as in forward.
+        max_swaps: the most swaps PAM applies after its greedy BUILD (`converged` tells whether it stopped by itself).
+        maps: per-mode maps from "vote", "entropy", "counts" (metrics.MODE_MAPS).
+        known_labels, resample, evidence, temperature, truncation, views, tiles: as in predict_multiple, for every sample.
+        Returns, on the model's device, what metrics.sample_modes returns — medoid [B,M] (the sample that stands for the mode, -1:
+        unused), assign [B,S], size, share (= size / S), spread, cost, swaps, converged, mode_map [B,M,H,W] uint8 (the medoid sample,
+        255 where unused), mode_vote / mode_entropy / mode_counts as asked for — and `samples` [B,S,H,W] uint8, the class maps."""
+        from . import metrics as MT
+        if isinstance(num_evaluations, bool) or int(num_evaluations) != num_evaluations or not 1 <= int(num_evaluations) <= MT.MODES_MAX_SAMPLES:
+            raise ValueError(f"num_evaluations: {num_evaluations!r} (expected an integer in [1, {MT.MODES_MAX_SAMPLES}])")
+        S = int(num_evaluations)
+        K = self.diffusion.num_classes
+        MT.whole_number(K, "num_classes", 2, MT.MODES_MAX_CLASSES, f"predict_modes: expected a model of 2 to {MT.MODES_MAX_CLASSES} classes")
+        MT.whole_number(modes, "modes", 1, MT.MODES_MAX_MODES, f"expected a whole number in [1, {MT.MODES_MAX_MODES}]")
+        MT.whole_number(max_swaps, "max_swaps", 0, 2 ** 31 - 1, "expected a whole number, at least 0")
+        maps = tuple(maps)
+        bad = [m for m in maps if m not in MT.MODE_MAPS]
+        if bad:
+            raise ValueError(f"maps: {bad} not available (choose from {MT.MODE_MAPS})")
+        if condition.ndim != 4:
+            raise ValueError(f"condition: expected [B,C,H,W], got {tuple(condition.shape)}")
+        B, H, W = int(condition.shape[0]), int(condition.shape[2]), int(condition.shape[3])
+        HW = H * W
+        if x is not None and tuple(x.shape) != (S, B, K, H, W):
+            raise ValueError(f"x: expected one-hot x_T of shape {(S, B, K, H, W)} = [S,B,K,H,W], got {tuple(x.shape)}")
+        init_t = None if t is None else int(t.item() if isinstance(t, Tensor) else t)
+        guide = self._check_guidance(known_labels, resample, evidence, (B, K, H, W), temperature, truncation, views, feature_condition, tiles)
+        dev = next(self.unet.parameters()).device
+        xr = x.transpose(0, 1).reshape(B * S, K, H, W) if x is not None else \
+            OneHotCategoricalBCHW(logits=torch.zeros((B * S, K, H, W), device=condition.device)).sample()
+        cond = condition.repeat_interleave(S, dim=0)
+        # (with views or tiles on a model that takes features: [V,B,...] / [R,B,...], the samples on dim 1)
+        fc_dim = 1 if ((guide.views is not None or guide.tiles is not None) and feature_condition is not None
+                       and feature_condition.ndim == 5) else 0
+        fc = feature_condition.repeat_interleave(S, dim=fc_dim) if feature_condition is not None else None
+        stack = torch.empty((B * S, HW), dtype=torch.uint8, device=dev)
+
+        def consume(eng, lo: int, hi: int) -> None:
+            # (the first hi - lo rows: with views the engine holds V times as many, view 0 first)
+            stack[lo:hi].copy_(eng.xt.reshape(-1, HW)[:hi - lo])
+
+        saved = self.step_T_sample
+        self.step_T_sample = "majority"
+        try:
+            self._sample(xr, cond, fc, init_t, None, consume, guide.repeat_interleave(S))
+        finally:
+            self.step_T_sample = saved
+        samples = stack.reshape(B, S, H, W)
+        out = MT.sample_modes(samples, K, modes, max_swaps=max_swaps, maps=maps)
+        out["samples"] = samples
+        return out
+
     def _forward_step(self, x: Tensor, condition: Tensor, feature_condition: Tensor, t: Tensor) -> dict:
         """One U-Net evaluation at per-sample timesteps `t` (diffusion_denoising.py:161-162 -> unet.py:744-808): the
         network's own output (probabilities, or logits with `softmax_output: no`) and, with `ce_head`, the extra head's

@@ -868,6 +868,58 @@ int ccdm_vote_reduce_stack(const uint8_t* stack /*dev [B,S,HW]*/, int B, int S, 
                            uint8_t* vote /*dev [B,HW] or NULL*/, float* entropy /*dev [B,HW] or NULL*/, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Mode summary of a multi-sample prediction (metrics.sample_modes, DenoisingModel.predict_modes; beyond the reference, which
+ * only looks at grids of samples): which distinct segmentations the S samples of an image propose, and how likely each is.
+ * k-medoids (PAM) over the samples under the reference's own distance, 1 - mean foreground IoU, in exact integers.
+ * Input: class maps a[b][i][p], uint8 [B,S,HW], classes in [0,K); a byte >= K belongs to no class.
+ * Limits: 2 <= K <= 32, 1 <= S <= 256, 1 <= M <= 16, 0 < HW < 2^31, B <= 65535; checked before anything is launched or read.
+ *
+ * Fixed-point distance.  For samples i, j of one image and every foreground class k = 1..K-1:
+ *   n_i[k] = #{p : a_i[p] == k},  I_k = #{p : a_i[p] == a_j[p] == k},  U_k = n_i[k] + n_j[k] - I_k,
+ *   q_k = 0 if U_k == 0, else (2*(U_k - I_k)*2^20 + U_k) / (2*U_k) rounded down: the Jaccard distance in units of 2^-20, round
+ *   half up, in int64;  Q[i][j] = sum_k q_k, an int32 (at most 31 * 2^20).  Q is symmetric with a zero diagonal.
+ * Q / ((K-1) * 2^20) is within 2^-21 of the reference's `batched_distance`.  No floating point enters the clustering, so
+ * nothing depends on a reduction order: two calls are bit-identical.
+ *
+ * Clustering: per image PAM on Q, every sum in int64.
+ *   BUILD  m_1 = argmin_i sum_j Q[i][j], lowest i on ties; near_j = Q[m_1][j].  For c = 2..M: gain(i) = sum_j max(0, near_j -
+ *          Q[i][j]) over the non-medoids i, the argmax with the lowest i on ties; a best gain of 0 ends BUILD (every sample
+ *          coincides with a medoid: fewer than M modes exist); otherwise i becomes the medoid of slot c and near is updated.
+ *   SWAP   best improvement.  cost = sum_j near_j.  For every (slot c in BUILD order, non-medoid h): cost'(c,h) = the cost with
+ *          slot c's medoid replaced by h; the lowest cost', ties to the lowest c and then the lowest h.  cost' < cost: apply it
+ *          and repeat; otherwise stop with converged = 1.  At most max_swaps swaps are applied; converged = 0 iff an improving
+ *          swap was left unapplied.
+ *   Assignment: every sample to the medoid with the lowest Q, lowest slot on ties.
+ *   Ordering: modes by size descending, ties by the lower medoid sample index; slots never filled come last with medoid -1,
+ *          size 0, spread 0.
+ *
+ *   ccdm_modes_distance : Q int32 [B][S][S].  `ws` is a workspace, int32 [B][S][S][K], cleared on `stream` by the call (it
+ *                         receives I_k of the pairs i <= j; I_k of a map with itself is n_i[k]).  One workgroup per (image,
+ *                         16 x 16 tile of pairs i <= j, share of the pixels) stages each 1024-pixel chunk of the tile's 32 maps
+ *                         once in LDS, counts I_k for its 256 pairs from there and adds them to `ws` with integer atomics
+ *                         (exact in any order); a second launch forms Q from `ws` and writes it with its mirror.  Class counts
+ *                         in registers, by K <= 2, <= 8, <= 32.  Dword loads when HW % 4 == 0 and `a` is 4-byte aligned, bytes
+ *                         otherwise.
+ *   ccdm_modes_pam      : one workgroup per image; Q in LDS for S <= 128 (64 KB), read from global memory above.  Outputs, all
+ *                         OVERWRITTEN: medoid int32 [B][M] (sample index, -1 unused), assign int32 [B][S] (the mode of every
+ *                         sample, in the output order), size int32 [B][M], spread int64 [B][M] (sum over the members of
+ *                         Q[medoid][.]), cost int64 [B] (sum of the spreads), swaps int32 [B], converged int32 [B].  max_swaps >= 0.
+ *   ccdm_modes_maps     : per (image, mode, pixel) the class counts over the mode's members (`assign`, `size` as ccdm_modes_pam
+ *                         leaves them).  vote uint8 [B][M][HW]: the majority class within the mode, lowest class on ties, 255
+ *                         for an unused mode.  counts int32 [B][M][HW][K] or NULL.  entropy fp32 [B][M][HW] or NULL: the entropy
+ *                         in nats of counts / size, formed in fp64 (0 log 0 = 0); 0 for an unused mode.
+ * B = 0 returns 0 without a launch.
+ * ------------------------------------------------------------------------------------------------- */
+int ccdm_modes_distance(const uint8_t* a /*dev [B,S,HW]*/, int B, int S, int HW, int K, int32_t* ws /*dev [B,S,S,K] workspace*/,
+                        int32_t* Q /*dev [B,S,S]*/, void* stream);
+int ccdm_modes_pam(const int32_t* Q /*dev [B,S,S]*/, int B, int S, int M, int max_swaps, int32_t* medoid /*dev [B,M]*/,
+                   int32_t* assign /*dev [B,S]*/, int32_t* size /*dev [B,M]*/, int64_t* spread /*dev [B,M]*/, int64_t* cost /*dev [B]*/,
+                   int32_t* swaps /*dev [B]*/, int32_t* converged /*dev [B]*/, void* stream);
+int ccdm_modes_maps(const uint8_t* a /*dev [B,S,HW]*/, const int32_t* assign /*dev [B,S]*/, const int32_t* size /*dev [B,M]*/, int B, int S,
+                    int M, int HW, int K, uint8_t* vote /*dev [B,M,HW]*/, int32_t* counts /*dev [B,M,HW,K] or NULL*/,
+                    float* entropy /*dev [B,M,HW] or NULL*/, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Training-time forward pieces of the categorical diffusion, BCHW fp32 like the reference's
  * tensors, per-sample coefficients (the host resolves t -> alpha_t / cumalpha_{t-1} incl. the t == 1 override).
  *   ccdm_mix_uniform : out = s[n]*x + (1-s[n])/K.   With s = 1-beta_t it is the probability table of
