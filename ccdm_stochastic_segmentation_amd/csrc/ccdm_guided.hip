@@ -17,15 +17,20 @@
 //             engine's rows are overlapping tiles of the canvas state, tile-major, and x0 of a canvas pixel is the mean over the c >= 1
 //             tiles that cover it, summed in tile order and multiplied once by fp32(1 / c); the draw is keyed by the canvas pixel and
 //             the sample, and the class goes to the canvas state and back to every covering tile, so the tiles stay crops of one state.
-//             A kernel pair of its own (k_tiled, k_tiled_staged) below the guided pair, on the same shared pieces: the geometric map is a
-//             run-time loop over a per-pixel number of contributors where the views' is an unrolled loop over at most four.
 //   slots     (serving.SamplingQueue, ccdm_slots_step; nothing reshaped) continuous batching: every engine row is a slot that holds a
 //             sample of some request at its own place in its own walk, so what the other entries take as uniform launch arguments —
-//             coefficients, mode, step row, key, sample index — comes per row from a device table.  A kernel pair of its own (k_slots,
-//             k_slots_staged) at the end of the kernels, on the same shared pieces.
-// THE definitions: include/ccdm_hip.h.  ONE kernel pair in two instantiations: VIEWS = false is ccdm_shaped_step and, at (1, 1) with
-// the evidence required, ccdm_evidence_step (a kernel of its own for that was 1.003x / 1.00x of this one: DESIGN.md section 4);
-// VIEWS = true is ccdm_views_step, which cannot stand in for the other at V = 1 (1.07x / 1.14x, its extra LDS pass).
+//             coefficients, mode, step row, key, sample index — comes per row from a device table.
+// THE definitions: include/ccdm_hip.h.  THREE kernel pairs — one thread per pixel up to KP = 4, staged through LDS above — on the shared
+// arithmetic (posterior_pixel_core, shape_row / shape_lds_row, stage_class_rows, store_onehot_rows, load_pixel_row) and ONE launch
+// prologue on the host (launch_step) behind each launcher's own geometry checks:
+//   k_guided / k_guided_staged  VIEWS = false is ccdm_shaped_step and, at (1, 1) with the evidence required, ccdm_evidence_step (a kernel
+//             of its own for that was 1.003x / 1.00x of this one: DESIGN.md section 4); VIEWS = true is ccdm_views_step, which cannot
+//             stand in for the other at V = 1 (1.07x / 1.14x, its extra LDS pass).
+//   k_tiled / k_tiled_staged    ccdm_tiled_step: a run-time loop over a per-pixel number of contributors where the views' is an unrolled
+//             loop over at most four.  Not one kernel with the views: their map is a bijection with a contiguous identity view (view 0
+//             staged in 16-byte pieces, store_onehot_rows for it, all V - 1 index rows in LDS at once); the tiles' is neither.
+//   k_slots / k_slots_staged    ccdm_slots_step.
+// The staged passes stay written out per kernel: as shared helpers they measured 1 - 2 % slower at K = 20 (profiles/guided_passes_refactor_isa.txt).
 //
 // Shaped for HBM: per pixel 4 K V + 1 bytes in (+ 4 K of evidence), V bytes out (+ 4 K V where xin, 4 K where out_probs is written);
 // measured, the launch's time is the core's arithmetic on the vector pipe, not those bytes.
@@ -41,8 +46,8 @@
 //            pixel's classes no longer fit the register file and the core's arrays spill — no dataset has that many classes, and the
 //            arithmetic is not written a second time for them.  The shaping works on the pixel's LDS row in place: a taken class is
 //            marked in its sign bit (all values are >= 0) and the marks are resolved — kept value or 0 — before the core reads the
-//            row.  A thread walks its own row with a k that is uniform over the wave: PITCH is odd, so the lanes' addresses tid *
-//            PITCH + k fall on distinct banks; only the marking store (a per-lane k) can collide.
+//            row.  A thread walks its own row with a k that is uniform over the wave: the pitch is odd, so the lanes' addresses tid *
+//            pitch + k fall on distinct banks; only the marking store (a per-lane k) can collide.
 //   views, staged: view 0's run is staged like any run, then every further view is added into the ONE row per pixel in a pass over
 //            the block's [pixel][class] run, the pixel's source index coming from LDS (sb, written by the pixel's thread, one view at
 //            a time).  A block's pixels are runs of image rows, and their sources in a mirrored view are the mirrored runs of the
@@ -112,7 +117,11 @@ __device__ __forceinline__ void load_pixel_row(float (&p)[KP], const float* cons
     }
 }
 
-// `a`: head = x0 (softmax = 0, head_stride = K), xt_next = xt, N = samples, no table, no noise buffer, no run block (launch_guided)
+// the staged kernels' LDS row pitch: odd, >= K
+template <int KP>
+constexpr int staged_pitch() { return (KP | 1) > CCDM_MAX_CLASSES ? CCDM_MAX_CLASSES : (KP | 1); }
+
+// `a`: head = x0 (softmax = 0, head_stride = K), xt_next = xt, N = samples, no table, no noise buffer, no run block (launch_step)
 template <int KP, bool VIEWS>
 __global__ __launch_bounds__(256) void k_guided(const ccdm_post_args a, const guided_args g, const float inv_t, const float top_r, const float al,
                                                 const float cu, const int mode, const int step, const int vec) {
@@ -169,7 +178,7 @@ __global__ __launch_bounds__(256) void k_guided(const ccdm_post_args a, const gu
 template <int KP, int BLK, bool VIEWS>
 __global__ __launch_bounds__(BLK) void k_guided_staged(const ccdm_post_args a, const guided_args g, const float inv_t, const float top_r,
                                                        const float al, const float cu, const int mode, const int step) {
-    constexpr int PITCH = (KP | 1) > CCDM_MAX_CLASSES ? CCDM_MAX_CLASSES : (KP | 1);      // odd, >= K
+    constexpr int PITCH = staged_pitch<KP>();
     static_assert(!VIEWS || 3 * BLK <= BLK * PITCH, "the mirrored views' pixel indices reuse the rows");
     __shared__ float sx[BLK * PITCH];
     __shared__ int sb[BLK];
@@ -355,7 +364,7 @@ __global__ __launch_bounds__(256) void k_tiled(const ccdm_post_args a, const til
 template <int KP, int BLK>
 __global__ __launch_bounds__(BLK) void k_tiled_staged(const ccdm_post_args a, const tiled_args g, const float inv_t, const float top_r,
                                                       const float al, const float cu, const int mode, const int step) {
-    constexpr int PITCH = (KP | 1) > CCDM_MAX_CLASSES ? CCDM_MAX_CLASSES : (KP | 1);      // odd, >= K
+    constexpr int PITCH = staged_pitch<KP>();
     static_assert(BLK <= BLK * PITCH, "the tile pixels' indices reuse the rows");
     __shared__ float sx[BLK * PITCH];
     __shared__ int sb[BLK];
@@ -448,7 +457,7 @@ __global__ __launch_bounds__(BLK) void k_tiled_staged(const ccdm_post_args a, co
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Slots (ccdm_slots_step): the plain step — no evidence, no shaping, one view — with every launch argument that describes the ROW
-// coming per engine row from a device table (include/ccdm_hip.h: ccdm_slot_row).  `a` as launch_guided fills it, without key and
+// coming per engine row from a device table (include/ccdm_hip.h: ccdm_slot_row).  `a` as launch_step fills it, without key and
 // offset.  A block's pixels may belong to several slots (HW need not be a multiple of the block): the slot is found per pixel, and the
 // two LDS passes of the staged kernel run per slot segment of the block, so an idle slot is neither read nor written.
 
@@ -479,7 +488,7 @@ __global__ __launch_bounds__(256) void k_slots(const ccdm_post_args a_in, const 
 
 template <int KP, int BLK>
 __global__ __launch_bounds__(BLK) void k_slots_staged(const ccdm_post_args a_in, const ccdm_slot_row* const table) {
-    constexpr int PITCH = (KP | 1) > CCDM_MAX_CLASSES ? CCDM_MAX_CLASSES : (KP | 1);      // odd, >= K
+    constexpr int PITCH = staged_pitch<KP>();
     __shared__ float sx[BLK * PITCH];
     __shared__ int sb[BLK];
     const unsigned HW = (unsigned)a_in.HW;
@@ -521,11 +530,12 @@ __global__ __launch_bounds__(BLK) void k_slots_staged(const ccdm_post_args a_in,
     }
 }
 
-// What the three entries hand to launch_guided
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Host side.  What an entry hands to its launcher; a launcher reads the fields its entry has
 struct guided_call {
     const float *x0, *evidence;
     int N, HW, K;
-    int H, W, V, flips;                     // VIEWS alone, where HW is H * W (formed here, behind the check of H and W)
+    int H, W, V, flips;                     // views: HW is H * W (formed behind the check of H and W); tiles: H x W is the canvas
     float inv_temperature, top_r, alpha_t, cumalpha_tm1;
     int mode, step_row;
     uint64_t philox_seed;
@@ -538,12 +548,42 @@ struct guided_call {
     void* stream;
 };
 
-// The one launcher.  `name`: the entry's, as its errors carry it; needs_evidence: a null evidence pointer is refused; takes_shaping:
-// (inv_temperature, top_r) are the caller's and are checked.  0, or fail()'s code.
+// pixels per block of every launch here
+static int step_block(const int K) { return K <= 32 ? 256 : 64; }
+
+// What the three launchers do alike behind their own geometry checks: the shaping's range where it is the caller's (takes_shaping),
+// ccdm_post_args for c.N samples of HW pixels whose core sees `xin`, the grid, the vec flag of the one-thread-per-pixel kernels, the
+// K -> KP fork.  entry(kp, go, vec) holds the entry's two launch lines: go(kernel, what it takes behind ccdm_post_args...).  0, or
+// fail()'s code.
+template <class F>
+static int launch_step(const char* name, const guided_call& c, const int HW, const bool takes_shaping, float* const xin, F&& entry) {
+    if (takes_shaping) {
+        CCDM_REQUIRE(std::isfinite(c.inv_temperature) && c.inv_temperature >= 0.05f && c.inv_temperature <= 20.0f,
+                     "%s: inv_temperature %g outside [1/20,20]", name, (double)c.inv_temperature);
+        CCDM_REQUIRE(std::isfinite(c.top_r) && c.top_r > 0.0f && c.top_r <= 1.0f, "%s: top_r %g outside (0,1]", name, (double)c.top_r);
+    }
+    const int K = c.K, blk = step_block(K);
+    ccdm_post_args a = {};
+    a.head = c.x0; a.softmax = 0; a.head_stride = K;
+    a.xt = c.xt; a.xt_next = c.xt;
+    a.N = c.N; a.HW = HW; a.K = K;
+    a.philox_seed = c.philox_seed; a.sample_offset = c.sample_offset;
+    a.xin = xin; a.xin_stride = xin ? c.xin_stride : 0;
+    a.out_probs = c.out_probs; a.out_onehot = c.out_onehot;
+    const dim3 grid((unsigned)(((size_t)c.N * HW + blk - 1) / blk)), block(blk);
+    const uintptr_t both = reinterpret_cast<uintptr_t>(c.x0) | reinterpret_cast<uintptr_t>(c.evidence);          // (null: no bits)
+    const int vec = (K == 2 && (both & 7) == 0) || (K == 4 && (both & 15) == 0);
+    const auto go = [&](auto kernel, auto... args) { hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)c.stream, a, args...); };
+    dispatch_kp<256>(K, [&](auto kp) { entry(kp, go, vec); });
+    CCDM_CHECK_LAUNCH(name);
+    return 0;
+}
+
+// `name`: the entry's, as its errors carry it; needs_evidence: a null evidence pointer is refused; takes_shaping: (inv_temperature,
+// top_r) are the caller's and are checked.  0, or fail()'s code.
 template <bool VIEWS>
 static int launch_guided(const char* name, const bool needs_evidence, const bool takes_shaping, const guided_call& c) {
     const int N = c.N, K = c.K;
-    const int blk = K <= 32 ? 256 : 64;
     int HW = c.HW;
     if constexpr (VIEWS) {
         CCDM_REQUIRE(c.V >= 1 && c.V <= 4, "%s: V=%d outside [1,4]", name, c.V);
@@ -552,115 +592,57 @@ static int launch_guided(const char* name, const bool needs_evidence, const bool
         CCDM_REQUIRE(c.H >= 1 && c.W >= 1 && (size_t)c.H * c.W <= 0x7FFFFFFFull, "%s: bad shape H=%d W=%d", name, c.H, c.W);
         HW = c.H * c.W;
     }
-    if (const int rc = check_step_args(name, c.x0 && c.xt && (c.evidence || !needs_evidence), N, HW, K, c.xin, c.xin_stride, c.mode, c.step_row, blk))
+    if (const int rc = check_step_args(name, c.x0 && c.xt && (c.evidence || !needs_evidence), N, HW, K, c.xin, c.xin_stride, c.mode, c.step_row,
+                                       step_block(K)))
         return rc;
     if constexpr (VIEWS)
         CCDM_REQUIRE((size_t)c.V * N * HW <= 0x7FFFFFFFull, "%s: too many pixels (V*N*H*W = %zu)", name, (size_t)c.V * N * HW);
-    if (takes_shaping) {
-        CCDM_REQUIRE(std::isfinite(c.inv_temperature) && c.inv_temperature >= 0.05f && c.inv_temperature <= 20.0f,
-                     "%s: inv_temperature %g outside [1/20,20]", name, (double)c.inv_temperature);
-        CCDM_REQUIRE(std::isfinite(c.top_r) && c.top_r > 0.0f && c.top_r <= 1.0f, "%s: top_r %g outside (0,1]", name, (double)c.top_r);
-    }
-    const size_t npix = (size_t)N * HW;
-    ccdm_post_args a = {};
-    a.head = c.x0; a.softmax = 0; a.head_stride = K;
-    a.xt = c.xt; a.xt_next = c.xt;
-    a.N = N; a.HW = HW; a.K = K;
-    a.philox_seed = c.philox_seed; a.sample_offset = c.sample_offset;
-    a.xin = c.xin; a.xin_stride = c.xin_stride;
-    a.out_probs = c.out_probs; a.out_onehot = c.out_onehot;
     const guided_args g = VIEWS ? guided_args{c.evidence, c.H, c.W, c.V, c.flips, 1.0f / (float)c.V} : guided_args{c.evidence, 0, 0, 1, 0, 1.0f};
-    const dim3 grid((unsigned)((npix + blk - 1) / blk)), block(blk);
-    hipStream_t s = (hipStream_t)c.stream;
-    const float it = c.inv_temperature, tr = c.top_r, al = c.alpha_t, cu = c.cumalpha_tm1;
-    const int mode = c.mode, step_row = c.step_row;
-    dispatch_kp<256>(K, [&](auto kp) {
+    return launch_step(name, c, HW, takes_shaping, c.xin, [&](auto kp, auto go, const int vec) {
         constexpr int KP = decltype(kp)::value;
-        if constexpr (KP <= 4) {
-            const uintptr_t both = reinterpret_cast<uintptr_t>(c.x0) | reinterpret_cast<uintptr_t>(c.evidence);          // (null: no bits)
-            const int vec = (K == 2 && (both & 7) == 0) || (K == 4 && (both & 15) == 0);
-            hipLaunchKernelGGL((k_guided<KP, VIEWS>), grid, block, 0, s, a, g, it, tr, al, cu, mode, step_row, vec);
-        } else {
-            hipLaunchKernelGGL((k_guided_staged<KP, (KP <= 32 ? 256 : 64), VIEWS>), grid, block, 0, s, a, g, it, tr, al, cu, mode, step_row);
-        }
+        if constexpr (KP <= 4) go(k_guided<KP, VIEWS>, g, c.inv_temperature, c.top_r, c.alpha_t, c.cumalpha_tm1, c.mode, c.step_row, vec);
+        else go(k_guided_staged<KP, (KP <= 32 ? 256 : 64), VIEWS>, g, c.inv_temperature, c.top_r, c.alpha_t, c.cumalpha_tm1, c.mode, c.step_row);
     });
-    CCDM_CHECK_LAUNCH(name);
-    return 0;
 }
 
-// What ccdm_tiled_step hands to launch_tiled: `c` with N = samples, H x W = the canvas, xt = the canvas state, out_probs / out_onehot the
-// canvas's, and xin / xin_stride the TILES' (next to their xt, tile_xt); V, flips and HW unused.
+// `c` with N = samples, H x W = the canvas, xt = the canvas state, out_probs / out_onehot the canvas's, and xin / xin_stride the TILES'
+// (next to their xt, tile_xt); V, flips and HW unused.
 static int launch_tiled(const char* name, const guided_call& c, const int h, const int w, const int sy, const int sx, uint8_t* const tile_xt) {
     const int N = c.N, K = c.K, Hc = c.H, Wc = c.W;
-    const int blk = K <= 32 ? 256 : 64;
     CCDM_REQUIRE(Hc >= 1 && Wc >= 1 && (size_t)Hc * Wc <= 0x7FFFFFFFull, "%s: bad shape Hc=%d Wc=%d", name, Hc, Wc);
     CCDM_REQUIRE(h >= 1 && h <= Hc && w >= 1 && w <= Wc, "%s: tile h=%d w=%d outside [1,Hc=%d] x [1,Wc=%d]", name, h, w, Hc, Wc);
     CCDM_REQUIRE(sy >= 1 && sy <= h && sx >= 1 && sx <= w, "%s: stride sy=%d sx=%d outside [1,h=%d] x [1,w=%d]", name, sy, sx, h, w);
     const int HW = Hc * Wc;
-    if (const int rc = check_step_args(name, c.x0 && c.xt && tile_xt, N, HW, K, c.xin, c.xin_stride, c.mode, c.step_row, blk)) return rc;
+    if (const int rc = check_step_args(name, c.x0 && c.xt && tile_xt, N, HW, K, c.xin, c.xin_stride, c.mode, c.step_row, step_block(K))) return rc;
     const int Ty = 1 + (Hc - h + sy - 1) / sy, Tx = 1 + (Wc - w + sx - 1) / sx;
     CCDM_REQUIRE((size_t)N * HW <= 0x7FFFFFFFull && (size_t)Ty * Tx * N * h * w <= 0x7FFFFFFFull,
                  "%s: too many pixels (N*Hc*Wc = %zu, R*N*h*w = %zu)", name, (size_t)N * HW, (size_t)Ty * Tx * N * h * w);
-    CCDM_REQUIRE(std::isfinite(c.inv_temperature) && c.inv_temperature >= 0.05f && c.inv_temperature <= 20.0f,
-                 "%s: inv_temperature %g outside [1/20,20]", name, (double)c.inv_temperature);
-    CCDM_REQUIRE(std::isfinite(c.top_r) && c.top_r > 0.0f && c.top_r <= 1.0f, "%s: top_r %g outside (0,1]", name, (double)c.top_r);
     int cy = 1, cx = 1, lo, hi;
     for (int y = 0; y < Hc; ++y) { covering_tiles(y, Hc, h, sy, Ty, lo, hi); cy = std::max(cy, hi - lo + 1); }
     for (int x = 0; x < Wc; ++x) { covering_tiles(x, Wc, w, sx, Tx, lo, hi); cx = std::max(cx, hi - lo + 1); }
-    const size_t npix = (size_t)N * HW;
-    ccdm_post_args a = {};
-    a.head = c.x0; a.softmax = 0; a.head_stride = K;
-    a.xt = c.xt; a.xt_next = c.xt;
-    a.N = N; a.HW = HW; a.K = K;
-    a.philox_seed = c.philox_seed; a.sample_offset = c.sample_offset;
-    a.out_probs = c.out_probs; a.out_onehot = c.out_onehot;
     const tiled_args g = {c.evidence, tile_xt, c.xin, c.xin_stride, Hc, Wc, h, w, sy, sx, Ty, Tx, cy * cx};
-    const dim3 grid((unsigned)((npix + blk - 1) / blk)), block(blk);
-    hipStream_t s = (hipStream_t)c.stream;
-    const float it = c.inv_temperature, tr = c.top_r, al = c.alpha_t, cu = c.cumalpha_tm1;
-    const int mode = c.mode, step_row = c.step_row;
-    dispatch_kp<256>(K, [&](auto kp) {
+    return launch_step(name, c, HW, true, nullptr, [&](auto kp, auto go, const int vec) {
         constexpr int KP = decltype(kp)::value;
-        if constexpr (KP <= 4) {
-            const uintptr_t both = reinterpret_cast<uintptr_t>(c.x0) | reinterpret_cast<uintptr_t>(c.evidence);          // (null: no bits)
-            const int vec = (K == 2 && (both & 7) == 0) || (K == 4 && (both & 15) == 0);
-            hipLaunchKernelGGL((k_tiled<KP>), grid, block, 0, s, a, g, it, tr, al, cu, mode, step_row, vec);
-        } else {
-            hipLaunchKernelGGL((k_tiled_staged<KP, (KP <= 32 ? 256 : 64)>), grid, block, 0, s, a, g, it, tr, al, cu, mode, step_row);
-        }
+        if constexpr (KP <= 4) go(k_tiled<KP>, g, c.inv_temperature, c.top_r, c.alpha_t, c.cumalpha_tm1, c.mode, c.step_row, vec);
+        else go(k_tiled_staged<KP, (KP <= 32 ? 256 : 64)>, g, c.inv_temperature, c.top_r, c.alpha_t, c.cumalpha_tm1, c.mode, c.step_row);
     });
-    CCDM_CHECK_LAUNCH(name);
-    return 0;
 }
 
-// The slots' launcher: the shapes of launch_guided; mode and step row are the table's, on the device, so the shared check gets neutral ones.
+// The shapes of launch_guided; mode and step row are the table's, on the device, so the shared check gets neutral ones.
 static int launch_slots(const char* name, const float* x0, const ccdm_slot_row* table, const int N, const int HW, const int K, uint8_t* xt, float* xin,
                         const int xin_stride, float* out_probs, int64_t* out_onehot, void* stream) {
-    const int blk = K <= 32 ? 256 : 64;
-    if (const int rc = check_step_args(name, x0 && table && xt, N, HW, K, xin, xin_stride, CCDM_STEP_SAMPLE, 0, blk)) return rc;
+    if (const int rc = check_step_args(name, x0 && table && xt, N, HW, K, xin, xin_stride, CCDM_STEP_SAMPLE, 0, step_block(K))) return rc;
     CCDM_REQUIRE((size_t)N * HW <= 0x7FFFFFFFull, "%s: too many pixels (N*HW = %zu)", name, (size_t)N * HW);
     CCDM_REQUIRE((reinterpret_cast<uintptr_t>(table) & 3) == 0, "%s: misaligned table", name);
-    const size_t npix = (size_t)N * HW;
-    ccdm_post_args a = {};
-    a.head = x0; a.softmax = 0; a.head_stride = K;
-    a.xt = xt; a.xt_next = xt;
-    a.N = N; a.HW = HW; a.K = K;
-    a.xin = xin; a.xin_stride = xin_stride;
-    a.out_probs = out_probs; a.out_onehot = out_onehot;
-    const dim3 grid((unsigned)((npix + blk - 1) / blk)), block(blk);
-    hipStream_t s = (hipStream_t)stream;
-    dispatch_kp<256>(K, [&](auto kp) {
+    guided_call c = {};                     // no evidence, key or offset: the table has the last two per row
+    c.x0 = x0; c.N = N; c.K = K;
+    c.xt = xt; c.xin_stride = xin_stride;
+    c.out_probs = out_probs; c.out_onehot = out_onehot; c.stream = stream;
+    return launch_step(name, c, HW, false, xin, [&](auto kp, auto go, const int vec) {
         constexpr int KP = decltype(kp)::value;
-        if constexpr (KP <= 4) {
-            const uintptr_t addr = reinterpret_cast<uintptr_t>(x0);
-            const int vec = (K == 2 && (addr & 7) == 0) || (K == 4 && (addr & 15) == 0);
-            hipLaunchKernelGGL((k_slots<KP>), grid, block, 0, s, a, table, vec);
-        } else {
-            hipLaunchKernelGGL((k_slots_staged<KP, (KP <= 32 ? 256 : 64)>), grid, block, 0, s, a, table);
-        }
+        if constexpr (KP <= 4) go(k_slots<KP>, table, vec);
+        else go(k_slots_staged<KP, (KP <= 32 ? 256 : 64)>, table);
     });
-    CCDM_CHECK_LAUNCH(name);
-    return 0;
 }
 
 }  // namespace ccdm

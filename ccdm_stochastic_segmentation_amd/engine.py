@@ -683,38 +683,33 @@ class SamplerEngine:
           canvas's.  evidence is then fp32 [n,Hc*Wc,K].  Not together with views.
         One launch: ccdm_tiled_step where there is a canvas, else ccdm_views_step where there are views (neutral shaping: 1.0, 1.0),
         else ccdm_shaped_step where there is shaping, else ccdm_evidence_step."""
-        if canvas is not None:
-            assert views is None and canvas is self._tile_canvas
-            n = canvas.n
-            assert evidence is None or (evidence.dtype == torch.float32 and evidence.is_cuda and evidence.is_contiguous()
-                                        and tuple(evidence.shape) == (n, canvas.Hc * canvas.Wc, self.K))
-            inv_t, top_r = shaping or (1.0, 1.0)
-            seed, off, xt, xin, stride = self._step_state_args(philox_seed, sample_offset)
-            hip.check(self.lib.ccdm_tiled_step(
-                self.out_probs.data_ptr(), None if evidence is None else evidence.data_ptr(), n, canvas.Hc, canvas.Wc, self.H, self.W,
-                canvas.sy, canvas.sx, self.K, float(inv_t), float(top_r), float(alpha_t), float(cumalpha_tm1), int(mode), int(step_row), seed,
-                off, canvas.xt.data_ptr(), xt, xin, stride, canvas.out_probs.data_ptr(), canvas.out_onehot.data_ptr(), self._stream()),
-                "tiled_step")
-            self._evidence_keepalive = evidence
-            return
         flips = () if views is None else tuple(int(f) for f in views)
         V = 1 + len(flips)
-        assert 1 <= V <= 4 and self.N % V == 0 and all(0 <= f <= 3 for f in flips)
-        n = self.N // V
-        assert evidence is None or (evidence.dtype == torch.float32 and evidence.is_cuda and evidence.is_contiguous()
-                                    and tuple(evidence.shape) == (n, self.H * self.W, self.K))
-        ev = None if evidence is None else evidence.data_ptr()
-        tail = (float(alpha_t), float(cumalpha_tm1), int(mode), int(step_row), *self._step_state_args(philox_seed, sample_offset),
-                self.out_probs.data_ptr(), self.out_onehot.data_ptr(), self._stream())
-        x0 = self.out_probs.data_ptr()
-        if views is not None:
-            inv_t, top_r = shaping or (1.0, 1.0)
-            hip.check(self.lib.ccdm_views_step(x0, ev, n, self.H, self.W, self.K, V, sum(f << (2 * (v + 1)) for v, f in enumerate(flips)),
-                                               float(inv_t), float(top_r), *tail), "views_step")
-        elif shaping is not None:
-            hip.check(self.lib.ccdm_shaped_step(x0, ev, n, self.H * self.W, self.K, float(shaping[0]), float(shaping[1]), *tail), "shaped_step")
+        if canvas is not None:
+            assert views is None and canvas is self._tile_canvas
+            n, pixels = canvas.n, canvas.Hc * canvas.Wc
         else:
-            hip.check(self.lib.ccdm_evidence_step(x0, ev, n, self.H * self.W, self.K, *tail), "evidence_step")
+            assert 1 <= V <= 4 and self.N % V == 0 and all(0 <= f <= 3 for f in flips)
+            n, pixels = self.N // V, self.H * self.W
+        assert evidence is None or (evidence.dtype == torch.float32 and evidence.is_cuda and evidence.is_contiguous()
+                                    and tuple(evidence.shape) == (n, pixels, self.K))
+        x0, ev = self.out_probs.data_ptr(), None if evidence is None else evidence.data_ptr()
+        inv_t, top_r = (float(v) for v in shaping or (1.0, 1.0))
+        seed, off, *state = self._step_state_args(philox_seed, sample_offset)
+        step = (float(alpha_t), float(cumalpha_tm1), int(mode), int(step_row), seed, off)
+        # the tail every entry ends in: the engine's x_t and xin, then the last-step outputs (the tiled entry: the canvas's) and the stream
+        outputs = self if canvas is None else canvas
+        tail = (*state, outputs.out_probs.data_ptr(), outputs.out_onehot.data_ptr(), self._stream())
+        if canvas is not None:
+            hip.check(self.lib.ccdm_tiled_step(x0, ev, n, canvas.Hc, canvas.Wc, self.H, self.W, canvas.sy, canvas.sx, self.K, inv_t, top_r, *step,
+                                               canvas.xt.data_ptr(), *tail), "tiled_step")
+        elif views is not None:
+            hip.check(self.lib.ccdm_views_step(x0, ev, n, self.H, self.W, self.K, V, sum(f << (2 * (v + 1)) for v, f in enumerate(flips)),
+                                               inv_t, top_r, *step, *tail), "views_step")
+        elif shaping is not None:
+            hip.check(self.lib.ccdm_shaped_step(x0, ev, n, pixels, self.K, inv_t, top_r, *step, *tail), "shaped_step")
+        else:
+            hip.check(self.lib.ccdm_evidence_step(x0, ev, n, pixels, self.K, *step, *tail), "evidence_step")
         self._evidence_keepalive = evidence
 
     def ce_logits(self) -> Optional[torch.Tensor]:

@@ -11,52 +11,12 @@ import torch
 
 from oracle import ccdm_oracle as O
 from ccdm_stochastic_segmentation_amd import hip
+from tests.guided_util import SHAPES, bits, coefficients, evidence_restatement, nhwk, random_inputs, sampler_evidence
 from tests.sampler_util import (DEV, FREE, H, SEED, SMALL_CFG, T_SMALL, T_STRIDED, W, assert_symbol_declared_bound_and_built, load_lib,
                                 make_sampler, onehot_np, sample_sharded_keywords, settings, small_model)
 
 SYMBOL = "ccdm_evidence_step"
 T_VALUES = [6, 4, 3, 1]          # t = 10004 walks the small model strided
-
-
-def evidence_restatement(x0, ev, xt, a, c, mode, step_row, seed, sample0):
-    """What ccdm_evidence_step computes, from the oracle's functions.  x0, ev: fp32 [N,HW,K]; xt: integer [N,HW].
-    x0' = x0 * ev in fp32; the O(K) posterior in the epilogue's op order; clamp at 1e-12; cascade normalisation; STEP_SAMPLE: the Exp(1)
-    race on the unguided step's counters (pixel, sample0 + n, step_row, k // 4), first maximum wins; last-step modes: the argmax.
-    Returns (probabilities fp32 [N,HW,K], class index int64 [N,HW])."""
-    N, HW, K = x0.shape
-    x0p = (torch.from_numpy(np.ascontiguousarray(x0, dtype=np.float32)) * torch.from_numpy(np.ascontiguousarray(ev, dtype=np.float32)))
-    theta = x0p.reshape(N, 1, HW, K).permute(0, 3, 1, 2)
-    xt_oh = O.one_hot_bchw(torch.from_numpy(np.asarray(xt).astype(np.int64)).reshape(N, 1, HW), K)
-    p_hat = O.normalise_probs(torch.clamp(O.theta_post_prob(xt_oh, theta, a, c), min=1e-12), "cascade")          # [N,1,HW,K]
-    if mode == hip.STEP_SAMPLE:
-        e = torch.from_numpy(O.philox_exponential(seed, step_row, sample0, N, HW, K)).reshape(N, 1, HW, K)
-        idx = O.sample_index(p_hat, e)
-    else:
-        idx = p_hat.argmax(dim=-1)
-    return p_hat.reshape(N, HW, K).numpy(), idx.reshape(N, HW).numpy().astype(np.int64)
-
-
-def random_inputs(rng, N, HW, K):
-    """x0: every entry >= 1e-3 (K <= 255: >= 1 / (3 K)), rows normalised; weights in [0,1], a fifth of them exactly 0, one class per
-    pixel with a weight in [0.5,1] (so no pixel is ruled out, and sum_k x0_k w_k >= 0.5e-3); x_t random."""
-    r = (rng.random((N, HW, K)) + 0.5).astype(np.float32)
-    x0 = (r / r.sum(-1, keepdims=True, dtype=np.float32)).astype(np.float32)
-    assert x0.min() >= 1e-3
-    ev = rng.random((N, HW, K)).astype(np.float32)
-    ev[rng.random((N, HW, K)) < 0.2] = 0.0
-    sure = rng.integers(0, K, (N, HW))
-    np.put_along_axis(ev, sure[..., None], rng.uniform(0.5, 1.0, (N, HW, 1)).astype(np.float32), axis=-1)
-    xt = rng.integers(0, K, (N, HW))
-    return x0, ev, xt
-
-
-def sampler_evidence(rng, N, K, onehot_share=0.0):
-    """[N,K,H,W] fp32: a soft map (weights in [0.05,1]), and on a share of the pixels a one-hot on a random class"""
-    ev = rng.uniform(0.05, 1.0, (N, K, H, W)).astype(np.float32)
-    pick = rng.random((N, H, W)) < onehot_share
-    cls = rng.integers(0, K, (N, H, W))
-    ev = np.where(pick[:, None], (np.arange(K)[None, :, None, None] == cls[:, None]).astype(np.float32), ev)
-    return torch.from_numpy(ev), torch.from_numpy(pick), torch.from_numpy(cls)
 
 
 # ------------------------------------------------------------------------------------------------ CPU
@@ -184,17 +144,9 @@ def test_sample_sharded_hands_the_callers_evidence_through():
 
 
 # ------------------------------------------------------------------------------------------------ GPU: the kernel alone
-SHAPES = [(3, 63, 2), (2, 300, 5), (2, 64, 20), (1, 64, 255)]       # a partial block; a block boundary inside a sample; staged; the largest K
-
-
 @pytest.fixture(scope="module")
 def lib():
     return load_lib()
-
-
-def coefficients(t, T=250):
-    _, alphas, cum = O.make_schedule("cosine", T, {"s": 0.008})
-    return O.posterior_coeffs(alphas, cum, t)
 
 
 def run_kernel(lib, x0, ev, xt, a, c, mode, *, step_row=0, seed=SEED, sample_offset=0, xin=None, probs=None, onehot=None, alias=False):
@@ -211,10 +163,6 @@ def run_kernel(lib, x0, ev, xt, a, c, mode, *, step_row=0, seed=SEED, sample_off
               SYMBOL)
     torch.cuda.synchronize()
     return {k: (None if v is None else v.cpu().numpy()) for k, v in d.items()}
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 @pytest.mark.gpu
@@ -379,11 +327,6 @@ def check_launch(rec, ev_nhwk, K):
         assert np.array_equal(bits(got_probs), bits(probs)), what
         assert np.array_equal(got_xt, xt0), what
     return probs, idx
-
-
-def nhwk(ev_bchw):
-    n, k = ev_bchw.shape[:2]
-    return ev_bchw.permute(0, 2, 3, 1).reshape(n, H * W, k).contiguous().numpy()
 
 
 @pytest.mark.gpu

@@ -13,8 +13,8 @@ import pytest
 import torch
 
 from ccdm_stochastic_segmentation_amd import SamplingQueue, hip, serving, step_values
+from tests.guided_util import bits, coefficients, evidence_restatement, random_inputs
 from tests.sampler_util import DEV, H, ROOT, T_SMALL, T_STRIDED, W, assert_symbol_declared_bound_and_built, load_lib, make_sampler, small_model
-from tests.test_evidence_sampling import bits, coefficients, evidence_restatement, random_inputs
 
 SYMBOL = "ccdm_slots_step"
 # the four requests of the scheduler test and of the end-to-end test: (name, n, t, vote, the tick before which it arrives)
@@ -221,7 +221,7 @@ def run_shaped_per_slot(lib, d, table, with_xin, alias):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("HW,K", [(195, 2), (195, 3), (195, 5), (195, 20), (195, 33), (256, 2), (256, 5)])
+@pytest.mark.parametrize("HW,K", [(195, 2), (195, 3), (195, 4), (195, 5), (195, 20), (195, 33), (256, 2), (256, 5)])
 def test_slots_kernel_equals_the_shaped_step_slot_by_slot(lib, HW, K):
     """Five slots with different coefficients, step rows, keys and sample indices: the four real modes and an idle slot.  HW = 195: blocks
     straddle slot boundaries (K <= 4: 256 threads; K <= 32: 256 staged pixels; K = 33: 64 staged pixels) and the runs are unaligned, with

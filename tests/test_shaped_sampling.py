@@ -13,89 +13,17 @@ import torch
 
 from oracle import ccdm_oracle as O
 from ccdm_stochastic_segmentation_amd import hip
+from tests.guided_util import (POWER_ERROR_ALLOWED, SHAPES, bits, coefficients, evidence_restatement, mixed_inputs, nhwk, posterior64, random_inputs,
+                               sampler_evidence, shape_rows, shaped_restatement, threshold_margin64, weighted)
+from tests.guided_util import run_shaped_kernel as run_kernel
 from tests.sampler_util import (DEV, H, SEED, SMALL_CFG, T_SMALL, T_STRIDED, W, assert_symbol_declared_bound_and_built, load_lib, make_sampler,
                                 onehot_np, sample_sharded_keywords, settings, small_model)
-from tests.test_evidence_sampling import SHAPES, bits, coefficients, evidence_restatement, nhwk, random_inputs, sampler_evidence
 
 SYMBOL = "ccdm_shaped_step"
 T_VALUES = [6, 4, 3, 1]          # t = 10004 walks the small model strided
-# test_tempered_kernel_against_float64: the kernel's largest relative error against the float64 definition on that test's inputs, measured
-# on an MI355X, and what the test allows the device's power for it (four times that: the ROCm installation states no ulp bound for exp2f
-# and log2f)
-POWER_ERROR_MEASURED = 1.851e-6
-POWER_ERROR_ALLOWED = 4 * POWER_ERROR_MEASURED
 # the inputs of the definition test (CPU) and of the tempered kernel test: a seed at which no pixel of any shape lies within 1e-5
 # (relative) of a truncation threshold at r in {0.9, 0.6}, tau in {1, 0.7, 1.5}, with or without evidence — the CPU test asserts it
 MARGIN_SEED = 4100
-
-
-# ------------------------------------------------------------------------------------------------ the definition, restated
-def shape_rows(v, inv_tau, r, dtype=np.float32):
-    """The shaping of include/ccdm_hip.h on rows v [...,K] (>= 0) in `dtype` arithmetic: temper relative to the row's maximum (skipped at
-    inv_tau == 1), then keep class pi(j) iff the mass of the classes before it in the order (q descending, index ascending) is below
-    r * Z (skipped at r == 1).  Sums are sequential (np.cumsum), the power is numpy's."""
-    q = np.array(v, dtype=dtype)
-    inv_tau, r = dtype(inv_tau), dtype(r)
-    if inv_tau != 1:
-        m = q.max(-1, keepdims=True)
-        u = q / np.where(m == 0, dtype(1), m)
-        t = np.where(u == 1, dtype(1), np.where(u == 0, dtype(0), np.power(u, inv_tau, dtype=dtype)))
-        q = np.where(m == 0, q, t).astype(dtype)
-    if r != 1:
-        theta = (r * np.cumsum(q, axis=-1, dtype=dtype)[..., -1:]).astype(dtype)
-        order = np.argsort(-q, axis=-1, kind="stable")
-        before = np.cumsum(np.take_along_axis(q, order, -1), axis=-1, dtype=dtype)
-        before = np.concatenate([np.zeros_like(before[..., :1]), before[..., :-1]], axis=-1)          # c_j
-        keep = np.zeros(q.shape, dtype=bool)
-        np.put_along_axis(keep, order, before < theta, -1)
-        q = np.where(keep, q, dtype(0))
-    return q
-
-
-def weighted(x0, ev):
-    """v = x0 * w in fp32 (x0 itself without evidence)"""
-    x0 = np.ascontiguousarray(x0, dtype=np.float32)
-    return x0 if ev is None else (x0 * np.ascontiguousarray(ev, dtype=np.float32)).astype(np.float32)
-
-
-def shaped_restatement(x0, ev, xt, inv_tau, r, a, c, mode, step_row, seed, sample0):
-    """What ccdm_shaped_step computes: the definition in numpy fp32, then the evidence restatement's step (O.theta_post_prob, the clamp,
-    O.normalise_probs(..., "cascade"), O.sample_index on O.philox_exponential) on the shaped row.  x0: fp32 [N,HW,K]; ev: the same or None;
-    xt: integer [N,HW].  Returns (probabilities fp32 [N,HW,K], class index int64 [N,HW])."""
-    q = shape_rows(weighted(x0, ev), np.float32(inv_tau), np.float32(r))
-    return evidence_restatement(q, np.ones_like(q), xt, a, c, mode, step_row, seed, sample0)
-
-
-def posterior64(q, xt, a, c):
-    """The step's posterior of rows q [N,HW,K] in float64, brute force over x_0 = d (Bayes, as test_the_restatement_is_bayes_rule forms it),
-    with the fp32 coefficients the step is handed."""
-    K = q.shape[-1]
-    a64, c64 = float(np.float32(a)), float(np.float32(c))
-    A = a64 * onehot_np(np.asarray(xt), K) + (1 - a64) / K
-    B = c64 * np.eye(K) + (1 - c64) / K
-    joint = A[..., :, None] * B[None, None]
-    theta = joint / joint.sum(axis=2, keepdims=True)
-    want = (theta * q.astype(np.float64)[..., None, :]).sum(-1)
-    return want / want.sum(-1, keepdims=True)
-
-
-def threshold_margin64(q64, r):
-    """Per row, the smallest relative distance |c_j - theta| / theta of a prefix mass c_j (j >= 1) to the threshold, in float64."""
-    theta = float(np.float32(r)) * q64.sum(-1, keepdims=True)
-    c = np.cumsum(-np.sort(-q64, axis=-1), axis=-1)
-    return (np.abs(c - theta) / theta).min(-1)
-
-
-def mixed_inputs(rng, N, HW, K):
-    """The evidence tests' random_inputs (flat rows) at the even pixels; at the odd ones peaked rows: softmax of 4 N(0,1) logits, floored
-    at 1e-6, normalised in fp32.  Flat rows alone never truncate at K = 2."""
-    x0, ev, xt = random_inputs(rng, N, HW, K)
-    logits = 4.0 * rng.standard_normal((N, HW, K))
-    p = np.exp(logits - logits.max(-1, keepdims=True))
-    p = np.maximum(p / p.sum(-1, keepdims=True), 1e-6).astype(np.float32)
-    p = (p / p.sum(-1, keepdims=True, dtype=np.float32)).astype(np.float32)
-    x0[:, 1::2] = p[:, 1::2]
-    return x0, ev, xt
 
 
 # ------------------------------------------------------------------------------------------------ CPU
@@ -304,25 +232,6 @@ def test_the_sampling_params_key_reaches_the_sampling_call():
 @pytest.fixture(scope="module")
 def lib():
     return load_lib()
-
-
-def run_kernel(lib, x0, ev, xt, inv_tau, r, a, c, mode, *, step_row=0, seed=SEED, sample_offset=0, xin=None, probs=None, onehot=None,
-               alias=False, symbol=SYMBOL):
-    """x0: fp32 [N,HW,K]; ev: the same or None; xt: integer [N,HW]; xin [N,HW,stride] / probs / onehot [N,HW,K] numpy or None; alias:
-    out_probs IS x0.  symbol = "ccdm_evidence_step": that entry on the same buffers (inv_tau, r unused).  Returns the buffers after the
-    launch (numpy)."""
-    N, HW, K = x0.shape
-    host = dict(x0=x0, ev=ev, xt=np.asarray(xt).astype(np.uint8), xin=xin, probs=probs, onehot=onehot)
-    d = {k: (None if v is None else torch.from_numpy(np.ascontiguousarray(v)).to(DEV)) for k, v in host.items()}
-
-    def ptr(name):
-        return None if d[name] is None else d[name].data_ptr()
-    shaping = (float(inv_tau), float(r)) if symbol == SYMBOL else ()
-    hip.check(getattr(lib, symbol)(ptr("x0"), ptr("ev"), N, HW, K, *shaping, float(a), float(c), mode, step_row, seed, sample_offset, ptr("xt"),
-                                   ptr("xin"), 0 if xin is None else xin.shape[2], ptr("x0") if alias else ptr("probs"), ptr("onehot"), 0),
-              symbol)
-    torch.cuda.synchronize()
-    return {k: (None if v is None else v.cpu().numpy()) for k, v in d.items()}
 
 
 def run_posterior_sample(lib, rows, xt, a, c, mode, row, off, seed=SEED):

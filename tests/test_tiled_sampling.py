@@ -13,11 +13,9 @@ import torch
 from oracle import ccdm_oracle as O
 from ccdm_stochastic_segmentation_amd import hip
 from ccdm_stochastic_segmentation_amd.models import Guidance, tile_origins
+from tests.guided_util import bits, coefficients, mixed_inputs, nhwk, run_shaped_kernel, shaped_restatement
 from tests.sampler_util import (DEV, H, SEED, SMALL_CFG, T_SMALL, T_STRIDED, W, assert_symbol_declared_bound_and_built, load_lib, make_sampler,
                                 onehot_np, sample_sharded_keywords, settings, small_model)
-from tests.test_evidence_sampling import bits, coefficients, nhwk
-from tests.test_shaped_sampling import mixed_inputs, shaped_restatement
-from tests.test_shaped_sampling import run_kernel as run_shaped_kernel
 
 SYMBOL = "ccdm_tiled_step"
 T_VALUES = [6, 4, 3, 1]          # t = 10004 walks the small model strided
@@ -286,7 +284,7 @@ def run_kernel(lib, x0t, ev, cxt, txt, N, geom, inv_tau, r, a, c, mode, *, step_
 # N = 3: 360 canvas pixels, so blocks straddle samples and the last block is partial; the last tiles are shifted in the second (c up to 4)
 # and in the fourth, where three tiles overlap along x (origins 8, 12, 14: c = 3 at x = 14, 15); the third is a row of five whole tiles
 KERNEL_GEOMS = [(12, 10, 8, 8, 4, 2), (12, 10, 8, 8, 3, 5), (8, 24, 8, 8, 8, 4), (8, 22, 8, 8, 8, 4)]
-KERNEL_KS = [2, 3, 5, 20, 40]
+KERNEL_KS = [2, 3, 4, 5, 20, 40]
 
 
 @pytest.mark.gpu

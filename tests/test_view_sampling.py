@@ -13,12 +13,10 @@ import torch
 from oracle import ccdm_oracle as O
 from ccdm_stochastic_segmentation_amd import hip
 from ccdm_stochastic_segmentation_amd.models import DenoisingModel, Guidance
+from tests.guided_util import (POWER_ERROR_ALLOWED, bits, coefficients, mixed_inputs, nhwk, posterior64, run_shaped_kernel, sampler_evidence, shape_rows,
+                               shaped_restatement, threshold_margin64, weighted)
 from tests.sampler_util import (DEV, H, SEED, SMALL_CFG, T_SMALL, T_STRIDED, W, assert_symbol_declared_bound_and_built, load_lib, make_sampler,
                                 onehot_np, sample_sharded_keywords, settings, small_model)
-from tests.test_evidence_sampling import bits, coefficients, nhwk, sampler_evidence
-from tests.test_shaped_sampling import (POWER_ERROR_ALLOWED, mixed_inputs, posterior64, shape_rows, shaped_restatement, threshold_margin64,
-                                        weighted)
-from tests.test_shaped_sampling import run_kernel as run_shaped_kernel
 
 SYMBOL = "ccdm_views_step"
 T_VALUES = [6, 4, 3, 1]          # t = 10004 walks the small model strided
