@@ -89,6 +89,8 @@ class SamplerEngine:
         self._handle = None
         self._tile_canvas: Optional[TileCanvas] = None          # tile_canvas(): the canvas of the tiled calls this engine's rows serve
         self._tile_canvas_key = None
+        self._bound_xt: Optional[torch.Tensor] = None           # bound_noise(): the draw; bound_terms(): the partial sums' workspace
+        self._bound_ws: Optional[torch.Tensor] = None
         with torch.cuda.device(device):
             # a private non-default stream: HIP graph capture is not allowed on the legacy default stream
             self.stream = torch.cuda.Stream(device=device)
@@ -580,6 +582,43 @@ class SamplerEngine:
         hip.check(self.lib.ccdm_slots_step(self.out_probs.data_ptr(), table.data_ptr(), self.N, self.H * self.W, self.K, self.xt.data_ptr(),
                                            None if self.stem_onehot_on_load else self.xin.ptr, self.Cs, self.out_probs.data_ptr(),
                                            self.out_onehot.data_ptr(), self._stream()), "slots_step")
+
+    def _bound_args(self, labels: torch.Tensor, table: torch.Tensor) -> int:
+        """What bound_noise and bound_terms check alike; the number of label rows."""
+        assert labels.dtype == torch.uint8 and labels.is_cuda and labels.is_contiguous() and labels.dim() == 2 and \
+            labels.shape[1] == self.H * self.W, (labels.dtype, tuple(labels.shape))
+        assert table.is_cuda and table.is_contiguous() and table.numel() * table.element_size() == self.N * C.sizeof(hip.BoundRow)
+        return int(labels.shape[0])
+
+    def bound_noise(self, labels: torch.Tensor, table: torch.Tensor, *, philox_seed: int = 0) -> torch.Tensor:
+        """x_t ~ q(x_t | x_0 = label) for every engine row at that row's own noise level (ccdm_bound_noise, asynchronous on the engine's
+        stream).  labels: uint8 [R,H*W] on the engine's device, class < K or 255 = not counted; table: the N rows of hip.BoundRow on the
+        device, 32 bytes each.  Returns the engine-owned uint8 [N,H,W] buffer that holds the draw — what `set_inputs` takes; an idle row
+        keeps what the buffer held."""
+        R = self._bound_args(labels, table)
+        if self._bound_xt is None:
+            self._bound_xt = torch.zeros((self.N, self.H, self.W), dtype=torch.uint8, device=self.device)
+        hip.check(self.lib.ccdm_bound_noise(labels.data_ptr(), table.data_ptr(), self.N, R, self.H * self.W, self.K,
+                                            int(philox_seed) & (2 ** 64 - 1), self._bound_xt.data_ptr(), self._stream()), "bound_noise")
+        return self._bound_xt
+
+    def bound_terms(self, labels: torch.Tensor, table: torch.Tensor, weights: Optional[torch.Tensor], floor: float, row_sum: torch.Tensor,
+                    row_weight: torch.Tensor, map: Optional[torch.Tensor] = None) -> None:
+        """The per-row sums of the bound's per-pixel terms behind a `run` whose table row has mode STEP_SOFTMAX_ONLY (ccdm_bound_terms,
+        asynchronous on the engine's stream): reads x0 from out_probs and x_t from the engine's state.  weights: fp32 [K] on the device or
+        None; row_sum, row_weight: float64 [N]; map: fp32 [N,H*W] or None."""
+        R = self._bound_args(labels, table)
+        assert weights is None or (weights.dtype == torch.float32 and weights.is_cuda and weights.is_contiguous() and weights.numel() == self.K)
+        for v in (row_sum, row_weight):
+            assert v.dtype == torch.float64 and v.is_cuda and v.is_contiguous() and v.numel() == self.N
+        assert map is None or (map.dtype == torch.float32 and map.is_cuda and map.is_contiguous() and map.numel() == self.N * self.H * self.W)
+        if self._bound_ws is None:
+            nbytes = int(self.lib.ccdm_bound_terms_workspace_bytes(self.N, self.H * self.W, self.K))
+            self._bound_ws = torch.zeros((nbytes // 8,), dtype=torch.float64, device=self.device)
+        hip.check(self.lib.ccdm_bound_terms(self.out_probs.data_ptr(), self.xt.data_ptr(), labels.data_ptr(), table.data_ptr(),
+                                            None if weights is None else weights.data_ptr(), self.N, R, self.H * self.W, self.K, float(floor),
+                                            self._bound_ws.data_ptr(), row_sum.data_ptr(), row_weight.data_ptr(),
+                                            None if map is None else map.data_ptr(), self._stream()), "bound_terms")
 
     def set_tables(self, t_rows: Sequence[float], coeffs: Sequence[Tuple[float, float, int]], per_sample: bool = False) -> None:
         """t_rows[i] = timestep of table row i; coeffs[i] = (alpha_t, cumalpha_tm1, mode).

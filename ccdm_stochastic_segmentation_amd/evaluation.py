@@ -313,7 +313,14 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
                             weighted by their shares) and `coverage` (the mean over raters of the distance to the nearest medoid),
                             each a mean over the images (mode_summary_scores); with `output_path` set, also written as
                             lidc_modes.json
-         mode_count (4): the modes looked for, 1 to 16;  mode_max_swaps (64): the most swaps of the clustering"""
+         mode_count (4): the modes looked for, 1 to 16;  mode_max_swaps (64): the most swaps of the clustering
+         label_bound: yes   the result gains "label_bound": the variational bound on -log p(rater's map | image) in nats
+                            (DenoisingModel.label_bound, one call per batch on the batch's images and all raters' maps): per rater the
+                            mean bound and bits per pixel over the images, their mean over the raters — an upper bound on the
+                            cross-entropy between the raters' distribution and the model's — and the per-timestep curve averaged over
+                            images and raters, with `images`, `timesteps`, `draws`, `complete`; with `output_path` set, also written as
+                            lidc_label_bound.json.  Under WORLD_SIZE > 1 every rank computes the same numbers (the bound is not sharded)
+         label_bound_timesteps (all): a list of timesteps (a partial sum) or a number of strata;  label_bound_draws (1)"""
     from . import distributed as D
     rank, local_rank, world = D.init_from_env()
     if device is None:
@@ -370,7 +377,15 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
     if modes is not None:
         modes_count = mode_count(section.get("mode_count", 4))
         modes_swaps = mode_max_swaps(section.get("mode_max_swaps", 64))
+    bound = [] if section.get("label_bound", False) else None                                    # the result of every batch
+    if bound is not None:
+        bound_ts = section.get("label_bound_timesteps")
+        bound_ts = [int(v) for v in bound_ts] if isinstance(bound_ts, (list, tuple)) else (None if bound_ts is None else int(bound_ts))
+        bound_draws = int(section.get("label_bound_draws", 1))
     for image, labels, _ in loader:                                              # Tester.test_step, :89-136
+        if bound is not None:
+            got = model.label_bound(labels.to(device).argmax(dim=2), image.to(device), timesteps=bound_ts, draws=bound_draws)
+            bound.append({k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in got.items()})
         image = image.to(device).repeat_interleave(S, dim=0)
         # x_T: uniform one-hot from the CPU generator, full batch on every rank (same seed => same draw)
         x = OneHotCategoricalBCHW(logits=torch.zeros(labels[:, 0].repeat_interleave(S, dim=0).shape)).sample().to(device)
@@ -486,7 +501,35 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
             os.makedirs(out_dir, exist_ok=True)
             with open(os.path.join(out_dir, "lidc_modes.json"), "w") as f:
                 json.dump(res["modes"], f, indent=1)
+    if bound is not None:
+        res["label_bound"] = label_bound_summary(bound, bound_draws)
+        r = res["label_bound"]
+        LOGGER.info("label bound: %.6g nats per map, %.4g bits per pixel over %d images (%d timesteps, %d draw(s)%s)", r["bound"],
+                    r["bits_per_pixel"], r["images"], len(r["timestep_curve"]), r["draws"], "" if r["complete"] else ", partial sum")
+        if params.get("output_path") and rank == 0:
+            import json
+            out_dir = expanduservars(params["output_path"])
+            os.makedirs(out_dir, exist_ok=True)
+            with open(os.path.join(out_dir, "lidc_label_bound.json"), "w") as f:
+                json.dump(res["label_bound"], f, indent=1)
     return res
+
+
+def label_bound_summary(parts: Sequence[Dict[str, object]], draws: int) -> Dict[str, object]:
+    """What eval_lidc_uncertainty reports of DenoisingModel.label_bound's results over the batches (`parts`: numpy arrays, [B,L] and
+    [B,L,M]): per rater the mean over the images of the bound (nats) and of the bits per pixel, their mean over the raters (the
+    cross-entropy bound of the rater distribution), and the per-timestep curve — the mean term per position of the estimator, with the
+    timestep where every label used the same one (None under stratified draws)."""
+    bound = np.concatenate([p["bound"] for p in parts])
+    bpp = np.concatenate([p["bits_per_pixel"] for p in parts])
+    terms = np.concatenate([p["terms"] for p in parts])
+    ts = np.concatenate([p["timesteps"] for p in parts])
+    same = [bool((ts[..., m] == ts[0, 0, m]).all()) for m in range(ts.shape[-1])]
+    return {"bound_per_rater": bound.mean(axis=0).tolist(), "bits_per_pixel_per_rater": bpp.mean(axis=0).tolist(),
+            "bound": float(bound.mean()), "bits_per_pixel": float(bpp.mean()), "prior": float(np.concatenate([p["prior"] for p in parts]).mean()),
+            "timestep_curve": terms.mean(axis=(0, 1)).tolist(),
+            "timesteps": [int(ts[0, 0, m]) if same[m] else None for m in range(ts.shape[-1])],
+            "images": int(bound.shape[0]), "raters": int(bound.shape[1]), "draws": int(draws), "complete": bool(all(p["complete"] for p in parts))}
 
 
 def eval_lidc_sampling_speed(params: dict, timesteps: Sequence[int] = (250, 200, 150, 100, 50, 25, 10), **kw) -> Dict[int, dict]:

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get("CCDM_LIB") or os.path.join(_HERE, "libccdm_hip.so")      # CCDM_LIB: A/B two builds on one GPU box
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["ccdm_conv.hip", "ccdm_conv_ks.hip", "ccdm_upconv.hip", "ccdm_stem.hip", "ccdm_head.hip", "ccdm_conv1x1.hip", "ccdm_misc.hip", "ccdm_attention.hip", "ccdm_attn_block.hip", "ccdm_sampler.hip", "ccdm_known.hip", "ccdm_guided.hip", "ccdm_metrics.hip", "ccdm_range.hip", "ccdm_resample.hip", "ccdm_engine.hip", "ccdm_vote.hip", "ccdm_segeval.hip", "ccdm_segexport.hip", "ccdm_csscore.hip", "ccdm_segcalib.hip", "ccdm_segboundary.hip", "ccdm_contourf.hip", "ccdm_uncscore.hip", "ccdm_lidcscore.hip", "ccdm_surfdist.hip", "ccdm_lesions.hip", "ccdm_lesionmatch.hip", "ccdm_modes.hip"]
+SOURCES = ["ccdm_conv.hip", "ccdm_conv_ks.hip", "ccdm_upconv.hip", "ccdm_stem.hip", "ccdm_head.hip", "ccdm_conv1x1.hip", "ccdm_misc.hip", "ccdm_attention.hip", "ccdm_attn_block.hip", "ccdm_sampler.hip", "ccdm_known.hip", "ccdm_guided.hip", "ccdm_metrics.hip", "ccdm_range.hip", "ccdm_resample.hip", "ccdm_engine.hip", "ccdm_vote.hip", "ccdm_segeval.hip", "ccdm_segexport.hip", "ccdm_csscore.hip", "ccdm_segcalib.hip", "ccdm_segboundary.hip", "ccdm_contourf.hip", "ccdm_uncscore.hip", "ccdm_lidcscore.hip", "ccdm_surfdist.hip", "ccdm_lesions.hip", "ccdm_lesionmatch.hip", "ccdm_modes.hip", "ccdm_bound.hip"]
 # -amdgpu-mfma-vgpr-form: MFMA accumulators stay in the (unified) VGPR file.  The default heuristic parks them in AccVGPRs and pays a
 # v_accvgpr_read/_write for every vector op that touches a score or an output accumulator: 240 extra instructions per key tile in
 # the attention kernels (2066 in ccdm_attention.hip, 576 in ccdm_attn_block.hip; the conv kernels have none either way).
@@ -30,6 +30,7 @@ PREC_F32, PREC_F16X3 = 0, 1
 PREC_F16 = 2             # CCDM_PREC_F16: the OPT-IN single-pass fast mode (one fp16 MFMA per product, ~2^-11 per operand) — outside the parity contract
 STEP_SAMPLE, STEP_LAST_CONFIDENCE, STEP_LAST_MAJORITY, STEP_LAST_KEEP, STEP_SOFTMAX_ONLY = 0, 1, 2, 3, 4
 SLOT_IDLE = -1           # CCDM_SLOT_IDLE: SlotRow.mode of a slot that holds nothing (ccdm_slots_step)
+BOUND_IDLE = -1          # CCDM_BOUND_IDLE: BoundRow.t of an engine row that holds nothing (ccdm_bound_noise, ccdm_bound_terms)
 STATS_MAX_SLICES = 64       # CCDM_STATS_MAX_SLICES: what a GroupNorm consumer reads
 F16X3_LIMIT = 4094.0        # CCDM_F16X3_LIMIT: the fp16 split is exact for staged |a| below this
 STATS_FOLD_SLICES = 16      # CCDM_STATS_FOLD_SLICES: what the engine folds a larger slice count to
@@ -88,6 +89,26 @@ class SlotRow(C.Structure):
         ("key_lo", C.c_uint32), ("key_hi", C.c_uint32),
         ("sample", C.c_uint32), ("reserved", C.c_uint32),
     ]
+
+
+class BoundRow(C.Structure):
+    """ccdm_bound_row: one row of the device table of ccdm_bound_noise / ccdm_bound_terms, the per-engine-row parameters of a label-bound pass."""
+    _fields_ = [
+        ("p_hit", C.c_float), ("p_miss", C.c_float),
+        ("alpha_t", C.c_float), ("cumalpha_tm1", C.c_float),
+        ("t", C.c_int32), ("sample", C.c_uint32),
+        ("label_row", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+# the same row as numpy sees it (32 bytes)
+BOUND_DTYPE_FIELDS = [("p_hit", "<f4"), ("p_miss", "<f4"), ("alpha_t", "<f4"), ("cumalpha_tm1", "<f4"), ("t", "<i4"), ("sample", "<u4"),
+                      ("label_row", "<i4"), ("reserved", "<i4")]
+
+
+def bound_dtype():
+    import numpy as np
+    return np.dtype(BOUND_DTYPE_FIELDS)
 
 
 POST_RUN_BYTES = 56      # sizeof(ccdm_post_run): the device-resident per-run fields of the epilogue
@@ -184,6 +205,10 @@ SIGNATURES = {
                                   C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ccdm_slots_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                   C.c_void_p]),
+    "ccdm_bound_noise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "ccdm_bound_terms_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "ccdm_bound_terms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ccdm_pairwise_class_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "ccdm_lidcscore": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ccdm_surfdist_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),

@@ -28,7 +28,8 @@ from .unet_spec import UNetSpec, make_unet_spec
 LOGGER = logging.getLogger(__name__)
 
 __all__ = ["build_model", "DiffusionModel", "DenoisingModel", "UNetModel", "OneHotCategoricalBCHW",
-           "linear_schedule", "cosine_schedule", "step_values", "resample_walk", "pass_key"]
+           "linear_schedule", "cosine_schedule", "step_values", "resample_walk", "pass_key",
+           "bound_timesteps", "bound_prior", "bound_rows"]
 
 
 # --------------------------------------------------------------------------------------------------
@@ -119,6 +120,81 @@ def pass_key(key: int, p: int) -> int:
     z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & 0xFFFFFFFFFFFFFFFF
     z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & 0xFFFFFFFFFFFFFFFF
     return z ^ (z >> 31)
+
+
+# --------------------------------------------------------------------------------------------------
+# the label bound's host arithmetic (DenoisingModel.label_bound; include/ccdm_hip.h has the definition)
+# --------------------------------------------------------------------------------------------------
+def bound_timesteps(T: int, timesteps, key: int, n_labels: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The estimator over t: (t int64 [n_labels, M], weight float64 [n_labels, M]).  None: every t in 1..T at weight 1.  A sequence:
+    those t at weight 1 (a partial sum unless it covers 1..T).  An int M <= T: stratified — stratum j = (floor(j T / M), floor((j + 1) T
+    / M)], one t drawn uniformly per label and stratum from np.random.Generator(np.random.Philox(key)) (labels outer, strata inner),
+    weighted by the stratum's size: unbiased in t, reproducible from the key."""
+    T, n_labels = int(T), int(n_labels)
+    if T < 1 or n_labels < 1:
+        raise ValueError(f"bound_timesteps: T = {T}, n_labels = {n_labels}")
+    if timesteps is None:
+        t = np.arange(1, T + 1, dtype=np.int64)
+        return np.tile(t, (n_labels, 1)), np.ones((n_labels, T), dtype=np.float64)
+    if isinstance(timesteps, (int, np.integer)) and not isinstance(timesteps, bool):
+        M = int(timesteps)
+        if not 1 <= M <= T:
+            raise ValueError(f"timesteps: {M} strata for T = {T} (expected 1 <= M <= T)")
+        edges = np.array([(j * T) // M for j in range(M + 1)], dtype=np.int64)
+        rng = np.random.Generator(np.random.Philox(key=int(key) & 0xFFFFFFFFFFFFFFFF))
+        t = rng.integers(edges[None, :-1] + 1, edges[None, 1:] + 1, size=(n_labels, M), dtype=np.int64)
+        return t, np.tile((edges[1:] - edges[:-1]).astype(np.float64), (n_labels, 1))
+    try:
+        ts = [int(v) for v in timesteps]
+        exact = all(float(v) == int(v) for v in timesteps)
+    except (TypeError, ValueError):
+        raise ValueError(f"timesteps: expected None, an int or a sequence of ints, got {timesteps!r}") from None
+    if not ts or not exact or any(not 1 <= v <= T for v in ts):
+        raise ValueError(f"timesteps: every t must be an integer in 1..{T}, got {list(timesteps)!r}")
+    if len(set(ts)) != len(ts):
+        raise ValueError(f"timesteps: repeated timestep in {ts!r}")
+    return np.tile(np.array(ts, dtype=np.int64), (n_labels, 1)), np.ones((n_labels, len(ts)), dtype=np.float64)
+
+
+def bound_prior(cumalpha_T: float, K: int) -> float:
+    """L_T per counted pixel of weight 1: KL(q(x_T | x_0) || uniform) = p_hit log(K p_hit) + (K - 1) p_miss log(K p_miss) in float64
+    (0 log 0 = 0), p_miss = (1 - cumalpha_T) / K, p_hit = cumalpha_T + p_miss."""
+    c, K = float(cumalpha_T), int(K)
+    p_miss = (1.0 - c) / K
+    p_hit = c + p_miss
+    return sum(n * p * math.log(K * p) for n, p in ((1, p_hit), (K - 1, p_miss)) if p > 0.0 and n > 0)
+
+
+def bound_rows(timesteps: np.ndarray, draws: int, rows: int, K: int, cumalphas: Sequence[float], coeffs: Callable[[int], Tuple[float, float]],
+               n_label_rows: Optional[int] = None) -> List[Tuple[np.ndarray, np.ndarray]]:
+    """The packing of the (label, timestep, draw) triples — labels outer, draws inner — into passes of `rows` engine rows, the tail
+    padded with idle rows.  timesteps: int [n_labels, M] (bound_timesteps); cumalphas[t - 1] = cumalpha_t; coeffs(t) = posterior_coeffs.
+    Per pass (table, slot): `table` the `rows` records of hip.bound_dtype() — p_hit / p_miss formed in float64 and rounded to fp32 once,
+    sample = label * draws + draw, label_row = label — and `slot` int64 [rows], (label * M + m) * draws + draw of the triple the row
+    holds, -1 for an idle row.  A label row outside [0, n_label_rows) is refused here: the kernels never see one."""
+    ts = np.asarray(timesteps)
+    draws, rows, K = int(draws), int(rows), int(K)
+    if ts.ndim != 2 or draws < 1 or rows < 1:
+        raise ValueError(f"bound_rows: timesteps {ts.shape}, draws = {draws}, rows = {rows}")
+    n_labels, M = ts.shape
+    n_label_rows = n_labels if n_label_rows is None else int(n_label_rows)
+    if n_labels > n_label_rows:
+        raise ValueError(f"bound_rows: label rows 0..{n_labels - 1} outside [0,{n_label_rows})")
+    triples = [(l, m, d) for l in range(n_labels) for m in range(M) for d in range(draws)]
+    passes = []
+    for p0 in range(0, len(triples), rows):
+        table = np.zeros(rows, dtype=hip.bound_dtype())
+        table["t"] = hip.BOUND_IDLE
+        slot = np.full(rows, -1, dtype=np.int64)
+        for n, (l, m, d) in enumerate(triples[p0:p0 + rows]):
+            t = int(ts[l, m])
+            c = float(cumalphas[t - 1])
+            p_miss = (1.0 - c) / K
+            a, cm1 = coeffs(t)
+            table[n] = (np.float32(c + p_miss), np.float32(p_miss), np.float32(a), np.float32(cm1), t, l * draws + d, l, 0)
+            slot[n] = (l * M + m) * draws + d
+        passes.append((table, slot))
+    return passes
 
 
 @dataclasses.dataclass(frozen=True)
@@ -457,6 +533,7 @@ class DenoisingModel(nn.Module):
         self.philox_seed = 0
         self.philox_call = 0            # index of the next sampling call's noise stream (see the class docstring)
         self.philox_advance = True
+        self.bound_call = 0             # index of the next label_bound call's key: a counter of its own, so a bound between two sampling calls changes neither
         self.sample_offset = 0          # global index of sample 0 when the batch is sharded over ranks
         self.noise_slice: Optional[Tuple[int, int]] = None   # (global_batch, first_sample) for torch_cpu sharding
         # each denoise step is replayed as one captured HIP graph (identical results to eager launches, tested)
@@ -580,11 +657,13 @@ class DenoisingModel(nn.Module):
         from .serving import SamplingQueue
         return SamplingQueue(self, capacity, image_shape)
 
-    def _philox_key(self) -> int:
-        """64-bit Philox key of the current sampling call: splitmix64 of (philox_seed, philox_call)."""
-        if int(self.philox_call) == 0:
+    def _philox_key(self, call: Optional[int] = None) -> int:
+        """64-bit Philox key of the current sampling call: splitmix64 of (philox_seed, philox_call).  `call`: another counter in
+        philox_call's place (label_bound's own, `bound_call`)."""
+        call = int(self.philox_call if call is None else call)
+        if call == 0:
             return int(self.philox_seed) & 0xFFFFFFFFFFFFFFFF        # call 0 uses the seed itself (the key the kernel tests pin)
-        z = (int(self.philox_seed) + 0x9E3779B97F4A7C15 * int(self.philox_call)) & 0xFFFFFFFFFFFFFFFF
+        z = (int(self.philox_seed) + 0x9E3779B97F4A7C15 * call) & 0xFFFFFFFFFFFFFFFF
         z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & 0xFFFFFFFFFFFFFFFF
         z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & 0xFFFFFFFFFFFFFFFF
         return z ^ (z >> 31)
@@ -1140,6 +1219,146 @@ class DenoisingModel(nn.Module):
         samples = stack.reshape(B, S, H, W)
         out = MT.sample_modes(samples, K, modes, max_swaps=max_swaps, maps=maps)
         out["samples"] = samples
+        return out
+
+    # ------------------------------------------------------------------ likelihood bound of held-out labels
+    BOUND_LOG_FLOOR = 1e-12             # the trainer's clamp under the logarithm (trainer.py:267)
+
+    @torch.no_grad()
+    def label_bound(self, labels: Tensor, condition: Tensor, feature_condition: Optional[Tensor] = None, *, timesteps=None,
+                    draws: int = 1, class_weights: Optional[Tensor] = None, rows: int = 64, return_map: bool = False) -> Dict[str, Any]:
+        """How probable the model finds label maps somebody drew: the variational bound, in nats,
+            -log p(y | image) <= L_T + sum_t E_{x_t ~ q(x_t | x_0 = y)} l_t(y, x_t)
+        whose per-timestep term is the reference's training loss (include/ccdm_hip.h has the definition).  No walk: every network kernel
+        reads its time-embedding row per engine row, so one pass of `rows` rows holds (label, timestep, draw) triples at different noise
+        levels — all 250 levels of one LIDC label are four 64-row passes.  Per pass: ccdm_bound_noise draws x_t, the network runs to x0
+        (STEP_SOFTMAX_ONLY), ccdm_bound_terms sums the per-pixel terms per row; one stream, one host synchronisation at the end.
+        labels: integer [B,H,W] or [B,L,H,W] (L maps per image, e.g. the raters), a class < K or 255 = pixel not counted; or one-hot float
+        [B,(L,)K,H,W], taken by argmax.  timesteps: None = every t in 1..T; a sequence = those t (a partial sum); an int M = M strata
+        with one t drawn per label and stratum, weighted by the stratum's size (unbiased; bound_timesteps).  draws: independent x_t per
+        (label, t), averaged.  class_weights: fp32 [K], the trainer's per-class mask (0 drops a class: Cityscapes' ignore).
+        Returns float64 tensors: "bound" [B,L], "bits_per_pixel" [B,L] = bound / (sum of the pixel weights * ln 2), "terms" [B,L,M] (mean
+        over draws, not weighted by the stratum), "timesteps" [B,L,M] (int64), "prior" [B,L], "pixels" [B,L] (int64: the counted pixels),
+        "complete" (bool: the estimator covers 1..T); with return_map "surprise" [B,L,H,W] fp32, the estimator-weighted sum of the
+        per-pixel terms (accumulated in 2^-32 fixed point: the same bits however the rows are packed).
+        The draws are keyed by (pixel, label, draw, t) under a key of the call's own counter `bound_call` (it advances with
+        `philox_advance`; `philox_call` is not touched) on a Philox counter range no sampling draw uses: a bound between two sampling calls
+        changes neither, and the result does not depend on `rows` (default slicing).  The floor 1e-12 under the logarithm is the
+        trainer's: where the model gives a class the posterior needs less than that, the term is capped — a bound up to those pixels.
+        Under WORLD_SIZE > 1 every rank computes the same numbers (no sharding).  Refused: rng = "torch_cpu", `softmax_output: no`, labels
+        whose geometry is not the call's, draws < 1, rows < 1, timesteps outside 1..T or repeated."""
+        if self.rng == "torch_cpu":
+            raise ValueError("label_bound: not available with rng = 'torch_cpu' (the host-noise parity mode has no reference stream for the "
+                             "forward draws); use rng = 'philox'")
+        if self.rng != "philox":
+            raise ValueError(f"rng: {self.rng!r}")
+        if not self.unet.spec.softmax_output:
+            raise ValueError("label_bound: needs a model whose output is a probability vector; with `softmax_output: no` x0 holds logits")
+        K, T = int(self.diffusion.num_classes), int(self.time_steps)
+        if isinstance(draws, bool) or int(draws) != draws or int(draws) < 1:
+            raise ValueError(f"draws: expected an integer >= 1, got {draws!r}")
+        if isinstance(rows, bool) or int(rows) != rows or int(rows) < 1:
+            raise ValueError(f"rows: expected an integer >= 1, got {rows!r}")
+        draws, rows = int(draws), int(rows)
+        if not isinstance(condition, Tensor) or condition.dim() != 4:
+            raise ValueError("condition: expected the images [B,C,H,W]")
+        B, _, H, W = (int(v) for v in condition.shape)
+        if not isinstance(labels, Tensor) or labels.dtype == torch.bool or labels.dtype.is_complex:
+            raise ValueError(f"labels: expected an integer or one-hot float tensor, got {getattr(labels, 'dtype', type(labels).__name__)}")
+        if labels.dtype.is_floating_point:
+            if labels.dim() not in (4, 5) or int(labels.shape[-3]) != K:
+                raise ValueError(f"labels: one-hot labels must be [B,K,H,W] or [B,L,K,H,W] with K = {K}, got {tuple(labels.shape)}")
+            idx = labels.detach().argmax(dim=-3)
+        else:
+            idx = labels.detach()
+            host = idx.cpu()
+            if bool(((host < 0) | (host > 255)).any()):
+                raise ValueError("labels: values must be classes in [0,K) or 255 (not counted)")
+        if idx.dim() == 3:
+            idx = idx[:, None]
+        if idx.dim() != 4 or (int(idx.shape[0]), int(idx.shape[2]), int(idx.shape[3])) != (B, H, W) or int(idx.shape[1]) < 1:
+            raise ValueError(f"labels: geometry {tuple(labels.shape)} does not match the call's: expected [{B},(L,){H},{W}] "
+                             f"(or one-hot [{B},(L,){K},{H},{W}])")
+        L = int(idx.shape[1])
+        dev = next(self.unet.parameters()).device
+        w_dev = None
+        if class_weights is not None:
+            w_dev = torch.as_tensor(class_weights, dtype=torch.float32).reshape(-1).to(dev).contiguous()
+            if w_dev.numel() != K or not bool(torch.isfinite(w_dev).all()) or bool((w_dev < 0).any()):
+                raise ValueError(f"class_weights: expected {K} finite weights >= 0")
+        key = self._philox_key(self.bound_call)
+        t_np, wt_np = bound_timesteps(T, timesteps, key, B * L)
+        complete = timesteps is None or (isinstance(timesteps, (int, np.integer)) and not isinstance(timesteps, bool)) or \
+            set(int(v) for v in t_np[0]) == set(range(1, T + 1))
+        labels_dev = idx.to(device=dev, dtype=torch.uint8).reshape(B * L, H * W).contiguous()
+        out = self._with_range_fallback(lambda: self._label_bound(labels_dev, condition, feature_condition, t_np, wt_np, draws, rows, w_dev,
+                                                                  return_map, key, (B, L, H, W)))
+        out["complete"] = bool(complete)
+        if self.philox_advance:
+            self.bound_call += 1
+        return out
+
+    def _label_bound(self, labels_dev: Tensor, condition: Tensor, feature_condition: Optional[Tensor], t_np: np.ndarray, wt_np: np.ndarray,
+                     draws: int, rows: int, w_dev: Optional[Tensor], return_map: bool, key: int, shape: Tuple[int, int, int, int]) -> Dict[str, Any]:
+        B, L, H, W = shape
+        K, T, R, M, HW = int(self.diffusion.num_classes), int(self.time_steps), B * L, int(t_np.shape[1]), H * W
+        dev = labels_dev.device
+        cum = [float(v) for v in self.diffusion.cumalphas.double().cpu()]
+        passes = bound_rows(t_np, draws, rows, K, cum, self.diffusion.posterior_coeffs, R)
+        P = len(passes)
+        tables = np.stack([tab for tab, _ in passes])                                    # [P, rows] records
+        slots = np.stack([slot for _, slot in passes])                                   # [P, rows], -1 = idle
+        busy = slots >= 0
+        label_of = np.where(busy, slots // (M * draws), 0)
+        m_of = np.where(busy, (slots // draws) % M, 0)
+        # everything the passes read, uploaded once: no host-to-device copy, no synchronisation inside the loop
+        tables_dev = torch.from_numpy(tables.view(np.int32).reshape(P, rows, 8)).to(dev)
+        rowmap_dev = torch.from_numpy(np.where(busy, tables["t"] - 1, 0).astype(np.int32)).to(dev)
+        image_of = torch.from_numpy(label_of // L).to(dev)
+        slot_dev = torch.from_numpy(np.where(busy, slots, R * M * draws)).to(dev)        # idle rows add their zeros to a slot of their own
+        eng = self._engine(torch.empty((rows, K, H, W), device="meta"), condition, feature_condition)
+        acc = torch.zeros((R * M * draws + 1,), dtype=torch.float64, device=dev)
+        row_sum = torch.zeros((rows,), dtype=torch.float64, device=dev)
+        row_weight = torch.zeros((rows,), dtype=torch.float64, device=dev)
+        pix_map = surprise_fx = scale_dev = label_dev = None
+        if return_map:
+            pix_map = torch.zeros((rows, HW), dtype=torch.float32, device=dev)
+            surprise_fx = torch.zeros((R + 1, HW), dtype=torch.int64, device=dev)
+            scale = np.where(busy, wt_np[label_of, m_of] / draws, 0.0) * 2.0 ** 32
+            scale_dev = torch.from_numpy(scale).to(dev)
+            label_dev = torch.from_numpy(np.where(busy, label_of, R)).to(dev)
+        with eng.enter():
+            cond = condition.to(dev, torch.float32)
+            feat = None if feature_condition is None else feature_condition.to(dev, torch.float32)
+            # all T levels, row t - 1 holds timestep t; every row's network pass stops at x0
+            eng.set_tables([float(t) for t in range(1, T + 1)], [(0.0, 1.0, hip.STEP_SOFTMAX_ONLY)] * T)
+            for p in range(P):
+                xt = eng.bound_noise(labels_dev, tables_dev[p], philox_seed=key)
+                eng.set_inputs(xt, cond.index_select(0, image_of[p]), None if feat is None else feat.index_select(0, image_of[p]))
+                eng.set_rows(rowmap_dev[p])
+                eng.run(1, with_epilogue=True, use_graph=False)
+                eng.bound_terms(labels_dev, tables_dev[p], w_dev, self.BOUND_LOG_FLOOR, row_sum, row_weight, pix_map)
+                acc.index_add_(0, slot_dev[p], row_sum)                                   # (one row per slot: no two addends meet)
+                if return_map:
+                    # integer adds: the same sum in any order, so the map does not depend on the packing either
+                    surprise_fx.index_add_(0, label_dev[p], torch.round(pix_map.double() * scale_dev[p][:, None]).to(torch.int64))
+                self._probe_ranges([eng])
+            counted = labels_dev < K
+            pixels = counted.sum(dim=1)
+            if w_dev is None:
+                weight = pixels.double()
+            else:
+                weight = (w_dev.double()[labels_dev.clamp(max=K - 1).long()] * counted).sum(dim=1)
+            terms = acc[:-1].reshape(R, M, draws).sum(dim=2) / draws
+        eng.leave()
+        eng.raise_if_flagged()                      # the call's one host synchronisation
+        prior = weight * bound_prior(cum[T - 1], K)
+        bound = prior + (terms * torch.from_numpy(wt_np).to(dev)).sum(dim=1)
+        out = {"bound": bound.reshape(B, L), "bits_per_pixel": (bound / (weight * math.log(2.0))).reshape(B, L),
+               "terms": terms.reshape(B, L, M), "timesteps": torch.from_numpy(t_np).to(dev).reshape(B, L, M), "prior": prior.reshape(B, L),
+               "pixels": pixels.reshape(B, L)}
+        if return_map:
+            out["surprise"] = (surprise_fx[:-1].double() * 2.0 ** -32).float().reshape(B, L, H, W)
         return out
 
     def _forward_step(self, x: Tensor, condition: Tensor, feature_condition: Tensor, t: Tensor) -> dict:

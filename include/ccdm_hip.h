@@ -519,6 +519,62 @@ int ccdm_slots_step(const float* x0 /*dev [N,HW,K]*/, const ccdm_slot_row* table
                     float* out_probs /*[N,HW,K] or NULL*/, int64_t* out_onehot /*[N,HW,K] or NULL*/, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * The variational bound on the likelihood of a held-out label map (DenoisingModel.label_bound):
+ *     -log p(y | image) <= L_T + sum_{t=1..T} E_{x_t ~ q(x_t | x_0 = y)} l_t(y, x_t)
+ * with l_t the reference's training loss (trainer.py:255-277).  Every network kernel reads its time-embedding row as rowmap[n] + step,
+ * so ONE network pass holds rows at different noise levels; the two launches here sit around it and read a device table of one
+ * 32-byte ccdm_bound_row per engine row.
+ * THE definition.  For a label map y [HW] (class < K; any byte >= K, conventionally 255, is a pixel that is not counted), a timestep
+ * t in 1..T and (a, c) = DiffusionModel.posterior_coeffs(t) (so (0, 1) at t = 1):
+ *   Draw (ccdm_bound_noise).  x_t ~ q(x_t | x_0 = y) = Cat(cumalpha_t onehot(y) + (1 - cumalpha_t) / K) per pixel: the Exp(1) race of
+ *     the step epilogue, argmax_k p_k / E_k with p_k = p_hit for k == y and p_miss otherwise, first maximum wins, E_k from word k % 4 of
+ *     Philox4x32-10(counter = (pixel, sample, t, 0x20000000 | k / 4), key = philox_seed).  The host forms p_miss = (1 - cumalpha_t) / K
+ *     and p_hit = cumalpha_t + p_miss in float64 and rounds each to fp32 once.  The tag is a range of its own (the epilogue uses fourth
+ *     words < 64, the clamp 0x80000000 | k / 4, the renoise 0x40000000 | k / 4); `sample` is the global index of the (label, draw) pair,
+ *     never the engine row, and the third word is the timestep itself: a draw depends on (pixel, label, draw, t, key) only, not on how
+ *     rows are packed into passes.  An uncounted pixel gets x_t = pixel % K without a draw.  Only xt_out is written.
+ *   Term (ccdm_bound_terms).  Per counted pixel, all in fp32, sums over k ascending, logf the accurate one:
+ *       p = theta_post(x_t, onehot(y), t):       A_k = a [k == x_t] + (1 - a) / K ;  theta_k = A_k (c [k == y] + (1 - c) / K) ;  p_k = theta_k / sum theta
+ *       q = theta_post_prob(x_t, x0, t):         b = (1 - c) / K ;  S = sum A_k ;  r_k = x0_k / (c A_k + b S) ;  R = sum r_k ;  q_k = A_k (c r_k + b R)
+ *       l = sum_k p_k (log p_k - log max(q_k, floor)),  0 where p_k = 0
+ *     — q in the O(K) closed form of the step epilogue up to and including A_k (c r_k + b R), without its clamp and normalisation, as in
+ *     the trainer; floor = 1e-12 is the trainer's.  A_k takes two values and theta_k four, so S and sum theta are written out
+ *     (S = (a + u) + (K - 1) u with u = (1 - a) / K, likewise sum theta: a few roundings where K equal addends in a row would make
+ *     K / 2); R is the k-ascending sum, l a compensated (Kahan) sum of its K terms.  At t = 1 (a row with alpha_t = 0 and cumalpha_tm1 = 1) p = onehot(y), q = x0 and the
+ *     term is evaluated as what it is, l = -logf(max(x0_y, floor)), the decoder term.  The pixel's weight is w = class_weights[y] (1
+ *     without class_weights): the trainer's `mask`.  The pixel's fp32 value is w * l (0 where w = 0).
+ *   Row sums.  row_sum[n] = sum_pix (double)(w l) and row_weight[n] = sum_pix (double)w over the counted pixels of engine row n, float64,
+ *     accumulated from the fp32 pixel values in a fixed order: per-(block, row) partials into the workspace, folded per row by one small
+ *     fixed-order launch (as ccdm_stats_fold).  No float atomics: two calls on the same inputs return the same bits.
+ *   map (optional) receives the pixel's fp32 value w * l, 0 at uncounted pixels and on idle rows; nothing else of the buffer is touched.
+ *   A row with t = CCDM_BOUND_IDLE (any t < 1) is idle: nothing of it is read (x0, xt, labels), no x_t is written, its sums are 0.  The
+ *   table lives on the device and is not read on the host; a row whose label_row is outside [0, R) is treated as idle by both kernels,
+ *   so no label row out of range is ever read (models.bound_rows refuses to build such a table).
+ * The floor makes this a bound only up to pixels where some q_k < floor with p_k > 0: there the term is capped at p_k (log p_k - log floor).
+ * The prior term L_T and the estimator over t (all, a subset, or stratified) are host arithmetic: models.bound_prior, models.bound_timesteps.
+ * x0 is read as contiguous [pixel][class] runs through LDS rows (256 pixels per block for K <= 32, 64 above); K in [1, CCDM_MAX_CLASSES].
+ * ccdm_bound_terms_workspace_bytes(N, HW, K) = 16 * (blocks + N) bytes (8-byte aligned device memory; 0 for a shape that is refused).
+ * Refused before anything is launched: a null labels / table / xt_out / x0 / xt / ws / row_sum / row_weight, a table that is not 4-byte
+ * aligned, N, R or HW < 1, K outside [1, CCDM_MAX_CLASSES], floor not in (0, 1), N * HW or R * HW > 2^31 - 1.
+ * ------------------------------------------------------------------------------------------------- */
+#define CCDM_BOUND_IDLE (-1)        /* ccdm_bound_row.t of a row that holds nothing */
+typedef struct ccdm_bound_row {
+    float p_hit; float p_miss;              /* the draw, from cumalpha_t */
+    float alpha_t; float cumalpha_tm1;      /* the term, posterior_coeffs(t) */
+    int32_t t;                              /* timestep = third Philox word; CCDM_BOUND_IDLE: row neither read nor written, its sums 0 */
+    uint32_t sample;                        /* global (label, draw) index: the second Philox word */
+    int32_t label_row;                      /* row of `labels` this engine row scores: many rows share one map, nothing is gathered */
+    int32_t reserved;
+} ccdm_bound_row;
+int ccdm_bound_noise(const uint8_t* labels /*dev [R,HW]*/, const ccdm_bound_row* table /*dev [N]*/, int N, int R, int HW, int K,
+                     uint64_t philox_seed, uint8_t* xt_out /*dev [N,HW]*/, void* stream);
+size_t ccdm_bound_terms_workspace_bytes(int N, int HW, int K);
+int ccdm_bound_terms(const float* x0 /*dev [N,HW,K]*/, const uint8_t* xt /*dev [N,HW]*/, const uint8_t* labels /*dev [R,HW]*/,
+                     const ccdm_bound_row* table /*dev [N]*/, const float* class_weights /*dev [K] or NULL*/, int N, int R, int HW, int K,
+                     float floor, void* ws, double* row_sum /*dev [N]*/, double* row_weight /*dev [N]*/, float* map /*dev [N,HW] or NULL*/,
+                     void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * LIDC metrics, device part: for every image and every pair (i, j) of class-index maps
  * a[img][i], b[img][j], the per-class pixel counts out[img][i][j][k] = {|a==k & b==k|, |a==k | b==k|}.
  * Replaces the [B,S,S',HW,K] boolean broadcast of `batched_distance` / `iou`
