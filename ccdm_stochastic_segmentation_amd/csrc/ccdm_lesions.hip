@@ -3,25 +3,9 @@
 // overlap thresholds.  The definition in include/ccdm_hip.h is the contract; tests/test_lidc_lesions.py restates it with numpy and
 // holds it against scipy.ndimage.label.
 //
-// Label stage (k_lesions_label), once per (map, class), not per pair: one workgroup of 512 threads, the whole map resident in LDS as
-// one int32 `parent` per pixel (-1 outside the mask), union-find with the smaller index as the root.
-//   1 runs      a wave takes chunks of 64 * NPIX consecutive pixels (NPIX = 4: one dword per lane when W % 4 == 0 and both stacks are
-//               4-byte aligned, so a dword never straddles a row; NPIX = 1: bytes).  A pixel's parent is the first pixel of its
-//               horizontal run inside the chunk: inside the lane from its own bits, across lanes from a ballot of the lanes a run
-//               cannot pass through (a bit clear, or the lane starts a row) and one shuffle of the nearest such lane's value.
-//   2 unions    per mask pixel: with the pixel to the left where a run was cut at a chunk seam; with the row above (the pixel above,
-//               unless the pixel to the left and the one above it are both in the mask: then the left pixel's union covers it; for
-//               8-connectivity the two diagonals where the pixel above is not in the mask).  les_unite: find both roots, LDS
-//               atomicMin of the smaller root into the larger root's parent, again from the displaced parent if the larger one was
-//               a root no more.
-//   3 flatten   every mask pixel's parent becomes its root; the root of a lesion is its smallest pixel index.
-//   4 rank      root flags by ballot per 64 pixels in raster order, one wave's prefix sum over the <= 256 chunk counts: the dense
-//               label of a root is 1 + the roots before it; written into the root's parent as -(label) - 1.
-//   5 write     int32 labels [H][W] to the workspace, the lesion count of the (map, class) behind the planes.
-// INVARIANT: parent[p] <= p for every mask pixel, at all times: step 1 writes a run's first pixel, atomicMin only ever lowers a value,
-// and the value it offers is a root smaller than the pixel it is offered to.  So a find walk strictly decreases and ends after at most
-// H*W reads, and a failed round of les_unite replaces its larger end by a strictly smaller pixel: at most 2*H*W rounds.  No workgroup
-// waits on another; no global atomics.
+// Label stage (k_lesions_label), once per (map, class), not per pair: one workgroup of 512 threads labels the mask by les_label of
+// ccdm_lesions_common.h (union-find in LDS with the smaller index as the root; the steps, the invariant parent[p] <= p and why every
+// loop ends are stated there), leaving int32 labels [H][W] in the workspace and the lesion count of the (map, class) behind the planes.
 // LDS at the limit (H*W = 16384): 16384 parents + 256 chunk counts = 66,560 B: two workgroups per CU.
 //
 // Pair stage (k_lesions_pairs), one workgroup of 256 threads per cell (b, i, j, c).  A pixel has class c in a map iff its label there
@@ -35,158 +19,22 @@
 
 namespace ccdm {
 
-constexpr int LES_THREADS = 512;          // of a label workgroup
-constexpr int LES_WAVES = LES_THREADS / 64;
-
 struct LesOverlaps {
     int T;
     int num[LES_MAX_T], den[LES_MAX_T];
 };
-
-// Another thread may lower the value at any time: never a cached read.
-__device__ __forceinline__ int les_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-
-__device__ __forceinline__ int les_find(const int* parent, int p) {
-    int q = les_load(parent + p);
-    while (q != p) {                                                 // q < p (the invariant): at most H*W steps
-        p = q;
-        q = les_load(parent + p);
-    }
-    return p;
-}
-
-// Joins the lesions of the mask pixels a and b.  A failed round (the larger root had been linked elsewhere meanwhile) goes on from the
-// parent it had, which is smaller: at most 2*H*W rounds.
-__device__ __forceinline__ void les_unite(int* parent, int a, int b) {
-    for (;;) {
-        a = les_find(parent, a);
-        b = les_find(parent, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }
-        const int old = atomicMin(parent + a, b);
-        if (old == a) return;
-        a = old;
-    }
-}
 
 template <int NPIX>
 __global__ __launch_bounds__(LES_THREADS) void k_lesions_label(const uint8_t* __restrict__ samples, const uint8_t* __restrict__ raters, long long nA,
                                                                int C, int c0, int H, int W, int conn8, int32_t* __restrict__ ws,
                                                                int32_t* __restrict__ counts) {
     extern __shared__ int les_lds[];
-    const int HW = H * W, n64 = (HW + 63) / 64;
-    int* parent = les_lds;                                           // [HW]
-    int* cc = les_lds + HW;                                          // [n64]: roots per 64 pixels, then the roots before them
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const size_t mc = blockIdx.x;
     const long long m = (long long)(mc / C);
     const uint32_t c = (uint32_t)(c0 + (int)(mc % C));
+    const size_t HW = (size_t)H * W;
     const uint8_t* map = m < nA ? samples + (size_t)m * HW : raters + (size_t)(m - nA) * HW;
-
-    // 1: runs.  Wave-uniform trip count: every lane stays active for the ballot and the shuffle.
-    constexpr int CH = 64 * NPIX;
-    const int nch = (HW + CH - 1) / CH;
-    for (int k = wave; k < nch; k += LES_WAVES) {
-        const int p0 = (k * 64 + lane) * NPIX;
-        uint32_t bits = 0;
-        if (p0 < HW) {
-            if constexpr (NPIX == 4) {
-                const uint32_t v = *reinterpret_cast<const uint32_t*>(map + p0);
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if ((v >> (8 * j) & 0xFFu) == c) bits |= 1u << j;
-            } else {
-                bits = map[p0] == c ? 1u : 0u;
-            }
-        }
-        const bool row_start = p0 % W == 0;
-        const bool breaker = bits != (1u << NPIX) - 1u || row_start || lane == 0;     // lane 0: a chunk's runs start inside it
-        int loc = p0;                                                // the run that leaves this lane to the right starts here
-#pragma unroll
-        for (int j = 0; j < NPIX; ++j)
-            if (!(bits >> j & 1u)) loc = p0 + j + 1;
-        const unsigned long long lower = __ballot(breaker) & ((1ull << lane) - 1ull);
-        const int from = __shfl(loc, lower ? 63 - __clzll((long long)lower) : 0);
-        int cur = row_start || lane == 0 ? p0 : from;                // a run cut at the chunk seam: step 2 joins it
-        if (p0 < HW) {
-#pragma unroll
-            for (int j = 0; j < NPIX; ++j) {
-                if (bits >> j & 1u) {
-                    parent[p0 + j] = cur;
-                } else {
-                    parent[p0 + j] = -1;
-                    cur = p0 + j + 1;
-                }
-            }
-        }
-    }
-    __syncthreads();
-
-    // 2: unions.  Whether a pixel is in the mask is the sign of its parent, which no union changes.
-    for (int p = threadIdx.x; p < HW; p += LES_THREADS) {
-        if (les_load(parent + p) < 0) continue;
-        const int y = p / W, x = p - y * W;
-        const bool left = x > 0 && les_load(parent + p - 1) >= 0;
-        if (left && p % CH == 0) les_unite(parent, p, p - 1);
-        if (y > 0) {
-            if (les_load(parent + p - W) >= 0) {
-                if (!(left && les_load(parent + p - W - 1) >= 0)) les_unite(parent, p, p - W);
-            } else if (conn8) {
-                if (x > 0 && !left && les_load(parent + p - W - 1) >= 0) les_unite(parent, p, p - W - 1);
-                if (x + 1 < W && les_load(parent + p - W + 1) >= 0) les_unite(parent, p, p - W + 1);
-            }
-        }
-    }
-    __syncthreads();
-
-    // 3: flatten
-    for (int p = threadIdx.x; p < HW; p += LES_THREADS)
-        if (les_load(parent + p) >= 0) parent[p] = les_find(parent, p);
-    __syncthreads();
-
-    // 4: rank the roots in raster order
-    for (int k = wave; k < n64; k += LES_WAVES) {
-        const int p = k * 64 + lane;
-        const unsigned long long roots = __ballot(p < HW && parent[p] == p);
-        if (lane == 0) cc[k] = __popcll(roots);
-    }
-    __syncthreads();
-    if (wave == 0) {
-        const int per = (n64 + 63) / 64;                             // <= 4
-        int s = 0;
-        for (int i = 0; i < per; ++i)
-            if (lane * per + i < n64) s += cc[lane * per + i];
-        int incl = s;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int t = __shfl_up(incl, off);
-            if (lane >= off) incl += t;
-        }
-        int before = incl - s;
-        for (int i = 0; i < per; ++i) {
-            if (lane * per + i < n64) {
-                const int t = cc[lane * per + i];
-                cc[lane * per + i] = before;
-                before += t;
-            }
-        }
-        if (lane == 63) counts[mc] = incl;
-    }
-    __syncthreads();
-    for (int k = wave; k < n64; k += LES_WAVES) {
-        const int p = k * 64 + lane;
-        const bool root = p < HW && parent[p] == p;
-        const unsigned long long roots = __ballot(root);
-        if (root) parent[p] = -(cc[k] + __popcll(roots & ((1ull << lane) - 1ull)) + 1) - 1;
-    }
-    __syncthreads();
-
-    // 5: the dense labels
-    int32_t* out = ws + mc * HW;
-    for (int p = threadIdx.x; p < HW; p += LES_THREADS) {
-        const int v = parent[p];
-        out[p] = v == -1 ? 0 : v < -1 ? -v - 1 : -parent[v] - 1;
-    }
+    les_label<NPIX>(les_lds, map, c, H, W, conn8, ws + mc * HW, counts + mc);
 }
 
 __global__ __launch_bounds__(256) void k_lesions_pairs(const int32_t* __restrict__ ws, const int32_t* __restrict__ counts, int B, int S, int L, int C,
@@ -287,18 +135,17 @@ extern "C" int ccdm_lesions(const uint8_t* samples, const uint8_t* raters, int B
     int32_t* counts = ws + (size_t)planes * HW;
     const bool vec = W % 4 == 0 && ((reinterpret_cast<uintptr_t>(samples) | reinterpret_cast<uintptr_t>(raters)) & 3) == 0;
     const int conn8 = connectivity == 8 ? 1 : 0;
-    const size_t label_lds = ((size_t)HW + (HW + 63) / 64) * sizeof(int);
+    const size_t label_lds = les_label_lds(HW);
     const int nmax = les_max_lesions(HW);
     const size_t pair_lds = (size_t)2 * nmax * sizeof(unsigned);
-    constexpr size_t label_lds_max = ((size_t)LES_MAX_PIXELS + LES_MAX_PIXELS / 64) * sizeof(int);
     constexpr size_t pair_lds_max = (size_t)2 * ((LES_MAX_PIXELS + 1) / 2) * sizeof(unsigned);
     static bool reserved[3] = {false, false, false};
     if (vec) {
-        if (label_lds > 48 * 1024 && les_reserve_lds(k_lesions_label<4>, label_lds_max, &reserved[0], "label") < 0) return -1;
+        if (label_lds > 48 * 1024 && les_reserve_lds(k_lesions_label<4>, LES_LABEL_LDS_MAX, &reserved[0], "label") < 0) return -1;
         hipLaunchKernelGGL(k_lesions_label<4>, dim3((unsigned)planes), dim3(LES_THREADS), label_lds, st, samples, raters, nA, C, c0, H, W, conn8, ws,
                            counts);
     } else {
-        if (label_lds > 48 * 1024 && les_reserve_lds(k_lesions_label<1>, label_lds_max, &reserved[1], "label") < 0) return -1;
+        if (label_lds > 48 * 1024 && les_reserve_lds(k_lesions_label<1>, LES_LABEL_LDS_MAX, &reserved[1], "label") < 0) return -1;
         hipLaunchKernelGGL(k_lesions_label<1>, dim3((unsigned)planes), dim3(LES_THREADS), label_lds, st, samples, raters, nA, C, c0, H, W, conn8, ws,
                            counts);
     }

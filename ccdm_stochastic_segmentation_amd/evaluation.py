@@ -239,6 +239,51 @@ def lesion_min_size(value) -> int:
     return value
 
 
+def detection_min_frequency(value):
+    """`detection_min_frequency`: the share of the samples a pixel needs to belong to a candidate, a decimal in [0, 1] (0.1 when absent);
+    with s samples n_min = max(1, ceil(value * s)), the value read as the decimal it is written as."""
+    from fractions import Fraction
+    try:
+        ok = not isinstance(value, bool) and isinstance(value, (int, float, str)) and 0 <= Fraction(str(value)) <= 1
+    except (ValueError, ZeroDivisionError):
+        ok = False
+    if not ok:
+        raise ValueError(f"detection_min_frequency: {value!r} (expected a share of the samples in [0, 1])")
+    return value
+
+
+def detection_rater_agreement(value, raters: int) -> int:
+    """`detection_rater_agreement` -> m_min, the raters a pixel needs to belong to a reference lesion: `majority` (the default) is
+    raters // 2 + 1, otherwise a whole number in 1..raters."""
+    if value == "majority":
+        return raters // 2 + 1
+    if isinstance(value, bool) or not isinstance(value, int) or not 1 <= value <= raters:
+        raise ValueError(f"detection_rater_agreement: {value!r} (expected 'majority' or a whole number in [1, {raters}])")
+    return value
+
+
+def detection_score(value) -> str:
+    """`detection_score`: the confidence of a candidate, `support` (the samples that draw it; the default) or `peak`."""
+    if value not in M.DETECTION_SCORES:
+        raise ValueError(f"detection_score: {value!r} (expected one of {list(M.DETECTION_SCORES)})")
+    return value
+
+
+def detection_fp_rates(values) -> List[float]:
+    """`detection_fp_rates`: the false positives per image at which the sensitivity is read (1/8 ... 8 when absent), none negative."""
+    values = list(values) if isinstance(values, (list, tuple)) else [values]
+    if not values or any(isinstance(v, bool) or not isinstance(v, (int, float)) or not 0 <= v < float("inf") for v in values):
+        raise ValueError(f"detection_fp_rates: {values!r} (expected at least one number of false positives per image, none negative)")
+    return values
+
+
+def detection_max_candidates(value) -> int:
+    """`detection_max_candidates`: the candidates and reference lesions kept per image and class, 1 to 1024 (64 when absent)."""
+    if isinstance(value, bool) or not isinstance(value, int) or not 1 <= value <= M.FINDINGS_MAX_CANDIDATES:
+        raise ValueError(f"detection_max_candidates: {value!r} (expected a whole number in [1, {M.FINDINGS_MAX_CANDIDATES}])")
+    return value
+
+
 def mode_count(value) -> int:
     """`mode_count`: how many modes the mode summary looks for, 1 to 16 (metrics.MODES_MAX_MODES)."""
     if isinstance(value, bool) or not isinstance(value, int) or not 1 <= value <= M.MODES_MAX_MODES:
@@ -307,6 +352,16 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
                             `output_path` set, also written as lidc_lesion_matching.json
          lesion_match_ious ([0.5, 0.75]): the IoUs a pair has to exceed, in [0.5, 1), each read as the decimal it is written as;
                             lesion_min_size (1): lesions of fewer pixels are dropped; lesion_connectivity as above
+         detection: yes     the result gains "detection": one dict per entry of `evaluations` with FROC, the sensitivity at fixed
+                            false positives per image (and their mean, the LUNA16 CPM) and the average precision of the first s
+                            samples read as one list of lesion candidates per image with a confidence each, against the lesions the
+                            raters agree on (metrics.detection_scores_from_findings; the records from one ccdm_findings call per batch
+                            and entry, kept per image and scored after the last batch); with `output_path` set, also written as
+                            lidc_detection.json
+         detection_min_frequency (0.1): the share of the samples a pixel needs to belong to a candidate;
+                            detection_rater_agreement (majority): the raters a pixel needs to belong to a reference lesion, `majority`
+                            or a whole number; detection_score (support): support or peak; detection_fp_rates ([1/8 ... 8]);
+                            detection_max_candidates (64); lesion_connectivity as above
          modes: yes         the result gains "modes": one dict per entry of `evaluations` with the mode summary of the first s
                             samples (metrics.sample_modes: k-medoids under the GED's own distance, on the device): the mean number
                             of modes found, the mean share of the largest, `ged_summary` (the GED between the raters and the medoids
@@ -373,6 +428,14 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
         match_conn = lesion_connectivity(section)
         match_thresholds = lesion_match_thresholds(section.get("lesion_match_ious", [0.5, 0.75]))
         match_min_size = lesion_min_size(section.get("lesion_min_size", 1))
+    detect = [[] for _ in evaluations] if section.get("detection", False) else None              # per entry: the findings of every batch
+    if detect is not None:
+        detect_conn = lesion_connectivity(section)
+        detect_freq = detection_min_frequency(section.get("detection_min_frequency", 0.1))
+        detect_m_min = detection_rater_agreement(section.get("detection_rater_agreement", "majority"), int(labels0.shape[0]))
+        detect_score = detection_score(section.get("detection_score", "support"))
+        detect_rates = detection_fp_rates(section.get("detection_fp_rates", list(M.DETECTION_FP_RATES)))
+        detect_cap = detection_max_candidates(section.get("detection_max_candidates", 64))
     modes = [[] for _ in evaluations] if section.get("modes", False) else None                   # per entry: the scores of every batch
     if modes is not None:
         modes_count = mode_count(section.get("mode_count", 4))
@@ -414,6 +477,9 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
             if match is not None:
                 match[i].append(M.lesion_match_stats(pred_idx[:, :s], lab_idx, num_classes, connectivity=match_conn,
                                                      thresholds=match_thresholds, min_size=match_min_size))
+            if detect is not None:
+                detect[i].append(M.sample_findings(pred_idx[:, :s], lab_idx, num_classes, n_min=max(1, M._ceil_fraction(detect_freq, s)),
+                                                   m_min=detect_m_min, connectivity=detect_conn, max_candidates=detect_cap))
             if modes is not None:
                 modes[i].append(mode_summary_scores(pred_idx[:, :s], lab_idx, num_classes, modes_count, modes_swaps))
         # log-mean vote exactly as the reference takes it (:125): log(0) = -inf stays -inf (one-hot "majority" predictions:
@@ -484,6 +550,19 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
             os.makedirs(out_dir, exist_ok=True)
             with open(os.path.join(out_dir, "lidc_lesion_matching.json"), "w") as f:
                 json.dump(res["lesion_matching"], f, indent=1)
+    if detect is not None:
+        res["detection"] = [M.detection_scores_from_findings(M.concat_findings(parts), score=detect_score, fp_rates=detect_rates)
+                            for parts in detect]
+        for s, r in zip(evaluations, res["detection"]):
+            LOGGER.info("detection (%d): CPM %s  AP %s by %s, candidates from %d of %d samples  (%d candidates, %d reference lesions)", s,
+                        r["cpm"], r["average_precision"], r["score"], r["n_min"], s, sum(c["candidates"] for c in r["per_class"]),
+                        sum(c["reference_lesions"] for c in r["per_class"]))
+        if params.get("output_path") and rank == 0:
+            import json
+            out_dir = expanduservars(params["output_path"])
+            os.makedirs(out_dir, exist_ok=True)
+            with open(os.path.join(out_dir, "lidc_detection.json"), "w") as f:
+                json.dump(res["detection"], f, indent=1)
     if modes is not None:
         res["modes"] = []
         for s, parts in zip(evaluations, modes):

@@ -22,6 +22,10 @@ And the lesion-level scores: `lesion_stats` (HIP kernel ccdm_lesions: connected-
 pairs and the fixed-point sum of their IoUs per threshold), `lesion_match_scores_from_stats` derives panoptic, segmentation and
 recognition quality on the host.
 
+And the lesion findings of the sample SET: `sample_findings` (HIP kernel ccdm_findings: per image and class the connected components of
+the pixels enough samples mark, each with the number of samples that draw it, and the components the raters agree on),
+`detection_scores_from_findings` derives FROC, the sensitivity at fixed false positives per image (CPM) and average precision on the host.
+
 And the mode summary of the samples themselves: `sample_modes` (HIP kernels ccdm_modes_distance, ccdm_modes_pam, ccdm_modes_maps:
 the pairwise fixed-point distance among the S samples of an image, k-medoids on it, per-mode vote and entropy maps) says which
 distinct segmentations the samples propose and which share of the samples each holds; everything stays on the device."""
@@ -508,8 +512,186 @@ def lesion_match_scores_from_stats(stats: Dict[str, object], *, class_names: Opt
     return res
 
 
+# ------------------------------------------------------------------------------------------------ findings of the sample set
+FINDING_CANDIDATE_FIELDS = ("size", "support", "peak", "mass", "ref_cov", "rater_hits", "ymin", "xmin", "ymax", "xmax", "sum_y", "sum_x")
+FINDING_REFERENCE_FIELDS = ("size", "cov", "best_support", "best_peak")
+FINDING_ARRAYS = ("counts", "candidates", "references")
+FINDING_SETTINGS = ("samples", "raters", "n_min", "m_min", "connectivity", "classes", "max_candidates")
+FINDINGS_MAX_CANDIDATES = 1024            # ccdm_findings' cap: what one workgroup's LDS tables hold
+DETECTION_SCORES = ("support", "peak")
+DETECTION_FP_RATES = (1 / 8, 1 / 4, 1 / 2, 1, 2, 4, 8)      # false positives per image of the LUNA16 score
+
+
+def sample_findings(samples_idx: torch.Tensor, raters_idx: Optional[torch.Tensor], num_classes: int, *, n_min: int, m_min: Optional[int] = None,
+                    connectivity: int = 8, max_candidates: int = 64, return_map: bool = False) -> Dict[str, object]:
+    """The lesions the S samples of an image propose TOGETHER, and how sure the set is of each (HIP kernel ccdm_findings; the
+    definition is in include/ccdm_hip.h).  samples_idx [B,S,H,W], raters_idx [B,L,H,W] or None: integer class maps on the GPU.  Per
+    image and scored class (1..K-1; class 0 when K == 1: C of them) the candidates are the connected components, under `connectivity`,
+    of the pixels that at least `n_min` samples give the class; the reference lesions those of the pixels at least `m_min` raters give
+    it (default: a majority, L // 2 + 1).  Both are numbered in raster order of their first pixel.  Returns, on the host as int64:
+      counts      [B,C,2]    the candidates and the reference lesions
+      candidates  [B,C,max_candidates,12]  per candidate FINDING_CANDIDATE_FIELDS: size; support (the samples with a pixel of the
+                             class inside it); peak, mass (the maximum and the sum of the per-pixel sample counts); ref_cov (its pixels
+                             inside a reference lesion); rater_hits (the raters with a pixel of the class inside it); the bounding
+                             box; the coordinate sums (centroid = sum / size).  Rows from the count on are zero.
+      references  [B,C,max_candidates,4]   per reference lesion FINDING_REFERENCE_FIELDS: size; cov (its pixels inside a candidate);
+                             best_support, best_peak (the maxima over the candidates that touch it, 0: none does)
+    and the settings "samples", "raters", "n_min", "m_min" (None without raters), "connectivity", "classes", "max_candidates".
+    return_map: also "confidence_map", uint8 [B,C,H,W] ON THE DEVICE: the support of the candidate that holds the pixel, 0 outside.
+    An (image, class) with more candidates or reference lesions than `max_candidates` (at most 1024) raises, naming the value needed."""
+    if not isinstance(samples_idx, torch.Tensor) or (raters_idx is not None and not isinstance(raters_idx, torch.Tensor)):
+        raise ValueError("sample_findings: expected tensors [B,S,H,W] and [B,L,H,W] (or None)")
+    if samples_idx.device.type != "cuda" or (raters_idx is not None and raters_idx.device.type != "cuda"):
+        raise hip.CcdmHipError("sample_findings needs GPU tensors (no CPU path)")
+    if samples_idx.dim() != 4 or (raters_idx is not None and (raters_idx.dim() != 4 or raters_idx.shape[0] != samples_idx.shape[0]
+                                                              or raters_idx.shape[2:] != samples_idx.shape[2:])):
+        raise ValueError(f"sample_findings: {tuple(samples_idx.shape)} / {None if raters_idx is None else tuple(raters_idx.shape)} "
+                         "(expected [B,S,H,W] and [B,L,H,W] or None)")
+    B, S, H, W = (int(v) for v in samples_idx.shape)
+    L = 0 if raters_idx is None else int(raters_idx.shape[1])
+    if raters_idx is not None and L == 0:
+        raise ValueError("sample_findings: raters_idx holds no rater (pass None)")
+    n_min = whole_number(n_min, "n_min", 1, None, "expected a whole number of samples, at least 1")
+    if L == 0:
+        m_min = None
+    else:
+        m_min = L // 2 + 1 if m_min is None else whole_number(m_min, "m_min", 1, None, "expected a whole number of raters, at least 1")
+    cap = whole_number(max_candidates, "max_candidates", 1, None, "expected a whole number, at least 1")
+    lib = hip.load()
+    s8 = samples_idx.to(torch.uint8).contiguous()
+    r8 = None if raters_idx is None else raters_idx.to(device=s8.device, dtype=torch.uint8).contiguous()
+    classes = list(range(1, num_classes)) if num_classes > 1 else [0]
+    Cn = len(classes)
+    dev = s8.device
+    counts = torch.zeros((B, Cn, 2), dtype=torch.int32, device=dev)
+    cand = torch.zeros((B, Cn, cap, len(FINDING_CANDIDATE_FIELDS)), dtype=torch.int32, device=dev)
+    ref = torch.zeros((B, Cn, cap, len(FINDING_REFERENCE_FIELDS)), dtype=torch.int32, device=dev)
+    conf = torch.zeros((B, Cn, H, W), dtype=torch.uint8, device=dev) if return_map else None
+    need = int(lib.ccdm_findings_workspace_bytes(B, S, L, H, W, num_classes, cap))
+    ws = torch.empty((max(need, 4) + 3) // 4, dtype=torch.int32, device=dev)
+    hip.check(lib.ccdm_findings(s8.data_ptr(), None if r8 is None else r8.data_ptr(), B, S, L, H, W, num_classes, int(connectivity), n_min,
+                                0 if m_min is None else m_min, cap, counts.data_ptr(), cand.data_ptr(), ref.data_ptr(),
+                                None if conf is None else conf.data_ptr(), ws.data_ptr(), need, torch.cuda.current_stream(dev).cuda_stream),
+              "findings")
+    n = counts.cpu().numpy().astype(np.int64)
+    if n.size and int(n.max()) > cap:
+        b, ci, side = (int(v) for v in np.unravel_index(int(n.argmax()), n.shape))
+        raise hip.CcdmHipError(f"sample_findings: image {b}, class {classes[ci]} has {int(n[b, ci, side])} "
+                               f"{'candidates' if side == 0 else 'reference lesions'}, max_candidates={cap} holds {cap}: "
+                               f"max_candidates={int(n.max())} needed")
+    out: Dict[str, object] = {"counts": n, "candidates": cand.cpu().numpy().astype(np.int64), "references": ref.cpu().numpy().astype(np.int64),
+                              "samples": S, "raters": L, "n_min": n_min, "m_min": m_min, "connectivity": int(connectivity), "classes": classes,
+                              "max_candidates": cap}
+    if conf is not None:
+        out["confidence_map"] = conf
+    return out
+
+
+def concat_findings(parts: Sequence[Dict[str, object]]) -> Dict[str, object]:
+    """The findings of several batches as one (concatenated along the images); the settings have to agree.  No confidence map."""
+    if not parts:
+        raise ValueError("concat_findings: no part")
+    for p in parts[1:]:
+        differ = [k for k in FINDING_SETTINGS if p[k] != parts[0][k]]
+        if differ:
+            raise ValueError(f"concat_findings: the parts differ in {differ}")
+    out: Dict[str, object] = {k: np.concatenate([np.asarray(p[k]) for p in parts]) for k in FINDING_ARRAYS}
+    out.update({k: (list(parts[0][k]) if k == "classes" else parts[0][k]) for k in FINDING_SETTINGS})
+    return out
+
+
+def detection_scores_from_findings(findings: Dict[str, object], *, score: str = "support", fp_rates: Sequence[float] = DETECTION_FP_RATES,
+                                   class_names: Optional[Sequence[str]] = None) -> Dict[str, object]:
+    """FROC, the sensitivity at fixed false positives per image and the average precision of the sample set as a lesion detector, from
+    the records of `sample_findings` (with raters), on the host in Python integers and Fractions until the last division (no GPU).
+    Per scored class, pooled over the images: a candidate's confidence is its `score` (support or peak), it is TRUE iff ref_cov >= 1;
+    a reference lesion is detected at a threshold iff its best_<score> reaches it.  With theta = S, S-1, ..., n_min:
+      FP(theta), TPc(theta)  the false / true candidates with score >= theta;  det(theta) the reference lesions with best >= theta
+      sensitivity = det / N_ref (None when the class has no reference lesion), fp_per_image = FP / images,
+      precision = TPc / (TPc + FP) (None where no candidate reaches theta)
+    per class ("per_class", one dict each):
+      froc               {"thresholds", "fp_per_image", "sensitivity", "precision"}: the curve, one entry per theta
+      sensitivity_at_fp  per entry of fp_rates the largest sensitivity among the thresholds with fp_per_image <= the rate (no
+                         interpolation; the empty threshold above S always qualifies, with 0);  cpm: their mean (the LUNA16 score)
+      average_precision  sum over descending theta of (R_i - R_(i-1)) * P_i with the lesion recall R = sensitivity, R_0 = 0
+      candidates, true_candidates, reference_lesions, images_without_reference
+    and over the classes that have a reference lesion the means "cpm" and "average_precision" (None: no class has one).  The result
+    holds lists, numbers, strings and None only: it survives a JSON round trip."""
+    if score not in DETECTION_SCORES:
+        raise ValueError(f"score: {score!r} (expected one of {DETECTION_SCORES})")
+    counts, cand, ref = (np.asarray(findings[k]).astype(np.int64) for k in FINDING_ARRAYS)
+    if counts.ndim != 3 or counts.shape[2] != 2:
+        raise ValueError(f"counts {counts.shape}: expected [B,C,2]")
+    B, Cn = int(counts.shape[0]), int(counts.shape[1])
+    if cand.ndim != 4 or cand.shape[:2] != (B, Cn) or cand.shape[3] != len(FINDING_CANDIDATE_FIELDS):
+        raise ValueError(f"candidates {cand.shape}: expected [{B},{Cn},cap,{len(FINDING_CANDIDATE_FIELDS)}]")
+    if ref.ndim != 4 or ref.shape[:2] != (B, Cn) or ref.shape[3] != len(FINDING_REFERENCE_FIELDS):
+        raise ValueError(f"references {ref.shape}: expected [{B},{Cn},cap,{len(FINDING_REFERENCE_FIELDS)}]")
+    if B < 1:
+        raise ValueError("detection_scores_from_findings: the findings hold no image")
+    if int(counts[..., 0].max()) > cand.shape[2] or int(counts[..., 1].max()) > ref.shape[2]:
+        raise ValueError(f"counts: up to {int(counts.max())} records, the arrays hold {cand.shape[2]} / {ref.shape[2]}")
+    S, L, n_min = int(findings["samples"]), int(findings["raters"]), int(findings["n_min"])
+    if L < 1:
+        raise ValueError("detection_scores_from_findings: findings without raters have no reference lesions to score against")
+    if not 1 <= n_min <= S:
+        raise ValueError(f"n_min: {n_min} outside [1, samples={S}]")
+    classes = [int(c) for c in findings["classes"]]
+    if len(classes) != Cn:
+        raise ValueError(f"classes: {len(classes)} entries for {Cn} scored classes")
+    if class_names is not None and len(class_names) != Cn:
+        raise ValueError(f"class_names: {len(class_names)} names for {Cn} scored classes")
+    try:
+        rates = [Fraction(str(r)) for r in fp_rates]
+    except (ValueError, ZeroDivisionError, TypeError):
+        rates = []
+    if not rates or any(isinstance(r, bool) for r in fp_rates) or any(r < 0 for r in rates):
+        raise ValueError(f"fp_rates: {fp_rates!r} (expected at least one rate of false positives per image, none negative)")
+    cand_field = FINDING_CANDIDATE_FIELDS.index(score)
+    ref_field = FINDING_REFERENCE_FIELDS.index("best_" + score)
+    ref_cov = FINDING_CANDIDATE_FIELDS.index("ref_cov")
+    thresholds = list(range(S, n_min - 1, -1))
+    ratio = lambda f: None if f is None else float(f)
+    per_class = []
+    for ci in range(Cn):
+        true_scores, false_scores, best = [], [], []
+        for b in range(B):
+            for rec in cand[b, ci, :int(counts[b, ci, 0])].tolist():
+                (true_scores if rec[ref_cov] >= 1 else false_scores).append(rec[cand_field])
+            best += [rec[ref_field] for rec in ref[b, ci, :int(counts[b, ci, 1])].tolist()]
+        n_ref = len(best)
+        fp = [sum(1 for v in false_scores if v >= t) for t in thresholds]
+        tp = [sum(1 for v in true_scores if v >= t) for t in thresholds]
+        det = [sum(1 for v in best if v >= t) for t in thresholds]
+        sens = [Fraction(d, n_ref) if n_ref else None for d in det]
+        prec = [Fraction(t, t + f) if t + f else None for t, f in zip(tp, fp)]
+        at_rate, ap = None, None
+        if n_ref:
+            at_rate = [max([Fraction(0)] + [s for s, f in zip(sens, fp) if Fraction(f, B) <= r]) for r in rates]
+            ap, before = Fraction(0), Fraction(0)
+            for s, p in zip(sens, prec):
+                if s > before:                                        # a lesion found at this threshold: a true candidate reaches it
+                    ap += (s - before) * p
+                before = s
+        per_class.append({"class": classes[ci], "candidates": len(true_scores) + len(false_scores), "true_candidates": len(true_scores),
+                          "reference_lesions": n_ref, "images_without_reference": int((counts[:, ci, 1] == 0).sum()),
+                          "froc": {"thresholds": thresholds, "fp_per_image": [float(Fraction(f, B)) for f in fp],
+                                   "sensitivity": [ratio(s) for s in sens], "precision": [ratio(p) for p in prec]},
+                          "sensitivity_at_fp": None if at_rate is None else [float(s) for s in at_rate],
+                          "cpm": None if at_rate is None else float(sum(at_rate) / len(at_rate)), "average_precision": ratio(ap)})
+    defined = [r for r in per_class if r["reference_lesions"]]
+    res: Dict[str, object] = {"images": B, "samples": S, "raters": L, "n_min": n_min, "m_min": findings["m_min"],
+                              "connectivity": int(findings["connectivity"]), "classes": classes, "score": score,
+                              "fp_rates": [float(r) for r in rates], "per_class": per_class,
+                              "cpm": float(np.mean([r["cpm"] for r in defined])) if defined else None,
+                              "average_precision": float(np.mean([r["average_precision"] for r in defined])) if defined else None}
+    if class_names is not None:
+        res["class_names"] = [str(c) for c in class_names]
+    return res
+
+
 # ------------------------------------------------------------------------------------------------ mode summary
-MODE_MAPS = ("vote", "entropy", "counts")
+MODE_MAPS =("vote", "entropy", "counts")
 MODES_MAX_CLASSES, MODES_MAX_SAMPLES, MODES_MAX_MODES = 32, 256, 16
 MODE_DISTANCE_ONE = 1 << 20               # Q counts the Jaccard distance of a class in units of 2^-20
 MODE_UNUSED = 255                         # mode_map / mode_vote of a mode that does not exist

@@ -1152,6 +1152,42 @@ class DenoisingModel(nn.Module):
                 out[m] = cast(Tensor, got[m])
         return out
 
+    def _sample_class_maps(self, condition: Tensor, feature_condition: Optional[Tensor], S: int, x: Optional[Tensor], t: Optional[Tensor],
+                           known_labels, resample, evidence, temperature, truncation, views, tiles) -> Tensor:
+        """One sampling call of B*S samples (condition repeat-interleaved, sample b*S + s = sample s of image b), every pass ending in its
+        argmax class ("majority"), the class maps read straight from the engine -> uint8 [B,S,H,W] on the model's device.  What
+        predict_modes and predict_findings sample; `philox_call` advances as for one call."""
+        K = self.diffusion.num_classes
+        if condition.ndim != 4:
+            raise ValueError(f"condition: expected [B,C,H,W], got {tuple(condition.shape)}")
+        B, H, W = int(condition.shape[0]), int(condition.shape[2]), int(condition.shape[3])
+        HW = H * W
+        if x is not None and tuple(x.shape) != (S, B, K, H, W):
+            raise ValueError(f"x: expected one-hot x_T of shape {(S, B, K, H, W)} = [S,B,K,H,W], got {tuple(x.shape)}")
+        init_t = None if t is None else int(t.item() if isinstance(t, Tensor) else t)
+        guide = self._check_guidance(known_labels, resample, evidence, (B, K, H, W), temperature, truncation, views, feature_condition, tiles)
+        dev = next(self.unet.parameters()).device
+        xr = x.transpose(0, 1).reshape(B * S, K, H, W) if x is not None else \
+            OneHotCategoricalBCHW(logits=torch.zeros((B * S, K, H, W), device=condition.device)).sample()
+        cond = condition.repeat_interleave(S, dim=0)
+        # (with views or tiles on a model that takes features: [V,B,...] / [R,B,...], the samples on dim 1)
+        fc_dim = 1 if ((guide.views is not None or guide.tiles is not None) and feature_condition is not None
+                       and feature_condition.ndim == 5) else 0
+        fc = feature_condition.repeat_interleave(S, dim=fc_dim) if feature_condition is not None else None
+        stack = torch.empty((B * S, HW), dtype=torch.uint8, device=dev)
+
+        def consume(eng, lo: int, hi: int) -> None:
+            # (the first hi - lo rows: with views the engine holds V times as many, view 0 first)
+            stack[lo:hi].copy_(eng.xt.reshape(-1, HW)[:hi - lo])
+
+        saved = self.step_T_sample
+        self.step_T_sample = "majority"
+        try:
+            self._sample(xr, cond, fc, init_t, None, consume, guide.repeat_interleave(S))
+        finally:
+            self.step_T_sample = saved
+        return stack.reshape(B, S, H, W)
+
     @torch.no_grad()
     def predict_modes(self, condition: Tensor, feature_condition: Optional[Tensor] = None, *, num_evaluations: int, modes: int,
                       x: Optional[Tensor] = None, t: Optional[Tensor] = None, max_swaps: int = 64,
@@ -1188,38 +1224,55 @@ class DenoisingModel(nn.Module):
         bad = [m for m in maps if m not in MT.MODE_MAPS]
         if bad:
             raise ValueError(f"maps: {bad} not available (choose from {MT.MODE_MAPS})")
-        if condition.ndim != 4:
-            raise ValueError(f"condition: expected [B,C,H,W], got {tuple(condition.shape)}")
-        B, H, W = int(condition.shape[0]), int(condition.shape[2]), int(condition.shape[3])
-        HW = H * W
-        if x is not None and tuple(x.shape) != (S, B, K, H, W):
-            raise ValueError(f"x: expected one-hot x_T of shape {(S, B, K, H, W)} = [S,B,K,H,W], got {tuple(x.shape)}")
-        init_t = None if t is None else int(t.item() if isinstance(t, Tensor) else t)
-        guide = self._check_guidance(known_labels, resample, evidence, (B, K, H, W), temperature, truncation, views, feature_condition, tiles)
-        dev = next(self.unet.parameters()).device
-        xr = x.transpose(0, 1).reshape(B * S, K, H, W) if x is not None else \
-            OneHotCategoricalBCHW(logits=torch.zeros((B * S, K, H, W), device=condition.device)).sample()
-        cond = condition.repeat_interleave(S, dim=0)
-        # (with views or tiles on a model that takes features: [V,B,...] / [R,B,...], the samples on dim 1)
-        fc_dim = 1 if ((guide.views is not None or guide.tiles is not None) and feature_condition is not None
-                       and feature_condition.ndim == 5) else 0
-        fc = feature_condition.repeat_interleave(S, dim=fc_dim) if feature_condition is not None else None
-        stack = torch.empty((B * S, HW), dtype=torch.uint8, device=dev)
-
-        def consume(eng, lo: int, hi: int) -> None:
-            # (the first hi - lo rows: with views the engine holds V times as many, view 0 first)
-            stack[lo:hi].copy_(eng.xt.reshape(-1, HW)[:hi - lo])
-
-        saved = self.step_T_sample
-        self.step_T_sample = "majority"
-        try:
-            self._sample(xr, cond, fc, init_t, None, consume, guide.repeat_interleave(S))
-        finally:
-            self.step_T_sample = saved
-        samples = stack.reshape(B, S, H, W)
+        samples = self._sample_class_maps(condition, feature_condition, S, x, t, known_labels, resample, evidence, temperature, truncation, views,
+                                          tiles)
         out = MT.sample_modes(samples, K, modes, max_swaps=max_swaps, maps=maps)
         out["samples"] = samples
         return out
+
+    @torch.no_grad()
+    def predict_findings(self, condition: Tensor, feature_condition: Optional[Tensor] = None, *, num_evaluations: int,
+                         min_frequency: float = 0.1, connectivity: int = 8, max_candidates: int = 64,
+                         x: Optional[Tensor] = None, t: Optional[Tensor] = None,
+                         known_labels: Optional[Tensor] = None, resample: Optional[Tuple[int, int]] = None,
+                         evidence: Optional[Tensor] = None, temperature: Optional[float] = None,
+                         truncation: Optional[float] = None, views: Optional[Sequence[str]] = None,
+                         tiles: Optional[Sequence[int]] = None) -> Dict[str, Any]:
+        """S = `num_evaluations` samples of every image of `condition` [B,C,H,W], read as ONE list of lesions per image and class with
+        a confidence each: a structure that 90 of 100 samples draw is a finding, one that 12 draw a hypothesis, where predict_multiple
+        folds the samples per pixel and loses which structure a pixel belongs to.
+
+        One sampling call of B*S samples laid out as predict_modes lays them out, every pass ending in its argmax class ("majority");
+        the class maps are read straight from the engine into a uint8 stack and handed to metrics.sample_findings without raters:
+        the candidates are the connected components (under `connectivity`) of the pixels that at least n_min = max(1,
+        ceil(min_frequency * S)) samples give the class, `min_frequency` read as the decimal it is written as (include/ccdm_hip.h has
+        the definition).  `philox_call` advances as for one call.  1 <= K <= 32, 1 <= S <= 255, H*W <= 16384.
+        x: optional one-hot x_T [S,B,K,H,W]; default: drawn as predict_multiple draws it.  t: as in forward.
+        max_candidates: the records kept per image and class (at most 1024); an image with more raises, naming the value needed.
+        known_labels, resample, evidence, temperature, truncation, views, tiles: as in predict_multiple, for every sample.
+        Returns `counts` int64 [B,C,2] and `candidates` int64 [B,C,max_candidates,12] on the host (metrics.FINDING_CANDIDATE_FIELDS:
+        size, support, peak, mass, ..., the box, the coordinate sums), `confidence_map` uint8 [B,C,H,W] (the support of the candidate
+        that holds the pixel, 0 outside) and `samples` uint8 [B,S,H,W] on the model's device, and `n_min`, `classes`."""
+        from . import metrics as MT
+        if isinstance(num_evaluations, bool) or int(num_evaluations) != num_evaluations or not 1 <= int(num_evaluations) <= 255:
+            raise ValueError(f"num_evaluations: {num_evaluations!r} (expected an integer in [1, 255])")
+        S = int(num_evaluations)
+        K = self.diffusion.num_classes
+        if isinstance(min_frequency, bool) or not isinstance(min_frequency, (int, float)) or not 0 <= min_frequency <= 1:
+            raise ValueError(f"min_frequency: {min_frequency!r} (expected a share of the samples in [0, 1])")
+        n_min = max(1, MT._ceil_fraction(min_frequency, S))
+        if connectivity not in (4, 8):
+            raise ValueError(f"connectivity: {connectivity!r} (expected 4 or 8)")
+        MT.whole_number(max_candidates, "max_candidates", 1, MT.FINDINGS_MAX_CANDIDATES,
+                        f"expected a whole number in [1, {MT.FINDINGS_MAX_CANDIDATES}]")
+        MT.whole_number(K, "num_classes", 1, 32, "predict_findings: expected a model of 1 to 32 classes")
+        if condition.ndim == 4 and int(condition.shape[2]) * int(condition.shape[3]) > 16384:
+            raise ValueError(f"condition: {tuple(condition.shape)} (predict_findings: maps of at most 16384 pixels)")
+        samples =self._sample_class_maps(condition, feature_condition, S, x, t, known_labels, resample, evidence, temperature, truncation, views,
+                                          tiles)
+        got = MT.sample_findings(samples, None, K, n_min=n_min, connectivity=connectivity, max_candidates=max_candidates, return_map=True)
+        return {"counts": got["counts"], "candidates": got["candidates"], "confidence_map": got["confidence_map"], "samples": samples,
+                "n_min": n_min, "classes": got["classes"]}
 
     # ------------------------------------------------------------------ likelihood bound of held-out labels
     BOUND_LOG_FLOOR = 1e-12             # the trainer's clamp under the logarithm (trainer.py:267)

@@ -705,6 +705,51 @@ int ccdm_lesion_match(int B, int S, int L, int H, int W, int K, const int32_t* t
                       size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * LIDC lesion findings of the sample set, device part (beyond the reference): which lesions the S samples of an image propose
+ * together and how sure the set is of each, and which lesions the raters agree on: the integers behind FROC, the sensitivity at
+ * fixed false positives per image and the average precision of the model as a lesion detector.
+ * Inputs: samples uint8 [B,S,H,W]; raters uint8 [B,L,H,W], or NULL with L = 0; device class maps as they lie in memory; K classes;
+ * connectivity 4 or 8 (as in ccdm_lesions); integers n_min in 1..S and m_min in 1..L (m_min is ignored when L = 0); cap >= 1.  The
+ * scored classes are those of ccdm_lesions: 1..K-1, or class 0 when K == 1: C of them.  A byte >= K belongs to no class.
+ * Per image b and scored class c: n(p) = the samples with class c at pixel p, m(p) = the raters with class c at p.  Candidate mask
+ * A = {p : n(p) >= n_min}, reference mask R = {p : m(p) >= m_min} (empty when L = 0).  CANDIDATES are the connected components of A,
+ * REFERENCE LESIONS those of R, both numbered 1.. in raster order of their first pixel (scipy.ndimage.label's order under the
+ * connectivity).
+ *   counts  int32 [B][C][2] = {n_cand, n_ref}: always the true counts.
+ *   cand    int32 [B][C][cap][12], record i-1 for candidate i = {size, support, peak, mass, ref_cov, rater_hits, ymin, xmin, ymax,
+ *           xmax, sum_y, sum_x}: size its pixels; support the samples that have at least one class-c pixel inside it; peak the
+ *           maximum and mass the sum of n(p) over its pixels; ref_cov its pixels that lie in R; rater_hits the raters that have a
+ *           class-c pixel inside it; then its bounding box (inclusive) and the sums of its pixels' coordinates (the centroid is
+ *           sum / size).  support >= peak >= n_min.
+ *   ref     int32 [B][C][cap][4], record i-1 for reference lesion i = {size, cov, best_support, best_peak}: cov its pixels that lie
+ *           in A; best_support and best_peak the maximum of support and of peak over the candidates that share at least one pixel
+ *           with it, 0 if none does.
+ *           Rows at or beyond the count are zeros; every element of counts, cand and ref is written: OVERWRITTEN per call.  When a
+ *           count exceeds cap, the records of that (image, class) on that side and the values derived from them (best_*, conf_map)
+ *           are not defined; nothing outside the arrays is touched.
+ *   conf_map  optional (may be NULL) uint8 [B][C][H][W]: the support of the candidate that holds the pixel, 0 outside A.
+ * Workspace (device, 4-byte aligned, ccdm_findings_workspace_bytes(B,S,L,H,W,K,cap) = B*C*(11*H*W + G*cap) bytes with
+ * G = ceil(S/8) + ceil(L/8)): the label planes int32 [B][C][2][H][W] (candidates, then reference lesions; 0 outside the mask), then
+ * n uint8 [B][C][H][W], then the two masks uint8 [B][C][2][H][W] (all valid after the call), then per candidate one byte per group of
+ * 8 samples and of 8 raters uint8 [B][C][G][cap]: bit s of group g says that map 8g + s has the class inside the candidate.
+ * Limits, checked before anything is launched or read, each refusal naming the argument: 1 <= K <= 32, 1 <= S <= 255,
+ * 0 <= L <= 255, H, W >= 1 and H*W <= 16384, connectivity in {4, 8}, 1 <= n_min <= S, 1 <= m_min <= L unless L = 0,
+ * 1 <= cap <= 1024 (a candidate and a reference record take 16 words of LDS together: 1024 of them are the 64 KB that leave room
+ * for two workgroups per CU), raters NULL exactly when L = 0, B >= 0.  Any alignment of the stacks is accepted: one dword per lane
+ * when W % 4 == 0 and both pointers are 4-byte aligned, bytes otherwise.  Four kernels on `stream`: counting (n and the masks); the
+ * union-find labelling of ccdm_lesions on the two masks, one workgroup per (image, class, mask); the samples and raters inside every
+ * candidate as bitsets, one workgroup per (image, class, group of 8 maps), LDS atomicOr; then one workgroup per (image, class) builds
+ * the records in LDS with integer atomics.
+ * Integers only, exact in any order: two identical calls are bit-identical.  B = 0 returns 0 without a launch and leaves the
+ * outputs as they are.
+ * ------------------------------------------------------------------------------------------------- */
+size_t ccdm_findings_workspace_bytes(int B, int S, int L, int H, int W, int K, int cap);
+int ccdm_findings(const uint8_t* samples /*dev [B,S,H,W]*/, const uint8_t* raters /*dev [B,L,H,W] or NULL*/, int B, int S, int L, int H,
+                  int W, int K, int connectivity, int n_min, int m_min, int cap, int32_t* counts /*dev [B][C][2]*/,
+                  int32_t* cand /*dev [B][C][cap][12]*/, int32_t* ref /*dev [B][C][cap][4]*/, uint8_t* conf_map /*dev [B][C][H][W] or NULL*/,
+                  void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Segmentation evaluation, device part (Cityscapes mIoU): the reference Evaluator's `infer_step` / `update_cm`
  * (evaluation/eval_cdm.py) in one pass, without a full-resolution probability tensor.  Per output pixel of [B,H,W]:
  *   - bilinear sample of the prediction [B,h,w] as ATen's upsample_bilinear2d (align_corners=False, no antialias) in fp32:
