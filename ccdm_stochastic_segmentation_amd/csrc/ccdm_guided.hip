@@ -20,7 +20,9 @@
 //   slots     (serving.SamplingQueue, ccdm_slots_step; nothing reshaped) continuous batching: every engine row is a slot that holds a
 //             sample of some request at its own place in its own walk, so what the other entries take as uniform launch arguments —
 //             coefficients, mode, step row, key, sample index — comes per row from a device table.
-// THE definitions: include/ccdm_hip.h.  THREE kernel pairs — one thread per pixel up to KP = 4, staged through LDS above — on the shared
+//   guided slots  (SamplingQueue(..., guided=True), ccdm_slots_guided_step) the slots with each request's own evidence, shaping and
+//             known labels: a second table and two slot-indexed pools, and the clamp at the known pixels in the same launch.
+// THE definitions: include/ccdm_hip.h.  FOUR kernel pairs — one thread per pixel up to KP = 4, staged through LDS above — on the shared
 // arithmetic (posterior_pixel_core, shape_row / shape_lds_row, stage_class_rows, store_onehot_rows, load_pixel_row) and ONE launch
 // prologue on the host (launch_step) behind each launcher's own geometry checks:
 //   k_guided / k_guided_staged  VIEWS = false is ccdm_shaped_step and, at (1, 1) with the evidence required, ccdm_evidence_step (a kernel
@@ -30,6 +32,8 @@
 //             loop over at most four.  Not one kernel with the views: their map is a bijection with a contiguous identity view (view 0
 //             staged in 16-byte pieces, store_onehot_rows for it, all V - 1 index rows in LDS at once); the tiles' is neither.
 //   k_slots / k_slots_staged    ccdm_slots_step.
+//   k_slots_guided / k_slots_guided_staged    ccdm_slots_guided_step.  Not one kernel with the plain slots: a plain queue launches
+//             the kernel it always launched.
 // The staged passes stay written out per kernel: as shared helpers they measured 1 - 2 % slower at K = 20 (profiles/guided_passes_refactor_isa.txt).
 //
 // Shaped for HBM: per pixel 4 K V + 1 bytes in (+ 4 K of evidence), V bytes out (+ 4 K V where xin, 4 K where out_probs is written);
@@ -87,7 +91,8 @@ __device__ __forceinline__ unsigned view_index(const guided_args& g, const int N
     return ((unsigned)v * (unsigned)N + n) * (unsigned)(g.H * g.W) + y * (unsigned)g.W + x;
 }
 
-// p[0 .. K) = the K floats of pixel `at` of src — times those of the same pixel of wsrc, where wsrc is not null (uniform) —, p[k >= K] = 0.
+// p[0 .. K) = the K floats of pixel `at` of src — times those of the same pixel of wsrc, where wsrc is not null (uniform; per slot in
+// k_slots_guided) —, p[k >= K] = 0.
 // vec: K == KP and the rows KP * 4-byte aligned (the launcher checks)
 template <int KP>
 __device__ __forceinline__ void load_pixel_row(float (&p)[KP], const float* const src, const size_t at, const float* const wsrc, const int K,
@@ -531,6 +536,105 @@ __global__ __launch_bounds__(BLK) void k_slots_staged(const ccdm_post_args a_in,
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
+// Guided slots (ccdm_slots_guided_step): the slot step with every slot's own guidance — the evidence multiply, the shaping and the
+// clamp at the known pixels, in the order a solo call runs them — from a second device table (include/ccdm_hip.h:
+// ccdm_slot_guide_row) and two slot-indexed pools, `ev` [N,HW,K] and `known` [N,HW].  The kernels are k_slots / k_slots_staged with
+// the three parts put in; the branches that are uniform in the other entries (evidence or not, shape_row's two parts) are per slot
+// here, so a wave that straddles two slots diverges — nothing in them crosses lanes.  The clamp is the pixel's own thread's, behind
+// the core's stores of the same pixel: one launch (DESIGN.md section 5.1 has the register counts).
+
+// the clamp of pixel i of slot row r / guide row gr where the slot has known labels and the pixel's label is one: the class, else `bi`
+__device__ __forceinline__ int slot_clamp(const ccdm_post_args& a, const ccdm_slot_row& r, const ccdm_slot_guide_row& gr, const uint8_t* const known,
+                                          const size_t i, float* const xin, const int bi) {
+    if (!(gr.flags & CCDM_SLOT_GUIDE_KNOWN)) return bi;
+    const int y = known[i];
+    if (y >= a.K) return bi;                 // free (255, or any byte that is no class)
+    return clamp_known_pixel(y, i, a.HW, a.K, gr.p_hit, gr.p_miss, r.mode, (uint32_t)r.step_row, r.key_lo, r.key_hi, a.sample_offset, a.xt_next,
+                             xin, a.xin_stride, a.out_probs, a.out_onehot);
+}
+
+template <int KP>
+__global__ __launch_bounds__(256) void k_slots_guided(const ccdm_post_args a_in, const ccdm_slot_row* const table,
+                                                      const ccdm_slot_guide_row* const guide, const float* const ev, const uint8_t* const known,
+                                                      const int vec) {
+    const size_t npix = (size_t)a_in.N * a_in.HW;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npix) return;
+    const unsigned n = (unsigned)i / (unsigned)a_in.HW;                  // (N * HW < 2^31: the launcher checks)
+    const ccdm_slot_row r = table[n];
+    if (!slot_runs(r.mode)) return;
+    const ccdm_slot_guide_row gr = guide[n];
+    const ccdm_post_args a = slot_post_args(a_in, r, n);
+    float q[KP];
+    load_pixel_row<KP>(q, a.head, i, (gr.flags & CCDM_SLOT_GUIDE_EVIDENCE) ? ev : nullptr, a.K, vec);
+    shape_row<KP>(q, a.K, gr.inv_temperature, gr.top_r);
+    posterior_pixel_core<KP>(a, i, q, r.step_row, r.alpha_t, r.cumalpha_tm1, r.mode, (int)a.xt[i]);
+    slot_clamp(a, r, gr, known, i, a.xin, 0);
+}
+
+template <int KP, int BLK>
+__global__ __launch_bounds__(BLK) void k_slots_guided_staged(const ccdm_post_args a_in, const ccdm_slot_row* const table,
+                                                             const ccdm_slot_guide_row* const guide, const float* const ev,
+                                                             const uint8_t* const known) {
+    constexpr int PITCH = staged_pitch<KP>();
+    __shared__ float sx[BLK * PITCH];
+    __shared__ int sb[BLK];
+    const unsigned HW = (unsigned)a_in.HW;
+    const unsigned npix = (unsigned)a_in.N * HW;
+    const unsigned i0 = blockIdx.x * (unsigned)BLK;
+    const int tid = threadIdx.x;
+    const int nvalid = (int)std::min<unsigned>((unsigned)BLK, npix - i0);
+    const int K = a_in.K;
+    const bool mine = tid < nvalid;
+    // the block's slots and their segments as in k_slots_staged; a segment with evidence is staged times the pool's segment (the one
+    // fp32 multiply of stage_class_rows<WEIGHTED>, as k_guided_staged has it)
+    const unsigned n_lo = i0 / HW, n_hi = (i0 + (unsigned)nvalid - 1u) / HW;
+    for (unsigned n = n_lo; n <= n_hi; ++n) {
+        if (!slot_runs(table[n].mode)) continue;
+        const unsigned s0 = std::max(n * HW, i0) - i0, s1 = std::min((n + 1u) * HW, i0 + (unsigned)nvalid) - i0;
+        const size_t at = (size_t)(i0 + s0) * K;
+        if (guide[n].flags & CCDM_SLOT_GUIDE_EVIDENCE)                   // uniform
+            stage_class_rows<BLK, PITCH, true>(sx + s0 * PITCH, a_in.head + at, ev + at, (int)(s1 - s0), (unsigned)K, tid);
+        else
+            stage_class_rows<BLK, PITCH, false>(sx + s0 * PITCH, a_in.head + at, nullptr, (int)(s1 - s0), (unsigned)K, tid);
+    }
+    __syncthreads();
+    int bi = 0;
+    if (mine) {
+        const unsigned n = (i0 + (unsigned)tid) / HW;
+        const ccdm_slot_row r = table[n];
+        if (slot_runs(r.mode)) {
+            const ccdm_slot_guide_row gr = guide[n];
+            const ccdm_post_args a = slot_post_args(a_in, r, n);
+            float x0[KP];
+            if constexpr (KP <= 32) {
+#pragma unroll
+                for (int k = 0; k < KP; ++k) x0[k] = k < K ? sx[tid * PITCH + k] : 0.f;
+                shape_row<KP>(x0, K, gr.inv_temperature, gr.top_r);
+            } else {
+                shape_lds_row(sx + tid * PITCH, K, gr.inv_temperature, gr.top_r);          // the thread's own row: no barrier
+#pragma unroll
+                for (int k = 0; k < KP; ++k) x0[k] = k < K ? sx[tid * PITCH + k] : 0.f;
+            }
+            // (&bi unconditionally, as in k_guided_staged: bi stays in a register)
+            posterior_pixel_core<KP>(a, (size_t)i0 + tid, x0, r.step_row, r.alpha_t, r.cumalpha_tm1, r.mode, (int)a.xt[i0 + tid], &bi);
+            // the clamp replaces the pixel's entry of sb[] in a drawing slot (store_onehot_rows below writes its one-hot); in the
+            // last-step modes, once per walk, the thread writes the label's one-hot into xin itself
+            bi = slot_clamp(a, r, gr, known, (size_t)i0 + tid, r.mode == CCDM_STEP_SAMPLE ? nullptr : a.xin, bi);
+        }
+    }
+    if (!a_in.xin) return;                                               // uniform
+    sb[tid] = bi;
+    __syncthreads();
+    const unsigned stride = (unsigned)a_in.xin_stride;
+    for (unsigned n = n_lo; n <= n_hi; ++n) {
+        if (table[n].mode != CCDM_STEP_SAMPLE) continue;
+        const unsigned s0 = std::max(n * HW, i0) - i0, s1 = std::min((n + 1u) * HW, i0 + (unsigned)nvalid) - i0;
+        store_onehot_rows<BLK>(a_in.xin + (size_t)(i0 + s0) * stride, sb + s0, (int)(s1 - s0), stride, K, tid);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
 // Host side.  What an entry hands to its launcher; a launcher reads the fields its entry has
 struct guided_call {
     const float *x0, *evidence;
@@ -551,7 +655,7 @@ struct guided_call {
 // pixels per block of every launch here
 static int step_block(const int K) { return K <= 32 ? 256 : 64; }
 
-// What the three launchers do alike behind their own geometry checks: the shaping's range where it is the caller's (takes_shaping),
+// What the launchers do alike behind their own geometry checks: the shaping's range where it is the caller's (takes_shaping),
 // ccdm_post_args for c.N samples of HW pixels whose core sees `xin`, the grid, the vec flag of the one-thread-per-pixel kernels, the
 // K -> KP fork.  entry(kp, go, vec) holds the entry's two launch lines: go(kernel, what it takes behind ccdm_post_args...).  0, or
 // fail()'s code.
@@ -645,9 +749,38 @@ static int launch_slots(const char* name, const float* x0, const ccdm_slot_row* 
     });
 }
 
+// launch_slots with the guide table and the two pools.  The guide rows are on the device: their shaping's range is the host's to check
+// where it forms a row, and whether a pool is needed is the table's to say (include/ccdm_hip.h: the caller's contract).  The vec
+// flag covers the evidence pool's alignment (launch_step: c.evidence).
+static int launch_slots_guided(const char* name, const float* x0, const ccdm_slot_row* table, const ccdm_slot_guide_row* guide, const float* ev,
+                               const uint8_t* known, const int N, const int HW, const int K, uint8_t* xt, float* xin, const int xin_stride,
+                               float* out_probs, int64_t* out_onehot, void* stream) {
+    if (const int rc = check_step_args(name, x0 && table && guide && xt, N, HW, K, xin, xin_stride, CCDM_STEP_SAMPLE, 0, step_block(K))) return rc;
+    CCDM_REQUIRE((size_t)N * HW <= 0x7FFFFFFFull, "%s: too many pixels (N*HW = %zu)", name, (size_t)N * HW);
+    CCDM_REQUIRE((reinterpret_cast<uintptr_t>(table) & 3) == 0, "%s: misaligned table", name);
+    CCDM_REQUIRE((reinterpret_cast<uintptr_t>(guide) & 3) == 0, "%s: misaligned guide table", name);
+    CCDM_REQUIRE((reinterpret_cast<uintptr_t>(ev) & 3) == 0, "%s: misaligned evidence pool", name);
+    guided_call c = {};
+    c.x0 = x0; c.evidence = ev; c.N = N; c.K = K;
+    c.xt = xt; c.xin_stride = xin_stride;
+    c.out_probs = out_probs; c.out_onehot = out_onehot; c.stream = stream;
+    return launch_step(name, c, HW, false, xin, [&](auto kp, auto go, const int vec) {
+        constexpr int KP = decltype(kp)::value;
+        if constexpr (KP <= 4) go(k_slots_guided<KP>, table, guide, ev, known, vec);
+        else go(k_slots_guided_staged<KP, (KP <= 32 ? 256 : 64)>, table, guide, ev, known);
+    });
+}
+
 }  // namespace ccdm
 
 using namespace ccdm;
+
+extern "C" int ccdm_slots_guided_step(const float* x0, const ccdm_slot_row* table, const ccdm_slot_guide_row* guide, const float* evidence,
+                                      const uint8_t* known, int N, int HW, int K, uint8_t* xt, float* xin, int xin_stride, float* out_probs,
+                                      int64_t* out_onehot, void* stream) {
+    return launch_slots_guided("ccdm_slots_guided_step", x0, table, guide, evidence, known, N, HW, K, xt, xin, xin_stride, out_probs, out_onehot,
+                               stream);
+}
 
 extern "C" int ccdm_slots_step(const float* x0, const ccdm_slot_row* table, int N, int HW, int K, uint8_t* xt, float* xin, int xin_stride,
                                float* out_probs, int64_t* out_onehot, void* stream) {

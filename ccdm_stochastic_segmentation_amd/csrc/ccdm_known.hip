@@ -10,8 +10,8 @@
 // transition kernels compose in closed form.  Every pixel, known or free; the same race on a third counter range (0x40000000 | kq).
 // Reads 1 byte and writes 1 byte per pixel (+ K floats where the stem reads its one-hot from memory).  Measured, these bytes are 4 %
 // (64 x 128x128, K = 2) and 11 % (4 x 128x256, K = 20 with xin) of the HBM rate at the launch's time: DESIGN.md section 4.
-// The race (race_hit_miss), the one-hot store (write_onehot) and the entry points' argument checks (check_step_args) are
-// ccdm_sampler_common.h's, shared with the epilogue and the evidence step.
+// The race (race_hit_miss), the clamp of one pixel (clamp_known_pixel, shared with the queue's guided step), the one-hot store
+// (write_onehot) and the entry points' argument checks (check_step_args) are ccdm_sampler_common.h's.
 #include "ccdm_common.h"
 #include "ccdm_sampler_common.h"
 
@@ -25,16 +25,7 @@ __global__ __launch_bounds__(256) void k_known_labels_step(const uint8_t* __rest
     if (i >= npix) return;
     const int y = known[i];
     if (y >= K) return;                      // free (255, or any byte that is no class): nothing of this pixel is touched
-    int x = y;
-    if (mode == CCDM_STEP_SAMPLE) {
-        const uint32_t pix = (uint32_t)(i % HW), smp = (uint32_t)(i / HW) + sample_offset;
-        x = race_hit_miss(K, y, p_hit, p_miss, pix, smp, step_row, 0x80000000u, k0, k1);      // (the epilogue's blocks have kq < 64)
-    } else {
-        if (out_probs) write_onehot(out_probs + i * K, K, x);
-        if (out_onehot) for (int k = 0; k < K; ++k) out_onehot[i * K + k] = (k == x) ? 1 : 0;
-    }
-    xt[i] = (uint8_t)x;
-    if (xin) write_onehot(xin + i * xin_stride, K, x);
+    clamp_known_pixel(y, i, HW, K, p_hit, p_miss, mode, step_row, k0, k1, sample_offset, xt, xin, xin_stride, out_probs, out_onehot);
 }
 
 // one thread per pixel; a byte >= K on entry (never produced by the host) counts as class K - 1

@@ -2,7 +2,7 @@
 // last-step outputs) — shared by the stand-alone epilogue kernel (ccdm_sampler.hip), the head kernel that ends in it (ccdm_head.hip)
 // and the guided steps (ccdm_guided.hip): ONE definition, so all produce the same bits from the same values.  See ccdm_sampler.hip
 // for the arithmetic order.  Also here, once each: the two LDS passes of the staged kernels (stage_class_rows, store_onehot_rows), the
-// per-thread one-hot store (write_onehot), the K -> KP ladder of the launchers (dispatch_kp) and the argument checks the step entry
+// per-thread one-hot store (write_onehot), the clamp of a known pixel (clamp_known_pixel), the K -> KP ladder of the launchers (dispatch_kp) and the argument checks the step entry
 // points share (check_step_args).
 #pragma once
 #include "ccdm_common.h"
@@ -51,6 +51,32 @@ __device__ __forceinline__ int race_hit_miss(const int K, const int own, const f
             }
         }
     }
+    return x;
+}
+
+// the per-thread form of the one-hot store: the K one-hot channels of one pixel
+__device__ __forceinline__ void write_onehot(float* const d, const int K, const int x) {
+    for (int k = 0; k < K; ++k) d[k] = (k == x) ? 1.0f : 0.0f;
+}
+
+// The clamp of ONE known pixel (include/ccdm_hip.h, ccdm_known_labels_step): pixel i of the flat [N,HW] map whose label is y < K.
+// CCDM_STEP_SAMPLE: the race on (p_hit, p_miss) under tag 0x80000000 (the epilogue's blocks have kq < 64); the last-step modes: the
+// label itself, its one-hot into out_probs / out_onehot.  The class goes to xt[i], its one-hot to xin where given, and back to the
+// caller.  ONE definition for the clamp's own kernel (ccdm_known.hip) and the queue's guided step (ccdm_guided.hip).
+__device__ __forceinline__ int clamp_known_pixel(const int y, const size_t i, const int HW, const int K, const float p_hit, const float p_miss,
+                                                 const int mode, const uint32_t step_row, const uint32_t k0, const uint32_t k1,
+                                                 const uint32_t sample_offset, uint8_t* const xt, float* const xin, const int xin_stride,
+                                                 float* const out_probs, int64_t* const out_onehot) {
+    int x = y;
+    if (mode == CCDM_STEP_SAMPLE) {
+        const uint32_t pix = (uint32_t)(i % HW), smp = (uint32_t)(i / HW) + sample_offset;
+        x = race_hit_miss(K, y, p_hit, p_miss, pix, smp, step_row, 0x80000000u, k0, k1);
+    } else {
+        if (out_probs) write_onehot(out_probs + i * K, K, x);
+        if (out_onehot) for (int k = 0; k < K; ++k) out_onehot[i * K + k] = (k == x) ? 1 : 0;
+    }
+    xt[i] = (uint8_t)x;
+    if (xin) write_onehot(xin + i * xin_stride, K, x);
     return x;
 }
 
@@ -299,11 +325,6 @@ __device__ __forceinline__ void store_onehot_rows(float* const dst, const int* c
             if (c < (unsigned)K) dst[idx] = (int)c == sb[p] ? 1.0f : 0.0f;
         }
     }
-}
-
-// the per-thread form: the K one-hot channels of one pixel
-__device__ __forceinline__ void write_onehot(float* const d, const int K, const int x) {
-    for (int k = 0; k < K; ++k) d[k] = (k == x) ? 1.0f : 0.0f;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------

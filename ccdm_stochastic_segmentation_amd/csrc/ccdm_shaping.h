@@ -1,6 +1,8 @@
 // The shaping of a pixel's x0 row before the reverse step — temper relative to the row's largest value, then cut to the smallest set of
 // classes whose mass reaches top_r (THE definition: include/ccdm_hip.h, ccdm_shaped_step) — in its two forms, on registers and on an LDS
-// row: ONE definition for the kernels that shape a row in front of posterior_pixel_core (ccdm_guided.hip).
+// row: ONE definition for the kernels that shape a row in front of posterior_pixel_core (ccdm_guided.hip).  The branches marked
+// uniform are so where (inv_t, top_r) are launch arguments; the guided slots hand in each slot's own pair, and a wave that straddles
+// two slots diverges there — nothing here crosses lanes.
 #pragma once
 #include "ccdm_common.h"
 

@@ -91,6 +91,7 @@ class SamplerEngine:
         self._tile_canvas_key = None
         self._bound_xt: Optional[torch.Tensor] = None           # bound_noise(): the draw; bound_terms(): the partial sums' workspace
         self._bound_ws: Optional[torch.Tensor] = None
+        self._slot_pools: Optional[Tuple[torch.Tensor, torch.Tensor]] = None          # a guided queue's evidence and known-label pools
         with torch.cuda.device(device):
             # a private non-default stream: HIP graph capture is not allowed on the legacy default stream
             self.stream = torch.cuda.Stream(device=device)
@@ -582,6 +583,43 @@ class SamplerEngine:
         hip.check(self.lib.ccdm_slots_step(self.out_probs.data_ptr(), table.data_ptr(), self.N, self.H * self.W, self.K, self.xt.data_ptr(),
                                            None if self.stem_onehot_on_load else self.xin.ptr, self.Cs, self.out_probs.data_ptr(),
                                            self.out_onehot.data_ptr(), self._stream()), "slots_step")
+
+    def _slot_guidance_pools(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The two slot-indexed pools of a guided queue — evidence fp32 [N,H*W,K] and known labels uint8 [N,H*W] (all free) — allocated on
+        first use with the engine's stream current, so a plain queue pays nothing."""
+        if self._slot_pools is None:
+            self._slot_pools = (torch.zeros((self.N, self.H * self.W, self.K), dtype=torch.float32, device=self.device),
+                                torch.full((self.N, self.H * self.W), 255, dtype=torch.uint8, device=self.device))
+        return self._slot_pools
+
+    def set_slot_guidance(self, n0: int, evidence: Optional[torch.Tensor], known: Optional[torch.Tensor]) -> None:
+        """The guidance of the samples set_slot_inputs has put into rows n0 .. n0 + n - 1: evidence fp32 [n,H*W,K] and known uint8
+        [n,H*W] (class < K = known, 255 = free), contiguous, on the engine's device, either None — copied into those rows of the two
+        pools slots_guided_step reads.  A row is read only where the slot's guide row sets its flag, so a None leaves the rows as they
+        are.  Asynchronous on the engine's stream, which the caller has made current (enter)."""
+        n0, HW = int(n0), self.H * self.W
+        ev_pool, known_pool = self._slot_guidance_pools()
+        for name, t, pool, dtype in (("evidence", evidence, ev_pool, torch.float32), ("known", known, known_pool, torch.uint8)):
+            if t is None:
+                continue
+            n = int(t.shape[0])
+            assert 0 <= n0 and n >= 1 and n0 + n <= self.N, (name, n0, n, self.N)
+            assert tuple(t.shape) == (n, *pool.shape[1:]) and t.dtype == dtype and t.is_cuda and t.is_contiguous(), (name, tuple(t.shape), t.dtype)
+            pool[n0:n0 + n].copy_(t)
+
+    def slots_guided_step(self, table: torch.Tensor, guide_table: torch.Tensor) -> None:
+        """slots_step with every slot's own guidance (ccdm_slots_guided_step, asynchronous on the engine's stream).  guide_table: the N
+        rows of hip.SlotGuideRow on the engine's device, 32 bytes each; the caller has checked every row's shaping
+        (DenoisingModel._check_shaping) and filled the pools' rows of the slots whose flags it sets (set_slot_guidance).  Both pools are
+        always passed."""
+        assert table.is_cuda and table.is_contiguous() and table.numel() * table.element_size() == self.N * C.sizeof(hip.SlotRow)
+        assert guide_table.is_cuda and guide_table.is_contiguous() and \
+            guide_table.numel() * guide_table.element_size() == self.N * C.sizeof(hip.SlotGuideRow)
+        ev_pool, known_pool = self._slot_guidance_pools()
+        hip.check(self.lib.ccdm_slots_guided_step(self.out_probs.data_ptr(), table.data_ptr(), guide_table.data_ptr(), ev_pool.data_ptr(),
+                                                  known_pool.data_ptr(), self.N, self.H * self.W, self.K, self.xt.data_ptr(),
+                                                  None if self.stem_onehot_on_load else self.xin.ptr, self.Cs, self.out_probs.data_ptr(),
+                                                  self.out_onehot.data_ptr(), self._stream()), "slots_guided_step")
 
     def _bound_args(self, labels: torch.Tensor, table: torch.Tensor) -> int:
         """What bound_noise and bound_terms check alike; the number of label rows."""

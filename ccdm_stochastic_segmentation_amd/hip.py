@@ -30,7 +30,8 @@ PREC_F32, PREC_F16X3 = 0, 1
 PREC_F16 = 2             # CCDM_PREC_F16: the OPT-IN single-pass fast mode (one fp16 MFMA per product, ~2^-11 per operand) — outside the parity contract
 STEP_SAMPLE, STEP_LAST_CONFIDENCE, STEP_LAST_MAJORITY, STEP_LAST_KEEP, STEP_SOFTMAX_ONLY = 0, 1, 2, 3, 4
 SLOT_IDLE = -1           # CCDM_SLOT_IDLE: SlotRow.mode of a slot that holds nothing (ccdm_slots_step)
-BOUND_IDLE = -1          # CCDM_BOUND_IDLE: BoundRow.t of an engine row that holds nothing (ccdm_bound_noise, ccdm_bound_terms)
+SLOT_GUIDE_EVIDENCE, SLOT_GUIDE_KNOWN = 1, 2      # CCDM_SLOT_GUIDE_*: SlotGuideRow.flags (ccdm_slots_guided_step)
+BOUND_IDLE = -1         # CCDM_BOUND_IDLE: BoundRow.t of an engine row that holds nothing (ccdm_bound_noise, ccdm_bound_terms)
 STATS_MAX_SLICES = 64       # CCDM_STATS_MAX_SLICES: what a GroupNorm consumer reads
 F16X3_LIMIT = 4094.0        # CCDM_F16X3_LIMIT: the fp16 split is exact for staged |a| below this
 STATS_FOLD_SLICES = 16      # CCDM_STATS_FOLD_SLICES: what the engine folds a larger slice count to
@@ -88,6 +89,15 @@ class SlotRow(C.Structure):
         ("mode", C.c_int32), ("step_row", C.c_int32),
         ("key_lo", C.c_uint32), ("key_hi", C.c_uint32),
         ("sample", C.c_uint32), ("reserved", C.c_uint32),
+    ]
+
+
+class SlotGuideRow(C.Structure):
+    """ccdm_slot_guide_row: one row of ccdm_slots_guided_step's second device table, the per-slot guidance of a guided sampling queue."""
+    _fields_ = [
+        ("inv_temperature", C.c_float), ("top_r", C.c_float),
+        ("p_hit", C.c_float), ("p_miss", C.c_float),
+        ("flags", C.c_int32), ("reserved", C.c_int32 * 3),
     ]
 
 
@@ -205,6 +215,8 @@ SIGNATURES = {
                                   C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ccdm_slots_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                   C.c_void_p]),
+    "ccdm_slots_guided_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                         C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ccdm_bound_noise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p]),
     "ccdm_bound_terms_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "ccdm_bound_terms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,

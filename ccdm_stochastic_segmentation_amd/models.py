@@ -651,11 +651,12 @@ class DenoisingModel(nn.Module):
         self._engines[key] = (wkey, eng)
         return eng
 
-    def sampling_queue(self, capacity: int, image_shape: Sequence[int]):
+    def sampling_queue(self, capacity: int, image_shape: Sequence[int], guided: bool = False):
         """A continuous-batching queue on this model (serving.SamplingQueue): requests of any size and walk length share one engine of
-        `capacity` rows, each reproducing its solo call bit for bit."""
+        `capacity` rows, each reproducing its solo call bit for bit.  guided: its requests take evidence=, known_labels=, temperature=
+        and truncation= as a solo call does."""
         from .serving import SamplingQueue
-        return SamplingQueue(self, capacity, image_shape)
+        return SamplingQueue(self, capacity, image_shape, guided=guided)
 
     def _philox_key(self, call: Optional[int] = None) -> int:
         """64-bit Philox key of the current sampling call: splitmix64 of (philox_seed, philox_call).  `call`: another counter in

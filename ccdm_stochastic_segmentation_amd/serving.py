@@ -32,7 +32,22 @@ Range overflow.  The engine's range flag is one per engine; it is copied next to
 request and every later one with hip.CcdmRangeError until `reset()`, which clears the flag and drops what is in flight.  There is no
 automatic fp32 re-run: the caller sets model.prec = hip.PREC_F32 (or pins layers in model.f32_layers) and resubmits.
 
-Not thread-safe: the caller drives `step`.  Requests take no guidance keyword and no feature_condition (not built)."""
+Guided requests.  SamplingQueue(..., guided=True) takes requests with the guidance of an annotator in the loop,
+
+    q = model.sampling_queue(64, (C, H, W), guided=True)
+    r = q.submit(condition, evidence=e, known_labels=y, temperature=0.7, truncation=0.9)          # any subset, or none
+
+checked by the model's own _check_evidence / _check_known_labels / _check_shaping, with a solo call's meaning and errors.  The tick's
+step is then ccdm_slots_guided_step: beside the slot table a second one of one hip.SlotGuideRow per slot — the shaping, the clamp's
+(p_hit, p_miss) of the slot's row (`plan_clamp`), two flags — filled by `slot_guide_rows`, and two slot-indexed pools in the engine
+(evidence, known labels) that an admission fills (SamplerEngine.set_slot_guidance) from the request's own device copies.  Per slot the
+launch does what a solo call's run_row does behind the network pass: evidence multiply, shaping, step, clamp.  The contract is the
+same: the result is torch.equal to model(x, condition, t=t, evidence=..., known_labels=..., temperature=..., truncation=...) under the
+request's call index and vote, whatever else — guided or not — is in flight.  A queue built without guided=True is the plain queue,
+launch for launch, and refuses every guidance keyword.
+
+Not thread-safe: the caller drives `step`.  Not built: `views`, `tiles` and `resample` in a queue (several engine rows per sample; a
+walk that revisits rows), evidence that changes from pass to pass, feature_condition."""
 from __future__ import annotations
 
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -47,7 +62,17 @@ from .models import DenoisingModel, OneHotCategoricalBCHW, step_values
 SLOT_DTYPE = np.dtype([("alpha_t", "<f4"), ("cumalpha_tm1", "<f4"), ("mode", "<i4"), ("step_row", "<i4"), ("key_lo", "<u4"), ("key_hi", "<u4"),
                        ("sample", "<u4"), ("reserved", "<u4")])
 
+# one row of ccdm_slots_guided_step's second table (hip.SlotGuideRow: 32 bytes)
+GUIDE_DTYPE = np.dtype([("inv_temperature", "<f4"), ("top_r", "<f4"), ("p_hit", "<f4"), ("p_miss", "<f4"), ("flags", "<i4"), ("reserved", "<i4", (3,))])
+
 GUIDANCE_KEYWORDS = ("known_labels", "resample", "evidence", "temperature", "truncation", "views", "tiles")
+# what a request of a guided queue takes, and why it takes no other
+QUEUED_GUIDANCE = ("evidence", "known_labels", "temperature", "truncation")
+NOT_QUEUED = {"views": "a sample with views is several engine rows", "tiles": "a tiled sample is several engine rows",
+              "resample": "a walk with resampling jumps visits rows more than once"}
+# a request's guidance as the scheduler's pure functions see it: (inv_temperature, top_r, has evidence, the clamp pair of every row of
+# its walk or None)
+Guide = Tuple[float, float, bool, Optional[List[Tuple[np.float32, np.float32]]]]
 
 # a walk: per row (emb row, alpha_t, cumalpha_tm1, mode); the row's index is its step_row
 Walk = List[Tuple[int, float, float, int]]
@@ -120,6 +145,35 @@ def slot_rows(capacity: int, active: Sequence[Tuple[int, int, int, int]], walks:
     return rowmap, table
 
 
+def plan_clamp(walk: Walk, K: int) -> List[Tuple[np.float32, np.float32]]:
+    """Per row of a walk the clamp's (p_hit, p_miss) as SamplerEngine.clamp_known_labels forms it: c + (1 - c) / K and (1 - c) / K in
+    float64, each rounded to fp32 once; c = the row's cumalpha_tm1, and 1.0 on the walk's last row (the labels themselves)."""
+    pairs = []
+    for j, (_, _, c, _) in enumerate(walk):
+        c = 1.0 if j == len(walk) - 1 else float(c)
+        p_miss = (1.0 - c) / K
+        pairs.append((np.float32(c + p_miss), np.float32(p_miss)))
+    return pairs
+
+
+def slot_guide_rows(capacity: int, active: Sequence[Tuple[int, int, int, int]], guides: Dict[int, Guide], table: Optional[np.ndarray] = None):
+    """The third upload of a guided queue's tick from its active list: the guide table GUIDE_DTYPE [capacity].  guides[request] = the
+    request's Guide; a request without an entry, and every idle slot, gets the neutral row (1, 1, 0, 0, flags 0).  Written into `table`
+    where given (a pinned buffer)."""
+    table = np.zeros(capacity, GUIDE_DTYPE) if table is None else table
+    table[:] = np.zeros((), GUIDE_DTYPE)
+    table["inv_temperature"] = 1.0
+    table["top_r"] = 1.0
+    for s, req, j, row in active:
+        if req not in guides:
+            continue
+        inv_t, top_r, has_evidence, clamp = guides[req]
+        p_hit, p_miss = clamp[row] if clamp is not None else (0.0, 0.0)
+        flags = (hip.SLOT_GUIDE_EVIDENCE if has_evidence else 0) | (hip.SLOT_GUIDE_KNOWN if clamp is not None else 0)
+        table[s] = (inv_t, top_r, p_hit, p_miss, flags, (0, 0, 0))
+    return table
+
+
 def simulate(capacity: int, arrivals: Sequence[Tuple[int, int, int, int]]):
     """Run the scheduler without a device.  arrivals: (tick, request id, n, walk length), submitted before that tick in the order
     listed.  Ticks run until nothing is held or waiting or still to arrive.  Returns the ticks as a list of (admitted, active, finished)."""
@@ -154,6 +208,9 @@ class QueueRequest:
         self.dropped = False
         self.cond: Optional[torch.Tensor] = None          # device copies, held until every sample has been admitted and has run
         self.xt_idx: Optional[torch.Tensor] = None
+        self.guide: Optional[Guide] = None                # a guided request's table values, and its maps on the device (held like cond)
+        self.ev: Optional[torch.Tensor] = None            # fp32 [n,H*W,K]
+        self.known: Optional[torch.Tensor] = None         # uint8 [n,H*W]
         self.buf: Optional[torch.Tensor] = None           # the result rows: [n,H,W,K] fp32 / int64, or [n,H*W] uint8 class indices
         self.flag: Optional[torch.Tensor] = None          # the engine's range flag as it stood behind the last finished sample
         self.event: Optional[torch.cuda.Event] = None
@@ -191,11 +248,14 @@ class QueueRequest:
 
 class SamplingQueue:
     """Continuous batching on one engine of `capacity` rows (module docstring).  image_shape = (C, H, W) of the conditioning image.
-    stats: ticks run, busy and idle slot-steps, requests finished.  Not thread-safe."""
+    guided: requests take evidence=, known_labels=, temperature= and truncation=, and every tick's step is ccdm_slots_guided_step;
+    without it the queue is the plain one, launch for launch.  stats: ticks run, busy and idle slot-steps, requests finished.  Not
+    thread-safe."""
 
-    RING = 4          # pinned upload buffers: a tick's rowmap and table stay untouched until the copy that reads them has run
+    RING = 4          # pinned upload buffers: a tick's rowmap and tables stay untouched until the copy that reads them has run
 
-    def __init__(self, model: DenoisingModel, capacity: int, image_shape: Sequence[int]):
+    def __init__(self, model: DenoisingModel, capacity: int, image_shape: Sequence[int], guided: bool = False):
+        self.guided = bool(guided)
         if int(capacity) < 1:
             raise ValueError(f"capacity: {capacity} (at least one slot)")
         if len(tuple(image_shape)) != 3:
@@ -263,12 +323,15 @@ class SamplingQueue:
             ts = list(range(T, 0, -1))
             eng.set_tables([float(t) for t in ts], [(*m.diffusion.posterior_coeffs(t), hip.STEP_SOFTMAX_ONLY) for t in ts])
             self._table_dev = torch.zeros((N, SLOT_DTYPE.itemsize // 4), dtype=torch.int32, device=dev)
+            self._guide_dev = torch.zeros((N, GUIDE_DTYPE.itemsize // 4), dtype=torch.int32, device=dev) if self.guided else None
         eng.leave()
         self._ring = []
         for _ in range(self.RING):
             rows = torch.zeros((N,), dtype=torch.int32).pin_memory()
             tab = torch.zeros((N, SLOT_DTYPE.itemsize // 4), dtype=torch.int32).pin_memory()
-            self._ring.append((rows, tab, rows.numpy(), tab.numpy().reshape(-1).view(SLOT_DTYPE), torch.cuda.Event()))
+            guide = torch.zeros((N, GUIDE_DTYPE.itemsize // 4), dtype=torch.int32).pin_memory() if self.guided else None
+            self._ring.append((rows, tab, rows.numpy(), tab.numpy().reshape(-1).view(SLOT_DTYPE), torch.cuda.Event(), guide,
+                               None if guide is None else guide.numpy().reshape(-1).view(GUIDE_DTYPE)))
         self._ring_at = 0
         self._engine, self._engine_key = eng, key
         return eng
@@ -282,8 +345,14 @@ class SamplingQueue:
     def submit(self, condition: torch.Tensor, x: Optional[torch.Tensor] = None, t=None, vote: Optional[str] = None, **guidance) -> QueueRequest:
         """Queue n samples: condition [n,C,H,W]; x the one-hot x_T [n,K,H,W], or None to draw it as predict_single does; t as
         model(x, condition, t=t) takes it (None, an int or a tensor; > 10000 = a strided walk); vote: the last row's vote, default
-        model.step_T_sample.  The request takes the Philox key of the model's current `philox_call` and advances it as a call does."""
+        model.step_T_sample.  The request takes the Philox key of the model's current `philox_call` and advances it as a call does.
+        A guided queue: evidence [n,K,H,W], known_labels [n,H,W], temperature, truncation — meaning, dtypes and errors as
+        model(x, condition, ...) has them (the model's own checks)."""
         for k in guidance:
+            if self.guided and k in QUEUED_GUIDANCE:
+                continue
+            if self.guided and k in NOT_QUEUED:
+                raise ValueError(f"{k}: not built for queued requests ({NOT_QUEUED[k]})")
             if k in GUIDANCE_KEYWORDS:
                 raise ValueError(f"{k}: guidance keywords are not built for queued requests")
             raise TypeError(f"submit() got an unexpected keyword argument {k!r}")
@@ -299,11 +368,17 @@ class SamplingQueue:
         init_t = None if t is None else int(t.item()) if isinstance(t, torch.Tensor) else int(t)
         vote = m.step_T_sample if vote is None else vote
         walk = plan_walk(m.time_steps, init_t, vote, m.diffusion.posterior_coeffs)
+        # the checks of a solo call, in its order (DenoisingModel._check_guidance), before anything is built or counted
+        shaping = m._check_shaping(guidance.get("temperature"), guidance.get("truncation"))
+        ev = None if guidance.get("evidence") is None else m._check_evidence(guidance["evidence"], (n, self.K, H, W))
+        known = None if guidance.get("known_labels") is None else m._check_known_labels(guidance["known_labels"], (n, H, W), self.K)
         eng = self._get_engine()
         if x is None:
             x = OneHotCategoricalBCHW(logits=torch.zeros((n, self.K, H, W), device=condition.device)).sample()
         r = QueueRequest(self, self._next_id, n, int(m.philox_call), m._philox_key(), int(m.sample_offset), vote, walk, init_t, x.device)
         self._next_id += 1
+        if shaping is not None or ev is not None or known is not None:
+            r.guide = (*(shaping or (1.0, 1.0)), ev is not None, None if known is None else plan_clamp(walk, self.K))
         if m.philox_advance:
             m.philox_call += 1
         dev = eng.device
@@ -311,6 +386,8 @@ class SamplingQueue:
             # fresh copies made on the engine's stream: the caller's tensors may go away at once
             r.xt_idx = m._to_index(x.to(dev), dev)
             r.cond = condition.to(dev, torch.float32).contiguous().clone()
+            r.ev = None if ev is None else ev.to(dev).clone()
+            r.known = None if known is None else known.to(dev).clone()
             if r.kind == "state":
                 r.buf = torch.empty((n, H * W), dtype=torch.uint8, device=dev)
             else:
@@ -344,11 +421,13 @@ class SamplingQueue:
         eng = self._get_engine()
         reqs = self._requests
         self._slots, self._pending, admitted, active, finished = schedule_tick(self._slots, self._pending, {i: len(r.walk) for i, r in reqs.items()})
-        rows_pin, tab_pin, rows_np, tab_np, ev = self._ring[self._ring_at]
+        rows_pin, tab_pin, rows_np, tab_np, ev, guide_pin, guide_np = self._ring[self._ring_at]
         self._ring_at = (self._ring_at + 1) % self.RING
-        ev.synchronize()                          # the copies that read this pair RING ticks ago have run (never recorded: returns at once)
+        ev.synchronize()                          # the copies that read these buffers RING ticks ago have run (never recorded: returns at once)
         slot_rows(self.capacity, active, {i: r.walk for i, r in reqs.items()}, {i: r.key for i, r in reqs.items()},
                   {i: r.sample0 for i, r in reqs.items()}, rows_np, tab_np)
+        if self.guided:
+            slot_guide_rows(self.capacity, active, {i: r.guide for i, r in reqs.items() if r.guide is not None}, guide_np)
         with eng.enter():
             # 1. admissions: runs of consecutive slots that take consecutive samples of one request go in one call
             g = 0
@@ -359,14 +438,21 @@ class SamplingQueue:
                     e += 1
                 r = reqs[rid]
                 eng.set_slot_inputs(s0, r.xt_idx[j0:j0 + e - g], r.cond[j0:j0 + e - g])
+                if r.ev is not None or r.known is not None:
+                    eng.set_slot_guidance(s0, None if r.ev is None else r.ev[j0:j0 + e - g], None if r.known is None else r.known[j0:j0 + e - g])
                 g = e
-            # 2. this tick's rowmap and slot table
+            # 2. this tick's rowmap and slot table (a guided queue: and its guide table)
             eng.set_rows(rows_pin, non_blocking=True)
             self._table_dev.copy_(tab_pin, non_blocking=True)
+            if self.guided:
+                self._guide_dev.copy_(guide_pin, non_blocking=True)
             ev.record(eng.stream)
             # 3. the network pass to x0, 4. every slot's own reverse step
             eng.run(1, first_row=0, use_graph=bool(self.model.use_graph))
-            eng.slots_step(self._table_dev)
+            if self.guided:
+                eng.slots_guided_step(self._table_dev, self._guide_dev)
+            else:
+                eng.slots_step(self._table_dev)
             # 5. results of the walks that ended
             for s, rid, j in finished:
                 r = reqs[rid]
@@ -376,7 +462,7 @@ class SamplingQueue:
                 r.event.record(eng.stream)
                 r.finished += 1
                 if r.done:
-                    r.cond = r.xt_idx = None          # (allocated on the engine's stream: their memory is reused in stream order)
+                    r.cond = r.xt_idx = r.ev = r.known = None         # (allocated on the engine's stream: their memory is reused in stream order)
                     del reqs[rid]
                     self.stats["requests_finished"] += 1
         eng.leave()

@@ -519,6 +519,45 @@ int ccdm_slots_step(const float* x0 /*dev [N,HW,K]*/, const ccdm_slot_row* table
                     float* out_probs /*[N,HW,K] or NULL*/, int64_t* out_onehot /*[N,HW,K] or NULL*/, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * The reverse step of a GUIDED sampling queue (serving.SamplingQueue(..., guided=True)): ccdm_slots_step with every slot's own
+ * guidance.  Launched like ccdm_slots_step and takes its table unchanged; beside it a second device table of one 32-byte row per slot
+ * and two slot-indexed pools (plain pointers: no per-slot device pointer is ever put into a table — a stale row of a pool is a wrong
+ * but harmless read, a stale pointer would be a fault).
+ * THE definition.  For slot n with table[n].mode one of the four real step modes the launch leaves in xt, in channels [0, K) of xin and
+ * in rows [n * HW, (n + 1) * HW) of out_probs / out_onehot exactly the bits that, with g = guide[n] and the pointers of ccdm_slots_step's
+ * definition (each offset to the slot),
+ *     ccdm_shaped_step(x0, g.flags & CCDM_SLOT_GUIDE_EVIDENCE ? evidence + n * HW * K : NULL, 1, HW, K, g.inv_temperature, g.top_r,
+ *                      alpha_t, cumalpha_tm1, mode, step_row, key, sample, xt, xin, xin_stride, out_probs, out_onehot)
+ * followed, where g.flags & CCDM_SLOT_GUIDE_KNOWN, by
+ *     ccdm_known_labels_step(known + n * HW, 1, HW, K, g.p_hit, g.p_miss, mode, step_row, key, sample, xt, xin, xin_stride, out_probs,
+ *                            out_onehot)
+ * leave: the order of a solo call (network, guided step, clamp).  Per pixel: v = x0, or x0 * evidence (one fp32 multiply); the
+ * slot's shaping ((1, 1): none); the step with the slot's key, sample, step row, coefficients and mode; then, by the same thread, the
+ * clamp where the pixel's `known` byte is a class < K — in CCDM_STEP_SAMPLE the Exp(1) race on (p_hit, p_miss) with fourth counter
+ * word 0x80000000 | k / 4, in the last-step modes the label and its one-hot.  One launch.  Neutral guide rows — (1, 1, ., ., 0) —
+ * give ccdm_slots_step bit for bit.  A slot that is idle is neither read nor written, its rows of the pools included.
+ * The caller's contract (on the device, so not checked here): a pool may be NULL only while no running slot sets its flag;
+ * inv_temperature in [1/20, 20] and top_r in (0, 1] are checked by the host where it forms a row (DenoisingModel._check_shaping);
+ * (p_hit, p_miss) is the pair ccdm_known_labels_step documents, float64 c + (1 - c) / K and (1 - c) / K each rounded to fp32 once,
+ * c = cumalpha_tm1 of the row and 1.0 on a walk's last row.
+ * The three shapes of ccdm_slots_step; K <= 4: the 8- / 16-byte loads need x0 and the evidence pool aligned alike.  Refused: what
+ * ccdm_slots_step refuses, a null guide table, a table or the evidence pool not 4-byte aligned.
+ * ------------------------------------------------------------------------------------------------- */
+#define CCDM_SLOT_GUIDE_EVIDENCE 1  /* ccdm_slot_guide_row.flags: the slot's row of the evidence pool multiplies its x0 */
+#define CCDM_SLOT_GUIDE_KNOWN 2     /* the slot's row of the known pool is clamped */
+typedef struct ccdm_slot_guide_row {
+    float inv_temperature; float top_r;     /* the slot's shaping as ccdm_shaped_step takes it; (1, 1): none */
+    float p_hit; float p_miss;              /* the clamp's pair of the slot's current row; read only with CCDM_SLOT_GUIDE_KNOWN */
+    int32_t flags;                          /* CCDM_SLOT_GUIDE_* */
+    int32_t reserved[3];                    /* zero */
+} ccdm_slot_guide_row;
+int ccdm_slots_guided_step(const float* x0 /*dev [N,HW,K]*/, const ccdm_slot_row* table /*dev [N]*/,
+                           const ccdm_slot_guide_row* guide /*dev [N]*/, const float* evidence /*dev [N,HW,K] or NULL*/,
+                           const uint8_t* known /*dev [N,HW]: class < K = known, 255 = free; or NULL*/, int N, int HW, int K,
+                           uint8_t* xt /*dev [N,HW]: x_t in, x_{t-1} out*/, float* xin /*dev [N,HW,xin_stride] or NULL*/, int xin_stride,
+                           float* out_probs /*[N,HW,K] or NULL*/, int64_t* out_onehot /*[N,HW,K] or NULL*/, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * The variational bound on the likelihood of a held-out label map (DenoisingModel.label_bound):
  *     -log p(y | image) <= L_T + sum_{t=1..T} E_{x_t ~ q(x_t | x_0 = y)} l_t(y, x_t)
  * with l_t the reference's training loss (trainer.py:255-277).  Every network kernel reads its time-embedding row as rowmap[n] + step,

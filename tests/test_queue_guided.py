@@ -1,0 +1,510 @@
+"""Guided requests in the sampling queue: serving.SamplingQueue(..., guided=True) on the per-slot guide-and-clamp kernel
+ccdm_slots_guided_step (include/ccdm_hip.h has the definition).  The guide table's rows are pure functions of the schedule and are checked
+on the CPU against a schedule derived by hand; the kernel is held bit for bit against ccdm_slots_step at neutral rows and against
+ccdm_shaped_step followed by ccdm_known_labels_step, one pair of calls per slot; the queue is held to its contract: whatever the arrival
+order and whatever else is in flight, a guided request's result is torch.equal to its solo call with the same keywords."""
+import ctypes as C
+import os
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+import torch
+
+from ccdm_stochastic_segmentation_amd import SamplingQueue, hip, serving, step_values
+from tests.guided_util import random_inputs, sampler_evidence
+from tests.sampler_util import (DEV, FREE, H, ROOT, T_SMALL, T_STRIDED, W, assert_symbol_declared_bound_and_built, load_lib, make_sampler,
+                                probabilities, small_model)
+from tests.test_sampling_queue import IDLE, MODES, run_slots, slot_buffers, slot_table
+
+SYMBOL = "ccdm_slots_guided_step"
+EV, KNOWN = hip.SLOT_GUIDE_EVIDENCE, hip.SLOT_GUIDE_KNOWN
+
+
+# ------------------------------------------------------------------------------------------------ CPU
+def test_guided_symbol_declared_bound_and_built():
+    """hip.py binds the symbol with argtypes that match the header's declaration (14 arguments), ccdm_guided.hip defines it and the library
+    cross-built from it exports it under the unchanged ABI number; the ctypes row and the numpy row have the header's size (32 bytes) and
+    offsets, by the C compiler's layout; the slot row beside it is what it was; every bad argument is refused before anything is launched."""
+    lib = assert_symbol_declared_bound_and_built(SYMBOL, 14, "ccdm_guided.hip")
+    fields = ["inv_temperature", "top_r", "p_hit", "p_miss", "flags", "reserved"]
+    src = '#include <stdio.h>\n#include <stddef.h>\n#include "ccdm_hip.h"\nint main(){ printf("%zu %zu %d %d", sizeof(ccdm_slot_guide_row), ' \
+          'sizeof(ccdm_slot_row), CCDM_SLOT_GUIDE_EVIDENCE, CCDM_SLOT_GUIDE_KNOWN);\n' + \
+          "".join(f'printf(" %zu", offsetof(ccdm_slot_guide_row, {f}));\n' for f in fields) + "return 0; }\n"
+    with tempfile.TemporaryDirectory() as d:
+        open(os.path.join(d, "t.c"), "w").write(src)
+        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(d, "t.c"), "-o", os.path.join(d, "t")])
+        out = [int(v) for v in subprocess.check_output([os.path.join(d, "t")]).decode().split()]
+    R = hip.SlotGuideRow
+    assert out == [32, 32, EV, KNOWN] + [getattr(R, f).offset for f in fields] == [32, 32, 1, 2, 0, 4, 8, 12, 16, 20]
+    assert C.sizeof(R) == 32 and C.alignment(R) == 4 and [f for f, _ in R._fields_] == fields
+    assert serving.GUIDE_DTYPE.itemsize == 32 and list(serving.GUIDE_DTYPE.names) == fields
+    assert [serving.GUIDE_DTYPE.fields[f][1] for f in fields] == out[4:]
+    assert serving.GUIDE_DTYPE.fields["reserved"][0].shape == (3,) and serving.GUIDE_DTYPE.fields["flags"][0] == np.dtype("<i4")
+    # the slot row: unchanged
+    slot_fields = ["alpha_t", "cumalpha_tm1", "mode", "step_row", "key_lo", "key_hi", "sample", "reserved"]
+    assert C.sizeof(hip.SlotRow) == 32 and [f for f, _ in hip.SlotRow._fields_] == slot_fields
+    assert serving.SLOT_DTYPE.itemsize == 32 and list(serving.SLOT_DTYPE.names) == slot_fields
+    assert [serving.SLOT_DTYPE.fields[f][1] for f in slot_fields] == [getattr(hip.SlotRow, f).offset for f in slot_fields] == list(range(0, 32, 4))
+    buf = np.zeros(64, np.float32)
+    p = buf.ctypes.data
+    good = dict(x0=p, table=p, guide=p, ev=p, known=p, N=1, HW=4, K=2, xt=p, xin=p, xin_stride=4, out_probs=p, out_onehot=p, stream=None)
+    for change, word in ((dict(x0=None), "null"), (dict(table=None), "null"), (dict(guide=None), "null"), (dict(xt=None), "null"),
+                         (dict(N=0), "shape"), (dict(HW=0), "shape"), (dict(K=0), "K="), (dict(K=256), "K="), (dict(xin_stride=1), "xin_stride"),
+                         (dict(N=1 << 16, HW=1 << 16), "pixels"), (dict(table=p + 1), "misaligned table"), (dict(guide=p + 2), "guide table"),
+                         (dict(ev=p + 1), "evidence pool")):
+        assert getattr(lib, SYMBOL)(*dict(good, **change).values()) < 0, change
+        assert word in hip.last_error(), (change, hip.last_error())
+
+
+def clamp_pairs(model, t, K):
+    """np.float32 of the float64 formula on posterior_coeffs' cumalpha_tm1, c = 1 on the walk's last row — formed here without the module
+    under test"""
+    ts = step_values(T_SMALL, t)
+    out = []
+    for j, tv in enumerate(ts):
+        c = 1.0 if j == len(ts) - 1 else float(model.diffusion.posterior_coeffs(tv)[1])
+        out.append((np.float32(c + (1.0 - c) / K), np.float32((1.0 - c) / K)))
+    return out
+
+
+def test_guide_rows_on_three_requests():
+    """Capacity 3; request 0 (2 samples, 6 rows: evidence and a temperature), request 1 (1 sample, strided: 4 rows: known labels and a
+    truncation) and request 2 (1 sample, t = 3: 3 rows, no guidance) all before tick 0.  By hand:
+      ticks 0-3  slots 0 1 hold request 0 (rows 0 .. 3), slot 2 request 1 (rows 0 .. 3, its last at tick 3); request 2 waits
+      ticks 4-5  slot 2 holds request 2 (rows 0, 1); request 0 runs rows 4, 5 and leaves at tick 5
+      tick 6     slots 0 1 idle, slot 2: request 2's row 2
+    Idle slots and request 2's slot hold the neutral row (1, 1, 0, 0, flags 0); the others their request's values, the clamp pair that of
+    the slot's current row."""
+    K = 5
+    model, _ = small_model(K)
+    ts = [None, int(T_STRIDED), 3]
+    walks = {i: serving.plan_walk(T_SMALL, t, "majority", model.diffusion.posterior_coeffs) for i, t in enumerate(ts)}
+    assert [len(walks[i]) for i in range(3)] == [6, 4, 3]
+    pairs = serving.plan_clamp(walks[1], K)
+    want_pairs = clamp_pairs(model, ts[1], K)
+    assert len(pairs) == 4 and all(type(v) is np.float32 for p in pairs for v in p)
+    assert [(p.tobytes(), m.tobytes()) for p, m in pairs] == [(p.tobytes(), m.tobytes()) for p, m in want_pairs]
+    assert pairs[-1] == (np.float32(1.0), np.float32(0.0)) and 0 < pairs[0][1] < pairs[0][0] < 1
+    inv_t = np.float32(1.0 / 0.7)
+    guides = {0: (float(inv_t), 1.0, True, None), 1: (1.0, float(np.float32(0.9)), False, pairs)}
+    ticks = serving.simulate(3, [(0, 0, 2, 6), (0, 1, 1, 4), (0, 2, 1, 3)])
+    want_active = [[(0, 0, 0, k), (1, 0, 1, k), (2, 1, 0, k)] for k in range(4)] + \
+                  [[(0, 0, 0, 4), (1, 0, 1, 4), (2, 2, 0, 0)], [(0, 0, 0, 5), (1, 0, 1, 5), (2, 2, 0, 1)], [(2, 2, 0, 2)]]
+    assert [active for _, active, _ in ticks] == want_active
+    neutral = (np.float32(1), np.float32(1), np.float32(0), np.float32(0), 0, [0, 0, 0])
+
+    def row(table, s):
+        r = table[s]
+        return (r["inv_temperature"], r["top_r"], r["p_hit"], r["p_miss"], int(r["flags"]), r["reserved"].tolist())
+    pinned = np.full(3, 0x7F, np.uint8).repeat(32).view(serving.GUIDE_DTYPE)          # a buffer that held something else
+    for k, (_, active, _) in enumerate(ticks):
+        table = serving.slot_guide_rows(3, active, guides)
+        assert table.dtype == serving.GUIDE_DTYPE and table.shape == (3,)
+        assert serving.slot_guide_rows(3, active, guides, pinned) is pinned and pinned.tobytes() == table.tobytes()
+        held = {s: (req, r_) for s, req, _, r_ in active}
+        for s in range(3):
+            if s not in held or held[s][0] == 2:
+                assert row(table, s) == neutral, (k, s)
+            elif held[s][0] == 0:
+                assert row(table, s) == (inv_t, np.float32(1), np.float32(0), np.float32(0), EV, [0, 0, 0]), (k, s)
+            else:
+                assert row(table, s) == (np.float32(1), np.float32(0.9), *want_pairs[held[s][1]], KNOWN, [0, 0, 0]), (k, s)
+    # both flags together
+    both = serving.slot_guide_rows(2, [(1, 0, 0, 2)], {0: (2.0, 0.5, True, pairs)})
+    assert row(both, 1) == (np.float32(2), np.float32(0.5), *want_pairs[2], EV | KNOWN, [0, 0, 0]) and row(both, 0) == neutral
+
+
+def test_guided_queue_refusals():
+    """A guided queue refuses what it does not build by name, and a bad map or value with the text of the solo call's own check; nothing
+    runs (no engine is built: these pass without a device)."""
+    K = 3
+    m, _ = small_model(K)
+    m.eval()
+    m.rng = "philox"
+    q = m.sampling_queue(4, (1, H, W), guided=True)
+    assert isinstance(q, SamplingQueue) and q.guided and not m.sampling_queue(4, (1, H, W)).guided
+    n = 2
+    cond = torch.zeros((n, 1, H, W))
+    for kw, value in (("views", ("x",)), ("tiles", (16, 16, 8, 8)), ("resample", (2, 2))):
+        with pytest.raises(ValueError, match=kw + ": not built for queued requests"):
+            q.submit(cond, **{kw: value})
+    with pytest.raises(TypeError, match="colour"):
+        q.submit(cond, colour=1)
+    ev = torch.full((n, K, H, W), 0.5)
+    known = torch.full((n, H, W), FREE, dtype=torch.int64)
+    outside = ev.clone()
+    outside[1, 2, 3, 4] = 1.5
+    ruled_out = ev.clone()
+    ruled_out[0, :, 5, 6] = 0.0
+    bad_class = known.clone()
+    bad_class[0, 0, 0] = K
+    cases = [
+        (dict(evidence=ev[:, :, :, 1:]), lambda: m._check_evidence(ev[:, :, :, 1:], (n, K, H, W)), "evidence: expected shape"),
+        (dict(evidence=ev[:1]), lambda: m._check_evidence(ev[:1], (n, K, H, W)), "evidence: expected shape"),
+        (dict(evidence=outside), lambda: m._check_evidence(outside, (n, K, H, W)), r"evidence: values must be weights in \[0,1\]; found 1.5"),
+        (dict(evidence=ruled_out), lambda: m._check_evidence(ruled_out, (n, K, H, W)), "evidence: a pixel whose K weights are all 0"),
+        (dict(evidence=ev.long()), lambda: m._check_evidence(ev.long(), (n, K, H, W)), "evidence: expected a floating-point tensor"),
+        (dict(known_labels=known.float()), lambda: m._check_known_labels(known.float(), (n, H, W), K), "known_labels: expected an integer tensor"),
+        (dict(known_labels=known[:, 1:]), lambda: m._check_known_labels(known[:, 1:], (n, H, W), K), "known_labels: expected shape"),
+        (dict(known_labels=bad_class), lambda: m._check_known_labels(bad_class, (n, H, W), K), "known_labels: values must be classes"),
+        (dict(temperature=0.01), lambda: m._check_shaping(0.01, None), "temperature: expected a real number in"),
+        (dict(temperature=float("nan")), lambda: m._check_shaping(float("nan"), None), "temperature: expected a real number in"),
+        (dict(truncation=0.0), lambda: m._check_shaping(None, 0.0), "truncation: expected a real number in"),
+        (dict(truncation=1.5, evidence=ev), lambda: m._check_shaping(None, 1.5), "truncation: expected a real number in"),
+    ]
+    for kw, solo_check, text in cases:
+        with pytest.raises(ValueError, match=text) as queued:
+            q.submit(cond, **kw)
+        with pytest.raises(ValueError) as alone:
+            solo_check()
+        assert str(queued.value) == str(alone.value), kw
+    # the plain queue refuses all of them as before
+    plain = m.sampling_queue(4, (1, H, W))
+    for kw in serving.GUIDANCE_KEYWORDS:
+        with pytest.raises(ValueError, match=kw + ": guidance keywords are not built for queued requests"):
+            plain.submit(cond, **{kw: 1.0})
+    assert m.philox_call == 0 and m._engines == {} and q.idle and plain.idle and q._engine is None
+
+
+# ------------------------------------------------------------------------------------------------ GPU: the kernel alone
+@pytest.fixture(scope="module")
+def lib():
+    return load_lib()
+
+
+HW = 195          # the slot test's shape: no multiple of 64 or 256, so slot boundaries fall inside a wave and inside a block
+KS = [2, 3, 5, 20, 33]          # vec, one thread per pixel without vec, staged 256, staged 256 on the 20-wide rung, staged 64 with LDS shaping
+TAIL = 64          # guard elements behind xt and xin
+RUNNING = [n for n, mode in enumerate(MODES) if mode != hip.SLOT_IDLE]
+KINDS = ["all", "evidence", "shaping", "known"]          # what the four running slots carry, rotated over them
+
+
+def stride_of(K):
+    return (K + 4) // 4 * 4 + 1          # odd and > K (K = 5: 9)
+
+
+def guide_inputs(K, rotation):
+    """The guide table, the two pools and — for the per-slot definition — each slot's arguments.  Running slot RUNNING[j] carries
+    KINDS[(j + rotation) % 4]; the idle slot's guide row sets both flags and a shaping, and its pool rows hold values that would change
+    any result they got into (NaN weights, label 0 everywhere)."""
+    rng = np.random.default_rng(8100 + K)
+    N = len(MODES)
+    _, ev, _ = random_inputs(rng, N, HW, K)          # weights in [0,1], a fifth of them exactly 0, no pixel ruled out
+    labels = rng.integers(0, K, (N, HW))
+    known = np.where(rng.random((N, HW)) < 0.4, labels, FREE).astype(np.uint8)
+    known[:, 7] = 200 if K <= 200 else FREE          # a byte that is no class counts as free
+    ev[IDLE] = np.nan
+    known[IDLE] = 0
+    table = slot_table()
+    guide = np.zeros(N, serving.GUIDE_DTYPE)
+    guide["inv_temperature"], guide["top_r"] = 1.0, 1.0
+    slots = {}
+    for j, n in enumerate(RUNNING):
+        kind = KINDS[(j + rotation) % 4]
+        has_ev, has_known = kind in ("all", "evidence"), kind in ("all", "known")
+        # shaping alone: a top_r that keeps one class; with the rest: a temperature and a cut that keeps several
+        inv_t, top_r = (np.float32(1 / 0.7), np.float32(0.9)) if kind == "all" else (np.float32(1.0), np.float32(1e-3)) if kind == "shaping" \
+            else (np.float32(1.0), np.float32(1.0))
+        c = float(table[n]["cumalpha_tm1"]) if table[n]["mode"] == hip.STEP_SAMPLE else 1.0
+        p_hit, p_miss = probabilities(c, K)
+        guide[n] = (inv_t, top_r, p_hit, p_miss, (EV if has_ev else 0) | (KNOWN if has_known else 0), (0, 0, 0))
+        slots[n] = dict(kind=kind, ev=has_ev, known=has_known, inv_t=float(inv_t), top_r=float(top_r), p_hit=float(p_hit), p_miss=float(p_miss))
+    guide[IDLE] = (0.5, 0.25, 0.75, 0.25, EV | KNOWN, (0, 0, 0))
+    return table, guide, ev, known, slots
+
+
+def padded(d):
+    """Copies of the slot buffers with xt and xin flat and TAIL guard elements behind them"""
+    g = {k: v.clone() for k, v in d.items()}
+    g["xt"] = torch.cat([d["xt"].reshape(-1), torch.full((TAIL,), 0x5A, dtype=torch.uint8, device=DEV)])
+    g["xin"] = torch.cat([d["xin"].reshape(-1), torch.full((TAIL,), -3.0, dtype=torch.float32, device=DEV)])
+    return g
+
+
+def unpadded(g, d, what):
+    """The guard elements are what they were; xt and xin back in the slot buffers' shapes"""
+    assert bool((g["xt"][-TAIL:] == 0x5A).all()), what + ": bytes behind N*HW of xt changed"
+    assert bool((g["xin"][-TAIL:] == -3.0).all()), what + ": floats behind the last row of xin changed"
+    g["xt"], g["xin"] = g["xt"][:-TAIL].reshape(d["xt"].shape), g["xin"][:-TAIL].reshape(d["xin"].shape)
+    return g
+
+
+def run_guided(lib, d, table, guide, ev, known, with_xin, alias):
+    """ccdm_slots_guided_step on guarded copies of the buffers `d`; ev / known: the pools (numpy) or None; alias: out_probs IS x0"""
+    g = padded(d)
+    N, HW_, K = g["x0"].shape
+    tab = torch.from_numpy(table.view(np.int32).reshape(N, 8)).to(DEV)
+    gui = torch.from_numpy(guide.view(np.int32).reshape(N, 8)).to(DEV)
+    ev_d = None if ev is None else torch.from_numpy(ev).to(DEV)
+    known_d = None if known is None else torch.from_numpy(known).to(DEV)
+    hip.check(getattr(lib, SYMBOL)(g["x0"].data_ptr(), tab.data_ptr(), gui.data_ptr(), None if ev is None else ev_d.data_ptr(),
+                                   None if known is None else known_d.data_ptr(), N, HW_, K, g["xt"].data_ptr(),
+                                   g["xin"].data_ptr() if with_xin else None, d["xin"].shape[2], (g["x0"] if alias else g["probs"]).data_ptr(),
+                                   g["onehot"].data_ptr(), 0), SYMBOL)
+    torch.cuda.synchronize()
+    return unpadded(g, d, f"xin={with_xin} alias={alias}")
+
+
+def run_definition(lib, d, table, ev, known, slots, with_xin, alias):
+    """The definition: per running slot ccdm_shaped_step with the slot's evidence and shaping, then — where it has known labels —
+    ccdm_known_labels_step with its clamp pair, N = 1, pointers offset to the slot."""
+    g = padded(d)
+    N, HW_, K = g["x0"].shape
+    stride = d["xin"].shape[2]
+    ev_d, known_d = torch.from_numpy(ev).to(DEV), torch.from_numpy(known).to(DEV)
+    for n, s in slots.items():
+        r = table[n]
+        x0 = g["x0"].data_ptr() + n * HW_ * K * 4
+        key = int(r["key_lo"]) | int(r["key_hi"]) << 32
+        state = (g["xt"].data_ptr() + n * HW_, g["xin"].data_ptr() + n * HW_ * stride * 4 if with_xin else None, stride,
+                 x0 if alias else g["probs"].data_ptr() + n * HW_ * K * 4, g["onehot"].data_ptr() + n * HW_ * K * 8, 0)
+        hip.check(lib.ccdm_shaped_step(x0, ev_d.data_ptr() + n * HW_ * K * 4 if s["ev"] else None, 1, HW_, K, s["inv_t"], s["top_r"],
+                                       float(r["alpha_t"]), float(r["cumalpha_tm1"]), int(r["mode"]), int(r["step_row"]), key, int(r["sample"]),
+                                       *state), "ccdm_shaped_step")
+        if s["known"]:
+            hip.check(lib.ccdm_known_labels_step(known_d.data_ptr() + n * HW_, 1, HW_, K, s["p_hit"], s["p_miss"], int(r["mode"]),
+                                                 int(r["step_row"]), key, int(r["sample"]), *state), "ccdm_known_labels_step")
+    torch.cuda.synchronize()
+    return unpadded(g, d, "definition")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("K", KS)
+def test_neutral_guide_rows_are_the_plain_slots_step(lib, K):
+    """Neutral guide rows (1, 1, 0, 0, flags 0) and NULL pools: xt, xin, out_probs and out_onehot are torch.equal to what ccdm_slots_step
+    leaves, for the four modes and the idle slot, with xin (stride > K) and without, out_probs aliased to x0 and not."""
+    d = slot_buffers(K, HW, stride_of(K))
+    table = slot_table()
+    guide = np.zeros(len(MODES), serving.GUIDE_DTYPE)
+    guide["inv_temperature"], guide["top_r"] = 1.0, 1.0
+    for with_xin in (True, False):
+        for alias in (False, True):
+            got, want = run_guided(lib, d, table, guide, None, None, with_xin, alias), run_slots(lib, d, table, with_xin, alias)
+            for k in d:
+                assert torch.equal(got[k], want[k]), f"xin={with_xin} alias={alias}: {k} differs in {int((got[k] != want[k]).sum())} places"
+            assert not torch.equal(got["xt"][0], d["xt"][0]) and torch.equal(got["xt"][IDLE], d["xt"][IDLE])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("K", KS)
+def test_mixed_guidance_equals_the_shaped_step_and_the_clamp_slot_by_slot(lib, K):
+    """Five slots, one idle; the running ones carry all three kinds of guidance, evidence only (with weights of 0), shaping only (a top_r
+    that keeps one class) and known labels only, rotated so that every kind meets every step mode.  Every buffer is torch.equal to what
+    ccdm_shaped_step followed by ccdm_known_labels_step leaves, called for each slot alone; the idle slot's rows of every buffer are the
+    fill they started with although its guide row sets both flags and its pool rows hold NaN weights and label 0; the image channels of
+    xin and the guard elements behind xt and xin are untouched."""
+    d = slot_buffers(K, HW, stride_of(K))
+    for rotation in range(4):
+        table, guide, ev, known, slots = guide_inputs(K, rotation)
+        for with_xin, alias in ((True, True), (True, False), (False, True)):
+            what = f"rotation={rotation} xin={with_xin} alias={alias}"
+            got = run_guided(lib, d, table, guide, ev, known, with_xin, alias)
+            want = run_definition(lib, d, table, ev, known, slots, with_xin, alias)
+            for k in d:
+                assert torch.equal(got[k], want[k]), f"{what}: {k} differs in {int((got[k] != want[k]).sum())} places"
+                assert torch.equal(got[k][IDLE], d[k][IDLE]), f"{what}: the idle slot's {k} changed"
+            assert not bool(torch.isnan(got["x0"]).any()) and not bool(torch.isnan(got["probs"]).any()), what
+            assert torch.equal(got["xin"][..., K:], d["xin"][..., K:]), what + ": an image channel changed"
+            if not with_xin:
+                assert torch.equal(got["xin"], d["xin"]), what
+            # the guidance took effect: a last-step slot with known labels returns them; the draw of a guided slot is not the plain one
+            plain = run_slots(lib, d, table, with_xin, alias)
+            for n, s in slots.items():
+                mode = MODES[n]
+                is_known = torch.from_numpy(known[n] < K).to(DEV)
+                labels = torch.from_numpy(known[n]).to(DEV)
+                if s["known"] and mode != hip.STEP_SAMPLE:
+                    assert torch.equal(got["xt"][n][is_known], labels[is_known]), (what, n)
+                    probs = (got["x0"] if alias else got["probs"])[n]
+                    assert bool((probs[is_known].max(-1).values == 1).all()) and bool((got["onehot"][n][is_known].sum(-1) == 1).all()), (what, n)
+                    assert torch.equal(got["onehot"][n][is_known].argmax(-1).to(torch.uint8), labels[is_known]), (what, n)
+                    if with_xin:
+                        assert torch.equal(got["xin"][n, :, :K][is_known].argmax(-1).to(torch.uint8), labels[is_known]), (what, n)
+                if mode == hip.STEP_SAMPLE:
+                    # (slot 0 carries the coefficients of t = 200 of 250: x0 barely moves its posterior, so evidence alone need not
+                    # change a draw there; the clamp redraws the known pixels on its own counters and does)
+                    assert s["kind"] not in ("all", "known") or not torch.equal(got["xt"][n], plain["xt"][n]), (what, n, s["kind"])
+                    if with_xin:
+                        assert torch.equal(got["xin"][n, :, :K].argmax(-1).to(torch.uint8), got["xt"][n]), (what, n)
+                        assert bool((got["xin"][n, :, :K].sum(-1) == 1).all()), (what, n)
+                if mode == hip.STEP_LAST_CONFIDENCE and s["kind"] == "shaping":
+                    # one class kept: the posterior of a one-hot x0 — not the plain one
+                    assert not torch.equal((got["x0"] if alias else got["probs"])[n], (plain["x0"] if alias else plain["probs"])[n]), (what, n)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("K", [2, 5, 33])
+def test_nothing_is_written_behind_the_buffers(lib, K):
+    """N * HW = 975 pixels: the last block of every kernel shape is partial (975 = 3 * 256 + 207 = 15 * 64 + 15).  With every running slot
+    guided in all three ways, the bytes behind N * HW of xt and the floats behind the last row of xin are what they were (run_guided
+    asserts it), and so is the last pixel's image channel."""
+    d = slot_buffers(K, HW, stride_of(K))
+    table, guide, ev, known, _ = guide_inputs(K, 0)
+    for n in RUNNING:
+        guide["flags"][n] = EV | KNOWN
+        guide["inv_temperature"][n], guide["top_r"][n] = np.float32(1 / 0.7), np.float32(0.9)
+    last = len(MODES) - 1
+    table["mode"][last] = hip.STEP_SAMPLE         # the slot that ends at the buffers' end draws and writes its one-hot
+    got = run_guided(lib, d, table, guide, ev, known, True, True)
+    assert torch.equal(got["xin"][..., K:], d["xin"][..., K:]) and not torch.equal(got["xt"][last], d["xt"][last])
+
+
+# ------------------------------------------------------------------------------------------------ GPU: the queue
+T_FULL = 10000 + T_SMALL          # the strided form of the full walk
+# (name, n, t, vote, guidance kinds): different sizes, walks, guidance and votes, so both result kinds appear
+REQUESTS = [("A", 3, T_FULL, None, ("evidence", "temperature")), ("B", 1, int(T_STRIDED), "confidence", ("known_labels", "truncation")),
+            ("C", 2, None, None, ())]
+CAPACITY = 4
+
+
+@pytest.fixture(scope="module", params=[2, 5], ids=["K2-fused-head", "K5-epilogue-xin"])
+def sampler(request):
+    """The small model, the three requests' inputs and guidance and — computed once — each request's solo call with the same keywords:
+    philox_call = the request's call index (A: 0 .. C: 2) and step_T_sample = its vote."""
+    s = make_sampler(request.param)
+    model, K = s["model"], s["K"]
+    model.philox_advance = True
+    rng = np.random.default_rng(1200 + K)
+    reqs = {}
+    for call, (name, n, t, vote, kinds) in enumerate(REQUESTS):
+        cond = torch.from_numpy(rng.uniform(-1, 1, (n, 1, H, W)).astype(np.float32)).to(DEV)
+        x = torch.nn.functional.one_hot(torch.from_numpy(rng.integers(0, K, (n, H, W))), K).permute(0, 3, 1, 2).float().contiguous().to(DEV)
+        kw = {}
+        if "evidence" in kinds:
+            kw["evidence"] = sampler_evidence(rng, n, K, onehot_share=0.2)[0]
+        if "known_labels" in kinds:
+            labels = torch.from_numpy(rng.integers(0, K, (n, H, W)))
+            kw["known_labels"] = torch.where(torch.from_numpy(rng.random((n, H, W)) < 0.3), labels, torch.full_like(labels, FREE))
+        if "temperature" in kinds:
+            kw["temperature"] = 0.7
+        if "truncation" in kinds:
+            kw["truncation"] = 0.8
+        reqs[name] = dict(name=name, n=n, t=t, vote=vote, call=call, cond=cond, x=x, kw=kw)
+        reqs[name]["solo"] = solo(model, reqs[name])
+        reqs[name]["unguided"] = solo(model, dict(reqs[name], kw={}))
+    s["reqs"] = reqs
+    return s
+
+
+def solo(model, r):
+    keep = model.philox_call, model.step_T_sample
+    model.philox_call, model.step_T_sample = r["call"], r["vote"] or "majority"
+    try:
+        return model(r["x"], r["cond"], t=None if r["t"] is None else torch.as_tensor(r["t"]), **r["kw"])["diffusion_out"]
+    finally:
+        model.philox_call, model.step_T_sample = keep
+
+
+def submit(q, model, r):
+    model.philox_call = r["call"]
+    return q.submit(r["cond"], x=r["x"], t=r["t"], vote=r["vote"], **(r["kw"] if q.guided else {}))
+
+
+def assert_equals_solo(res, r, what=""):
+    out = res.result()["diffusion_out"]
+    want = r["solo"]
+    assert out.dtype == want.dtype and out.shape == want.shape and out.device == want.device, (what, r["name"])
+    assert torch.equal(out, want), f"{what} request {r['name']}: {int((out != want).sum())} of {out.numel()} values differ from the solo call"
+
+
+def run_schedule(q, model, reqs, arrivals):
+    res = {}
+    for tick in range(max(arrivals) + 1):
+        for name in arrivals.get(tick, []):
+            res[name] = submit(q, model, reqs[name])
+        q.step()
+    q.run_until_idle()
+    return res
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("use_graph", [True, False], ids=["graph", "eager"])
+@pytest.mark.parametrize("arrivals", [{0: ["A", "B", "C"]}, {0: ["C"], 1: ["B"], 3: ["A"]}], ids=["at-once", "staggered"])
+def test_every_guided_request_equals_its_solo_call(sampler, arrivals, use_graph):
+    """Three requests on a guided queue of capacity 4 (six samples: the last are admitted as slots come free): evidence and a temperature
+    (A, a class map), known labels and a truncation (B, the confidence probabilities), no guidance (C).  Each result is torch.equal to the
+    solo call with the same keywords, the form and dtype included; the guidance changed the results; B's known pixels are its labels."""
+    model, reqs = sampler["model"], sampler["reqs"]
+    model.use_graph = use_graph
+    try:
+        q = model.sampling_queue(CAPACITY, (1, H, W), guided=True)
+        res = run_schedule(q, model, reqs, arrivals)
+        assert all(r.done for r in res.values()) and q.idle and q.stats["requests_finished"] == 3
+        assert q.stats["busy_slot_steps"] == 3 * 6 + 1 * 4 + 2 * 6
+        for name, r in res.items():
+            assert_equals_solo(r, reqs[name], f"graph={use_graph}")
+        assert reqs["B"]["solo"].dtype == torch.float32 and reqs["A"]["solo"].dtype == torch.int64
+        # the keywords matter (so the comparison is not of two unguided results) ...
+        for name in "AB":
+            assert not torch.equal(reqs[name]["unguided"], reqs[name]["solo"]), name
+        # ... and the known pixels of B's result carry B's labels with probability 1
+        labels = reqs["B"]["kw"]["known_labels"].to(DEV)
+        out = res["B"].result()["diffusion_out"]
+        is_known = labels != FREE
+        assert torch.equal(out.argmax(1)[is_known], labels[is_known]) and bool((out.max(1).values[is_known] == 1).all())
+        assert res["A"].ev is None and res["B"].known is None and res["B"].cond is None          # released when done
+    finally:
+        model.use_graph = True
+
+
+@pytest.mark.gpu
+def test_a_plain_call_and_a_plain_queue_between_ticks_change_nothing(sampler):
+    """Between the ticks of a guided queue: a plain model(x, image) call and the ticks of a plain queue on the same model.  Every guided
+    request still equals its solo call; the plain call returns what it returns alone; the plain queue's request equals its solo call,
+    and the plain queue launches ccdm_slots_step alone — counted on its engine — while the guided one never launches it."""
+    model, reqs = sampler["model"], sampler["reqs"]
+    guided, plain = model.sampling_queue(CAPACITY, (1, H, W), guided=True), model.sampling_queue(CAPACITY, (1, H, W))
+    calls = {}
+
+    def spy(eng, who):
+        for name in ("slots_step", "slots_guided_step", "set_slot_guidance"):
+            def counted(*a, _f=getattr(eng, name), _k=(who, name), **kw):
+                calls[_k] = calls.get(_k, 0) + 1
+                return _f(*a, **kw)
+            setattr(eng, name, counted)
+    spy(guided.engine, "guided")
+    spy(plain.engine, "plain")
+    res = {n: submit(guided, model, reqs[n]) for n in "ABC"}
+    unguided_c = dict(reqs["C"], kw={})
+    plain_res, call_out = None, None
+    for tick in range(14):
+        guided.step()
+        if tick == 1:
+            plain_res = submit(plain, model, unguided_c)
+        if tick == 2:
+            call_out = solo(model, reqs["C"])
+        plain.step()
+    assert guided.idle and plain.idle
+    for name, r in res.items():
+        assert_equals_solo(r, reqs[name], "beside a plain queue")
+    assert torch.equal(call_out, reqs["C"]["solo"])
+    assert_equals_solo(plain_res, reqs["C"], "the plain queue's")
+    assert calls[("plain", "slots_step")] == plain.stats["ticks"] == 6 and ("plain", "slots_guided_step") not in calls
+    assert ("plain", "set_slot_guidance") not in calls and plain.engine._slot_pools is None          # a plain queue pays nothing
+    assert calls[("guided", "slots_guided_step")] == guided.stats["ticks"] and ("guided", "slots_step") not in calls
+    assert calls[("guided", "set_slot_guidance")] >= 2 and guided.engine._slot_pools is not None
+    with pytest.raises(ValueError, match="temperature: guidance keywords are not built for queued requests"):
+        plain.submit(reqs["C"]["cond"], temperature=1.0)
+
+
+@pytest.mark.gpu
+def test_a_set_range_flag_fails_a_guided_request_until_reset(sampler):
+    """A range flag set by hand on the guided queue's engine (the plain queue's test sets it the same way) makes the next finishing
+    guided request raise CcdmRangeError, and submit refuses until reset(); after it the request reproduces its solo result."""
+    model, reqs = sampler["model"], sampler["reqs"]
+    q = model.sampling_queue(CAPACITY, (1, H, W), guided=True)
+    assert_equals_solo(submit(q, model, reqs["B"]), reqs["B"], "before the flag")
+    eng = q.engine
+    with eng.enter():
+        eng.flag.fill_(1)
+    eng.leave()
+    bad = submit(q, model, reqs["B"])
+    with pytest.raises(hip.CcdmRangeError):
+        bad.result()
+    with pytest.raises(hip.CcdmRangeError):
+        submit(q, model, reqs["A"])
+    q.reset()
+    assert q.idle
+    assert_equals_solo(submit(q, model, reqs["A"]), reqs["A"], "after reset")

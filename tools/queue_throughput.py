@@ -18,12 +18,23 @@ repetition, in rotating order.  Per variant: samples/s of every repetition, thei
 the per-slot parameters (and of one stream where the guided call takes two sub-batch streams); the gap between (c) and (d) is the price
 of the unfused step that every guided call already pays.
 
+`--guided`: the annotator-in-the-loop form of the same question, on the same windows.  Every request carries an evidence map, a
+known-label map that covers a quarter of the pixels and temperature = 0.7:
+    guided_queue      the requests through a queue built with guided=True (every tick's step is ccdm_slots_guided_step)
+    guided_solo       the same requests as closed calls model(x, image, evidence=, known_labels=, temperature=0.7) at batch 8
+    guided_solo_64    the same samples and guidance as closed calls at batch `--capacity`: per step the launches a guided tick fuses —
+                      the network to x0, the shaped step (k_guided), the clamp (k_known_labels_step) — at the queue's batch
+    guided_solo_64_one_stream   the same pinned to one stream (substreams = 1), as the queue runs: its two step kernels run on all
+                      `--capacity` rows at once, the launches to hold ccdm_slots_guided_step's time against in a kernel trace
+    queue             the plain queue on the same images without the guidance, in the same run: what the guidance costs a queue
+Acceptance there: guided_queue exceeds guided_solo by more than the latter's spread.
+
 Prints one JSON line.
 
 `--only a,b` runs those variants alone (a kernel trace of one variant: rocprofv3 --kernel-trace --stats -- python tools/queue_throughput.py
 --only queue --requests 8 --steps 50, then tools/trace_gaps.py on its output); the comparisons that need a missing variant are left out.
 
-    python tools/queue_throughput.py [--requests 16] [--request-size 8] [--capacity 64] [--reps 3] [--steps 250] [--only queue,guided_64]"""
+    python tools/queue_throughput.py [--requests 16] [--request-size 8] [--capacity 64] [--reps 3] [--steps 250] [--only queue,guided_64] [--guided]"""
 import argparse
 import json
 import os
@@ -45,6 +56,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--steps", type=int, default=250, help="rows of every walk (< T: strided)")
     ap.add_argument("--only", default="", help="comma-separated variants to run (default: all)")
+    ap.add_argument("--guided", action="store_true", help="guided requests: guided_queue against guided_solo and the plain queue")
     a = ap.parse_args()
     if a.reps < 3:
         raise SystemExit("queue_throughput: at least three repetitions (a variant's own spread has to be known)")
@@ -91,8 +103,40 @@ def main():
                 model.substreams = 0
         return run
 
+    # --guided: per sample an evidence map (weights in [0.05, 1]) and a known-label map that covers a quarter of the pixels; host tensors,
+    # as a caller has them (the model's checks read them on the host either way)
+    if a.guided:
+        evidence = torch.from_numpy(rng.uniform(0.05, 1.0, (total, K, H, W)).astype(np.float32))
+        labels = torch.from_numpy(rng.integers(0, K, (total, H, W)))
+        known = torch.where(torch.from_numpy(rng.random((total, H, W)) < 0.25), labels, torch.full_like(labels, 255))
+        guided_queue = model.sampling_queue(cap, (1, H, W), guided=True)
+
+    def guidance(i, size=None):
+        size = size or n
+        return dict(evidence=evidence[i:i + size], known_labels=known[i:i + size], temperature=0.7)
+
+    def run_guided_queue():
+        rs = [guided_queue.submit(image[i:i + n], x=x[i:i + n], t=t, **guidance(i)) for i in range(0, total, n)]
+        guided_queue.run_until_idle()
+        return [r.result()["diffusion_out"] for r in rs]
+
+    def run_guided_solo():
+        return [model(x[i:i + n], image[i:i + n], t=tt, **guidance(i))["diffusion_out"] for i in range(0, total, n)]
+
+    def run_guided_solo_64(substreams=0):
+        def run():
+            model.substreams = substreams
+            try:
+                return [model(x[i:i + cap], image[i:i + cap], t=tt, **guidance(i, cap))["diffusion_out"] for i in range(0, total, cap)]
+            finally:
+                model.substreams = 0
+        return run
+
     variants = {"queue": run_queue, "solo_throughput": run_solo("throughput"), "solo_latency": run_solo("latency"),
                 "guided_64": run_batch(temperature=1.0), "guided_64_one_stream": run_batch(1, temperature=1.0), "plain_64": run_batch()}
+    if a.guided:
+        variants = {"guided_queue": run_guided_queue, "guided_solo": run_guided_solo, "guided_solo_64": run_guided_solo_64(),
+                    "guided_solo_64_one_stream": run_guided_solo_64(1), "queue": run_queue}
     if a.only:
         unknown = [v for v in a.only.split(",") if v not in variants]
         if unknown:
@@ -102,7 +146,7 @@ def main():
     for name, fn in variants.items():                        # untimed: engines, graph capture, the plain call's mode calibration
         fn()
         torch.cuda.synchronize(dev)
-        modes[name] = None if name == "queue" else list(model.last_mode)
+        modes[name] = None if name in ("queue", "guided_queue") else list(model.last_mode)
     rate = {name: [] for name in variants}
     order = list(variants)
     for _ in range(a.reps):
@@ -117,16 +161,21 @@ def main():
     spread = {k: (max(v) - min(v)) / med[k] for k, v in rate.items()}
     res = {"shape": {"K": K, "size": [H, W], "steps": a.steps, "requests": a.requests, "request_size": n, "capacity": cap},
            "reps": a.reps, "mode_streams_graph": modes, "queue_stats": dict(queue.stats),
+           **({"guided_queue_stats": dict(guided_queue.stats)} if a.guided else {}),
            "samples_per_s": {k: {"median": round(med[k], 2), "min": round(min(v), 2), "max": round(max(v), 2), "spread": round(spread[k], 4),
                                  "all": [round(r, 2) for r in v]} for k, v in rate.items()}}
     for num, den in (("queue", "solo_throughput"), ("queue", "solo_latency"), ("queue", "guided_64"), ("queue", "guided_64_one_stream"),
-                     ("guided_64", "plain_64")):
+                     ("guided_64", "plain_64"), ("guided_queue", "guided_solo"), ("guided_queue", "guided_solo_64"),
+                     ("guided_queue", "guided_solo_64_one_stream"),
+                     ("guided_queue", "queue")):
         if num in med and den in med:
             res[f"{num}_over_{den}"] = round(med[num] / med[den], 4)
     if all(k in med for k in ("queue", "solo_throughput", "solo_latency")):
         b_best = max(med["solo_throughput"], med["solo_latency"])
         b_spread = max(spread["solo_throughput"], spread["solo_latency"])
         res["accepted"] = bool(med["queue"] > b_best * (1.0 + b_spread))
+    if "guided_queue" in med and "guided_solo" in med:
+        res["accepted"] = bool(med["guided_queue"] > med["guided_solo"] * (1.0 + spread["guided_solo"]))
     if "queue" in med and "guided_64" in med:
         res["queue_short_of_guided_64_by_more_than_its_spread"] = bool(med["queue"] < med["guided_64"] * (1.0 - spread["guided_64"]))
     print(json.dumps(res), flush=True)
