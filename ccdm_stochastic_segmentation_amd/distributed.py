@@ -14,6 +14,8 @@ from typing import Optional, Tuple
 import torch
 import torch.distributed as dist
 
+from .guidance import known_keywords, sample_axis
+
 
 def shard_range(n: int, rank: int, world: int) -> Tuple[int, int]:
     """Contiguous [start, stop) of rank's samples; the first n % world ranks get one extra."""
@@ -165,14 +167,13 @@ def _check_same_host_rng(world: int, device) -> None:
 
 
 def sample_sharded(model, x: torch.Tensor, condition: torch.Tensor, feature_condition: Optional[torch.Tensor] = None,
-                   t: Optional[torch.Tensor] = None, gather=True, *, known_labels: Optional[torch.Tensor] = None,
-                   resample: Optional[Tuple[int, int]] = None, evidence: Optional[torch.Tensor] = None,
-                   temperature: Optional[float] = None, truncation: Optional[float] = None, views=None, tiles=None) -> torch.Tensor:
+                   t: Optional[torch.Tensor] = None, gather=True, **guidance) -> torch.Tensor:
     """Run `model` (a DenoisingModel-like callable) on this rank's shard of the global batch and return the
     full [N,K,H,W] prediction on every rank, or only the local shard (gather=False).
     gather=True: fp32 probabilities travel as they are; int64 one-hot ("majority") predictions travel as their uint8 argmax map
     (K*8 x fewer bytes: 16 MB instead of 1.3 GB at BASELINE config C5) and are rebuilt on arrival;
     gather="index": force the index form for any output (fp32 one-hot of a shortened walk).
+    **guidance: the keywords of guidance.GUIDANCE_KEYWORDS; one that is None is not handed on.
     known_labels: handed to the model as it is — x, condition and feature_condition are sliced here, this map is NOT: the caller passes
     the slice [lo:hi] = shard_range(N, rank, world) of its global map (the draw at the known pixels is keyed by the global sample index,
     so the shards reproduce the single-process samples).
@@ -183,6 +184,7 @@ def sample_sharded(model, x: torch.Tensor, condition: torch.Tensor, feature_cond
     feature_condition [V,N,...] (DenoisingModel's `views`) is sliced along its sample axis.
     tiles: (h, w, sy, sx), handed to the model as it is (the tiled draw is keyed by the canvas pixel and the global sample index, never by
     the engine row or tile); a feature_condition [R,N,...] (DenoisingModel's `tiles`) is sliced along its sample axis."""
+    known_keywords("sample_sharded", guidance)
     world = dist.get_world_size() if dist.is_initialized() else 1
     rank = dist.get_rank() if dist.is_initialized() else 0
     n = x.shape[0]
@@ -192,24 +194,9 @@ def sample_sharded(model, x: torch.Tensor, condition: torch.Tensor, feature_cond
     model.sample_offset = lo
     model.noise_slice = (n, lo)
     try:
-        kw = {} if t is None else {"t": t}
-        if known_labels is not None:
-            kw["known_labels"] = known_labels
-        if resample is not None:
-            kw["resample"] = resample
-        if evidence is not None:
-            kw["evidence"] = evidence
-        if temperature is not None:
-            kw["temperature"] = temperature
-        if truncation is not None:
-            kw["truncation"] = truncation
-        if views is not None:
-            kw["views"] = views
-        if tiles is not None:
-            kw["tiles"] = tiles
-        per_view = ((views is not None and len(views) > 0) or tiles is not None) and feature_condition is not None \
-            and feature_condition.ndim == 5
-        fc = None if feature_condition is None else (feature_condition[:, lo:hi] if per_view else feature_condition[lo:hi])
+        kw = {k: v for k, v in dict(guidance, t=t).items() if v is not None}
+        fc = None if feature_condition is None else \
+            feature_condition.narrow(sample_axis(feature_condition, guidance.get("views"), guidance.get("tiles")), lo, hi - lo)
         out = model(x[lo:hi], condition[lo:hi], fc, **kw)["diffusion_out"].contiguous()
     finally:
         model.sample_offset = 0

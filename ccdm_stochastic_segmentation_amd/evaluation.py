@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import metrics as M
+from .guidance import VIEW_FLIPS, tile_origins
 from .models import OneHotCategoricalBCHW, build_model
 
 LOGGER = logging.getLogger(__name__)
@@ -189,16 +190,14 @@ def view_features(encoder, image: torch.Tensor, views) -> torch.Tensor:
     """The feature condition of a call with `views` (DenoisingModel's keyword): [V,B,Cf,h,w], view 0 the encoder's features of the
     image, view v >= 1 those of the image mirrored as views[v - 1] says — the encoder runs once per view on the mirrored pixels, its
     output is not flipped after the fact (a ViT's features of a mirrored image are not the mirrored features)."""
-    from .models import DenoisingModel
-    flips = [DenoisingModel.VIEW_FLIPS[v] for v in views]
+    flips = [VIEW_FLIPS[v] for v in views]
     return torch.stack([encoder(image)] + [encoder(torch.flip(image, [d for b, d in ((1, 3), (2, 2)) if f & b])) for f in flips], 0)
 
 
 def tile_features(encoder, image: torch.Tensor, tiles) -> torch.Tensor:
     """The feature condition of a call with `tiles` = (h, w, sy, sx) (DenoisingModel's keyword): [R,B,Cf,hf,wf], tile r the encoder's
-    features of the image cropped to tile r (models.tile_origins, r = i * Tx + j) — the encoder runs once per tile on the cropped
+    features of the image cropped to tile r (guidance.tile_origins, r = i * Tx + j) — the encoder runs once per tile on the cropped
     pixels, as the network does."""
-    from .models import tile_origins
     h, w, sy, sx = (int(v) for v in tiles)
     oys, oxs = tile_origins(int(image.shape[2]), int(image.shape[3]), h, w, sy, sx)
     return torch.stack([encoder(image[:, :, oy:oy + h, ox:ox + w]) for oy in oys for ox in oxs], 0)

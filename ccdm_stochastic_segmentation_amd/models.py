@@ -12,17 +12,18 @@ Inference only: there is no autograd through the HIP kernels.
 """
 from __future__ import annotations
 
-import dataclasses
 import logging
 import math
-from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple, Union, cast
+from typing import Any, Callable, Dict, List, Mapping, Optional, Sequence, Tuple, Union, cast
 
 import numpy as np
 import torch
 from torch import Tensor, nn
 
+from . import guidance as G
 from . import hip
 from .engine import SamplerEngine, TileCanvas
+from .guidance import GUIDANCE_KEYWORDS, KNOWN_FREE, VIEW_FLIPS, Guidance, resample_walk, tile_origins  # noqa: F401  (their home is guidance.py)
 from .unet_spec import UNetSpec, make_unet_spec
 
 LOGGER = logging.getLogger(__name__)
@@ -68,45 +69,6 @@ def step_values(time_steps: int, init_t: Optional[int]) -> List[int]:
         LOGGER.warning(f"Override default {time_steps} time steps with {len(vals)}.")
         return vals
     return list(range(init_t, 0, -1))
-
-
-def resample_walk(S: int, jump_length: int, resamples: int) -> List[Tuple[int, int, Optional[int]]]:
-    """The order in which a walk of S table rows with RePaint's resampling jumps (Lugmayr et al. 2022) visits its rows: a list of
-    (row, pass, renoise_from).  Level L is the state before row L, R = S - L rows remain below it.  Jump points are the levels with
-    R in {j, 2j, 3j, ...} and R < S - j (j = jump_length): the walk never jumps back to the pure-noise level (RePaint's rule).  Each
-    jump point has `resamples` - 1 jumps; walking down, a level that has jumps left uses one: the state is renoised from level L to
-    level L - j and the walk continues at row L - j.  `pass` counts the earlier visits of the row (it selects the noise key of the
-    visit, see pass_key); `renoise_from` is the level the state is renoised from before this row runs, or None.
-    A deviation from RePaint: no jump starts at R = 0.  The last row returns an argmax or a probability map, not a draw of the chain,
-    so there is nothing to renoise.  resamples = 1 or jump_length = 0 gives the plain walk; so does a jump_length with no jump point.
-    The length is S + (resamples - 1) * j * #{m >= 1 : m * j < S - j}."""
-    S, j, r = int(S), int(jump_length), int(resamples)
-    left = {R: r - 1 for R in range(j, S - j, j)} if (j > 0 and r > 1) else {}
-    visits = [0] * S
-    walk: List[Tuple[int, int, Optional[int]]] = []
-    L, renoise_from = 0, None
-    while L < S:
-        walk.append((L, visits[L], renoise_from))
-        visits[L] += 1
-        renoise_from = None
-        L += 1
-        if left.get(S - L, 0) > 0:
-            left[S - L] -= 1
-            renoise_from = L
-            L -= j
-    return walk
-
-
-def tile_origins(Hc: int, Wc: int, h: int, w: int, sy: int, sx: int) -> Tuple[List[int], List[int]]:
-    """The tiling of a canvas Hc x Wc by tiles h x w at strides (sy, sx), 1 <= sy <= h <= Hc and 1 <= sx <= w <= Wc, as include/ccdm_hip.h
-    defines it (ccdm_tiled_step derives the same origins): (oys, oxs) with oys[i] = min(i * sy, Hc - h) for the Ty = 1 + ceil((Hc - h) /
-    sy) tiles along y — the last tile is pushed back so that it ends at the border; the origins are distinct and leave no gap — and the
-    same along x.  Tile r = i * len(oxs) + j covers rows oys[i] .. oys[i] + h - 1 and columns oxs[j] .. oxs[j] + w - 1."""
-    Hc, Wc, h, w, sy, sx = (int(v) for v in (Hc, Wc, h, w, sy, sx))
-    if not (1 <= sy <= h <= Hc and 1 <= sx <= w <= Wc):
-        raise ValueError(f"tiles: need 1 <= sy <= h <= Hc and 1 <= sx <= w <= Wc, got canvas {Hc}x{Wc}, tile {h}x{w}, strides ({sy}, {sx})")
-    return ([min(i * sy, Hc - h) for i in range(1 + -((h - Hc) // sy))],
-            [min(j * sx, Wc - w) for j in range(1 + -((w - Wc) // sx))])
 
 
 def pass_key(key: int, p: int) -> int:
@@ -195,34 +157,6 @@ def bound_rows(timesteps: np.ndarray, draws: int, rows: int, K: int, cumalphas: 
             slot[n] = (l * M + m) * draws + d
         passes.append((table, slot))
     return passes
-
-
-@dataclasses.dataclass(frozen=True)
-class Guidance:
-    """What guides one sampling call, as DenoisingModel._check_guidance returns it: `known` uint8 [N,H*W] (_check_known_labels), `jumps`
-    (jump_length, resamples) (_check_resample), `evidence` fp32 [N,H*W,K] (_check_evidence), `shaping` (inv_temperature, top_r)
-    (_check_shaping), `views` the flip codes of views 1 .. V - 1 (_check_views: bit 0 mirrors x, bit 1 mirrors y; view 0 is the identity),
-    `tiles` (h, w, sy, sx) (_check_tiles); None each where the call has none."""
-    known: Optional[Tensor] = None
-    jumps: Optional[Tuple[int, int]] = None
-    evidence: Optional[Tensor] = None
-    shaping: Optional[Tuple[float, float]] = None
-    views: Optional[Tuple[int, ...]] = None
-    tiles: Optional[Tuple[int, int, int, int]] = None
-
-    def __bool__(self) -> bool:
-        """The walk has something to do between the network's steps (jumps need known labels)."""
-        return self.known is not None or self.evidence is not None or self.shaping is not None or self.views is not None \
-            or self.tiles is not None
-
-    def walk(self, S: int) -> List[Tuple[int, int, Optional[int]]]:
-        """The (row, pass, renoise_from) entries of a walk of S table rows: resample_walk's; [(s, 0, None) ...] without jumps."""
-        return resample_walk(S, *(self.jumps or (0, 1)))
-
-    def repeat_interleave(self, S: int) -> "Guidance":
-        """For a batch in which every sample is repeated S times (predict_multiple(batched=True))."""
-        return Guidance(*(v.repeat_interleave(S, dim=0) if isinstance(v, Tensor) else v
-                          for v in (self.known, self.jumps, self.evidence, self.shaping, self.views, self.tiles)))
 
 
 class OneHotCategoricalBCHW:
@@ -435,93 +369,9 @@ class DenoisingModel(nn.Module):
     hip.PREC_F32 (exact fp32 MFMA everywhere, the validation mode).  hip.PREC_F16 is the OPT-IN single-pass fast mode (every conv on the
     general kernel with one fp16 MFMA per product; attention cores keep the split): narrower arithmetic than the reference's, outside the
     parity contract, never a default.
-    `known_labels` (keyword of `forward`, `forward_denoising`, `predict_multiple`): sample segmentations that agree with labels already at
-    hand — an integer map [N,H,W] holding a class in [0,K) where the label is known and 255 where the pixel is free.  The replacement
-    method of RePaint (Lugmayr et al. 2022) for categorical diffusion, no retraining: after every reverse step each known pixel is
-    overwritten with a draw from the forward process at that step's noise level, q(x_{t-1} | x_0 = y) = Cat(cumalpha_{t-1} onehot(y) +
-    (1 - cumalpha_{t-1}) / K) (ccdm_known_labels_step, one launch per step and sub-batch), so the network sees known pixels that carry the
-    right amount of noise and denoises the free ones in agreement with them.  x_T is left as given (at t = T the forward process is
-    uniform to within cumalpha_T); the state a walk returns carries the labels themselves: its last row is clamped with cumalpha = 1, at
-    t = 1 (where cumalpha_0 = 1 anyway) and on a walk that stops above it.  The draw is keyed by (pixel, global sample index, step row)
-    under the call's Philox key on counters the epilogue never uses: results do not depend on `substreams`, `use_graph` or how the
-    batch is sharded (a caller that shards passes its shard's slice of the map).  A conditioned call walks every engine one step at a
-    time and takes the static execution-mode rule (no `calibrate_mode` measurement); rng = "torch_cpu" has no reference stream for this
-    draw and is refused.  Without the keyword nothing changes: no extra launch, no per-step stepping.
-    `resample` = (jump_length, resamples) (keyword next to `known_labels`, which it needs): RePaint's resampling jumps.  With the
-    clamp alone the free pixels get one reverse step per noise level to agree with known pixels that were drawn independently of them.
-    A resampled walk goes back up the chain by `jump_length` levels at every jump point and walks down again, `resamples` times per
-    band (`resample_walk` is the order of the rows), so the free pixels are denoised again with the known ones in view.  Going up is
-    one launch of ccdm_renoise_step whatever the jump length: every pixel is redrawn from q(x_t | x_{t-j}) = Cat(r onehot(x_{t-j}) +
-    (1 - r) / K), r = cumalpha_t / cumalpha_{t-j}.  Pass p of a row draws under pass_key(key, p), so a revisit sees fresh noise and the
-    walk up to the first jump is the plain conditioned walk bit for bit.  The step tables, the captured graphs and the independence of
-    `substreams`, `use_graph` and sharding are those of a conditioned call.  None, (j, 1), (0, r) and a jump_length without a jump
-    point change nothing.
-    `evidence` (keyword next to `known_labels`): sample under per-pixel SOFT evidence — a float map [N,K,H,W] of class weights in
-    [0,1], w_k proportional to the likelihood p(e | x_0 = k) of independent evidence e at that pixel: a scribble the annotator is fairly
-    sure of (0.9 on its class, 0.1 elsewhere), another model's or rater's probability map, classes that are impossible in a region
-    (weight 0), a per-class re-weighting for prior shift; all-ones is no evidence.  Exact for categorical diffusion, no gradient, no
-    scale, no retraining: the network predicts x0 = p(x_0 | x_t), Bayes gives p(x_0 | x_t, e) proportional to x0_k w_k, and the
-    reverse step's posterior is linear in that vector up to its normalisation — so every row's network pass stops at x0
-    (STEP_SOFTMAX_ONLY) and ccdm_evidence_step multiplies it by w and does the row's step with the counters of the unguided draw
-    (all-ones evidence reproduces the unguided call bit for bit).  The call walks like one with known labels: one step at a time, the
-    static execution-mode rule, results independent of `substreams`, `use_graph` and sharding (a caller that shards passes its shard's
-    slice).  Per walk entry: renoise (if a jump precedes), the network, the evidence step, the clamp — `evidence` composes with
-    `known_labels` and `resample`, whose rules do not change.  A pixel whose weights are all 0, a value outside [0,1], rng =
-    "torch_cpu" and a model with `softmax_output: no` (its x0 holds logits) are refused.
-    `temperature`, `truncation` (keywords next to `known_labels`): the two controls of a generative sampler, applied per pixel to the
-    network's x0 before the reverse step (ccdm_shaped_step; include/ccdm_hip.h has the definition).  temperature tau in [0.05, 20]
-    raises x0, relative to the pixel's largest value, to the power 1 / tau: below 1 the samples get less diverse and individually more
-    accurate, above 1 the reverse.  truncation r in (0, 1] ("top-r", the truncation sampling of Improved VQ-Diffusion, Tang et al.
-    2022) keeps the smallest set of classes whose mass reaches r and drops the rest, so a draw never picks a class the network gives
-    1 % to; it matters most on short strided walks.  Temper first, then truncate; nothing is renormalised, because the step posterior
-    is linear in x0 up to its own normalisation.  The last row's vote sees the shaped x0 too.  A shaped call walks like one with
-    evidence (every row's network pass stops at x0, one ccdm_shaped_step launch per walk entry, which also applies the evidence where
-    the call has some: no ccdm_evidence_step launch then), takes the static execution-mode rule and composes with `known_labels`,
-    `resample` and `evidence`.  A set keyword runs this path even at the neutral value 1.0, which reproduces the plain call bit for
-    bit; None for both changes nothing.  One (tau, r) per call: every row and every pass of predict_multiple uses it.  A training or
-    validation call, rng = "torch_cpu" and a model with `softmax_output: no` are refused.
-    `views` (keyword next to `known_labels`): flip test-time augmentation inside the sampler.  A tuple of distinct names from "hflip"
-    (mirrors x), "vflip" (mirrors y) and "hvflip" (both); the identity is always view 0, so V = 1 + len(views) <= 4.  At every reverse
-    step the network runs on all V mirror images of (x_t, image) and x0 is their mean, each mapped back: x0_sym = 1/V sum_g g^-1
-    x0(g x_t, g image), a denoiser that is exactly equivariant under the listed flips where the trained one is only approximately so.
-    Exact for categorical diffusion (a mean of probability vectors is one; the step posterior is linear in x0 up to its own
-    normalisation), no retraining, V network passes per step.  The V views of a sample are V rows of the engine's batch, view-major
-    (row v * n + j of a sub-batch of n samples is view v of sample j; the host mirrors x_T, the image and the features with torch.flip);
-    every row's network pass stops at x0 and ONE ccdm_views_step launch per walk entry takes the mean, applies `evidence`, `temperature`
-    and `truncation` where the call has them (it replaces those launches), draws with the counters of the plain call — keyed by the
-    identity view's pixel and the sample, never by the engine row — and writes the drawn class to every view at its mirrored place
-    (include/ccdm_hip.h has the definition).  Results are read from view 0.  A call with views takes the static execution-mode rule
-    (`auto_substreams` sees V * N samples) and does not depend on `substreams`, `use_graph` or sharding.  A model that takes a
-    `feature_condition` needs the features of every view from the caller's own encoder, [V,N,Cf,h,w] with view v computed from the
-    mirrored image.  Refused: unknown or duplicate names, a training or validation call, rng = "torch_cpu", `softmax_output: no`, and
-    `known_labels` / `resample` together with views (the clamp and the renoise draw per engine row, so the views would stop being
-    mirror images of one another: not built).  `views=()` or None is the plain call: no code path changes.
-    `tiles` = (h, w, sy, sx) (keyword next to `known_labels`): sample a canvas larger than the geometry the network was trained at — a
-    180x180 slice with a 128x128 model, a whole frame with a model trained on crops.  `x` is then the canvas x_T [N,K,Hc,Wc] and
-    `condition` the canvas image [N,C,Hc,Wc].  Windows sampled independently and pasted would disagree at the seams; this is the
-    MultiDiffusion construction (Bar-Tal et al. 2023) instead: ONE chain runs on the canvas, at every reverse step the network runs on
-    overlapping h x w tiles of the current canvas state (strides sy <= h, sx <= w; `tile_origins` has the tiling: the last tile along an
-    axis is pushed back to end at the border) and x0 of a canvas pixel is the mean over the c >= 1 tiles that cover it.  Exact for
-    categorical diffusion in the sense of `views` (a mean of probability vectors is one; the step posterior is linear in x0 up to its
-    own normalisation), no retraining, R network passes of h x w per step.  The R tiles of a sample are R rows of the engine's batch,
-    tile-major (row r * n + j of a sub-batch of n samples is tile r of sample j; the host crops x_T and the image by plain slicing);
-    every row's network pass stops at x0 and ONE ccdm_tiled_step launch per walk entry takes the per-pixel mean, applies `evidence`
-    (a canvas map [N,K,Hc,Wc]), `temperature` and `truncation` where the call has them (it replaces those launches), draws with the
-    counters of a plain call at the canvas's size — keyed by the canvas pixel and the sample, never by the engine row or tile — and
-    writes the drawn class to the canvas state and to every covering tile, so the tiles stay crops of one state (include/ccdm_hip.h
-    has the definition).  Results [N,K,Hc,Wc] are read from the canvas holder (engine.TileCanvas), which is also what `consume` gets.
-    A tiled call takes the static execution-mode rule (`auto_substreams` sees R * N samples of h x w; sub-batches split by sample, all
-    tiles of a sample in one engine) and does not depend on `substreams`, `use_graph` or sharding; one tile that is the canvas
-    reproduces the plain call bit for bit.  A model that takes a `feature_condition` needs the features of every tile from the caller's
-    own encoder, [R,N,Cf,hf,wf] (evaluation.tile_features).  Refused: anything but four integers, a stride < 1 or beyond the tile, a
-    tile larger than the canvas, a training or validation call, rng = "torch_cpu", `softmax_output: no`, and `views`, `known_labels`
-    or `resample` together with tiles (the clamp and the renoise draw per engine row, so overlapping tiles would stop being crops of
-    one state: not built).  The mean is uniform (no feathered weights) and all R * N rows run in one engine (no chunking).  None is the
-    plain call: no code path changes."""
+    The guidance keywords of a sampling call (guidance.GUIDANCE_KEYWORDS) are described, keyword by keyword, in guidance.py's docstring."""
 
-    VIEW_FLIPS = {"hflip": 1, "vflip": 2, "hvflip": 3}        # ccdm_views_step's two bits per view: bit 0 mirrors x, bit 1 mirrors y
-
-    KNOWN_FREE = 255        # the value of a free pixel in `known_labels`
+    VIEW_FLIPS, KNOWN_FREE = VIEW_FLIPS, KNOWN_FREE           # (aliases: their home is guidance.py)
 
     def __init__(self, diffusion: DiffusionModel, unet: UNetModel, dataset_file: str, step_T_sample: str = "majority"):
         super().__init__()
@@ -593,16 +443,10 @@ class DenoisingModel(nn.Module):
                 evidence: Optional[Tensor] = None, temperature: Optional[float] = None,
                 truncation: Optional[float] = None, views: Optional[Sequence[str]] = None,
                 tiles: Optional[Sequence[int]] = None) -> Union[Tensor, dict]:
-        if evidence is not None and (self.training or validation):
-            self._check_evidence(evidence, None, sampling=False)
+        guidance = dict(known_labels=known_labels, resample=resample, evidence=evidence, temperature=temperature, truncation=truncation,
+                        views=views, tiles=tiles)
         if self.training or validation:
-            self._check_tiles(tiles, sampling=False)
-            self._check_shaping(temperature, truncation, sampling=False)
-            self._check_views(views, sampling=False)
-        if known_labels is not None and (self.training or validation):
-            raise ValueError("known_labels: only a sampling call (eval mode, validation=False) takes known labels")
-        if resample is not None and (self.training or validation):
-            raise ValueError("resample: only a sampling call (eval mode, validation=False) has a walk to resample")
+            G.refuse_outside_sampling(self, guidance)
         if self.training:
             if not isinstance(t, Tensor):
                 raise ValueError("'t' needs to be a Tensor at training time")
@@ -611,13 +455,7 @@ class DenoisingModel(nn.Module):
             return self.forward_step(x, condition, feature_condition, t)
         if validation:
             return self.forward_step(x, condition, feature_condition, t)
-        if t is None:
-            return self.forward_denoising(x, condition, feature_condition, label_ref_logits=label_ref_logits, known_labels=known_labels,
-                                          resample=resample, evidence=evidence, temperature=temperature, truncation=truncation,
-                                          views=views, tiles=tiles)
-        return self.forward_denoising(x, condition, feature_condition, cast(int, t.item()), label_ref_logits, known_labels=known_labels,
-                                      resample=resample, evidence=evidence, temperature=temperature, truncation=truncation, views=views,
-                                      tiles=tiles)
+        return self.forward_denoising(x, condition, feature_condition, None if t is None else cast(int, t.item()), label_ref_logits, **guidance)
 
     # ------------------------------------------------------------------ engine plumbing
     def _weights_key(self) -> Tuple[int, int]:
@@ -816,197 +654,21 @@ class DenoisingModel(nn.Module):
         """`consume` (predict_multiple): instead of returning the call's output, hand every sub-batch engine (eng, lo, hi) to
         consume(eng, lo, hi) once the call has succeeded, with the engine's stream current; the result is then {}.  With `tiles` the
         first argument is the sub-batch's canvas holder (engine.TileCanvas: the xt / out_probs / out_onehot of the canvas) instead.
-        `known_labels`: integer [N,H,W], a class where the label is known, 255 where the pixel is free (see the class docstring).
-        `resample`: (jump_length, resamples), RePaint's resampling jumps of a walk with known labels (class docstring).
-        `evidence`: float [N,K,H,W], per-pixel class weights in [0,1] (class docstring).
-        `temperature` in [0.05, 20], `truncation` in (0, 1]: temper and truncate x0 before every reverse step (class docstring).
-        `views`: names from "hflip", "vflip", "hvflip": x0 is averaged over these mirror images of the input (class docstring).
+        `known_labels`: integer [N,H,W], a class where the label is known, 255 where the pixel is free (see guidance.py's docstring).
+        `resample`: (jump_length, resamples), RePaint's resampling jumps of a walk with known labels (guidance.py's docstring).
+        `evidence`: float [N,K,H,W], per-pixel class weights in [0,1] (guidance.py's docstring).
+        `temperature` in [0.05, 20], `truncation` in (0, 1]: temper and truncate x0 before every reverse step (guidance.py's docstring).
+        `views`: names from "hflip", "vflip", "hvflip": x0 is averaged over these mirror images of the input (guidance.py's docstring).
         `tiles`: (h, w, sy, sx): x and condition are a canvas larger than the network's geometry, sampled as ONE chain whose x0 is the
-          per-pixel mean over overlapping h x w tiles at strides (sy, sx) (class docstring)."""
-        guide = self._check_guidance(known_labels, resample, evidence, None if x is None else tuple(x.shape), temperature, truncation,
-                                     views, feature_condition, tiles)
+          per-pixel mean over overlapping h x w tiles at strides (sy, sx) (guidance.py's docstring)."""
+        guidance = dict(known_labels=known_labels, resample=resample, evidence=evidence, temperature=temperature, truncation=truncation,
+                        views=views, tiles=tiles)
+        guide = G.check_guidance(self, guidance, None if x is None else tuple(x.shape), feature_condition)
         return self._sample(x, condition, feature_condition, init_t, label_ref_logits, consume, guide)
-
-    def _check_guidance(self, known_labels, resample, evidence, shape: Optional[Tuple[int, int, int, int]], temperature=None,
-                        truncation=None, views=None, feature_condition=None, tiles=None) -> Guidance:
-        """The host-side checks of a call's guidance keywords (before anything runs), in this order; shape: the call's (N,K,H,W)."""
-        geom = self._check_tiles(tiles, views=views, known_labels=known_labels, resample=resample, feature_condition=feature_condition,
-                                 shape=shape)
-        flips = self._check_views(views, known_labels=known_labels, resample=resample, feature_condition=feature_condition, shape=shape)
-        shaping = self._check_shaping(temperature, truncation)
-        ev = None if evidence is None else self._check_evidence(evidence, shape)
-        jumps = self._check_resample(resample, known_labels)
-        known = None if known_labels is None else self._check_known_labels(known_labels, (shape[0], shape[2], shape[3]), shape[1])
-        return Guidance(known, jumps, ev, shaping, flips, geom)
-
-    def _check_tiles(self, tiles, sampling: bool = True, *, views=None, known_labels=None, resample=None, feature_condition=None,
-                     shape: Optional[Tuple[int, int, int, int]] = None) -> Optional[Tuple[int, int, int, int]]:
-        """The one host-side check of a call's `tiles` (before anything runs): (h, w, sy, sx) as four ints, or None where the call has
-        none.  shape: the call's (N,K,Hc,Wc), the canvas."""
-        if tiles is None:
-            return None
-        if isinstance(tiles, (str, bytes)) or not isinstance(tiles, (tuple, list)) or len(tiles) != 4 or not all(
-                isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) for v in tiles):
-            raise ValueError(f"tiles: expected (h, w, sy, sx), four integers (tile height and width, strides along y and x), got {tiles!r}")
-        h, w, sy, sx = (int(v) for v in tiles)
-        if not (1 <= sy <= h and 1 <= sx <= w):
-            raise ValueError(f"tiles: need 1 <= sy <= h and 1 <= sx <= w (a stride beyond the tile would leave gaps), got tile {h}x{w}, "
-                             f"strides ({sy}, {sx})")
-        if shape is not None and (h > int(shape[2]) or w > int(shape[3])):
-            raise ValueError(f"tiles: the tile {h}x{w} is larger than the canvas {int(shape[2])}x{int(shape[3])}")
-        if not sampling or self.training:
-            raise ValueError("tiles: only a sampling call (eval mode, validation=False) has a canvas to sample")
-        if self.rng == "torch_cpu":
-            raise ValueError("tiles: not available with rng = 'torch_cpu' (the host-noise parity mode replays the reference's draws, and the "
-                             "reference has no tiled step to be in parity with); use rng = 'philox'")
-        if not self.unet.spec.softmax_output:
-            raise ValueError("tiles: needs a model whose output is a probability vector; with `softmax_output: no` x0 holds logits, "
-                             "whose mean is not the mean of the probabilities")
-        if views is not None and len(views) > 0:
-            raise ValueError("tiles: not available together with views (not built)")
-        if known_labels is not None or resample is not None:
-            raise ValueError(f"tiles: not available together with {'known_labels' if known_labels is not None else 'resample'} (the clamp "
-                             "and the renoise draw per engine row, so overlapping tiles would stop being crops of one state)")
-        if feature_condition is not None and self.unet.spec.feature_condition_idx:
-            R = None if shape is None else math.prod(len(o) for o in tile_origins(int(shape[2]), int(shape[3]), h, w, sy, sx))
-            want = None if shape is None else (R, int(shape[0]))
-            if not isinstance(feature_condition, Tensor) or feature_condition.ndim != 5 or \
-                    (want is not None and tuple(feature_condition.shape[:2]) != want):
-                raise ValueError(f"tiles: this model takes a feature_condition, and with tiles it needs the features of every tile, "
-                                 f"[R,N,Cf,hf,wf]{'' if R is None else f' with R = {R}'} (tile r from the caller's encoder on the cropped "
-                                 f"image: evaluation.tile_features), got {tuple(getattr(feature_condition, 'shape', ()))}")
-        return h, w, sy, sx
-
-    def _check_views(self, views, sampling: bool = True, *, known_labels=None, resample=None, feature_condition=None,
-                     shape: Optional[Tuple[int, int, int, int]] = None) -> Optional[Tuple[int, ...]]:
-        """The one host-side check of a call's `views` (before anything runs): the flip codes of views 1 .. V - 1 as ccdm_views_step
-        takes them (VIEW_FLIPS), or None where the call has no views (None or an empty sequence: the plain call).  shape: the call's
-        (N,K,H,W)."""
-        if views is None:
-            return None
-        if isinstance(views, (str, bytes)) or not isinstance(views, (tuple, list)):
-            raise ValueError(f"views: expected a sequence of names from {list(self.VIEW_FLIPS)}, got {views!r}")
-        if len(views) == 0:
-            return None
-        bad = [v for v in views if not isinstance(v, str) or v not in self.VIEW_FLIPS]
-        if bad:
-            raise ValueError(f"views: unknown name(s) {bad} (expected names from {list(self.VIEW_FLIPS)}; the identity is always a view)")
-        if len(set(views)) != len(views):
-            raise ValueError(f"views: duplicate name(s) in {list(views)} (every view counts once in the mean)")
-        if not sampling or self.training:
-            raise ValueError("views: only a sampling call (eval mode, validation=False) has a denoiser to average")
-        if self.rng == "torch_cpu":
-            raise ValueError("views: not available with rng = 'torch_cpu' (the host-noise parity mode replays the reference's draws, and the "
-                             "reference has no view-averaged step to be in parity with); use rng = 'philox'")
-        if not self.unet.spec.softmax_output:
-            raise ValueError("views: needs a model whose output is a probability vector; with `softmax_output: no` x0 holds logits, "
-                             "whose mean is not the mean of the probabilities")
-        if known_labels is not None or resample is not None:
-            raise ValueError(f"views: not available together with {'known_labels' if known_labels is not None else 'resample'} (the clamp "
-                             "and the renoise draw per engine row, so the views would stop being mirror images of one another)")
-        if feature_condition is not None and self.unet.spec.feature_condition_idx:
-            V = 1 + len(views)
-            want = None if shape is None else (V, int(shape[0]))
-            if not isinstance(feature_condition, Tensor) or feature_condition.ndim != 5 or \
-                    (want is not None and tuple(feature_condition.shape[:2]) != want):
-                raise ValueError(f"views: this model takes a feature_condition, and with views it needs the features of every view, "
-                                 f"[V,N,Cf,h,w] with V = {V} (view v from the caller's encoder on the mirrored image), got "
-                                 f"{tuple(getattr(feature_condition, 'shape', ()))}")
-        return tuple(self.VIEW_FLIPS[v] for v in views)
-
-    def _check_shaping(self, temperature, truncation, sampling: bool = True) -> Optional[Tuple[float, float]]:
-        """The one host-side check of a call's `temperature` and `truncation` (before anything runs): (inv_temperature, top_r) as
-        ccdm_shaped_step takes them — inv_temperature = 1 / temperature in float64, rounded to fp32 once — or None where neither
-        keyword is set.  A keyword that is not set counts as 1.0."""
-        if temperature is None and truncation is None:
-            return None
-        name = "temperature" if temperature is not None else "truncation"
-
-        def real(v) -> bool:
-            return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
-        if temperature is not None and not (real(temperature) and 0.05 <= float(temperature) <= 20.0):          # (a NaN fails both)
-            raise ValueError(f"temperature: expected a real number in [0.05, 20], got {temperature!r}")
-        if truncation is not None and not (real(truncation) and 0.0 < float(truncation) <= 1.0):
-            raise ValueError(f"truncation: expected a real number in (0, 1], got {truncation!r}")
-        if not sampling or self.training:
-            raise ValueError(f"{name}: only a sampling call (eval mode, validation=False) has a draw to shape")
-        if self.rng == "torch_cpu":
-            raise ValueError(f"{name}: not available with rng = 'torch_cpu' (the host-noise parity mode replays the reference's draws, and the "
-                             "reference has no shaped step to be in parity with); use rng = 'philox'")
-        if not self.unet.spec.softmax_output:
-            raise ValueError(f"{name}: needs a model whose output is a probability vector; with `softmax_output: no` x0 holds logits, "
-                             "which cannot be tempered or truncated as probabilities")
-        inv_temperature = 1.0 if temperature is None else float(np.float32(1.0 / float(temperature)))
-        return inv_temperature, (1.0 if truncation is None else float(np.float32(float(truncation))))
-
-    def _check_evidence(self, evidence: Tensor, shape: Optional[Tuple[int, int, int, int]], sampling: bool = True) -> Tensor:
-        """The one host-side check of a call's `evidence` (before anything runs): the map as contiguous fp32 [N,H*W,K] on the model's
-        device.  shape: the call's (N,K,H,W)."""
-        if not sampling or self.training:
-            raise ValueError("evidence: only a sampling call (eval mode, validation=False) takes evidence")
-        if self.rng == "torch_cpu":
-            raise ValueError("evidence: not available with rng = 'torch_cpu' (the host-noise parity mode replays the reference's draws, and the "
-                             "reference has no guided step to be in parity with); "
-                             "use rng = 'philox'")
-        if not self.unet.spec.softmax_output:
-            raise ValueError("evidence: needs a model whose output is a probability vector; with `softmax_output: no` x0 holds logits, "
-                             "which weights cannot multiply")
-        if not isinstance(evidence, Tensor) or not evidence.dtype.is_floating_point:
-            raise ValueError(f"evidence: expected a floating-point tensor of class weights in [0,1], got "
-                             f"{getattr(evidence, 'dtype', type(evidence).__name__)}")
-        shape = tuple(int(v) for v in cast(tuple, shape))
-        if tuple(evidence.shape) != shape:
-            raise ValueError(f"evidence: expected shape {shape} = [N,K,H,W], got {tuple(evidence.shape)}")
-        host = evidence.detach().to(torch.float32).cpu()
-        if not bool(torch.isfinite(host).all()):
-            raise ValueError("evidence: values must be finite weights in [0,1]; found NaN or infinity")
-        if bool((host < 0).any()) or bool((host > 1).any()):
-            bad = host[(host < 0) | (host > 1)][0]
-            raise ValueError(f"evidence: values must be weights in [0,1]; found {float(bad)}")
-        if bool((host.max(dim=1).values <= 0).any()):
-            raise ValueError("evidence: a pixel whose K weights are all 0 rules out every class there")
-        N, K, H, W = shape
-        return host.permute(0, 2, 3, 1).reshape(N, H * W, K).contiguous().to(next(self.unet.parameters()).device)
-
-    def _check_resample(self, resample, known_labels) -> Optional[Tuple[int, int]]:
-        """The one host-side check of a call's `resample` (before anything runs): (jump_length, resamples) as two ints, or None where
-        the pair asks for no jump."""
-        if resample is None:
-            return None
-        if known_labels is None:
-            raise ValueError("resample: needs known_labels (the jumps harmonise the free pixels with the known ones; without any there "
-                             "is nothing to harmonise)")
-        if self.rng == "torch_cpu":
-            raise ValueError("resample: not available with rng = 'torch_cpu' (the host-noise parity mode has no reference stream for the "
-                             "renoising draws); use rng = 'philox'")
-        ok = isinstance(resample, (tuple, list)) and len(resample) == 2 and all(
-            isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) for v in resample)
-        if not ok or int(resample[0]) < 0 or int(resample[1]) < 1:
-            raise ValueError(f"resample: expected (jump_length, resamples), two integers with jump_length >= 0 and resamples >= 1, got {resample!r}")
-        j, r = int(resample[0]), int(resample[1])
-        return None if (j == 0 or r == 1) else (j, r)
-
-    def _check_known_labels(self, known_labels: Tensor, shape: Tuple[int, int, int], K: int) -> Tensor:
-        """The one host-side check of a call's `known_labels` (before anything runs): the map as uint8 [N,H*W] on the model's device."""
-        if self.rng == "torch_cpu":
-            raise ValueError("known_labels: not available with rng = 'torch_cpu' (the host-noise parity mode has no reference stream for "
-                             "the draw at the known pixels); use rng = 'philox'")
-        if not isinstance(known_labels, Tensor) or known_labels.dtype in (torch.bool,) or known_labels.dtype.is_floating_point \
-                or known_labels.dtype.is_complex:
-            raise ValueError(f"known_labels: expected an integer tensor (a class in [0,{K}) where the label is known, {self.KNOWN_FREE} where the "
-                             f"pixel is free), got {getattr(known_labels, 'dtype', type(known_labels).__name__)}")
-        shape = tuple(int(v) for v in shape)
-        if tuple(known_labels.shape) != shape:
-            raise ValueError(f"known_labels: expected shape {shape} = [N,H,W], got {tuple(known_labels.shape)}")
-        host = known_labels.detach().cpu()
-        bad = ((host < 0) | (host >= K)) & (host != self.KNOWN_FREE)
-        if bool(bad.any()):
-            raise ValueError(f"known_labels: values must be classes in [0,{K}) or {self.KNOWN_FREE} (free); found {int(host[bad][0])}")
-        return host.to(torch.uint8).reshape(shape[0], shape[1] * shape[2]).contiguous().to(next(self.unet.parameters()).device)
 
     def _sample(self, x: Optional[Tensor], condition: Tensor, feature_condition: Tensor, init_t: Optional[int],
                 label_ref_logits: Optional[Tensor], consume, guide: Guidance) -> dict:
-        """One sampling call; `guide`: what _check_guidance returned."""
+        """One sampling call; `guide`: what guidance.check_guidance returned."""
         out = self._with_range_fallback(lambda: self._forward_denoising(x, condition, feature_condition, init_t, label_ref_logits,
                                                                         consume, guide))
         if self.philox_advance:
@@ -1038,14 +700,14 @@ class DenoisingModel(nn.Module):
         x: optional one-hot x_T [S,B,K,H,W]; default: drawn per pass as predict_single does (uniform one-hot on condition's device).
         t: as in forward (e.g. 10000 + steps for a strided walk).
         known_labels: integer [B,H,W] (a class where the label is known, 255 where the pixel is free): every pass is conditioned on it
-          (class docstring), so `vote` equals the label and `entropy` is 0 at the known pixels.
-        resample: (jump_length, resamples): every pass walks with RePaint's resampling jumps (class docstring); needs known_labels.
-        evidence: float [B,K,H,W] per-pixel class weights in [0,1] (class docstring): every pass is sampled under it.
-        temperature, truncation: every pass tempers and truncates x0 before every reverse step (class docstring), all with the same pair.
-        views: every pass averages x0 over these mirror images of the input (class docstring); a model that takes a feature_condition
+          (guidance.py), so `vote` equals the label and `entropy` is 0 at the known pixels.
+        resample: (jump_length, resamples): every pass walks with RePaint's resampling jumps (guidance.py); needs known_labels.
+        evidence: float [B,K,H,W] per-pixel class weights in [0,1] (guidance.py): every pass is sampled under it.
+        temperature, truncation: every pass tempers and truncates x0 before every reverse step (guidance.py), all with the same pair.
+        views: every pass averages x0 over these mirror images of the input (guidance.py); a model that takes a feature_condition
           then needs [V,B,Cf,h,w].
-        tiles: (h, w, sy, sx): `condition` is a canvas larger than the network's geometry and every pass samples it tiled (class
-          docstring); a model that takes a feature_condition then needs [R,B,Cf,hf,wf].  The passes are folded from the canvas.
+        tiles: (h, w, sy, sx): `condition` is a canvas larger than the network's geometry and every pass samples it tiled
+          (guidance.py); a model that takes a feature_condition then needs [R,B,Cf,hf,wf].  The passes are folded from the canvas.
         batched=False: S sampling calls of B samples, each advancing `philox_call` exactly like S calls of model(x_i, condition);
           after each call the pass is folded into device accumulators straight from the engine (ccdm_vote_accumulate), so memory
           is one pass plus the accumulators.  The range-error fallback and the execution-mode choice apply per pass.
@@ -1065,22 +727,16 @@ class DenoisingModel(nn.Module):
         bad = [m for m in maps if m not in self.MULTI_MAPS or (m == "counts" and voting != "majority")]
         if bad:
             raise ValueError(f"maps: {bad} not available (choose from {self.MULTI_MAPS}; 'counts' with voting='majority')")
-        if condition.ndim != 4:
-            raise ValueError(f"condition: expected [B,C,H,W], got {tuple(condition.shape)}")
+        guidance = dict(known_labels=known_labels, resample=resample, evidence=evidence, temperature=temperature, truncation=truncation,
+                        views=views, tiles=tiles)
+        init_t, guide, batch = self._samples_per_image(condition, feature_condition, S, x, t, guidance, interleaved=batched)
         B, H, W = int(condition.shape[0]), int(condition.shape[2]), int(condition.shape[3])
         K, HW = self.diffusion.num_classes, H * W
-        if x is not None and tuple(x.shape) != (S, B, K, H, W):
-            raise ValueError(f"x: expected one-hot x_T of shape {(S, B, K, H, W)} = [S,B,K,H,W], got {tuple(x.shape)}")
-        init_t = None if t is None else int(t.item() if isinstance(t, Tensor) else t)
-        guide = self._check_guidance(known_labels, resample, evidence, (B, K, H, W), temperature, truncation, views, feature_condition, tiles)
         dev = next(self.unet.parameters()).device
         lib = hip.load()
         majority = voting == "majority"
         want_mi = "mutual_info" in maps
         w = float(np.float32(1.0 / S))          # the reference's (1 / S) as the fp32 scalar torch multiplies an fp32 tensor by
-
-        def draw(n: int) -> Tensor:             # predict_single's x_T (eval_cdm.py:160-165)
-            return OneHotCategoricalBCHW(logits=torch.zeros((n, K, H, W), device=condition.device)).sample()
 
         def stream() -> int:
             return torch.cuda.current_stream(dev).cuda_stream
@@ -1102,14 +758,10 @@ class DenoisingModel(nn.Module):
                                                        ptr(counts, lo * HW * K), ptr(ent_sum, lo * HW), stream()), "vote_accumulate")
 
                 for i in range(S):
-                    self._sample(x[i] if x is not None else draw(B), condition, feature_condition, init_t, None, consume, guide)
+                    self._sample(x[i] if x is not None else self._draw_x_T(B, H, W, condition.device), condition, feature_condition, init_t, None,
+                                 consume, guide)
             else:
-                xr = x.transpose(0, 1).reshape(B * S, K, H, W) if x is not None else draw(B * S)
-                cond = condition.repeat_interleave(S, dim=0)
-                # (with views or tiles on a model that takes features: [V,B,...] / [R,B,...], the samples on dim 1)
-                fc_dim = 1 if ((guide.views is not None or guide.tiles is not None) and feature_condition is not None
-                               and feature_condition.ndim == 5) else 0
-                fc = feature_condition.repeat_interleave(S, dim=fc_dim) if feature_condition is not None else None
+                xr, cond, fc = batch
                 # the pass outputs of all B*S samples: class maps (1 byte a pixel) or probabilities
                 buf = torch.empty((B * S, HW) if majority else (B * S, HW, K), dtype=torch.uint8 if majority else torch.float32, device=dev)
 
@@ -1117,7 +769,7 @@ class DenoisingModel(nn.Module):
                     # (the first hi - lo rows: with views the engine holds V times as many, view 0 first)
                     buf[lo:hi].copy_(eng.xt.reshape(-1, HW)[:hi - lo] if majority else eng.out_probs.reshape(-1, HW, K)[:hi - lo])
 
-                self._sample(xr, cond, fc, init_t, None, consume, guide.repeat_interleave(S))
+                self._sample(xr, cond, fc, init_t, None, consume, guide)
                 if majority:
                     vote8 = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
                     mean = torch.empty((B, H, W, K), dtype=torch.float32, device=dev) if "mean" in maps else None
@@ -1153,28 +805,42 @@ class DenoisingModel(nn.Module):
                 out[m] = cast(Tensor, got[m])
         return out
 
-    def _sample_class_maps(self, condition: Tensor, feature_condition: Optional[Tensor], S: int, x: Optional[Tensor], t: Optional[Tensor],
-                           known_labels, resample, evidence, temperature, truncation, views, tiles) -> Tensor:
-        """One sampling call of B*S samples (condition repeat-interleaved, sample b*S + s = sample s of image b), every pass ending in its
-        argmax class ("majority"), the class maps read straight from the engine -> uint8 [B,S,H,W] on the model's device.  What
-        predict_modes and predict_findings sample; `philox_call` advances as for one call."""
+    def _draw_x_T(self, n: int, H: int, W: int, device) -> Tensor:
+        """predict_single's x_T (eval_cdm.py:160-165): uniform one-hot [n,K,H,W]."""
+        return OneHotCategoricalBCHW(logits=torch.zeros((n, self.diffusion.num_classes, H, W), device=device)).sample()
+
+    def _samples_per_image(self, condition: Tensor, feature_condition: Optional[Tensor], S: int, x: Optional[Tensor], t: Optional[Tensor],
+                           guidance: Mapping, interleaved: bool = True):
+        """What a call of S samples per image of `condition` [B,C,H,W] checks and lays out: (init_t, guide, batch) — `guide` the checked
+        guidance (guidance.check_guidance) of the B images.  interleaved: `batch` = (xr, cond, fc), the ONE batch of B*S samples (x_T
+        [S,B,K,H,W] or a fresh draw, condition and features repeat-interleaved: sample b*S + s = sample s of image b) and `guide` repeated
+        like it; else `batch` is None."""
         K = self.diffusion.num_classes
         if condition.ndim != 4:
             raise ValueError(f"condition: expected [B,C,H,W], got {tuple(condition.shape)}")
         B, H, W = int(condition.shape[0]), int(condition.shape[2]), int(condition.shape[3])
-        HW = H * W
         if x is not None and tuple(x.shape) != (S, B, K, H, W):
             raise ValueError(f"x: expected one-hot x_T of shape {(S, B, K, H, W)} = [S,B,K,H,W], got {tuple(x.shape)}")
         init_t = None if t is None else int(t.item() if isinstance(t, Tensor) else t)
-        guide = self._check_guidance(known_labels, resample, evidence, (B, K, H, W), temperature, truncation, views, feature_condition, tiles)
-        dev = next(self.unet.parameters()).device
-        xr = x.transpose(0, 1).reshape(B * S, K, H, W) if x is not None else \
-            OneHotCategoricalBCHW(logits=torch.zeros((B * S, K, H, W), device=condition.device)).sample()
+        guide = G.check_guidance(self, guidance, (B, K, H, W), feature_condition)
+        if not interleaved:
+            return init_t, guide, None
+        xr = x.transpose(0, 1).reshape(B * S, K, H, W) if x is not None else self._draw_x_T(B * S, H, W, condition.device)
         cond = condition.repeat_interleave(S, dim=0)
         # (with views or tiles on a model that takes features: [V,B,...] / [R,B,...], the samples on dim 1)
-        fc_dim = 1 if ((guide.views is not None or guide.tiles is not None) and feature_condition is not None
-                       and feature_condition.ndim == 5) else 0
-        fc = feature_condition.repeat_interleave(S, dim=fc_dim) if feature_condition is not None else None
+        fc = None if feature_condition is None else \
+            feature_condition.repeat_interleave(S, dim=G.sample_axis(feature_condition, guide.views, guide.tiles))
+        return init_t, guide.repeat_interleave(S), (xr, cond, fc)
+
+    def _sample_class_maps(self, condition: Tensor, feature_condition: Optional[Tensor], S: int, x: Optional[Tensor], t: Optional[Tensor],
+                           guidance: Mapping) -> Tensor:
+        """One sampling call of B*S samples (condition repeat-interleaved, sample b*S + s = sample s of image b), every pass ending in its
+        argmax class ("majority"), the class maps read straight from the engine -> uint8 [B,S,H,W] on the model's device.  What
+        predict_modes and predict_findings sample; `philox_call` advances as for one call.  guidance: the call's keywords by name."""
+        init_t, guide, (xr, cond, fc) = self._samples_per_image(condition, feature_condition, S, x, t, guidance)
+        B, H, W = int(condition.shape[0]), int(condition.shape[2]), int(condition.shape[3])
+        HW = H * W
+        dev = next(self.unet.parameters()).device
         stack = torch.empty((B * S, HW), dtype=torch.uint8, device=dev)
 
         def consume(eng, lo: int, hi: int) -> None:
@@ -1184,7 +850,7 @@ class DenoisingModel(nn.Module):
         saved = self.step_T_sample
         self.step_T_sample = "majority"
         try:
-            self._sample(xr, cond, fc, init_t, None, consume, guide.repeat_interleave(S))
+            self._sample(xr, cond, fc, init_t, None, consume, guide)
         finally:
             self.step_T_sample = saved
         return stack.reshape(B, S, H, W)
@@ -1192,11 +858,7 @@ class DenoisingModel(nn.Module):
     @torch.no_grad()
     def predict_modes(self, condition: Tensor, feature_condition: Optional[Tensor] = None, *, num_evaluations: int, modes: int,
                       x: Optional[Tensor] = None, t: Optional[Tensor] = None, max_swaps: int = 64,
-                      maps: Sequence[str] = ("vote", "entropy"),
-                      known_labels: Optional[Tensor] = None, resample: Optional[Tuple[int, int]] = None,
-                      evidence: Optional[Tensor] = None, temperature: Optional[float] = None,
-                      truncation: Optional[float] = None, views: Optional[Sequence[str]] = None,
-                      tiles: Optional[Sequence[int]] = None) -> Dict[str, Tensor]:
+                      maps: Sequence[str] = ("vote", "entropy"), **guidance) -> Dict[str, Tensor]:
         """S = `num_evaluations` samples of every image of `condition` [B,C,H,W], summarised on the device as M = `modes` distinct
         segmentations with the share of the samples behind each: "three hypotheses: no nodule 55 %, small nodule 30 %, large nodule
         15 %", where predict_multiple folds the samples per pixel and loses which segmentations they were.
@@ -1209,11 +871,12 @@ class DenoisingModel(nn.Module):
         x: optional one-hot x_T [S,B,K,H,W]; default: drawn as predict_multiple draws it.  t: as in forward.
         max_swaps: the most swaps PAM applies after its greedy BUILD (`converged` tells whether it stopped by itself).
         maps: per-mode maps from "vote", "entropy", "counts" (metrics.MODE_MAPS).
-        known_labels, resample, evidence, temperature, truncation, views, tiles: as in predict_multiple, for every sample.
+        **guidance: the keywords of guidance.GUIDANCE_KEYWORDS, as in predict_multiple, for every sample.
         Returns, on the model's device, what metrics.sample_modes returns — medoid [B,M] (the sample that stands for the mode, -1:
         unused), assign [B,S], size, share (= size / S), spread, cost, swaps, converged, mode_map [B,M,H,W] uint8 (the medoid sample,
         255 where unused), mode_vote / mode_entropy / mode_counts as asked for — and `samples` [B,S,H,W] uint8, the class maps."""
         from . import metrics as MT
+        G.known_keywords("DenoisingModel.predict_modes", guidance)
         if isinstance(num_evaluations, bool) or int(num_evaluations) != num_evaluations or not 1 <= int(num_evaluations) <= MT.MODES_MAX_SAMPLES:
             raise ValueError(f"num_evaluations: {num_evaluations!r} (expected an integer in [1, {MT.MODES_MAX_SAMPLES}])")
         S = int(num_evaluations)
@@ -1225,8 +888,7 @@ class DenoisingModel(nn.Module):
         bad = [m for m in maps if m not in MT.MODE_MAPS]
         if bad:
             raise ValueError(f"maps: {bad} not available (choose from {MT.MODE_MAPS})")
-        samples = self._sample_class_maps(condition, feature_condition, S, x, t, known_labels, resample, evidence, temperature, truncation, views,
-                                          tiles)
+        samples = self._sample_class_maps(condition, feature_condition, S, x, t, guidance)
         out = MT.sample_modes(samples, K, modes, max_swaps=max_swaps, maps=maps)
         out["samples"] = samples
         return out
@@ -1234,11 +896,7 @@ class DenoisingModel(nn.Module):
     @torch.no_grad()
     def predict_findings(self, condition: Tensor, feature_condition: Optional[Tensor] = None, *, num_evaluations: int,
                          min_frequency: float = 0.1, connectivity: int = 8, max_candidates: int = 64,
-                         x: Optional[Tensor] = None, t: Optional[Tensor] = None,
-                         known_labels: Optional[Tensor] = None, resample: Optional[Tuple[int, int]] = None,
-                         evidence: Optional[Tensor] = None, temperature: Optional[float] = None,
-                         truncation: Optional[float] = None, views: Optional[Sequence[str]] = None,
-                         tiles: Optional[Sequence[int]] = None) -> Dict[str, Any]:
+                         x: Optional[Tensor] = None, t: Optional[Tensor] = None, **guidance) -> Dict[str, Any]:
         """S = `num_evaluations` samples of every image of `condition` [B,C,H,W], read as ONE list of lesions per image and class with
         a confidence each: a structure that 90 of 100 samples draw is a finding, one that 12 draw a hypothesis, where predict_multiple
         folds the samples per pixel and loses which structure a pixel belongs to.
@@ -1250,11 +908,12 @@ class DenoisingModel(nn.Module):
         the definition).  `philox_call` advances as for one call.  1 <= K <= 32, 1 <= S <= 255, H*W <= 16384.
         x: optional one-hot x_T [S,B,K,H,W]; default: drawn as predict_multiple draws it.  t: as in forward.
         max_candidates: the records kept per image and class (at most 1024); an image with more raises, naming the value needed.
-        known_labels, resample, evidence, temperature, truncation, views, tiles: as in predict_multiple, for every sample.
+        **guidance: the keywords of guidance.GUIDANCE_KEYWORDS, as in predict_multiple, for every sample.
         Returns `counts` int64 [B,C,2] and `candidates` int64 [B,C,max_candidates,12] on the host (metrics.FINDING_CANDIDATE_FIELDS:
         size, support, peak, mass, ..., the box, the coordinate sums), `confidence_map` uint8 [B,C,H,W] (the support of the candidate
         that holds the pixel, 0 outside) and `samples` uint8 [B,S,H,W] on the model's device, and `n_min`, `classes`."""
         from . import metrics as MT
+        G.known_keywords("DenoisingModel.predict_findings", guidance)
         if isinstance(num_evaluations, bool) or int(num_evaluations) != num_evaluations or not 1 <= int(num_evaluations) <= 255:
             raise ValueError(f"num_evaluations: {num_evaluations!r} (expected an integer in [1, 255])")
         S = int(num_evaluations)
@@ -1269,8 +928,7 @@ class DenoisingModel(nn.Module):
         MT.whole_number(K, "num_classes", 1, 32, "predict_findings: expected a model of 1 to 32 classes")
         if condition.ndim == 4 and int(condition.shape[2]) * int(condition.shape[3]) > 16384:
             raise ValueError(f"condition: {tuple(condition.shape)} (predict_findings: maps of at most 16384 pixels)")
-        samples =self._sample_class_maps(condition, feature_condition, S, x, t, known_labels, resample, evidence, temperature, truncation, views,
-                                          tiles)
+        samples = self._sample_class_maps(condition, feature_condition, S, x, t, guidance)
         got = MT.sample_findings(samples, None, K, n_min=n_min, connectivity=connectivity, max_candidates=max_candidates, return_map=True)
         return {"counts": got["counts"], "candidates": got["candidates"], "confidence_map": got["confidence_map"], "samples": samples,
                 "n_min": n_min, "classes": got["classes"]}
@@ -1301,13 +959,9 @@ class DenoisingModel(nn.Module):
         trainer's: where the model gives a class the posterior needs less than that, the term is capped — a bound up to those pixels.
         Under WORLD_SIZE > 1 every rank computes the same numbers (no sharding).  Refused: rng = "torch_cpu", `softmax_output: no`, labels
         whose geometry is not the call's, draws < 1, rows < 1, timesteps outside 1..T or repeated."""
-        if self.rng == "torch_cpu":
-            raise ValueError("label_bound: not available with rng = 'torch_cpu' (the host-noise parity mode has no reference stream for the "
-                             "forward draws); use rng = 'philox'")
-        if self.rng != "philox":
+        if self.rng not in ("philox", "torch_cpu"):
             raise ValueError(f"rng: {self.rng!r}")
-        if not self.unet.spec.softmax_output:
-            raise ValueError("label_bound: needs a model whose output is a probability vector; with `softmax_output: no` x0 holds logits")
+        G.require(self, "label_bound", sampling=None)         # (not rng = "torch_cpu", a model whose x0 holds probabilities)
         K, T = int(self.diffusion.num_classes), int(self.time_steps)
         if isinstance(draws, bool) or int(draws) != draws or int(draws) < 1:
             raise ValueError(f"draws: expected an integer >= 1, got {draws!r}")
@@ -1438,7 +1092,7 @@ class DenoisingModel(nn.Module):
     def _forward_denoising(self, x: Optional[Tensor], condition: Tensor, feature_condition: Tensor,
                            init_t: Optional[int] = None, label_ref_logits: Optional[Tensor] = None, consume=None,
                            guide: Guidance = Guidance()) -> dict:
-        """`guide`: the call's checked guidance (_check_guidance), on the model's device."""
+        """`guide`: the call's checked guidance (guidance.check_guidance), on the model's device."""
         known, evidence, shaping, views, tiles = guide.known, guide.evidence, guide.shaping, guide.views, guide.tiles
         V = 1 if views is None else 1 + len(views)
         if label_ref_logits is not None:
@@ -1467,7 +1121,7 @@ class DenoisingModel(nn.Module):
         R = len(oys) * len(oxs)
         canvases: Dict[int, TileCanvas] = {}                 # the canvas holder of the sub-batch that starts at sample `lo`
         table = coeffs if not stop_at_x0 else [(a_, c_, hip.STEP_SOFTMAX_ONLY) for a_, c_, m_ in coeffs]
-        # known labels: cumalpha of the state each row produces; the last row returns the labels themselves (class docstring)
+        # known labels: cumalpha of the state each row produces; the last row returns the labels themselves (guidance.py)
         clamp_c = [1.0 if j == S - 1 else c_ for j, (a_, c_, m_) in enumerate(coeffs)]
         key = self._philox_key()
         # The rows in the order the walk visits them — (row, 0, None) for row 0 .. S - 1 unless resampling jumps are taken — and per entry
@@ -1498,22 +1152,21 @@ class DenoisingModel(nn.Module):
             h_, w_ = cast(tuple, tiles)[:2]
             return torch.cat([a[:, :, oy:oy + h_, ox:ox + w_] for oy in oys for ox in oxs], 0)
 
+        rows = tiled if tiles is not None else None if views is None else mirrored         # a sub-batch's tensor as the engine's rows
+        fc_axis = G.sample_axis(feature_condition, views, tiles)
+
         def prepare(nsub_: int):
             bounds = [(N * j) // nsub_ for j in range(nsub_ + 1)]
             parts_ = []
             for j in range(nsub_):
                 lo, hi = bounds[j], bounds[j + 1]
-                if tiles is not None:
-                    xs, cs, fc = tiled(x[lo:hi]), tiled(condition[lo:hi]), None
-                    if feature_condition is not None and self.unet.spec.feature_condition_idx:         # [R,N,...] (_check_tiles)
-                        fc = feature_condition[:, lo:hi].flatten(0, 1)
-                elif views is None:
-                    xs, cs = x[lo:hi], condition[lo:hi]
-                    fc = feature_condition[lo:hi] if feature_condition is not None else None
-                else:
-                    xs, cs, fc = mirrored(x[lo:hi]), mirrored(condition[lo:hi]), None
-                    if feature_condition is not None and self.unet.spec.feature_condition_idx:         # [V,N,...] (_check_views)
-                        fc = feature_condition[:, lo:hi].flatten(0, 1)
+                xs, cs = (x[lo:hi], condition[lo:hi]) if rows is None else (rows(x[lo:hi]), rows(condition[lo:hi]))
+                fc = None
+                # [N,...]; with views or tiles [V,N,...] / [R,N,...] (check_views, check_tiles), which a model without an injection point
+                # ignores
+                if feature_condition is not None and (rows is None or self.unet.spec.feature_condition_idx):
+                    fc = feature_condition.narrow(fc_axis, lo, hi - lo)
+                    fc = fc.flatten(0, 1) if fc_axis == 1 else fc
                 eng = self._engine(xs, cs, fc, slot=j)
                 with eng.enter():
                     eng.set_inputs(self._to_index(xs, eng.device), cs.to(eng.device), fc)

@@ -37,7 +37,7 @@ Guided requests.  SamplingQueue(..., guided=True) takes requests with the guidan
     q = model.sampling_queue(64, (C, H, W), guided=True)
     r = q.submit(condition, evidence=e, known_labels=y, temperature=0.7, truncation=0.9)          # any subset, or none
 
-checked by the model's own _check_evidence / _check_known_labels / _check_shaping, with a solo call's meaning and errors.  The tick's
+checked by a solo call's own guidance.check_guidance, with a solo call's meaning and errors.  The tick's
 step is then ccdm_slots_guided_step: beside the slot table a second one of one hip.SlotGuideRow per slot — the shaping, the clamp's
 (p_hit, p_miss) of the slot's row (`plan_clamp`), two flags — filled by `slot_guide_rows`, and two slot-indexed pools in the engine
 (evidence, known labels) that an admission fills (SamplerEngine.set_slot_guidance) from the request's own device copies.  Per slot the
@@ -55,7 +55,9 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from . import guidance as G
 from . import hip
+from .guidance import GUIDANCE_KEYWORDS  # noqa: F401  (its home is guidance.py; the name stays readable here)
 from .models import DenoisingModel, OneHotCategoricalBCHW, step_values
 
 # one row of ccdm_slots_step's table as numpy sees it (hip.SlotRow: 32 bytes)
@@ -65,7 +67,6 @@ SLOT_DTYPE = np.dtype([("alpha_t", "<f4"), ("cumalpha_tm1", "<f4"), ("mode", "<i
 # one row of ccdm_slots_guided_step's second table (hip.SlotGuideRow: 32 bytes)
 GUIDE_DTYPE = np.dtype([("inv_temperature", "<f4"), ("top_r", "<f4"), ("p_hit", "<f4"), ("p_miss", "<f4"), ("flags", "<i4"), ("reserved", "<i4", (3,))])
 
-GUIDANCE_KEYWORDS = ("known_labels", "resample", "evidence", "temperature", "truncation", "views", "tiles")
 # what a request of a guided queue takes, and why it takes no other
 QUEUED_GUIDANCE = ("evidence", "known_labels", "temperature", "truncation")
 NOT_QUEUED = {"views": "a sample with views is several engine rows", "tiles": "a tiled sample is several engine rows",
@@ -349,13 +350,12 @@ class SamplingQueue:
         A guided queue: evidence [n,K,H,W], known_labels [n,H,W], temperature, truncation — meaning, dtypes and errors as
         model(x, condition, ...) has them (the model's own checks)."""
         for k in guidance:
+            G.known_keywords("submit", (k,))
             if self.guided and k in QUEUED_GUIDANCE:
                 continue
             if self.guided and k in NOT_QUEUED:
                 raise ValueError(f"{k}: not built for queued requests ({NOT_QUEUED[k]})")
-            if k in GUIDANCE_KEYWORDS:
-                raise ValueError(f"{k}: guidance keywords are not built for queued requests")
-            raise TypeError(f"submit() got an unexpected keyword argument {k!r}")
+            raise ValueError(f"{k}: guidance keywords are not built for queued requests")
         self._check_model()
         if self._flagged:
             self._engine.raise_range_error()
@@ -368,10 +368,9 @@ class SamplingQueue:
         init_t = None if t is None else int(t.item()) if isinstance(t, torch.Tensor) else int(t)
         vote = m.step_T_sample if vote is None else vote
         walk = plan_walk(m.time_steps, init_t, vote, m.diffusion.posterior_coeffs)
-        # the checks of a solo call, in its order (DenoisingModel._check_guidance), before anything is built or counted
-        shaping = m._check_shaping(guidance.get("temperature"), guidance.get("truncation"))
-        ev = None if guidance.get("evidence") is None else m._check_evidence(guidance["evidence"], (n, self.K, H, W))
-        known = None if guidance.get("known_labels") is None else m._check_known_labels(guidance["known_labels"], (n, H, W), self.K)
+        # the checks of a solo call, in its order (guidance.check_guidance), before anything is built or counted
+        guide = G.check_guidance(m, guidance, (n, self.K, H, W))
+        shaping, ev, known = guide.shaping, guide.evidence, guide.known
         eng = self._get_engine()
         if x is None:
             x = OneHotCategoricalBCHW(logits=torch.zeros((n, self.K, H, W), device=condition.device)).sample()

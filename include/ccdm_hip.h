@@ -449,7 +449,7 @@ int ccdm_views_step(const float* x0 /*dev [V*N,HW,K]*/, const float* evidence /*
  * tiles of the current canvas state, the tiles' x0 are averaged per canvas pixel and one draw is made per canvas pixel.  A mean of
  * probability vectors is one and the step posterior is linear in x0 up to its own normalisation, so the tiled step is the step on the
  * per-pixel mean of the covering tiles' x0.
- * THE geometry (host: models.tile_origins; the kernel derives the same origins from the six integers).  Canvas Hc x Wc, tile h x w,
+ * THE geometry (host: guidance.tile_origins; the kernel derives the same origins from the six integers).  Canvas Hc x Wc, tile h x w,
  * strides sy, sx with 1 <= sy <= h <= Hc and 1 <= sx <= w <= Wc:
  *   Ty = 1 + ceil((Hc - h) / sy) tiles along y with origins oy_i = min(i * sy, Hc - h): the last tile is pushed back so that it ends at
  *   the border; the origins are distinct and leave no gap.  The same along x: Tx, ox_j = min(j * sx, Wc - w).
@@ -537,7 +537,7 @@ int ccdm_slots_step(const float* x0 /*dev [N,HW,K]*/, const ccdm_slot_row* table
  * word 0x80000000 | k / 4, in the last-step modes the label and its one-hot.  One launch.  Neutral guide rows — (1, 1, ., ., 0) —
  * give ccdm_slots_step bit for bit.  A slot that is idle is neither read nor written, its rows of the pools included.
  * The caller's contract (on the device, so not checked here): a pool may be NULL only while no running slot sets its flag;
- * inv_temperature in [1/20, 20] and top_r in (0, 1] are checked by the host where it forms a row (DenoisingModel._check_shaping);
+ * inv_temperature in [1/20, 20] and top_r in (0, 1] are checked by the host where it forms a row (guidance.check_shaping);
  * (p_hit, p_miss) is the pair ccdm_known_labels_step documents, float64 c + (1 - c) / K and (1 - c) / K each rounded to fp32 once,
  * c = cumalpha_tm1 of the row and 1.0 on a walk's last row.
  * The three shapes of ccdm_slots_step; K <= 4: the 8- / 16-byte loads need x0 and the evidence pool aligned alike.  Refused: what

@@ -10,7 +10,7 @@ import pytest
 import torch
 
 from oracle import ccdm_oracle as O
-from ccdm_stochastic_segmentation_amd import hip
+from ccdm_stochastic_segmentation_amd import guidance, hip
 from tests.guided_util import SHAPES, bits, coefficients, evidence_restatement, nhwk, random_inputs, sampler_evidence
 from tests.sampler_util import (DEV, FREE, H, SEED, SMALL_CFG, T_SMALL, T_STRIDED, W, assert_symbol_declared_bound_and_built, load_lib,
                                 make_sampler, onehot_np, sample_sharded_keywords, settings, small_model)
@@ -38,7 +38,7 @@ def test_evidence_symbol_declared_bound_and_built():
 
 
 def test_evidence_argument_validation():
-    """Every refusal of _check_evidence is a ValueError naming `evidence`, through forward, forward_denoising and predict_multiple, before
+    """Every refusal of guidance.check_evidence is a ValueError naming `evidence`, through forward, forward_denoising and predict_multiple, before
     anything runs (a model that was never moved to a GPU: nothing can run); the accepted forms and the returned layout."""
     m, _ = small_model(3)
     m.eval()
@@ -91,7 +91,7 @@ def test_evidence_argument_validation():
     good[:, 1:, :4] = 0.0
     good[:, 0, :4] = 1.0
     for dtype in (torch.float64, torch.float32, torch.float16):
-        got = m._check_evidence(good.to(dtype), (N, K, H, W))
+        got = guidance.check_evidence(m, good.to(dtype), (N, K, H, W))
         assert got.dtype == torch.float32 and tuple(got.shape) == (N, H * W, K) and got.is_contiguous()
         assert torch.equal(got.reshape(N, H, W, K).permute(0, 3, 1, 2), good.to(dtype).float())
 

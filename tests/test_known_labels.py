@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from oracle import ccdm_oracle as O
-from ccdm_stochastic_segmentation_amd import hip
+from ccdm_stochastic_segmentation_amd import guidance, hip
 from tests.sampler_util import (DEV, FREE, H, SEED, SMALL_CFG, T_SMALL, T_STRIDED, W, assert_symbol_declared_bound_and_built, clamp_restatement,
                                 load_lib, make_sampler, onehot_np, probabilities, sample_sharded_keywords, settings, small_model)
 
@@ -61,7 +61,7 @@ def test_known_labels_argument_validation():
     # the accepted forms: any integer dtype, classes and 255
     good = torch.full((N, H, W), FREE, dtype=torch.int32)
     good[:, :4] = 2
-    u8 = m._check_known_labels(good, (N, H, W), K)
+    u8 = guidance.check_known_labels(m, good, (N, H, W), K)
     assert u8.dtype == torch.uint8 and tuple(u8.shape) == (N, H * W) and torch.equal(u8.reshape(N, H, W).int(), good)
 
 

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 import torch
 
-from ccdm_stochastic_segmentation_amd import SamplingQueue, hip, serving, step_values
+from ccdm_stochastic_segmentation_amd import SamplingQueue, guidance, hip, serving, step_values
 from tests.guided_util import random_inputs, sampler_evidence
 from tests.sampler_util import (DEV, FREE, H, ROOT, T_SMALL, T_STRIDED, W, assert_symbol_declared_bound_and_built, load_lib, make_sampler,
                                 probabilities, small_model)
@@ -141,18 +141,18 @@ def test_guided_queue_refusals():
     bad_class = known.clone()
     bad_class[0, 0, 0] = K
     cases = [
-        (dict(evidence=ev[:, :, :, 1:]), lambda: m._check_evidence(ev[:, :, :, 1:], (n, K, H, W)), "evidence: expected shape"),
-        (dict(evidence=ev[:1]), lambda: m._check_evidence(ev[:1], (n, K, H, W)), "evidence: expected shape"),
-        (dict(evidence=outside), lambda: m._check_evidence(outside, (n, K, H, W)), r"evidence: values must be weights in \[0,1\]; found 1.5"),
-        (dict(evidence=ruled_out), lambda: m._check_evidence(ruled_out, (n, K, H, W)), "evidence: a pixel whose K weights are all 0"),
-        (dict(evidence=ev.long()), lambda: m._check_evidence(ev.long(), (n, K, H, W)), "evidence: expected a floating-point tensor"),
-        (dict(known_labels=known.float()), lambda: m._check_known_labels(known.float(), (n, H, W), K), "known_labels: expected an integer tensor"),
-        (dict(known_labels=known[:, 1:]), lambda: m._check_known_labels(known[:, 1:], (n, H, W), K), "known_labels: expected shape"),
-        (dict(known_labels=bad_class), lambda: m._check_known_labels(bad_class, (n, H, W), K), "known_labels: values must be classes"),
-        (dict(temperature=0.01), lambda: m._check_shaping(0.01, None), "temperature: expected a real number in"),
-        (dict(temperature=float("nan")), lambda: m._check_shaping(float("nan"), None), "temperature: expected a real number in"),
-        (dict(truncation=0.0), lambda: m._check_shaping(None, 0.0), "truncation: expected a real number in"),
-        (dict(truncation=1.5, evidence=ev), lambda: m._check_shaping(None, 1.5), "truncation: expected a real number in"),
+        (dict(evidence=ev[:, :, :, 1:]), lambda: guidance.check_evidence(m, ev[:, :, :, 1:], (n, K, H, W)), "evidence: expected shape"),
+        (dict(evidence=ev[:1]), lambda: guidance.check_evidence(m, ev[:1], (n, K, H, W)), "evidence: expected shape"),
+        (dict(evidence=outside), lambda: guidance.check_evidence(m, outside, (n, K, H, W)), r"evidence: values must be weights in \[0,1\]; found 1.5"),
+        (dict(evidence=ruled_out), lambda: guidance.check_evidence(m, ruled_out, (n, K, H, W)), "evidence: a pixel whose K weights are all 0"),
+        (dict(evidence=ev.long()), lambda: guidance.check_evidence(m, ev.long(), (n, K, H, W)), "evidence: expected a floating-point tensor"),
+        (dict(known_labels=known.float()), lambda: guidance.check_known_labels(m, known.float(), (n, H, W), K), "known_labels: expected an integer tensor"),
+        (dict(known_labels=known[:, 1:]), lambda: guidance.check_known_labels(m, known[:, 1:], (n, H, W), K), "known_labels: expected shape"),
+        (dict(known_labels=bad_class), lambda: guidance.check_known_labels(m, bad_class, (n, H, W), K), "known_labels: values must be classes"),
+        (dict(temperature=0.01), lambda: guidance.check_shaping(m, 0.01, None), "temperature: expected a real number in"),
+        (dict(temperature=float("nan")), lambda: guidance.check_shaping(m, float("nan"), None), "temperature: expected a real number in"),
+        (dict(truncation=0.0), lambda: guidance.check_shaping(m, None, 0.0), "truncation: expected a real number in"),
+        (dict(truncation=1.5, evidence=ev), lambda: guidance.check_shaping(m, None, 1.5), "truncation: expected a real number in"),
     ]
     for kw, solo_check, text in cases:
         with pytest.raises(ValueError, match=text) as queued:

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from oracle import ccdm_oracle as O
-from ccdm_stochastic_segmentation_amd import hip
+from ccdm_stochastic_segmentation_amd import guidance, hip
 from ccdm_stochastic_segmentation_amd.models import pass_key, resample_walk, step_values
 from tests.sampler_util import (DEV, FREE, H, SEED, SMALL_CFG, T_SMALL, T_STRIDED, W, assert_symbol_declared_bound_and_built, clamp_restatement,
                                 load_lib, make_sampler, probabilities, renoise_restatement, sample_sharded_keywords, settings, small_model)
@@ -97,8 +97,8 @@ def test_resample_argument_validation():
     m.eval()
     assert m.philox_call == 0 and m._engines == {}          # nothing ran
     # the accepted forms; a pair that asks for no jump is no pair
-    assert m._check_resample((2, 3), ok) == (2, 3) and m._check_resample([np.int64(1), 2], ok) == (1, 2)
-    assert m._check_resample((2, 1), ok) is None and m._check_resample((0, 4), ok) is None and m._check_resample(None, None) is None
+    assert guidance.check_resample(m, (2, 3), ok) == (2, 3) and guidance.check_resample(m, [np.int64(1), 2], ok) == (1, 2)
+    assert guidance.check_resample(m, (2, 1), ok) is None and guidance.check_resample(m, (0, 4), ok) is None and guidance.check_resample(m, None, None) is None
 
 
 def test_sample_sharded_hands_resample_through():

@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from oracle import ccdm_oracle as O
-from ccdm_stochastic_segmentation_amd import hip
+from ccdm_stochastic_segmentation_amd import guidance, hip
 from tests.guided_util import (POWER_ERROR_ALLOWED, SHAPES, bits, coefficients, evidence_restatement, mixed_inputs, nhwk, posterior64, random_inputs,
                                sampler_evidence, shape_rows, shaped_restatement, threshold_margin64, weighted)
 from tests.guided_util import run_shaped_kernel as run_kernel
@@ -50,7 +50,7 @@ def test_shaped_symbol_declared_bound_and_built():
 
 
 def test_shaping_keyword_validation():
-    """Every refusal of _check_shaping is a ValueError naming the keyword, through forward, forward_denoising and predict_multiple, before
+    """Every refusal of guidance.check_shaping is a ValueError naming the keyword, through forward, forward_denoising and predict_multiple, before
     anything runs (a model that was never moved to a GPU: nothing can run); the accepted forms and what they become."""
     m, _ = small_model(3)
     m.eval()
@@ -92,15 +92,15 @@ def test_shaping_keyword_validation():
                 call(**{name: 0.5})
     assert m.philox_call == 0 and m._engines == {} and logits_model._engines == {}          # nothing ran
     # the accepted forms: Python ints and floats, numpy scalars, the ends of both ranges; (inv_temperature as fp32, top_r as fp32)
-    assert m._check_shaping(None, None) is None
-    assert m._check_shaping(1, 1) == (1.0, 1.0) and m._check_shaping(1.0, None) == (1.0, 1.0) and m._check_shaping(None, 1.0) == (1.0, 1.0)
-    assert m._check_shaping(np.float32(0.5), np.float64(0.25)) == (2.0, 0.25) and m._check_shaping(np.int64(2), np.int32(1)) == (0.5, 1.0)
-    assert m._check_shaping(20, 1e-6) == (float(np.float32(0.05)), float(np.float32(1e-6))) and m._check_shaping(0.05, None) == (20.0, 1.0)
-    assert m._check_shaping(0.7, 0.9) == (float(np.float32(1.0 / 0.7)), float(np.float32(0.9)))
+    assert guidance.check_shaping(m, None, None) is None
+    assert guidance.check_shaping(m, 1, 1) == (1.0, 1.0) and guidance.check_shaping(m, 1.0, None) == (1.0, 1.0) and guidance.check_shaping(m, None, 1.0) == (1.0, 1.0)
+    assert guidance.check_shaping(m, np.float32(0.5), np.float64(0.25)) == (2.0, 0.25) and guidance.check_shaping(m, np.int64(2), np.int32(1)) == (0.5, 1.0)
+    assert guidance.check_shaping(m, 20, 1e-6) == (float(np.float32(0.05)), float(np.float32(1e-6))) and guidance.check_shaping(m, 0.05, None) == (20.0, 1.0)
+    assert guidance.check_shaping(m, 0.7, 0.9) == (float(np.float32(1.0 / 0.7)), float(np.float32(0.9)))
     # Guidance carries the pair: set means guided, and a repeated batch keeps it
     from ccdm_stochastic_segmentation_amd.models import Guidance
     assert not Guidance() and Guidance(shaping=(1.0, 1.0)) and Guidance(shaping=(2.0, 0.5)).repeat_interleave(3).shaping == (2.0, 0.5)
-    assert m._check_guidance(None, None, None, (N, K, H, W), 0.5, None).shaping == (2.0, 1.0)
+    assert guidance.check_guidance(m, dict(temperature=0.5), (N, K, H, W)).shaping == (2.0, 1.0)
 
 
 @pytest.mark.parametrize("N,HW,K", SHAPES)

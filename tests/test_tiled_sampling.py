@@ -11,7 +11,7 @@ import pytest
 import torch
 
 from oracle import ccdm_oracle as O
-from ccdm_stochastic_segmentation_amd import hip
+from ccdm_stochastic_segmentation_amd import guidance, hip
 from ccdm_stochastic_segmentation_amd.models import Guidance, tile_origins
 from tests.guided_util import bits, coefficients, mixed_inputs, nhwk, run_shaped_kernel, shaped_restatement
 from tests.sampler_util import (DEV, H, SEED, SMALL_CFG, T_SMALL, T_STRIDED, W, assert_symbol_declared_bound_and_built, load_lib, make_sampler,
@@ -116,7 +116,7 @@ def test_tile_origins_against_a_brute_force_restatement(geom, oys, oxs):
 
 
 def test_tiles_keyword_validation():
-    """Every refusal of _check_tiles is a ValueError that begins with the keyword, through forward, forward_denoising and predict_multiple,
+    """Every refusal of guidance.check_tiles is a ValueError that begins with the keyword, through forward, forward_denoising and predict_multiple,
     before anything runs (a model that was never moved to a GPU: nothing can run); tiles=None gives no guidance."""
     m, _ = small_model(3)
     m.eval()
@@ -165,24 +165,24 @@ def test_tiles_keyword_validation():
         with pytest.raises(ValueError, match="^tiles.*known_labels"):
             call(tiles=ok, known_labels=known, resample=(2, 2))
     with pytest.raises(ValueError, match="^tiles.*resample"):
-        m._check_tiles(ok, resample=(2, 2))
+        guidance.check_tiles(m, ok, resample=(2, 2))
     # a model that takes a feature_condition needs the features of every tile: R = 2 * 2 here
     feat_model, _ = small_model(3)
     feat_model.eval()
     feat_model.unet.spec.feature_condition_idx = [1]                       # (only the check reads it: nothing runs)
     for fc in (torch.zeros(N, 4, 8, 8), torch.zeros(3, N, 4, 8, 8), torch.zeros(4, N + 1, 4, 8, 8)):
         with pytest.raises(ValueError, match="^tiles.*feature_condition"):
-            feat_model._check_guidance(None, None, None, (N, K, Hc, Wc), feature_condition=fc, tiles=ok)
-    assert feat_model._check_guidance(None, None, None, (N, K, Hc, Wc), feature_condition=torch.zeros(4, N, 4, 8, 8), tiles=ok).tiles == ok
-    assert m._check_guidance(None, None, None, (N, K, Hc, Wc), feature_condition=torch.zeros(N, 4, 8, 8), tiles=ok).tiles == ok   # ignored there
+            guidance.check_guidance(feat_model, dict(tiles=ok), (N, K, Hc, Wc), feature_condition=fc)
+    assert guidance.check_guidance(feat_model, dict(tiles=ok), (N, K, Hc, Wc), feature_condition=torch.zeros(4, N, 4, 8, 8)).tiles == ok
+    assert guidance.check_guidance(m, dict(tiles=ok), (N, K, Hc, Wc), feature_condition=torch.zeros(N, 4, 8, 8)).tiles == ok   # ignored there
     assert m.philox_call == 0 and m._engines == {} and logits_model._engines == {}          # nothing ran
     # the accepted forms and what they become
-    assert m._check_tiles(None) is None and m._check_tiles([32, 32, np.int64(16), 8]) == ok
-    g = m._check_guidance(None, None, None, (N, K, Hc, Wc), tiles=None)
+    assert guidance.check_tiles(m, None) is None and guidance.check_tiles(m, [32, 32, np.int64(16), 8]) == ok
+    g = guidance.check_guidance(m, dict(tiles=None), (N, K, Hc, Wc))
     assert g == Guidance() and not g
-    g = m._check_guidance(None, None, None, (N, K, Hc, Wc), tiles=list(ok))
+    g = guidance.check_guidance(m, dict(tiles=list(ok)), (N, K, Hc, Wc))
     assert g and g.tiles == ok and g.repeat_interleave(3).tiles == ok and g.views is None and g.shaping is None
-    assert m._check_guidance(None, None, None, (N, K, 32, 32), tiles=(32, 32, 32, 32)).tiles == (32, 32, 32, 32)
+    assert guidance.check_guidance(m, dict(tiles=(32, 32, 32, 32)), (N, K, 32, 32)).tiles == (32, 32, 32, 32)
 
 
 def test_sample_sharded_hands_tiles_through():

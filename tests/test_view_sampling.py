@@ -11,7 +11,7 @@ import pytest
 import torch
 
 from oracle import ccdm_oracle as O
-from ccdm_stochastic_segmentation_amd import hip
+from ccdm_stochastic_segmentation_amd import guidance, hip
 from ccdm_stochastic_segmentation_amd.models import DenoisingModel, Guidance
 from tests.guided_util import (POWER_ERROR_ALLOWED, bits, coefficients, mixed_inputs, nhwk, posterior64, run_shaped_kernel, sampler_evidence, shape_rows,
                                shaped_restatement, threshold_margin64, weighted)
@@ -143,7 +143,7 @@ def test_the_restatement_meets_the_definition(Hh, Ww):
 
 
 def test_views_keyword_validation():
-    """Every refusal of _check_views is a ValueError naming the keyword, through forward, forward_denoising and predict_multiple, before
+    """Every refusal of guidance.check_views is a ValueError naming the keyword, through forward, forward_denoising and predict_multiple, before
     anything runs (a model that was never moved to a GPU: nothing can run); views=() and None give no guidance."""
     m, _ = small_model(3)
     m.eval()
@@ -184,24 +184,24 @@ def test_views_keyword_validation():
         with pytest.raises(ValueError, match="^views.*known_labels"):
             call(views=("hflip",), known_labels=known, resample=(2, 2))
     with pytest.raises(ValueError, match="^views.*resample"):
-        m._check_views(("hflip",), resample=(2, 2))
+        guidance.check_views(m, ("hflip",), resample=(2, 2))
     # a model that takes a feature_condition needs the features of every view
     feat_model, _ = small_model(3)
     feat_model.eval()
     feat_model.unet.spec.feature_condition_idx = [1]                       # (only the check reads it: nothing runs)
     for fc in (torch.zeros(N, 4, 8, 8), torch.zeros(3, N, 4, 8, 8), torch.zeros(2, N + 1, 4, 8, 8)):
         with pytest.raises(ValueError, match="^views.*feature_condition"):
-            feat_model._check_guidance(None, None, None, (N, K, H, W), None, None, ("hflip",), fc)
-    assert feat_model._check_guidance(None, None, None, (N, K, H, W), None, None, ("hflip",), torch.zeros(2, N, 4, 8, 8)).views == (HFLIP,)
-    assert m._check_guidance(None, None, None, (N, K, H, W), None, None, ("hflip",), torch.zeros(N, 4, 8, 8)).views == (HFLIP,)   # ignored there
+            guidance.check_guidance(feat_model, dict(views=("hflip",)), (N, K, H, W), fc)
+    assert guidance.check_guidance(feat_model, dict(views=("hflip",)), (N, K, H, W), torch.zeros(2, N, 4, 8, 8)).views == (HFLIP,)
+    assert guidance.check_guidance(m, dict(views=("hflip",)), (N, K, H, W), torch.zeros(N, 4, 8, 8)).views == (HFLIP,)   # ignored there
     assert m.philox_call == 0 and m._engines == {} and logits_model._engines == {}          # nothing ran
     # the accepted forms and what they become
-    assert m._check_views(None) is None and m._check_views(()) is None and m._check_views([]) is None
-    assert m._check_views(("hflip",)) == (HFLIP,) and m._check_views(["vflip", "hflip"]) == (VFLIP, HFLIP)
-    assert m._check_views(("hflip", "vflip", "hvflip")) == (HFLIP, VFLIP, HVFLIP) and DenoisingModel.VIEW_FLIPS["hvflip"] == HFLIP | VFLIP
-    g = m._check_guidance(None, None, None, (N, K, H, W), views=())
+    assert guidance.check_views(m, None) is None and guidance.check_views(m, ()) is None and guidance.check_views(m, []) is None
+    assert guidance.check_views(m, ("hflip",)) == (HFLIP,) and guidance.check_views(m, ["vflip", "hflip"]) == (VFLIP, HFLIP)
+    assert guidance.check_views(m, ("hflip", "vflip", "hvflip")) == (HFLIP, VFLIP, HVFLIP) and DenoisingModel.VIEW_FLIPS["hvflip"] == HFLIP | VFLIP
+    g = guidance.check_guidance(m, dict(views=()), (N, K, H, W))
     assert g == Guidance() and not g
-    g = m._check_guidance(None, None, None, (N, K, H, W), views=("hvflip",))
+    g = guidance.check_guidance(m, dict(views=("hvflip",)), (N, K, H, W))
     assert g and g.views == (HVFLIP,) and g.repeat_interleave(3).views == (HVFLIP,) and g.shaping is None
 
 
