@@ -1056,9 +1056,10 @@ int conv_out_slices(const ccdm_conv_args& a) {
     return conv_slices(a.Hout, a.Wout, a.stride, false, a.fine_slices);
 }
 
-int launch_conv(const ccdm_conv_args& a, hipStream_t s) {
+// The launch plan (ConvPlan, ccdm_conv_common.h; reported by ccdm_conv_plan): every check of the call's shape and every decision a launch
+// rests on.  No pointer of `a` is followed: a pointer field says "operand present" or "absent".
+int conv_plan(const ccdm_conv_args& a, ConvPlan& p) {
     const int C = a.C0 + a.C1;
-    CCDM_REQUIRE(a.in0 && a.out && a.w, "conv: null in0/out/w");
     CCDM_REQUIRE(a.ksize == 1 || a.ksize == 3, "conv: ksize %d (need 1 or 3)", a.ksize);
     CCDM_REQUIRE(a.stride == 1 || a.stride == 2, "conv: stride %d", a.stride);
     CCDM_REQUIRE(a.stride == 1 || a.ksize == 3, "conv: stride 2 is built for 3x3 only");
@@ -1090,18 +1091,18 @@ int launch_conv(const ccdm_conv_args& a, hipStream_t s) {
     CCDM_REQUIRE(a.Hout == (Hc + 2 * pad - a.ksize) / a.stride + 1 && a.Wout == (Wc + 2 * pad - a.ksize) / a.stride + 1,
                  "conv: output %dx%d inconsistent with input %dx%d k%d s%d up%d", a.Hout, a.Wout, a.Hin, a.Win, a.ksize, a.stride, a.up);
 
-    ConvK k;
-    k.a = a;
-    k.core_unmasked = 0;
+    p = ConvPlan{};
     const int prec = a.prec & 255;
-    k.cin_pad = cin_pad_for(C, prec);
-    k.cin_pad_skip = a.skip0 ? cin_pad_for(a.SC0 + a.SC1, prec) : 0;
-    k.skip_wide = 0;
+    p.cin_pad = cin_pad_for(C, prec);
+    p.cin_pad_skip = a.skip0 ? cin_pad_for(a.SC0 + a.SC1, prec) : 0;
     int NI;
-    conv_ntiles(up2 ? 4 * a.Cout : a.Cout, &k.ntiles, &NI);
+    conv_ntiles(up2 ? 4 * a.Cout : a.Cout, &p.ntiles, &NI);
     // the sub-pixel form tiles the low-resolution input space
     const int tH = up2 ? a.Hin : a.Hout, tW = up2 ? a.Win : a.Wout;
     const ConvGeo g = conv_geo(tH, tW, a.stride, up2, a.fine_slices != 0);
+    p.g = g;
+    p.tile_h = g.TH; p.tile_w = g.TW;
+    p.slices = conv_slices(tH, tW, a.stride, up2, a.fine_slices);
     // small spatial stages have few pixel tiles: spread the output-channel tiles over blocks instead;
     // wide tiles take at most 2 n-tiles per block (register budget of the staged B chunk)
     if (up2) NI = g.TW == 16 ? 4 : 1;
@@ -1110,57 +1111,48 @@ int launch_conv(const ccdm_conv_args& a, hipStream_t s) {
         // two n-tiles per block share one staged halo (half the staging work) but need 236 VGPRs and 64 KB of LDS (two blocks
         // per CU): worth it only when there are blocks to spare.  Measured at the 32x32 stage (64 samples x 4 tiles): one n-tile
         // per block 25.6 us vs 28.0; at 64x64 outputs (16 tiles per sample) two n-tiles win, 67.8 vs 70.6.  (A partitioning
-        // choice only: every output element is computed by the same instruction sequence either way.)
-        const long blocks2 = (long)a.N * conv_slices(a.Hout, a.Wout, a.stride, false, a.fine_slices) * (k.ntiles / 2);
-        NI = (k.ntiles % 2 == 0 && blocks2 >= 512) ? 2 : 1;
+        // choice only: every output element is computed by the same instruction sequence either way — the ONE rule of this file
+        // that reads N; tests/test_batch_rules.py holds both sides of the threshold to equal bits, statistics partials included.)
+        const long blocks2 = (long)a.N * p.slices * (p.ntiles / 2);
+        NI = (p.ntiles % 2 == 0 && blocks2 >= 512) ? 2 : 1;
     }
-    k.tiles_x = cdiv(tW, g.TW);
-    k.tiles_y = cdiv(tH, g.TH);
-    k.slices = conv_slices(tH, tW, a.stride, up2, a.fine_slices);
-    // few-pixel images: K split over the waves, weight fragments straight from L2 (ccdm_conv_ks.hip) — one statistics slice per 8x8 tile
-    const bool ks = conv_takes_ks(a);
-    if (ks) k.slices = conv_ks_slices(a);
-    k.wscale = reinterpret_cast<const float*>(static_cast<const char*>(a.w) +
-                                              (up2 ? packed_frag_bytes(4 * a.Cout, C, 2, prec) : packed_frag_bytes(a.Cout, C, a.ksize, prec)));
-    const int want_slices = (up2 && NI == 1 ? 4 : 1) * k.slices;      // one phase per block: every (slice, phase) pair leaves a partial
-    if (a.out_stats) CCDM_REQUIRE(a.out_slices == want_slices, "conv: out_slices %d != %d", a.out_slices, want_slices);
+    p.ntiles_per_block = NI;
+    p.wscale_off = up2 ? packed_frag_bytes(4 * a.Cout, C, 2, prec) : packed_frag_bytes(a.Cout, C, a.ksize, prec);
+    p.out_slices = (up2 && NI == 1 ? 4 : 1) * p.slices;      // one phase per block: every (slice, phase) pair leaves a partial
     if (up2 && upconv_eligible(a)) {               // low-resolution Upsample convs: wave = phase, weight fragments straight from L2
-        const int rcu = launch_upconv(a, k.slices, k.ntiles, k.wscale, s);
-        if (rcu) return rcu;
-        CCDM_CHECK_LAUNCH("upconv");
+        upconv_plan(a, p);
         return 0;
     }
-    if (conv1x1_eligible(a, k.slices)) {           // AttentionBlock.proj_out + residual at the low-resolution stages: no LDS staging at all
-        const int rc1 = launch_conv1x1(a, k.slices, k.ntiles, k.wscale, s);
-        if (rc1) return rc1;
-        CCDM_CHECK_LAUNCH("conv1x1");
+    if (conv1x1_eligible(a, p.slices)) {           // AttentionBlock.proj_out + residual at the low-resolution stages: no LDS staging at all
+        conv1x1_plan(a, p);
         return 0;
     }
-    if (ks) {
-        const int rck = launch_conv_ks(a, k.ntiles, k.wscale, s);
-        if (rck) return rck;
-        CCDM_CHECK_LAUNCH("conv_ks");
+    // few-pixel images: K split over the waves, weight fragments straight from L2 (ccdm_conv_ks.hip) — one statistics slice per 8x8 tile
+    if (conv_takes_ks(a)) {
+        CCDM_REQUIRE(conv_ks_describe(a, p), "conv_ks: geometry not built");
         return 0;
     }
+    p.kernel = CCDM_CONV_KERNEL_GENERAL;
     const int HP = ((g.TH - 1) * a.stride + a.ksize) * ((g.TW - 1) * a.stride + a.ksize);
     const int ck = chunk_ck(a, g);
-    {   // wide skip chunks (k_conv, SKW): the wide-tile F16X3 one-n-tile variant, skip sources in multiples of 32 channels
-        k.skip_wide = (a.skip0 && prec == CCDM_PREC_F16X3 && a.ksize == 3 && a.stride == 1 && !a.up && g.TW == 32 && NI == 1 && ck == 16 &&
-                       a.SC0 % 32 == 0 && a.SC1 % 32 == 0 && !(a.prec >> 8)) ? 1 : 0;
-    }
+    p.chunk = ck;
+    // wide skip chunks (k_conv, SKW): the wide-tile F16X3 one-n-tile variant, skip sources in multiples of 32 channels
+    p.skip_wide = (a.skip0 && prec == CCDM_PREC_F16X3 && a.ksize == 3 && a.stride == 1 && !a.up && g.TW == 32 && NI == 1 && ck == 16 &&
+                   a.SC0 % 32 == 0 && a.SC1 % 32 == 0 && !(a.prec >> 8)) ? 1 : 0;
     {   // core halo items need no per-lane padding mask when every tile column and every channel quad exists (see ConvK)
         const int SC = a.SC0 + a.SC1;
         const bool chan_ok = a.C0 % ck == 0 && a.C1 % ck == 0 && (!a.skip0 || (a.SC0 % ck == 0 && a.SC1 % ck == 0 && SC > 0));
-        k.core_unmasked = ((up2 ? a.Win : Wc) % (g.TW * a.stride) == 0 && chan_ok) ? 1 : 0;
+        p.core_unmasked = ((up2 ? a.Win : Wc) % (g.TW * a.stride) == 0 && chan_ok) ? 1 : 0;
     }
     CCDM_REQUIRE(a.C1 == 0 || a.C0 % ck == 0, "conv: first source has %d channels; a concatenated input must split at a multiple of the %d-channel chunk", a.C0, ck);
     CCDM_REQUIRE(a.SC1 == 0 || a.SC0 % ck == 0, "conv: first skip source has %d channels; a concatenated input must split at a multiple of the %d-channel chunk", a.SC0, ck);
-    CCDM_REQUIRE((k.cin_pad + k.cin_pad_skip) / ck <= 64, "conv: %d input (+%d skip) channels make more than 64 chunks of %d (chunk descriptors live in the 64 lanes of a register)",
-                 k.cin_pad, k.cin_pad_skip, ck);
+    CCDM_REQUIRE((p.cin_pad + p.cin_pad_skip) / ck <= 64, "conv: %d input (+%d skip) channels make more than 64 chunks of %d (chunk descriptors live in the 64 lanes of a register)",
+                 p.cin_pad, p.cin_pad_skip, ck);
     size_t lds = (size_t)HP * conv_pixb(prec, ck);
     lds = (lds + 15) / 16 * 16;
     if (prec != CCDM_PREC_F32) lds += (size_t)(up2 ? 4 : a.ksize * a.ksize) * (ck / 16) * NI * FRAG_BYTES;     // staged B chunk
-    const int ksp = tap_split(a, g) ? 3 : 1;
+    p.tap_split = tap_split(a, g) ? 1 : 0;
+    const int ksp = p.tap_split ? 3 : 1;
     const size_t red = (size_t)g.waves * ksp * NI * 32 * 16;
     if (lds < red) lds = red;
     const size_t epi = (size_t)g.waves * ksp * g.MI * 32 * EPI_ROW * 4;   // epilogue transpose buffer (wave-private rows)
@@ -1172,10 +1164,52 @@ int launch_conv(const ccdm_conv_args& a, hipStream_t s) {
         lds += (size_t)C * 8;
     }
     CCDM_REQUIRE(lds <= 160 * 1024, "conv: LDS %zu too large", lds);
-    dim3 grid(a.N * k.slices, k.ntiles / NI);
-    const int rc = prec == CCDM_PREC_F32 ? launch_prec<CCDM_PREC_F32>(k, g, NI, ck, grid, lds, s)
-                   : prec == CCDM_PREC_F16 ? launch_prec<CCDM_PREC_F16>(k, g, NI, ck, grid, lds, s)
-                                           : launch_prec<CCDM_PREC_F16X3>(k, g, NI, ck, grid, lds, s);
+    p.lds_bytes = (int)lds;
+    p.grid_x = a.N * p.slices; p.grid_y = p.ntiles / NI; p.block = g.waves * ksp * 64;
+    return 0;
+}
+
+int launch_conv(const ccdm_conv_args& a, hipStream_t s) {
+    CCDM_REQUIRE(a.in0 && a.out && a.w, "conv: null in0/out/w");
+    ConvPlan p;
+    const int rcp = conv_plan(a, p);
+    if (rcp) return rcp;
+    if (a.out_stats) CCDM_REQUIRE(a.out_slices == p.out_slices, "conv: out_slices %d != %d", a.out_slices, p.out_slices);
+    const float* wscale = reinterpret_cast<const float*>(static_cast<const char*>(a.w) + p.wscale_off);
+    if (p.kernel == CCDM_CONV_KERNEL_UPCONV) {
+        const int rcu = launch_upconv(a, p, wscale, s);
+        if (rcu) return rcu;
+        CCDM_CHECK_LAUNCH("upconv");
+        return 0;
+    }
+    if (p.kernel == CCDM_CONV_KERNEL_1X1 || p.kernel == CCDM_CONV_KERNEL_1X1_MULTI) {
+        const int rc1 = launch_conv1x1(a, p, wscale, s);
+        if (rc1) return rc1;
+        CCDM_CHECK_LAUNCH("conv1x1");
+        return 0;
+    }
+    if (p.kernel == CCDM_CONV_KERNEL_KS) {
+        const int rck = launch_conv_ks(a, p.ntiles, wscale, s);
+        if (rck) return rck;
+        CCDM_CHECK_LAUNCH("conv_ks");
+        return 0;
+    }
+    ConvK k;
+    k.a = a;
+    k.cin_pad = p.cin_pad;
+    k.cin_pad_skip = p.cin_pad_skip;
+    k.ntiles = p.ntiles;
+    k.slices = p.slices;
+    k.tiles_x = cdiv(a.up == 2 ? a.Win : a.Wout, p.g.TW);
+    k.tiles_y = cdiv(a.up == 2 ? a.Hin : a.Hout, p.g.TH);
+    k.skip_wide = p.skip_wide;
+    k.wscale = wscale;
+    k.core_unmasked = p.core_unmasked;
+    const int prec = a.prec & 255;
+    const dim3 grid(p.grid_x, p.grid_y);
+    const int rc = prec == CCDM_PREC_F32 ? launch_prec<CCDM_PREC_F32>(k, p.g, p.ntiles_per_block, p.chunk, grid, (size_t)p.lds_bytes, s)
+                   : prec == CCDM_PREC_F16 ? launch_prec<CCDM_PREC_F16>(k, p.g, p.ntiles_per_block, p.chunk, grid, (size_t)p.lds_bytes, s)
+                                           : launch_prec<CCDM_PREC_F16X3>(k, p.g, p.ntiles_per_block, p.chunk, grid, (size_t)p.lds_bytes, s);
     if (rc) return rc;
     CCDM_CHECK_LAUNCH("conv");
     return 0;
@@ -1199,6 +1233,15 @@ extern "C" int ccdm_upconv_slices(int Hin, int Win) {
 extern "C" int ccdm_conv_out_slices(const ccdm_conv_args* a) {
     if (!a) return ccdm::fail("ccdm_conv_out_slices: null args");
     return ccdm::conv_out_slices(*a);
+}
+
+extern "C" int ccdm_conv_plan(const ccdm_conv_args* a, ccdm_conv_plan_info* out) {
+    if (!a || !out) return ccdm::fail("ccdm_conv_plan: null args");
+    ccdm::ConvPlan p;
+    const int rc = ccdm::conv_plan(*a, p);
+    if (rc) return rc;
+    *out = p;       // the reported part of the plan
+    return 0;
 }
 
 extern "C" int ccdm_conv_slices_ex(int Hin, int Win, int ksize, int stride, int up, int fine) {

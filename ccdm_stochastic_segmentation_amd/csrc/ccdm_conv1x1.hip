@@ -282,24 +282,42 @@ bool conv1x1_eligible(const ccdm_conv_args& a, int slices) {
     return ppb > 0 && HW <= 16384;
 }
 
-int launch_conv1x1(const ccdm_conv_args& a, int slices, int ntiles, const float* wscale, hipStream_t s) {
-    Conv1x1K k;
-    k.in = a.in0; k.w = a.w; k.wscale = wscale; k.bias = a.bias; k.resid = a.resid; k.out = a.out; k.out_stats = a.out_stats;
-    k.C = a.C0; k.Cout = a.Cout; k.HW = a.Hout * a.Wout; k.ntiles = ntiles;
-    k.px_per_block = conv1x1_px_per_block(a, slices);
-    k.slices = k.HW / k.px_per_block;
-    k.a = a;
-    const dim3 grid(a.N * k.slices, a.Cout / 32), block(k.px_per_block / 32 * 64);
-    const size_t lds = a.stats0 ? (size_t)a.C0 * 8 + (size_t)((unsigned)a.C0 > block.x ? (unsigned)a.C0 : block.x) * 16 : 0;   // (scale, shift) table + the statistics exchange
-    // wide outputs without statistics (qkv): walk several n-tiles per block so that ~512 blocks remain
+// The plan of a conv1x1_eligible call (conv_plan, ccdm_conv.hip): p.slices comes in as the general rule's statistics slices and leaves
+// as this kernel's pixel blocks per sample (the same number when statistics are written).
+void conv1x1_plan(const ccdm_conv_args& a, ConvPlan& p) {
+    const int HW = a.Hout * a.Wout, ppb = conv1x1_px_per_block(a, p.slices);
+    p.slices = HW / ppb;
+    p.tile_h = 1; p.tile_w = ppb;
+    p.chunk = 16;
+    p.block = ppb / 32 * 64;
+    p.lds_bytes = a.stats0 ? a.C0 * 8 + (a.C0 > p.block ? a.C0 : p.block) * 16 : 0;   // (scale, shift) table + the statistics exchange
+    // wide outputs without statistics (qkv): walk several n-tiles per block so that ~512 blocks remain.  (The ONE rule of this file that
+    // reads N — a partitioning choice only: a tile's products, their order and its epilogue are those of the one-tile kernel whichever
+    // block walks it; tests/test_batch_rules.py holds the walk's exits to equal bits.)
     const int nt_real = a.Cout / 32;
-    const long xb = (long)a.N * k.slices;
+    const long xb = (long)a.N * p.slices;
     int ntb = (int)((xb * nt_real + 256) / 512);
     ntb = ntb < 1 ? 1 : (ntb > nt_real ? nt_real : ntb);
-    if (!a.out_stats && a.C0 <= 128 && block.x <= 256 && ntb > 1) {
-        const dim3 gridm((unsigned)xb, (unsigned)((nt_real + ntb - 1) / ntb));
-        if (a.stats0) hipLaunchKernelGGL((k_conv1x1_multi<true>), gridm, block, lds, s, k, ntb);
-        else hipLaunchKernelGGL((k_conv1x1_multi<false>), gridm, block, 0, s, k, ntb);
+    const bool multi = !a.out_stats && a.C0 <= 128 && p.block <= 256 && ntb > 1;
+    p.kernel = multi ? CCDM_CONV_KERNEL_1X1_MULTI : CCDM_CONV_KERNEL_1X1;
+    p.ntiles_per_block = multi ? ntb : 1;
+    p.grid_x = (int)xb;
+    p.grid_y = multi ? (nt_real + ntb - 1) / ntb : nt_real;
+}
+
+int launch_conv1x1(const ccdm_conv_args& a, const ConvPlan& p, const float* wscale, hipStream_t s) {
+    Conv1x1K k;
+    k.in = a.in0; k.w = a.w; k.wscale = wscale; k.bias = a.bias; k.resid = a.resid; k.out = a.out; k.out_stats = a.out_stats;
+    k.C = a.C0; k.Cout = a.Cout; k.HW = a.Hout * a.Wout; k.ntiles = p.ntiles;
+    k.px_per_block = p.tile_w;
+    k.slices = p.slices;
+    k.a = a;
+    const dim3 grid(p.grid_x, p.grid_y), block(p.block);
+    const size_t lds = (size_t)p.lds_bytes;
+    if (p.kernel == CCDM_CONV_KERNEL_1X1_MULTI) {
+        const int ntb = p.ntiles_per_block;
+        if (a.stats0) hipLaunchKernelGGL((k_conv1x1_multi<true>), grid, block, lds, s, k, ntb);
+        else hipLaunchKernelGGL((k_conv1x1_multi<false>), grid, block, 0, s, k, ntb);
         return 0;
     }
     if (a.stats0) {

@@ -69,16 +69,29 @@ struct ConvK {   // kernel-side copy of ccdm_conv_args (+ derived)
                              // core halo items need no per-lane padding mask, only the wave-uniform row test
 };
 
+// The launch plan of one conv call: what ccdm_conv_plan reports (include/ccdm_hip.h) plus what only the launchers need.  conv_plan
+// (ccdm_conv.hip) is the one place where a launch decision is taken — kernel family, tiling, chunk width, n-tiles per block, grid —
+// and launch_conv / launch_upconv / launch_conv1x1 / launch_conv_ks run what it says.  Host code: it follows no pointer of the call.
+struct ConvPlan : ccdm_conv_plan_info {
+    ConvGeo g;               // tile geometry of the general kernel and of the sub-pixel form
+    int cin_pad, cin_pad_skip;
+    size_t wscale_off;       // byte offset of the F16X3 per-channel scale table behind the packed fragments of `w`
+};
+int conv_plan(const ccdm_conv_args& a, ConvPlan& p);
+
 // plain 1x1 conv (+bias +residual +statistics) of a low-resolution tensor without LDS staging (ccdm_conv1x1.hip)
 bool conv1x1_eligible(const ccdm_conv_args& a, int slices);
-int launch_conv1x1(const ccdm_conv_args& a, int slices, int ntiles, const float* wscale, hipStream_t s);
+void conv1x1_plan(const ccdm_conv_args& a, ConvPlan& p);          // p.slices: the general rule's slices on entry, this kernel's pixel blocks on return
+int launch_conv1x1(const ccdm_conv_args& a, const ConvPlan& p, const float* wscale, hipStream_t s);
 
 // 3x3 conv of a few-pixel image, K split over the waves of a block, weight fragments straight from L2 (ccdm_conv_ks.hip)
 bool conv_ks_eligible(const ccdm_conv_args& a);
 int conv_ks_slices(const ccdm_conv_args& a);            // statistics slices that kernel leaves (one per 8x8 tile)
+bool conv_ks_describe(const ccdm_conv_args& a, ConvPlan& p);     // fills p from the plan launch_conv_ks runs; false = not for this kernel
 int launch_conv_ks(const ccdm_conv_args& a, int ntiles, const float* wscale, hipStream_t s);
 // Upsample + conv 3x3 in sub-pixel form at the low-resolution decoder levels: wave = phase, weight fragments straight from L2 (ccdm_upconv.hip)
 bool upconv_eligible(const ccdm_conv_args& a);
-int launch_upconv(const ccdm_conv_args& a, int slices, int ntiles, const float* wscale, hipStream_t s);
+void upconv_plan(const ccdm_conv_args& a, ConvPlan& p);
+int launch_upconv(const ccdm_conv_args& a, const ConvPlan& p, const float* wscale, hipStream_t s);
 
 }  // namespace ccdm

@@ -488,6 +488,22 @@ bool conv_ks_eligible(const ccdm_conv_args& a) {
     return conv_ks_plan(a, k, lds, ni);
 }
 
+// what conv_plan reports of a launch of this kernel (ccdm_conv.hip): the geometry launch_conv_ks takes from the same conv_ks_plan
+bool conv_ks_describe(const ccdm_conv_args& a, ConvPlan& p) {
+    ConvKS k;
+    size_t lds;
+    int NI;
+    if (!conv_ks_plan(a, k, lds, NI)) return false;
+    p.kernel = CCDM_CONV_KERNEL_KS;
+    p.tile_h = p.tile_w = 8;
+    p.chunk = 16 * k.nks_m;                         // the halo tile is staged once with every input channel
+    p.ntiles_per_block = NI;
+    p.slices = p.out_slices = k.tiles_x * k.tiles_y;
+    p.grid_x = a.N * k.tiles_x * k.tiles_y; p.grid_y = a.Cout / (32 * NI); p.block = KS_NT;
+    p.lds_bytes = (int)lds;
+    return true;
+}
+
 // statistics slices a launch of this kernel leaves: one per 8x8 tile
 int conv_ks_slices(const ccdm_conv_args& a) { return (a.Hout / 8) * (a.Wout / 8); }
 

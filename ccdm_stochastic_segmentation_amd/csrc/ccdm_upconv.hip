@@ -262,9 +262,24 @@ bool upconv_eligible(const ccdm_conv_args& a) {
     return a.Hin % UP_TH == 0 && (a.Win % 16 == 0 || a.Win == 8);
 }
 
+// The plan of an upconv_eligible call (conv_plan, ccdm_conv.hip); p.slices and p.ntiles are the sub-pixel form's.
+void upconv_plan(const ccdm_conv_args& a, ConvPlan& p) {
+    p.kernel = CCDM_CONV_KERNEL_UPCONV;
+    p.tile_h = UP_TH; p.tile_w = a.Win == 8 ? 8 : 16;
+    p.chunk = a.C0;                                 // the halo tile is staged once with every input channel
+    // channel tiles per block: two from one staged tile while >= 512 blocks remain (a partitioning choice only: every output element
+    // and every statistics partial is computed by the same instruction sequence either way)
+    const int ctiles = a.Cout / 32;
+    p.ntiles_per_block = (ctiles % 2 == 0 && (long)a.N * p.slices * (ctiles / 2) >= 512) ? 2 : 1;
+    p.grid_x = a.N * p.slices; p.grid_y = ctiles / p.ntiles_per_block; p.block = 256;
+    const int a_bytes = UP_HH * (p.tile_w + 2) * conv_pixb(CCDM_PREC_F16X3, a.C0);          // UpGeo<C, TW>::A_BYTES
+    p.lds_bytes = p.ntiles_per_block == 1 ? std::max(a_bytes, UP_EPI_BYTES) : a_bytes + UP_EPI_BYTES;     // one tile per block: the epilogue aliases the halo tile
+}
+
 template <int C, int TW>
-static int launch_upconv_ct(const UpK& k, dim3 grid, bool alias, hipStream_t s) {
+static int launch_upconv_ct(const UpK& k, dim3 grid, bool alias, size_t planned_lds, hipStream_t s) {
     const size_t lds = alias ? (size_t)std::max(UpGeo<C, TW>::A_BYTES, UP_EPI_BYTES) : (size_t)UpGeo<C, TW>::A_BYTES + UP_EPI_BYTES;
+    if (lds != planned_lds) return fail("upconv: the plan reserves %zu bytes of LDS, the kernel needs %zu", planned_lds, lds);
     auto kern = alias ? k_upconv<C, TW, true> : k_upconv<C, TW, false>;
     static bool configured[2] = {false, false};          // (per instantiation and form: the attribute is set once, not on every enqueue)
     if (lds > 64 * 1024 && !configured[alias ? 1 : 0]) {
@@ -276,26 +291,24 @@ static int launch_upconv_ct(const UpK& k, dim3 grid, bool alias, hipStream_t s) 
     return 0;
 }
 template <int C>
-static int launch_upconv_c(const UpK& k, dim3 grid, bool alias, hipStream_t s) {
-    return k.Win == 8 ? launch_upconv_ct<C, 8>(k, grid, alias, s) : launch_upconv_ct<C, 16>(k, grid, alias, s);
+static int launch_upconv_c(const UpK& k, dim3 grid, bool alias, size_t lds, hipStream_t s) {
+    return k.Win == 8 ? launch_upconv_ct<C, 8>(k, grid, alias, lds, s) : launch_upconv_ct<C, 16>(k, grid, alias, lds, s);
 }
 
-int launch_upconv(const ccdm_conv_args& a, int slices, int ntiles, const float* wscale, hipStream_t s) {
+int launch_upconv(const ccdm_conv_args& a, const ConvPlan& p, const float* wscale, hipStream_t s) {
     UpK k;
     k.in = a.in0; k.w = a.w; k.wscale = wscale; k.bias = a.bias; k.out = a.out; k.out_stats = a.out_stats;
-    k.N = a.N; k.Hin = a.Hin; k.Win = a.Win; k.Cout = a.Cout; k.ntiles = ntiles; k.slices = slices;
-    k.tiles_x = a.Win == 8 ? 1 : a.Win / 16; k.tiles_y = a.Hin / UP_TH;
-    // channel tiles per block: two from one staged tile while >= 512 blocks remain (a partitioning choice only: every output element
-    // and every statistics partial is computed by the same instruction sequence either way)
-    const int ctiles = a.Cout / 32;
-    k.ctb = (ctiles % 2 == 0 && (long)a.N * slices * (ctiles / 2) >= 512) ? 2 : 1;
-    const dim3 grid(a.N * slices, ctiles / k.ctb);
+    k.N = a.N; k.Hin = a.Hin; k.Win = a.Win; k.Cout = a.Cout; k.ntiles = p.ntiles; k.slices = p.slices;
+    k.tiles_x = a.Win / p.tile_w; k.tiles_y = a.Hin / p.tile_h;
+    k.ctb = p.ntiles_per_block;
+    const dim3 grid(p.grid_x, p.grid_y);
     const bool alias = k.ctb == 1;
+    const size_t lds = (size_t)p.lds_bytes;
     switch (a.C0) {
-        case 32: return launch_upconv_c<32>(k, grid, alias, s);
-        case 64: return launch_upconv_c<64>(k, grid, alias, s);
-        case 96: return launch_upconv_c<96>(k, grid, alias, s);
-        default: return launch_upconv_c<128>(k, grid, alias, s);
+        case 32: return launch_upconv_c<32>(k, grid, alias, lds, s);
+        case 64: return launch_upconv_c<64>(k, grid, alias, lds, s);
+        case 96: return launch_upconv_c<96>(k, grid, alias, lds, s);
+        default: return launch_upconv_c<128>(k, grid, alias, lds, s);
     }
 }
 

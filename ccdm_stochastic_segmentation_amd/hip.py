@@ -63,6 +63,24 @@ class ConvArgs(C.Structure):
     ]
 
 
+CONV_KERNEL_GENERAL, CONV_KERNEL_KS, CONV_KERNEL_UPCONV, CONV_KERNEL_1X1, CONV_KERNEL_1X1_MULTI = 0, 1, 2, 3, 4      # CCDM_CONV_KERNEL_*
+
+
+class ConvPlanInfo(C.Structure):
+    """ccdm_conv_plan_info: the launch plan ccdm_conv_plan reports for a ConvArgs (host code only: nothing is launched)."""
+    _fields_ = [
+        ("kernel", C.c_int32),
+        ("tile_h", C.c_int32), ("tile_w", C.c_int32),
+        ("chunk", C.c_int32),
+        ("ntiles", C.c_int32), ("ntiles_per_block", C.c_int32),
+        ("skip_wide", C.c_int32), ("tap_split", C.c_int32),
+        ("slices", C.c_int32), ("out_slices", C.c_int32),
+        ("core_unmasked", C.c_int32),
+        ("grid_x", C.c_int32), ("grid_y", C.c_int32), ("block", C.c_int32),
+        ("lds_bytes", C.c_int32),
+    ]
+
+
 class PostArgs(C.Structure):
     _fields_ = [
         ("head", C.c_void_p), ("softmax", C.c_int32), ("head_stride", C.c_int32),
@@ -172,6 +190,7 @@ SIGNATURES = {
     "ccdm_conv_slices": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "ccdm_conv_slices_ex": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "ccdm_conv_out_slices": (C.c_int, [C.POINTER(ConvArgs)]),
+    "ccdm_conv_plan": (C.c_int, [C.POINTER(ConvArgs), C.POINTER(ConvPlanInfo)]),
     "ccdm_upconv_supported": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "ccdm_upconv_slices": (C.c_int, [C.c_int, C.c_int]),
     "ccdm_pack_upconv_weight": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
@@ -383,6 +402,14 @@ def check(rc: int, what: str = "") -> int:
     if rc is None or rc < 0:
         raise CcdmHipError(f"{what}: {last_error()}")
     return rc
+
+
+def conv_plan(args: ConvArgs) -> ConvPlanInfo:
+    """The launch plan of a conv call (ccdm_conv_plan): which kernel ccdm_conv2d would run for `args` and how it partitions the work.
+    Host-side, no GPU needed; the pointer fields of `args` only say which operands are present."""
+    info = ConvPlanInfo()
+    check(load().ccdm_conv_plan(C.byref(args), C.byref(info)), "conv_plan")
+    return info
 
 
 def pack_conv_weight(w, ksize: int, prec: int = PREC_F32, cout_absmax=None):

@@ -111,6 +111,33 @@ int ccdm_conv_slices_ex(int Hin, int Win, int ksize, int stride, int up, int fin
  * kernel with its own tiling — 3x3 F16X3 convs of images of at most 256 pixels leave one slice per 8x8 tile (16x16: 4, where the
  * rule says 2).  A function of the layer's shape and operands, never of N.  What a caller should size out_stats by. */
 int ccdm_conv_out_slices(const ccdm_conv_args* a);
+/* The launch plan of THIS conv: which kernel ccdm_conv2d would run for `a` and how it partitions the work.  Host code only — nothing is
+ * launched and no pointer of `a` is followed (a pointer field counts as "operand present" or "absent"; out_stats != NULL = "statistics
+ * wanted", out_slices is not checked).  The launchers take every one of these decisions from the function that fills this struct.
+ * Everything here is a function of the layer's shape and operands, never of N — except ntiles_per_block, the one field a batch size
+ * may change: the partitions it chooses between compute every output element and every statistics partial with the same
+ * instruction sequence (tests/test_batch_rules.py holds both sides of each threshold to equal bits).  Returns 0, or a negative
+ * error for a call ccdm_conv2d refuses by its shape.  Added in ABI 11 as a compatible extension. */
+enum { CCDM_CONV_KERNEL_GENERAL = 0,     /* k_conv: every input staged through LDS                                  (ccdm_conv.hip)    */
+       CCDM_CONV_KERNEL_KS = 1,          /* few-pixel 3x3: K split over the waves of a block                         (ccdm_conv_ks.hip) */
+       CCDM_CONV_KERNEL_UPCONV = 2,      /* low-resolution sub-pixel Upsample conv: wave = phase                     (ccdm_upconv.hip)  */
+       CCDM_CONV_KERNEL_1X1 = 3,         /* LDS-free 1x1, one n-tile per block                                       (ccdm_conv1x1.hip) */
+       CCDM_CONV_KERNEL_1X1_MULTI = 4 }; /* LDS-free 1x1 without output statistics, several n-tiles per block        (ccdm_conv1x1.hip) */
+typedef struct ccdm_conv_plan_info {
+    int32_t kernel;                 /* CCDM_CONV_KERNEL_* */
+    int32_t tile_h, tile_w;         /* pixel tile of a block's walk (up = 2: of the low-resolution input; 1x1 kernels: 1 x pixels per block) */
+    int32_t chunk;                  /* input channels staged per chunk (the 1x1 kernels: channels per k-step in flight, 16) */
+    int32_t ntiles;                 /* 32-channel output tiles of the packed weights (padded; up = 2: four phases per channel tile) */
+    int32_t ntiles_per_block;       /* n-tiles one block computes: NI of k_conv / k_conv_ks, ntb of the 1x1 multi kernel, ctb of k_upconv */
+    int32_t skip_wide;              /* the fused 1x1 skip runs in 32-channel core-only chunks (needs ntiles_per_block == 1) */
+    int32_t tap_split;              /* the 3x3 kernel rows are split over three wave groups */
+    int32_t slices;                 /* blocks per sample along grid.x */
+    int32_t out_slices;             /* statistics partials per sample (= ccdm_conv_out_slices) */
+    int32_t core_unmasked;          /* general kernel: core halo items need no per-lane padding mask */
+    int32_t grid_x, grid_y, block;  /* the launch: blocks and threads per block */
+    int32_t lds_bytes;              /* dynamic LDS of the launch */
+} ccdm_conv_plan_info;
+int ccdm_conv_plan(const ccdm_conv_args* a, ccdm_conv_plan_info* out);
 /* Upsample (nearest x2) + conv 3x3 in sub-pixel form (unet.py:106-116), `up = 2`:
  *   out(2y+dy, 2x+dx) = sum over a,b in {0,1} of W'[dy,dx][a,b] . in(y+dy-1+a, x+dx-1+b),
  *   W'[dy][..][a] = the 3x3 kernel rows that land on low-resolution row y+dy-1+a  (dy=0: {r0}, {r1+r2}; dy=1: {r0+r1}, {r2}; columns alike):

@@ -30,9 +30,11 @@ def gn_stats(x_nhwc: torch.Tensor, slices: int = 1) -> torch.Tensor:
 
 
 def conv2d(srcs, weight, bias, ksize, *, stats=None, gamma=None, beta=None, act=hip.ACT_NONE, stride=1, up=False,
-           emb=None, emb_rows=None, film=None, resid=None, want_stats=True, prec=hip.PREC_F32, skip=None, bench=None, fine=False, diag=0):
+           emb=None, emb_rows=None, film=None, resid=None, want_stats=True, prec=hip.PREC_F32, skip=None, bench=None, fine=False, diag=0,
+           plan=None):
     """srcs: list of 1-2 NHWC cuda tensors; weight OIHW numpy/torch cpu; stats: list of stats tensors or None.
     emb: [rows, E] cpu tensor added per output channel (row per sample via emb_rows) ; film: (table cpu [rows, 2C]).
+    plan: a dict that receives the launch plan of this very call (ccdm_conv_plan of the argument struct that is launched).
     Returns (out NHWC cuda, out_stats or None)."""
     lib = hip.load()
     a = srcs[0]
@@ -104,6 +106,9 @@ def conv2d(srcs, weight, bias, ksize, *, stats=None, gamma=None, beta=None, act=
             assert S == lib.ccdm_upconv_slices(Hin, Win)
         ost = torch.empty((N, S, cout, 2), dtype=torch.float64, device=DEV)
         args.out_stats, args.out_slices = ost.data_ptr(), S
+    if plan is not None:
+        info = hip.conv_plan(args)
+        plan.update({f: getattr(info, f) for f, _ in hip.ConvPlanInfo._fields_})
     hip.check(lib.ccdm_conv2d(C.byref(args), 0), "conv2d")
     sync()
     if bench is not None:       # tools/bench_conv.py: {"iters": n} in, {"ms": mean launch time} out

@@ -124,6 +124,8 @@ def assert_symbol_declared_bound_and_built(symbol, nargs, source):
         words = arg.replace("*", " * ").split()
         want.append(C.c_void_p if "*" in words else CTYPE_OF[[w for w in words if w != "const"][0]])
     res, args = hip.SIGNATURES[symbol]
+    # (a pointer to an argument struct may be bound by its type, C.POINTER(hip.ConvArgs), as ccdm_conv_out_slices is: still a pointer)
+    args = [C.c_void_p if isinstance(t, type) and issubclass(t, C._Pointer) else t for t in args]
     assert res is C.c_int and args == want and len(args) == nargs
     assert source in hip.SOURCES and symbol in open(os.path.join(hip.CSRC, source)).read()
     assert hip.ABI_VERSION == 11 and hip.MAX_CLASSES == 255

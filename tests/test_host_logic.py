@@ -640,3 +640,177 @@ def test_a_walk_without_jumps_is_the_plain_walk():
     r = Guidance(known, (2, 2), ev).repeat_interleave(3)
     assert r.jumps == (2, 2) and torch.equal(r.known, known.repeat_interleave(3, dim=0)) and torch.equal(r.evidence, ev.repeat_interleave(3, dim=0))
     assert Guidance().repeat_interleave(3) == Guidance()
+
+
+# ------------------------------------------------------------------------------------------------ the conv launch plan (ccdm_conv_plan)
+# The launch rules that read the batch size, asked of the library instead of restated: the tests of tests/test_batch_rules.py hold both
+# sides of each threshold to equal bits on the GPU; these hold the thresholds themselves, and what the BASELINE configurations run.
+@pytest.fixture(scope="module")
+def plan_util():
+    import __graft_entry__ as g
+    g.build()
+    from tests import plan_util as PU
+    return PU
+
+
+def lidc_spec():
+    return P.make_unet_spec(image_size=128, in_channels=3, out_channels=2, **LIDC_BP)
+
+
+def c4_spec():
+    fce = dict(type="dino", channels=384, output_stride=8, scale="single", target_layer=10)
+    return P.make_unet_spec(image_size=256, in_channels=23, out_channels=20, feature_cond_encoder=fce, **LIDC_BP)
+
+
+def test_conv_plan_symbol_declared_bound_and_built(plan_util):
+    """ccdm_conv_plan is declared, bound (hip.SIGNATURES, hip.ConvPlanInfo with the C compiler's layout) and built under the unchanged ABI
+    number; it refuses null arguments and the shapes ccdm_conv2d refuses, launches nothing and follows no pointer (every pointer field of
+    these calls is the same invalid address)."""
+    from tests.sampler_util import assert_symbol_declared_bound_and_built
+    lib = assert_symbol_declared_bound_and_built("ccdm_conv_plan", 2, "ccdm_conv.hip")
+    src = r'''
+    #include <stdio.h>
+    #include <stddef.h>
+    #include "ccdm_hip.h"
+    int main(){ printf("%zu %zu %zu %zu %zu\n", sizeof(ccdm_conv_plan_info), offsetof(ccdm_conv_plan_info, ntiles_per_block),
+                       offsetof(ccdm_conv_plan_info, out_slices), offsetof(ccdm_conv_plan_info, grid_x), offsetof(ccdm_conv_plan_info, lds_bytes));
+                return 0; }'''
+    import tempfile
+    with tempfile.TemporaryDirectory() as d:
+        open(os.path.join(d, "t.c"), "w").write(src)
+        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(d, "t.c"), "-o", os.path.join(d, "t")])
+        out = [int(v) for v in subprocess.check_output([os.path.join(d, "t")]).decode().split()]
+    I = hip.ConvPlanInfo
+    assert out == [ctypes.sizeof(I), I.ntiles_per_block.offset, I.out_slices.offset, I.grid_x.offset, I.lds_bytes.offset]
+    assert (hip.CONV_KERNEL_GENERAL, hip.CONV_KERNEL_KS, hip.CONV_KERNEL_UPCONV, hip.CONV_KERNEL_1X1, hip.CONV_KERNEL_1X1_MULTI) == (0, 1, 2, 3, 4)
+    a, info = plan_util.conv_args(2, 32, 32, 32, 32), hip.ConvPlanInfo()
+    assert lib.ccdm_conv_plan(None, ctypes.byref(info)) < 0 and "null" in hip.last_error()
+    assert lib.ccdm_conv_plan(ctypes.byref(a), None) < 0 and "null" in hip.last_error()
+    assert lib.ccdm_conv_plan(ctypes.byref(a), ctypes.byref(info)) == 0
+    assert info.out_slices == lib.ccdm_conv_out_slices(ctypes.byref(a)) == 4 and (info.grid_x, info.grid_y, info.block) == (8, 1, 256)
+    for change, text in ((dict(k=5), "ksize"), (dict(c0=30), "multiples of 4"), (dict(c0=48, gn=True), "GroupNorm(32, 48)"),
+                         (dict(k=1, stride=2), "stride 2"), (dict(c0=16, c1=16, prec=hip.PREC_F32), "chunk")):
+        b = plan_util.conv_args(*[change.pop(f, v) for f, v in (("N", 2), ("H", 32), ("W", 32), ("c0", 32), ("cout", 32), ("k", 3))], **change)
+        assert lib.ccdm_conv_plan(ctypes.byref(b), ctypes.byref(info)) < 0 and text in hip.last_error(), (text, hip.last_error())
+    # every kernel family is reported
+    fam = {name: plan_util.plan(*shape, **kw)["kernel"] for name, shape, kw in (
+        ("general", (2, 128, 128, 32, 32), dict(gn=True, act=hip.ACT_SILU)), ("ks", (2, 8, 8, 128, 128), dict(gn=True, act=hip.ACT_SILU)),
+        ("upconv", (2, 16, 16, 64, 64), dict(up=2)), ("1x1", (2, 8, 8, 128, 128, 1), dict(resid=True)),
+        ("1x1_multi", (64, 16, 16, 96, 288, 1), dict(gn=True, want_stats=False)))}
+    assert fam == {"general": hip.CONV_KERNEL_GENERAL, "ks": hip.CONV_KERNEL_KS, "upconv": hip.CONV_KERNEL_UPCONV, "1x1": hip.CONV_KERNEL_1X1,
+                   "1x1_multi": hip.CONV_KERNEL_1X1_MULTI}
+    # the diagnostic bit routes every one of them to the general kernel
+    assert plan_util.plan(2, 8, 8, 128, 128, 1, resid=True, diag=hip.DIAG_GENERAL_KERNEL)["kernel"] == hip.CONV_KERNEL_GENERAL
+
+
+@pytest.mark.parametrize("prec", [hip.PREC_F16X3, hip.PREC_F32], ids=["f16x3", "f32"])
+@pytest.mark.parametrize("H,W", [(48, 128), (44, 100)])
+def test_conv_plan_two_n_tiles_per_block_threshold(plan_util, H, W, prec):
+    """The general kernel computes two n-tiles per block exactly when the padded tile count is even and N * slices * (ntiles / 2) >= 512:
+    the table of tests/plan_util.py (24 wide tiles and 24 slices per sample) on both sides of the threshold, in both precisions, for the
+    operand sets tests/test_batch_rules.py runs.  Crossing it also moves a fused 1x1 skip from wide core-only chunks to narrow ones."""
+    for cout, ntiles, n2, n1 in plan_util.NI_TABLE:
+        for N, ni in ([(1, 1), (3, 1), (21, 1), (22, 1), (64, 1), (1000, 1)] if n2 is None else [(1, 1), (3, 1), (n1, 1), (n2, 2), (4 * n2, 2)]):
+            p = plan_util.plan(N, H, W, 64, cout, gn=True, act=hip.ACT_SILU, emb=True, prec=prec)
+            assert (p["kernel"], p["tile_h"], p["tile_w"], p["slices"], p["out_slices"]) == (hip.CONV_KERNEL_GENERAL, 8, 32, 24, 24), p
+            assert (p["ntiles"], p["ntiles_per_block"]) == (ntiles, ni), (cout, N, p)
+            assert (p["grid_x"], p["grid_y"], p["block"]) == (24 * N, ntiles // ni, 256)
+            assert p["core_unmasked"] == int(W % 32 == 0) and p["chunk"] == (32 if prec == hip.PREC_F32 else 16) and not p["tap_split"]
+    for kw in (dict(c1=32 if prec != hip.PREC_F32 else 64, gn=True, act=hip.ACT_SILU, emb=True), dict(gn=True, act=hip.ACT_SILU, resid=True),
+               dict(gn=True, act=hip.ACT_SILU, film=True), dict(k=1, c1=32 if prec != hip.PREC_F32 else 64), dict(gn=True, act=hip.ACT_SILU, skip=(64, 64))):
+        lo, hi = (plan_util.plan(N, H, W, 64, 64, kw.get("k", 3), prec=prec, **{f: v for f, v in kw.items() if f != "k"}) for N in (21, 22))
+        assert (lo["kernel"], lo["ntiles_per_block"], hi["kernel"], hi["ntiles_per_block"]) == (hip.CONV_KERNEL_GENERAL, 1, hip.CONV_KERNEL_GENERAL, 2), kw
+        if "skip" in kw:
+            assert (lo["skip_wide"], hi["skip_wide"]) == ((1, 0) if prec == hip.PREC_F16X3 else (0, 0))
+    # upsample on load from half the size; 16 -> 128 channels
+    lo, hi = (plan_util.plan(N, H // 2, W // 2, 32, 64, up=1, gn=True, act=hip.ACT_SILU, emb=True, prec=prec) for N in (21, 22))
+    assert (lo["ntiles_per_block"], hi["ntiles_per_block"], hi["slices"], hi["tile_w"]) == (1, 2, 24, 32)
+    lo, hi = (plan_util.plan(N, H, W, 16, 128, prec=prec) for N in (10, 11))
+    assert (lo["ntiles_per_block"], hi["ntiles_per_block"]) == (1, 2)
+
+
+def test_conv_plan_latency_slicing_reaches_two_n_tiles_at_batch_8(plan_util):
+    """fine_slices = 2 gives a 128x128 conv 64 one-tile slices: 8 * 64 * 1 = 512 blocks of two n-tiles for 32 -> 64 at N = 8, where the
+    default slicing (12 slices) keeps one n-tile per block; at N = 2 both run one."""
+    fine, dflt = (plan_util.plan(8, 128, 128, 32, 64, fine=f) for f in (2, 0))
+    assert (fine["slices"], fine["ntiles_per_block"], dflt["slices"], dflt["ntiles_per_block"]) == (64, 2, 12, 1)
+    assert [plan_util.plan(2, 128, 128, 32, 64, fine=f)["ntiles_per_block"] for f in (2, 0)] == [1, 1]
+    assert plan_util.plan(7, 128, 128, 32, 64, fine=2)["ntiles_per_block"] == 1
+
+
+def test_conv_plan_of_the_baseline_configurations(plan_util):
+    """What the BASELINE configurations run, from make_unet_spec's layers: no conv of the LIDC network reaches two n-tiles per block at
+    N = 64 (its wide-tile layers have one n-tile, or too few blocks at 32x32); C4's 64-channel convs at 64x128 run two at N = 16 and one
+    at N = 8 — the shard of a two-rank run; beside them only the qkv convs on the 1x1 kernel's n-tile walk differ between the two batches."""
+    lidc = plan_util.spec_conv_calls(lidc_spec(), 64, 128, 128, 4)
+    assert len(lidc) == 86 and lidc[0][0] == "input_blocks.0.0" and lidc[-1][0] == "out.2"
+    for name, a in lidc:
+        p = plan_util.plan_dict(hip.conv_plan(a))
+        if p["kernel"] == hip.CONV_KERNEL_GENERAL:      # (the Upsample convs run ccdm_upconv.hip, whose ctb rule has its own test at N = 64)
+            assert a.up != 2 and p["ntiles_per_block"] == 1, (name, p)
+        if p["kernel"] == hip.CONV_KERNEL_GENERAL and p["tile_w"] == 32:
+            assert p["ntiles"] == 1 or a.N * p["slices"] * (p["ntiles"] // 2) < 512, (name, p)
+    wide_two = [n for n, a in lidc if hip.conv_plan(a).tile_w == 32 and hip.conv_plan(a).ntiles > 1]
+    assert wide_two and all(hip.conv_plan(a).slices == 4 for n, a in lidc if n in wide_two)      # the 32x32 stage: 64 * 4 * 1 = 256 blocks
+    c4 = {N: plan_util.spec_conv_calls(c4_spec(), N, 256, 512, 24) for N in (16, 8)}
+    changed = []
+    for (name, a16), (name8, a8) in zip(c4[16], c4[8]):
+        p16, p8 = plan_util.plan_dict(hip.conv_plan(a16)), plan_util.plan_dict(hip.conv_plan(a8))
+        assert name == name8
+        if p16["ntiles_per_block"] != p8["ntiles_per_block"] and name.endswith(".qkv"):
+            assert p16["kernel"] == hip.CONV_KERNEL_1X1_MULTI, name          # the n-tile walk of the 1x1 kernel (its own tests)
+        elif p16["ntiles_per_block"] != p8["ntiles_per_block"]:
+            changed.append(name)
+            assert (p16["kernel"], p8["kernel"]) == (hip.CONV_KERNEL_GENERAL, hip.CONV_KERNEL_GENERAL), name
+            assert (a16.Hout, a16.Wout, a16.Cout, p16["tile_w"], p16["slices"]) == (64, 128, 64, 32, 32), name
+            assert (p16["ntiles_per_block"], p8["ntiles_per_block"]) == (2, 1), name
+    at_level = [n for n, a in c4[16] if (a.Hout, a.Wout, a.Cout, a.up, a.stride) == (64, 128, 64, 0, 1) and a.ksize == 3]
+    assert changed == at_level and len(changed) >= 8, (changed, at_level)
+
+
+def test_conv_plan_1x1_multi_tile_walk(plan_util):
+    """ntb of the LDS-free 1x1 kernel without output statistics, (N * pixel blocks * tiles + 256) / 512 clamped to [1, tiles]: the cases of
+    tests/test_batch_rules.py (an odd ntb with a ragged last group, a last group of one, all tiles of the layer in one block, one k-step),
+    the plain kernel below ntb = 2 and whenever statistics are wanted, with or without GroupNorm on load."""
+    for c0, cout, H, W, N, ntb in plan_util.CONV1X1_MULTI_CASES:
+        if N is None:
+            N = plan_util.smallest_batch_with_ntb(c0, cout, H, W, ntb)
+            assert N == 192
+        for gn in ((False, True) if c0 % 32 == 0 else (False,)):
+            p = plan_util.plan(N, H, W, c0, cout, 1, gn=gn, want_stats=False)
+            ppb = 128 if H * W % 128 == 0 else (64 if H * W % 64 == 0 else 32)
+            assert (p["kernel"], p["ntiles_per_block"], p["tile_w"], p["block"]) == (hip.CONV_KERNEL_1X1_MULTI, ntb, ppb, ppb * 2), (c0, cout, N, p)
+            assert (p["slices"], p["grid_x"], p["grid_y"]) == (H * W // ppb, N * H * W // ppb, -(-(cout // 32) // ntb))
+            small = plan_util.plan(2, H, W, c0, cout, 1, gn=gn, want_stats=False)
+            assert (small["kernel"], small["ntiles_per_block"], small["grid_y"]) == (hip.CONV_KERNEL_1X1, 1, cout // 32)
+            assert plan_util.plan(N, H, W, c0, cout, 1, gn=gn, resid=True, want_stats=False)["ntiles_per_block"] == ntb
+        assert plan_util.plan(N, H, W, c0, cout, 1)["ntiles_per_block"] == 1                  # statistics wanted: one n-tile per block
+    assert plan_util.plan(64, 8, 12, 64, 384, 1, want_stats=False)["block"] == 64             # one-wave blocks
+    with pytest.raises(hip.CcdmHipError, match=r"GroupNorm\(32, 16\)"):                        # the one-k-step case has no GroupNorm form
+        plan_util.plan(192, 16, 16, 16, 64, 1, gn=True, want_stats=False)
+
+
+def test_conv_plan_depends_on_the_batch_only_through_the_block_partition(plan_util):
+    """Over every conv of the LIDC and C4 networks and the threshold cases: the kernel family, the tile geometry, the chunk width, the
+    tap split, the slices and the statistics partials of a call are the same at every N; only the n-tiles per block (with them the grid,
+    the LDS of the staged B chunk, the 1x1 kernel's multi form and the wide skip chunks, which need one n-tile per block) may differ."""
+    fixed = ("tile_h", "tile_w", "chunk", "ntiles", "tap_split", "slices", "out_slices", "core_unmasked", "block")
+    family = {hip.CONV_KERNEL_1X1_MULTI: hip.CONV_KERNEL_1X1}
+    calls = plan_util.spec_conv_calls(lidc_spec(), 1, 128, 128, 4) + plan_util.spec_conv_calls(c4_spec(), 1, 256, 512, 24)
+    calls += [("table", plan_util.conv_args(1, H, W, 64, cout, gn=True, act=hip.ACT_SILU, skip=(64, 64), prec=prec))
+              for H, W in plan_util.NI_GEOMETRIES for cout, *_ in plan_util.NI_TABLE for prec in (hip.PREC_F16X3, hip.PREC_F32)]
+    calls += [("1x1", plan_util.conv_args(1, H, W, c0, cout, 1, want_stats=False)) for c0, cout, H, W, _, _ in plan_util.CONV1X1_MULTI_CASES]
+    calls += [("fine", plan_util.conv_args(1, 128, 128, 32, 64, fine=2)), ("up", plan_util.conv_args(1, 32, 32, 64, 64, up=2))]
+    seen_ni = set()
+    for name, a in calls:
+        base = None
+        for N in (1, 2, 3, 5, 6, 8, 10, 11, 16, 21, 22, 27, 64, 128, 192, 1024):
+            a.N = N
+            p = plan_util.plan_dict(hip.conv_plan(a))
+            key = tuple(p[f] for f in fixed) + (family.get(p["kernel"], p["kernel"]),)
+            base = base or key
+            assert key == base, (name, N, p)
+            assert p["grid_x"] == N * p["slices"] and p["grid_y"] * p["ntiles_per_block"] >= (a.Cout // 32 if p["kernel"] != hip.CONV_KERNEL_GENERAL else p["ntiles"])
+            assert not p["skip_wide"] or p["ntiles_per_block"] == 1, (name, N, p)
+            seen_ni.add((p["kernel"], p["ntiles_per_block"]))
+    assert {(hip.CONV_KERNEL_GENERAL, 1), (hip.CONV_KERNEL_GENERAL, 2), (hip.CONV_KERNEL_UPCONV, 2), (hip.CONV_KERNEL_1X1_MULTI, 5)} <= seen_ni
