@@ -314,6 +314,38 @@ def mode_summary_scores(pred_idx: torch.Tensor, lab_idx: torch.Tensor, num_class
             "converged": modes["converged"].cpu().numpy().astype(np.float64)}
 
 
+def consensus_metric(value) -> str:
+    """`consensus_metric`: the score the consensus map is chosen for, `iou` or `dice` (metrics.CONSENSUS_METRICS)."""
+    if not isinstance(value, str) or value not in M.CONSENSUS_METRICS:
+        raise ValueError(f"consensus_metric: {value!r} (expected one of {M.CONSENSUS_METRICS})")
+    return value
+
+
+def _rater_scores(label: torch.Tensor, lab_idx: torch.Tensor, num_classes: int) -> Tuple[np.ndarray, np.ndarray]:
+    """One map per image, label [B,H,W], against the raters lab_idx [B,L,H,W] -> (IoU, Dice), float64 [B] each: the mean over the raters
+    of the mean over the foreground classes, an empty class on both sides counting 1 (the reference's 0/0)."""
+    counts = M.pairwise_class_counts(label[:, None], lab_idx, num_classes)[:, 0].astype(np.int64)      # [B,L,K,2]: (intersection, union)
+    inter, uni = counts[..., 1:, 0], counts[..., 1:, 1]
+    both = uni + inter                                                                                  # n_a + n_b
+    iou = np.where(uni > 0, inter / np.maximum(uni, 1), 1.0)
+    dice = np.where(both > 0, 2 * inter / np.maximum(both, 1), 1.0)
+    return iou.mean(axis=-1).mean(axis=-1), dice.mean(axis=-1).mean(axis=-1)
+
+
+def consensus_scores(pred_idx: torch.Tensor, lab_idx: torch.Tensor, num_classes: int, metric: str) -> Dict[str, np.ndarray]:
+    """Per image of pred_idx [B,S,H,W] against the raters lab_idx [B,L,H,W], float64 [B] each: IoU and Dice of the consensus map
+    (metrics.sample_consensus for `metric`) and of the majority-vote map (every class thresholded at S // 2 + 1) against the raters,
+    the expected `metric` the samples themselves predict for either (the mean over the classes), and the chosen threshold over S."""
+    S = int(pred_idx.shape[1])
+    cons = M.sample_consensus(pred_idx, num_classes, metric=metric, maps=("label",))
+    major = M.threshold_maps(cons["frequency"], torch.full_like(cons["thresholds"], S // 2 + 1), S, metric, maps=("label",))["label"]
+    iou_c, dice_c = _rater_scores(cons["label"], lab_idx, num_classes)
+    iou_m, dice_m = _rater_scores(major, lab_idx, num_classes)
+    return {"iou_consensus": iou_c, "dice_consensus": dice_c, "iou_majority": iou_m, "dice_majority": dice_m,
+            "expected": cons["expected"].cpu().numpy().mean(axis=1), "expected_majority": cons["expected_majority"].cpu().numpy().mean(axis=1),
+            "threshold_share": cons["threshold"].cpu().numpy().astype(np.float64).mean(axis=1) / float(S)}
+
+
 @torch.no_grad()
 def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optional[int] = None, synthetic_weights_seed: Optional[int] = None,
                           model=None) -> Dict[str, object]:
@@ -368,6 +400,14 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
                             each a mean over the images (mode_summary_scores); with `output_path` set, also written as
                             lidc_modes.json
          mode_count (4): the modes looked for, 1 to 16;  mode_max_swaps (64): the most swaps of the clustering
+         consensus: yes     the result gains "consensus": one dict per entry of `evaluations` for the single map the first s samples
+                            give (metrics.sample_consensus: per class the thresholded sample frequency with the largest expected
+                            score under the samples, on the device): the IoU and Dice of that map and of the majority-vote map
+                            (threshold s // 2 + 1) against the raters — the mean over the images of the mean over the raters of the
+                            mean over the foreground classes, 0/0 = 1 —, the expected score the samples predicted for either and the
+                            mean chosen threshold over s (consensus_scores); with `output_path` set, also written as
+                            lidc_consensus.json
+         consensus_metric (iou): iou or dice, the score the map is chosen for
          label_bound: yes   the result gains "label_bound": the variational bound on -log p(rater's map | image) in nats
                             (DenoisingModel.label_bound, one call per batch on the batch's images and all raters' maps): per rater the
                             mean bound and bits per pixel over the images, their mean over the raters — an upper bound on the
@@ -439,6 +479,9 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
     if modes is not None:
         modes_count = mode_count(section.get("mode_count", 4))
         modes_swaps = mode_max_swaps(section.get("mode_max_swaps", 64))
+    consensus = [[] for _ in evaluations] if section.get("consensus", False) else None           # per entry: the scores of every batch
+    if consensus is not None:
+        cons_metric = consensus_metric(section.get("consensus_metric", "iou"))
     bound = [] if section.get("label_bound", False) else None                                    # the result of every batch
     if bound is not None:
         bound_ts = section.get("label_bound_timesteps")
@@ -481,6 +524,8 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
                                                    m_min=detect_m_min, connectivity=detect_conn, max_candidates=detect_cap))
             if modes is not None:
                 modes[i].append(mode_summary_scores(pred_idx[:, :s], lab_idx, num_classes, modes_count, modes_swaps))
+            if consensus is not None:
+                consensus[i].append(consensus_scores(pred_idx[:, :s], lab_idx, num_classes, cons_metric))
         # log-mean vote exactly as the reference takes it (:125): log(0) = -inf stays -inf (one-hot "majority" predictions:
         # a class any sample rejects is out; where every class is rejected by someone argmax falls to class 0)
         mean_pred = torch.log(prediction).mean(dim=1).argmax(dim=1)
@@ -579,6 +624,22 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
             os.makedirs(out_dir, exist_ok=True)
             with open(os.path.join(out_dir, "lidc_modes.json"), "w") as f:
                 json.dump(res["modes"], f, indent=1)
+    if consensus is not None:
+        res["consensus"] = []
+        for s, parts in zip(evaluations, consensus):
+            per_image = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
+            res["consensus"].append({"samples": int(s), "images": int(per_image["expected"].size), "metric": cons_metric,
+                                     **{k: float(v.mean()) for k, v in per_image.items()}})
+            r = res["consensus"][-1]
+            LOGGER.info("consensus (%d, %s): IoU %.4g  Dice %.4g  (majority vote: %.4g, %.4g)  expected %.4g (%.4g)  threshold %.3g of the samples",
+                        s, cons_metric, r["iou_consensus"], r["dice_consensus"], r["iou_majority"], r["dice_majority"], r["expected"],
+                        r["expected_majority"], r["threshold_share"])
+        if params.get("output_path") and rank == 0:
+            import json
+            out_dir = expanduservars(params["output_path"])
+            os.makedirs(out_dir, exist_ok=True)
+            with open(os.path.join(out_dir, "lidc_consensus.json"), "w") as f:
+                json.dump(res["consensus"], f, indent=1)
     if bound is not None:
         res["label_bound"] = label_bound_summary(bound, bound_draws)
         r = res["label_bound"]

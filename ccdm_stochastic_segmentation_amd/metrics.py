@@ -28,7 +28,11 @@ the pixels enough samples mark, each with the number of samples that draw it, an
 
 And the mode summary of the samples themselves: `sample_modes` (HIP kernels ccdm_modes_distance, ccdm_modes_pam, ccdm_modes_maps:
 the pairwise fixed-point distance among the S samples of an image, k-medoids on it, per-mode vote and entropy maps) says which
-distinct segmentations the samples propose and which share of the samples each holds; everything stays on the device."""
+distinct segmentations the samples propose and which share of the samples each holds; everything stays on the device.
+
+And the single map to report: `sample_consensus` (HIP kernels ccdm_consensus, ccdm_consensus_maps: among the S + 1 thresholded frequency
+maps of an image and class the one with the largest expected IoU or Dice under the samples, in exact integers; `threshold_maps` for
+the maps of given thresholds)."""
 from __future__ import annotations
 
 import math
@@ -774,4 +778,98 @@ def sample_modes(samples_idx: torch.Tensor, num_classes: int, modes: int, max_sw
             out["mode_entropy"] = entropy.reshape(B, M, H, W)
     if return_distance:
         out["distance"] = Q
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ metric-optimal consensus
+CONSENSUS_METRICS = ("iou", "dice")
+CONSENSUS_MAPS = ("label", "mask")
+CONSENSUS_ONE = 1 << 20                   # a curve value counts the score against one sample in units of 2^-20
+CONSENSUS_MAX_SAMPLES = 255               # the frequency planes are bytes
+
+
+def threshold_maps(frequency: torch.Tensor, thresholds: torch.Tensor, num_samples: int, metric: str = "iou",
+                   maps: Sequence[str] = ("label",)) -> Dict[str, torch.Tensor]:
+    """The maps of given thresholds (HIP kernel ccdm_consensus_maps): frequency uint8 [B,C,H,W] and thresholds int32 [B,C,2] on the GPU
+    as sample_consensus returns them (or any thresholds j >= 1: S // 2 + 1 is the majority vote's), `metric` picking the column ->
+    `mask` uint8 [B,C,H,W] = frequency >= threshold and / or `label` uint8 [B,H,W]: the scored class with the largest frequency among
+    the masks that hold the pixel, the lowest on ties, class 0 where none does."""
+    if metric not in CONSENSUS_METRICS:
+        raise ValueError(f"metric: {metric!r} (choose from {CONSENSUS_METRICS})")
+    maps = tuple(maps)
+    bad = [m for m in maps if m not in CONSENSUS_MAPS]
+    if bad or not maps:
+        raise ValueError(f"maps: {list(maps) if not maps else bad} not available (choose from {CONSENSUS_MAPS})")
+    if frequency.device.type != "cuda":
+        raise hip.CcdmHipError("threshold_maps needs GPU tensors (no CPU path)")
+    B, C, H, W = (int(v) for v in frequency.shape)
+    if frequency.dtype != torch.uint8 or thresholds.dtype != torch.int32 or tuple(thresholds.shape) != (B, C, 2):
+        raise ValueError(f"thresholds: expected int32 [{B},{C},2] beside frequency uint8 [B,C,H,W], got {thresholds.dtype} {tuple(thresholds.shape)} "
+                         f"beside {frequency.dtype}")
+    lib = hip.load()
+    dev = frequency.device
+    freq, best = frequency.contiguous(), thresholds.to(dev).contiguous()
+    mask = torch.empty((B, C, H, W), dtype=torch.uint8, device=dev) if "mask" in maps else None
+    label = torch.empty((B, H, W), dtype=torch.uint8, device=dev) if "label" in maps else None
+    hip.check(lib.ccdm_consensus_maps(freq.data_ptr(), best.data_ptr(), B, int(num_samples), H * W, C + 1, CONSENSUS_METRICS.index(metric),
+                                      None if mask is None else mask.data_ptr(), None if label is None else label.data_ptr(),
+                                      torch.cuda.current_stream(dev).cuda_stream), "consensus_maps")
+    out = {}
+    if label is not None:
+        out["label"] = label
+    if mask is not None:
+        out["mask"] = mask
+    return out
+
+
+def sample_consensus(samples_idx: torch.Tensor, num_classes: int, metric: str = "iou", maps: Sequence[str] = ("label",)) -> Dict[str, torch.Tensor]:
+    """The single map to report for S samples per image: samples_idx [B,S,H,W] integer class maps on the GPU -> per image and scored
+    class k = 1..K-1 the threshold j on the sample frequency n[p] whose mask {n >= j} has the largest expected `metric` ("iou" or
+    "dice") under the samples themselves, among j = 1..S+1 (S + 1: the empty map; S // 2 + 1: the majority vote against class 0).  Held
+    in exact integers, a score against one sample in units of 2^-20 (include/ccdm_hip.h has the definition, with every tie rule).
+    2 <= num_classes <= 32, 1 <= S <= 255.  O(S HW) work per image and class.  Device tensors, nothing is copied to the host:
+      threshold   int32 [B,C]        the best j of `metric`;  thresholds int32 [B,C,2]: of IoU and of Dice
+      curve       int64 [B,C,2,S+1]  the sum over the samples of the fixed-point score of every j, for IoU and for Dice
+      expected    float64 [B,C]      curve at the best j / (S * 2^20): the expected `metric` of the consensus
+      expected_majority float64 [B,C]  the same at j = S // 2 + 1
+      frequency   uint8 [B,C,H,W]    n
+      label       uint8 [B,H,W]      ("label" in maps) the consensus map: the class whose mask holds the pixel, by the largest n and then
+                                     the lowest class where several do, class 0 where none does
+      mask        uint8 [B,C,H,W]    ("mask") n >= threshold, 0 / 1."""
+    if not isinstance(samples_idx, torch.Tensor) or samples_idx.dim() != 4 or samples_idx.dtype.is_floating_point or samples_idx.dtype.is_complex \
+            or samples_idx.dtype == torch.bool:
+        raise ValueError(f"samples_idx: expected integer class maps [B,S,H,W], got {getattr(samples_idx, 'dtype', type(samples_idx).__name__)} "
+                         f"{tuple(getattr(samples_idx, 'shape', ()))}")
+    K = whole_number(num_classes, "num_classes", 2, MODES_MAX_CLASSES, f"expected a whole number in [2, {MODES_MAX_CLASSES}]")
+    if metric not in CONSENSUS_METRICS:
+        raise ValueError(f"metric: {metric!r} (choose from {CONSENSUS_METRICS})")
+    B, S, H, W = (int(v) for v in samples_idx.shape)
+    if not 1 <= S <= CONSENSUS_MAX_SAMPLES:
+        raise ValueError(f"samples_idx: S={S} samples per image (expected 1 to {CONSENSUS_MAX_SAMPLES})")
+    if H * W < 1:
+        raise ValueError(f"samples_idx: empty maps {H}x{W}")
+    maps = tuple(maps)
+    bad = [m for m in maps if m not in CONSENSUS_MAPS]
+    if bad:
+        raise ValueError(f"maps: {bad} not available (choose from {CONSENSUS_MAPS})")
+    if samples_idx.device.type != "cuda":
+        raise hip.CcdmHipError("sample_consensus needs GPU tensors (no CPU path)")
+    lib = hip.load()
+    dev, HW, C, m = samples_idx.device, H * W, K - 1, CONSENSUS_METRICS.index(metric)
+    a8 = samples_idx.reshape(B, S, HW).to(torch.uint8).contiguous()
+    freq = torch.empty((B, C, H, W), dtype=torch.uint8, device=dev)
+    curve = torch.empty((B, C, 2, S + 1), dtype=torch.int64, device=dev)
+    best = torch.empty((B, C, 2), dtype=torch.int32, device=dev)
+    nbytes = int(lib.ccdm_consensus_workspace_bytes(B, S, HW, K))
+    ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.int32, device=dev)
+    hip.check(lib.ccdm_consensus(a8.data_ptr(), B, S, HW, K, freq.data_ptr(), curve.data_ptr(), best.data_ptr(), ws.data_ptr(), nbytes,
+                                 torch.cuda.current_stream(dev).cuda_stream), "consensus")
+    # (divided by a device tensor: by a host scalar the device multiplies by the reciprocal, which is not the rounded quotient)
+    denom = torch.full((), float(S * CONSENSUS_ONE), dtype=torch.float64, device=dev)
+    of_metric = curve[:, :, m]                                                                    # [B,C,S+1]
+    out = {"threshold": best[:, :, m].contiguous(), "thresholds": best, "curve": curve,
+           "expected": torch.gather(of_metric, 2, (best[:, :, m].long() - 1)[:, :, None])[:, :, 0].to(torch.float64) / denom,
+           "expected_majority": of_metric[:, :, S // 2].to(torch.float64) / denom, "frequency": freq}
+    if maps:
+        out.update(threshold_maps(freq, best, S, metric, maps))
     return out

@@ -894,6 +894,41 @@ class DenoisingModel(nn.Module):
         return out
 
     @torch.no_grad()
+    def predict_consensus(self, condition: Tensor, feature_condition: Optional[Tensor] = None, *, num_evaluations: int, metric: str = "iou",
+                          x: Optional[Tensor] = None, t: Optional[Tensor] = None, maps: Sequence[str] = ("label",),
+                          **guidance) -> Dict[str, Tensor]:
+        """S = `num_evaluations` samples of every image of `condition` [B,C,H,W], answered with the ONE map to report: per class the
+        thresholded sample frequency with the largest expected `metric` ("iou" or "dice") under the samples themselves.  The majority
+        vote of predict_multiple is the best map for per-pixel accuracy; under IoU and Dice the best threshold is in general not 1/2,
+        and with many empty samples it is the empty map.
+
+        One sampling call of B*S samples laid out as predict_modes lays them out, every pass ending in its argmax class ("majority");
+        the class maps are read straight from the engine into a uint8 stack and handed to metrics.sample_consensus (include/ccdm_hip.h
+        has the definition).  `philox_call` advances as for one call.  2 <= K <= 32, 1 <= S <= 255.
+        x: optional one-hot x_T [S,B,K,H,W]; default: drawn as predict_multiple draws it.  t: as in forward.
+        maps: from "label", "mask" (metrics.CONSENSUS_MAPS).
+        **guidance: the keywords of guidance.GUIDANCE_KEYWORDS, as in predict_multiple, for every sample.
+        Returns, on the model's device, what metrics.sample_consensus returns — threshold [B,K-1], thresholds, curve, expected,
+        expected_majority, frequency, label [B,H,W] / mask [B,K-1,H,W] as asked for — and `samples` [B,S,H,W] uint8, the class maps."""
+        from . import metrics as MT
+        G.known_keywords("DenoisingModel.predict_consensus", guidance)
+        if isinstance(num_evaluations, bool) or int(num_evaluations) != num_evaluations or not 1 <= int(num_evaluations) <= MT.CONSENSUS_MAX_SAMPLES:
+            raise ValueError(f"num_evaluations: {num_evaluations!r} (expected an integer in [1, {MT.CONSENSUS_MAX_SAMPLES}])")
+        S = int(num_evaluations)
+        K = self.diffusion.num_classes
+        MT.whole_number(K, "num_classes", 2, MT.MODES_MAX_CLASSES, f"predict_consensus: expected a model of 2 to {MT.MODES_MAX_CLASSES} classes")
+        if metric not in MT.CONSENSUS_METRICS:
+            raise ValueError(f"metric: {metric!r} (choose from {MT.CONSENSUS_METRICS})")
+        maps = tuple(maps)
+        bad = [m for m in maps if m not in MT.CONSENSUS_MAPS]
+        if bad:
+            raise ValueError(f"maps: {bad} not available (choose from {MT.CONSENSUS_MAPS})")
+        samples = self._sample_class_maps(condition, feature_condition, S, x, t, guidance)
+        out = MT.sample_consensus(samples, K, metric=metric, maps=maps)
+        out["samples"] = samples
+        return out
+
+    @torch.no_grad()
     def predict_findings(self, condition: Tensor, feature_condition: Optional[Tensor] = None, *, num_evaluations: int,
                          min_frequency: float = 0.1, connectivity: int = 8, max_candidates: int = 64,
                          x: Optional[Tensor] = None, t: Optional[Tensor] = None, **guidance) -> Dict[str, Any]:

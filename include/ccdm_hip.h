@@ -1087,6 +1087,53 @@ int ccdm_modes_maps(const uint8_t* a /*dev [B,S,HW]*/, const int32_t* assign /*d
                     float* entropy /*dev [B,M,HW] or NULL*/, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Metric-optimal consensus of a multi-sample prediction (metrics.sample_consensus, DenoisingModel.predict_consensus; beyond the
+ * reference): which single map to report.  The majority vote is the Bayes prediction for per-pixel accuracy; under IoU and Dice the
+ * best threshold on the sample frequency is in general not 1/2, and with many empty samples it can be the empty map.  The samples
+ * stand in for the posterior: the expected score of a candidate map is its mean score against them, and the candidates are the
+ * S + 1 nested thresholded frequency maps (the majority vote among them).  In exact integers.
+ * Input: class maps a[b][s][p], uint8 [B,S,HW], classes in [0,K); a byte >= K belongs to no class.  The scored classes are
+ * k = 1..K-1: C = K-1 of them.
+ * Limits, checked before anything is launched or read, each refusal naming the argument: 2 <= K <= 32, 1 <= S <= 255,
+ * 0 < HW < 2^31, 0 <= B <= 65535, non-null pointers (of ccdm_consensus_maps' mask and label one may be NULL), curve 8-byte and
+ * best and workspace 4-byte aligned, workspace_bytes >= ccdm_consensus_workspace_bytes(B,S,HW,K) = B*C*S*(S+1)*4, metric in {0, 1}.
+ * B = 0 returns 0 without a launch and leaves the outputs as they are.
+ *
+ * Per image b and scored class k:
+ *   n[p] = #{s : a_s[p] == k}, in 0..S: the frequency plane.
+ *   Candidate masks P_j = {p : n[p] >= j}, j = 1..S+1: nested, P_{S+1} the empty map.
+ *   A_j = |P_j|,  n_s = #{p : a_s[p] == k},  I_{j,s} = #{p : a_s[p] == k and n[p] >= j}.
+ *   IoU term of (j, s):  U = A_j + n_s - I_{j,s};  2^20 if U == 0 (the reference's 0/0 = 1), else (2*I*2^20 + U) / (2*U) rounded down in
+ *   int64: the quotient I / U in units of 2^-20, round half up.
+ *   Dice term of (j, s): the same with numerator 2*I and denominator D = A_j + n_s: 2^20 if D == 0, else (2*(2*I)*2^20 + D) / (2*D).
+ *   curve[b][k-1][m][j-1] = sum_s term, int64, m = 0 (IoU), m = 1 (Dice); the expected score is curve / (S * 2^20).
+ *   best[b][k-1][m] = the j with the largest curve value, the LOWEST j on ties: the largest mask among equals.
+ * No floating point enters, so nothing depends on a reduction order: two calls are bit-identical.
+ *
+ *   ccdm_consensus      : outputs, all OVERWRITTEN: freq uint8 [B][C][HW] (the planes n), curve int64 [B][C][2][S+1], best int32 [B][C][2].
+ *                         The workspace receives h[b][k-1][s][m] = #{p : a_s[p] == k and n[p] == m}, int32 [B][C][S][S+1], cleared on
+ *                         `stream` by the call.  Three launches on `stream`, no host round trip.  Counting: the stack is streamed once,
+ *                         one dword per lane when HW % 4 == 0 and the pointer is 4-byte aligned, bytes otherwise; class counts in
+ *                         registers as byte counters, by K <= 2, <= 8, <= 32.  Histogram: one workgroup per (image, class, group of 16
+ *                         samples, share of the pixels) counts into an LDS table [16][S+1] (at most 16 KB) with LDS integer atomics and
+ *                         adds it to h with global integer atomics (exact in any order); pixels with n[p] == 0 are skipped before a
+ *                         sample is read.  Selection: one workgroup per (image, class); I_{j,s} = sum_{m >= j} h[s][m] as suffix sums
+ *                         of the rows of h, in place; A_j from the column sums of h (the pixels with n == m are counted by m samples:
+ *                         sum_s h[s][m] / m, exact); the terms of threshold j summed by the threads the block has for it (integers: any
+ *                         order), every quotient an fp64 division set right by its int64 remainder (exact for these ranges); a
+ *                         block argmax with the tie rule.
+ *   ccdm_consensus_maps : from `freq` and `best` as ccdm_consensus leaves them (read on the device), for one metric m:
+ *                         mask uint8 [B][C][HW] or NULL: n[p] >= best[b][k-1][m], written as 0 / 1;
+ *                         label uint8 [B][HW] or NULL: among the scored classes whose mask holds p the one with the largest n[p], the
+ *                         lowest class on ties; class 0 if no mask holds p.  For K = 2 label equals mask.  One streaming launch.
+ * ------------------------------------------------------------------------------------------------- */
+size_t ccdm_consensus_workspace_bytes(int B, int S, int HW, int K);
+int ccdm_consensus(const uint8_t* samples /*dev [B,S,HW]*/, int B, int S, int HW, int K, uint8_t* freq /*dev [B,C,HW]*/,
+                   int64_t* curve /*dev [B,C,2,S+1]*/, int32_t* best /*dev [B,C,2]*/, void* workspace, uint64_t workspace_bytes, void* stream);
+int ccdm_consensus_maps(const uint8_t* freq /*dev [B,C,HW]*/, const int32_t* best /*dev [B,C,2]*/, int B, int S, int HW, int K, int metric,
+                        uint8_t* mask /*dev [B,C,HW] or NULL*/, uint8_t* label /*dev [B,HW] or NULL*/, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * Training-time forward pieces of the categorical diffusion, BCHW fp32 like the reference's
  * tensors, per-sample coefficients (the host resolves t -> alpha_t / cumalpha_{t-1} incl. the t == 1 override).
  *   ccdm_mix_uniform : out = s[n]*x + (1-s[n])/K.   With s = 1-beta_t it is the probability table of
