@@ -13,7 +13,10 @@ from __future__ import annotations
 
 import logging
 import os
-from typing import Dict, List, Optional, Sequence, Tuple
+from dataclasses import dataclass
+from fractions import Fraction
+from types import SimpleNamespace
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -208,6 +211,38 @@ def _as_list(v) -> List[int]:
 
 
 # ------------------------------------------------------------------------------------------------ evaluation
+def soft_label_bins(value) -> int:
+    """`soft_label_bins`: the level bins of the reliability curve, a whole number from 1 (10 when absent)."""
+    if int(value) < 1:
+        raise ValueError(f"soft_label_bins: {value!r} (expected a whole number, at least 1)")
+    return int(value)
+
+
+def soft_label_thresholds(values) -> List[float]:
+    """`soft_label_thresholds`: the shares at which the soft Dice cuts both frequencies, each in (0, 1] ([0.1, ..., 0.9] when absent)."""
+    thresholds = [float(t) for t in values]
+    if not thresholds or any(not 0.0 < t <= 1.0 for t in thresholds):
+        raise ValueError(f"soft_label_thresholds: {values!r} (expected values in (0, 1])")
+    return thresholds
+
+
+def surface_distance_quantile(value) -> Tuple[int, int]:
+    """`surface_distance_percentile` -> the quantile (num, den), the value read as the decimal it is written as (95 -> (19, 20))."""
+    quantile = Fraction(str(value)) / 100
+    if not 0 < quantile <= 1:
+        raise ValueError(f"surface_distance_percentile: {value!r} (expected a value in (0, 100])")
+    return quantile.numerator, quantile.denominator
+
+
+def lesion_overlaps(values) -> List[Tuple[int, int]]:
+    """`lesion_overlaps` -> [(num, den), ...]: the shares of a lesion the other mask has to cover, each in [0, 1] and read as the decimal it is
+    written as (0.5 -> (1, 2); 0: any overlap)."""
+    fractions = [Fraction(str(v)) for v in (values if isinstance(values, (list, tuple)) else [values])]
+    if not fractions or any(not 0 <= f <= 1 for f in fractions):
+        raise ValueError(f"lesion_overlaps: {values!r} (expected values in [0, 1])")
+    return [(f.numerator, f.denominator) for f in fractions]
+
+
 def lesion_connectivity(section: dict) -> int:
     """`lesion_connectivity` of the `evaluation` section: 4 or 8 (8 when absent)."""
     value = section.get("lesion_connectivity", 8)
@@ -219,7 +254,6 @@ def lesion_connectivity(section: dict) -> int:
 def lesion_match_thresholds(values) -> List[Tuple[int, int]]:
     """`lesion_match_ious` -> [(num, den), ...], each value read as the decimal it is written as (0.5 -> (1, 2), 0.75 -> (3, 4)).
     A pair is matched when its IoU EXCEEDS the value; only above 1/2 is the matching unique, so the values lie in [0.5, 1)."""
-    from fractions import Fraction
     values = list(values) if isinstance(values, (list, tuple)) else [values]
     try:
         fractions = [Fraction(str(v)) for v in values]
@@ -241,7 +275,6 @@ def lesion_min_size(value) -> int:
 def detection_min_frequency(value):
     """`detection_min_frequency`: the share of the samples a pixel needs to belong to a candidate, a decimal in [0, 1] (0.1 when absent);
     with s samples n_min = max(1, ceil(value * s)), the value read as the decimal it is written as."""
-    from fractions import Fraction
     try:
         ok = not isinstance(value, bool) and isinstance(value, (int, float, str)) and 0 <= Fraction(str(value)) <= 1
     except (ValueError, ZeroDivisionError):
@@ -346,6 +379,111 @@ def consensus_scores(pred_idx: torch.Tensor, lab_idx: torch.Tensor, num_classes:
             "threshold_share": cons["threshold"].cpu().numpy().astype(np.float64).mean(axis=1) / float(S)}
 
 
+@dataclass(frozen=True)
+class LidcScore:
+    """One optional score of eval_lidc_uncertainty, on with `key: yes` in the `evaluation` section: the result gains `key`, one dict per entry
+    of `evaluations`, also written as lidc_<key>.json under `output_path`."""
+    key: str
+    configure: Callable      # (section, ctx) -> settings: every check of the option's keys, before the first batch; ctx: raters, num_classes
+    collect: Callable        # (settings, pred_idx[:, :s], lab_idx, s) -> part: the metrics call of one batch and entry
+    finish: Callable         # (settings, parts, s, ctx) -> dict: the scores of an entry from the parts of every batch
+    log: Callable            # (s, r): one line on an entry's scores
+
+
+def _soft_label_settings(section: dict, ctx) -> dict:
+    scoring = {"bins": soft_label_bins(section.get("soft_label_bins", 10))}
+    if section.get("soft_label_thresholds") is not None:
+        scoring["thresholds"] = soft_label_thresholds(section["soft_label_thresholds"])
+    return {"num_classes": ctx.num_classes, "scoring": scoring}
+
+
+def _detection_settings(section: dict, ctx) -> dict:
+    connectivity = lesion_connectivity(section)
+    min_frequency = detection_min_frequency(section.get("detection_min_frequency", 0.1))
+    m_min = detection_rater_agreement(section.get("detection_rater_agreement", "majority"), ctx.raters)
+    scoring = {"score": detection_score(section.get("detection_score", "support")),
+               "fp_rates": detection_fp_rates(section.get("detection_fp_rates", list(M.DETECTION_FP_RATES)))}
+    findings = {"num_classes": ctx.num_classes, "m_min": m_min, "connectivity": connectivity,
+                "max_candidates": detection_max_candidates(section.get("detection_max_candidates", 64))}
+    return {"min_frequency": min_frequency, "findings": findings, "scoring": scoring}
+
+
+def _mean_per_image(parts: Sequence[Dict[str, np.ndarray]], s: int, **settings) -> Dict[str, object]:
+    """The per-image scores of every batch (float64 [B] each) as their means over the images, behind `samples`, `images` and the settings."""
+    per_image = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
+    return {"samples": int(s), "images": int(next(iter(per_image.values())).size), **settings, **{k: float(v.mean()) for k, v in per_image.items()}}
+
+
+def _mode_scores(parts: Sequence[Dict[str, np.ndarray]], s: int, settings: dict) -> Dict[str, object]:
+    scores = _mean_per_image(parts, s, mode_count=settings["count"], max_swaps=settings["max_swaps"])
+    return {("modes_found" if k == "found" else k): v for k, v in scores.items()}
+
+
+# in the order their keys are checked and their results are added; label_bound, once per batch on the images, stands beside them
+LIDC_SCORES = (
+    LidcScore("soft_labels", _soft_label_settings,
+              collect=lambda st, pred_idx, lab_idx, s: M.vote_joint_counts(pred_idx, lab_idx, st["num_classes"]),
+              finish=lambda st, parts, s, ctx: M.soft_label_scores_from_counts(np.concatenate([j for j, _ in parts]),
+                                                                                np.concatenate([m for _, m in parts]), **st["scoring"]),
+              log=lambda s, r: LOGGER.info("soft labels (%d): ECE %.4g  Brier %.4g  Dice %.4g  NCC %s", s, r["ece_soft"], r["brier_soft"],
+                                           r["dice_soft"], r["ncc"])),
+    LidcScore("surface_distances",
+              configure=lambda section, ctx: {"num_classes": ctx.num_classes,
+                                              "q": surface_distance_quantile(section.get("surface_distance_percentile", 95))},
+              collect=lambda st, pred_idx, lab_idx, s: M.surface_distance_stats(pred_idx, lab_idx, **st),
+              finish=lambda st, parts, s, ctx: M.surface_scores_from_stats(M.concat_surface_stats(parts)),
+              log=lambda s, r: LOGGER.info("surface distances (%d): HD%g %s  ASSD %s  HD %s  (%d of %d cells defined)", s, r["percentile"],
+                                           r["hd_percentile"], r["assd"], r["hd"], r["cells_defined"], r["cells_defined"] + r["cells_undefined"])),
+    LidcScore("lesions",
+              configure=lambda section, ctx: {"num_classes": ctx.num_classes, "connectivity": lesion_connectivity(section),
+                                              "overlaps": lesion_overlaps(section.get("lesion_overlaps", [0, 0.5]))},
+              collect=lambda st, pred_idx, lab_idx, s: M.lesion_stats(pred_idx, lab_idx, **st),
+              finish=lambda st, parts, s, ctx: M.lesion_scores_from_stats(M.concat_lesion_stats(parts)),
+              log=lambda s, r: LOGGER.info("lesions (%d): recall %s  precision %s  F1 %s at overlaps %s  count error %.4g  (%d of %d cells without "
+                                           "a lesion)", s, r["recall"], r["precision"], r["f1"], r["thresholds"], r["count_error"],
+                                           r["cells_both_empty"], r["cells"])),
+    LidcScore("lesion_matching",
+              configure=lambda section, ctx: {"num_classes": ctx.num_classes, "connectivity": lesion_connectivity(section),
+                                              "thresholds": lesion_match_thresholds(section.get("lesion_match_ious", [0.5, 0.75])),
+                                              "min_size": lesion_min_size(section.get("lesion_min_size", 1))},
+              collect=lambda st, pred_idx, lab_idx, s: M.lesion_match_stats(pred_idx, lab_idx, **st),
+              finish=lambda st, parts, s, ctx: M.lesion_match_scores_from_stats(M.concat_lesion_match_stats(parts)),
+              log=lambda s, r: LOGGER.info("lesion matching (%d): PQ %s  SQ %s  RQ %s at IoU > %s  pooled PQ %s  (%d of %d cells without a lesion)",
+                                           s, r["pq"], r["sq"], r["rq"], r["ious"], r["pq_pooled"], r["cells_both_empty"], r["cells"])),
+    LidcScore("detection", _detection_settings,
+              collect=lambda st, pred_idx, lab_idx, s: M.sample_findings(pred_idx, lab_idx, n_min=max(1, M._ceil_fraction(st["min_frequency"], s)),
+                                                                         **st["findings"]),
+              finish=lambda st, parts, s, ctx: M.detection_scores_from_findings(M.concat_findings(parts), **st["scoring"]),
+              log=lambda s, r: LOGGER.info("detection (%d): CPM %s  AP %s by %s, candidates from %d of %d samples  (%d candidates, %d reference "
+                                           "lesions)", s, r["cpm"], r["average_precision"], r["score"], r["n_min"], s,
+                                           sum(c["candidates"] for c in r["per_class"]), sum(c["reference_lesions"] for c in r["per_class"]))),
+    LidcScore("modes",
+              configure=lambda section, ctx: {"num_classes": ctx.num_classes, "count": mode_count(section.get("mode_count", 4)),
+                                              "max_swaps": mode_max_swaps(section.get("mode_max_swaps", 64))},
+              collect=lambda st, pred_idx, lab_idx, s: mode_summary_scores(pred_idx, lab_idx, **st),
+              finish=lambda st, parts, s, ctx: _mode_scores(parts, s, st),
+              log=lambda s, r: LOGGER.info("modes (%d): %.3g of %d found  largest share %.3g  GED of the summary %.4g  coverage %.4g", s,
+                                           r["modes_found"], r["mode_count"], r["largest_share"], r["ged_summary"], r["coverage"])),
+    LidcScore("consensus",
+              configure=lambda section, ctx: {"num_classes": ctx.num_classes, "metric": consensus_metric(section.get("consensus_metric", "iou"))},
+              collect=lambda st, pred_idx, lab_idx, s: consensus_scores(pred_idx, lab_idx, **st),
+              finish=lambda st, parts, s, ctx: _mean_per_image(parts, s, metric=st["metric"]),
+              log=lambda s, r: LOGGER.info("consensus (%d, %s): IoU %.4g  Dice %.4g  (majority vote: %.4g, %.4g)  expected %.4g (%.4g)  threshold "
+                                           "%.3g of the samples", s, r["metric"], r["iou_consensus"], r["dice_consensus"], r["iou_majority"],
+                                           r["dice_majority"], r["expected"], r["expected_majority"], r["threshold_share"])),
+)
+
+
+def _write_result(params: dict, rank: int, key: str, result) -> None:
+    """lidc_<key>.json under `output_path`, by rank 0, when the path is set."""
+    if params.get("output_path") and rank == 0:
+        import json
+        out_dir = expanduservars(params["output_path"])
+        os.makedirs(out_dir, exist_ok=True)
+        with open(os.path.join(out_dir, f"lidc_{key}.json"), "w") as f:
+            json.dump(result, f, indent=1)
+
+
 @torch.no_grad()
 def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optional[int] = None, synthetic_weights_seed: Optional[int] = None,
                           model=None) -> Dict[str, object]:
@@ -442,46 +580,9 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
     majority = getattr(model, "step_T_sample", None) in (None, "majority")
     section = params.get("evaluation") or {}
     sampling = sampling_keywords(params)
-    soft = [([], []) for _ in evaluations] if section.get("soft_labels", False) else None       # per entry: (joint, moments) of every batch
-    surf = [[] for _ in evaluations] if section.get("surface_distances", False) else None        # per entry: the stats of every batch
-    if surf is not None:
-        from fractions import Fraction
-        quantile = Fraction(str(section.get("surface_distance_percentile", 95))) / 100
-        if not 0 < quantile <= 1:
-            raise ValueError(f"surface_distance_percentile: {section.get('surface_distance_percentile')!r} (expected a value in (0, 100])")
-        surf_q = (quantile.numerator, quantile.denominator)
-    les = [[] for _ in evaluations] if section.get("lesions", False) else None                   # per entry: the stats of every batch
-    if les is not None:
-        from fractions import Fraction
-        les_conn = int(section.get("lesion_connectivity", 8))
-        if les_conn not in (4, 8):
-            raise ValueError(f"lesion_connectivity: {section.get('lesion_connectivity')!r} (expected 4 or 8)")
-        shares = section.get("lesion_overlaps", [0, 0.5])
-        shares = list(shares) if isinstance(shares, (list, tuple)) else [shares]
-        fractions = [Fraction(str(v)) for v in shares]
-        if not fractions or any(not 0 <= f <= 1 for f in fractions):
-            raise ValueError(f"lesion_overlaps: {section.get('lesion_overlaps')!r} (expected values in [0, 1])")
-        les_overlaps = [(f.numerator, f.denominator) for f in fractions]
-    match = [[] for _ in evaluations] if section.get("lesion_matching", False) else None         # per entry: the stats of every batch
-    if match is not None:
-        match_conn = lesion_connectivity(section)
-        match_thresholds = lesion_match_thresholds(section.get("lesion_match_ious", [0.5, 0.75]))
-        match_min_size = lesion_min_size(section.get("lesion_min_size", 1))
-    detect = [[] for _ in evaluations] if section.get("detection", False) else None              # per entry: the findings of every batch
-    if detect is not None:
-        detect_conn = lesion_connectivity(section)
-        detect_freq = detection_min_frequency(section.get("detection_min_frequency", 0.1))
-        detect_m_min = detection_rater_agreement(section.get("detection_rater_agreement", "majority"), int(labels0.shape[0]))
-        detect_score = detection_score(section.get("detection_score", "support"))
-        detect_rates = detection_fp_rates(section.get("detection_fp_rates", list(M.DETECTION_FP_RATES)))
-        detect_cap = detection_max_candidates(section.get("detection_max_candidates", 64))
-    modes = [[] for _ in evaluations] if section.get("modes", False) else None                   # per entry: the scores of every batch
-    if modes is not None:
-        modes_count = mode_count(section.get("mode_count", 4))
-        modes_swaps = mode_max_swaps(section.get("mode_max_swaps", 64))
-    consensus = [[] for _ in evaluations] if section.get("consensus", False) else None           # per entry: the scores of every batch
-    if consensus is not None:
-        cons_metric = consensus_metric(section.get("consensus_metric", "iou"))
+    ctx = SimpleNamespace(raters=int(labels0.shape[0]), num_classes=num_classes, evaluations=evaluations)
+    # per option that is on: (option, settings, per entry the parts of every batch)
+    scores = [(option, option.configure(section, ctx), [[] for _ in evaluations]) for option in LIDC_SCORES if section.get(option.key, False)]
     bound = [] if section.get("label_bound", False) else None                                    # the result of every batch
     if bound is not None:
         bound_ts = section.get("label_bound_timesteps")
@@ -509,23 +610,8 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
             lcm = int(np.lcm(s, lab_idx.shape[1]))
             hm[i] += np.sum(M.batched_hungarian_matching(lab_idx.repeat_interleave(lcm // lab_idx.shape[1], dim=1),
                                                           pred_idx[:, :s].repeat_interleave(lcm // s, dim=1), num_classes))
-            if soft is not None:
-                joint, moments = M.vote_joint_counts(pred_idx[:, :s], lab_idx, num_classes)
-                soft[i][0].append(joint); soft[i][1].append(moments)
-            if surf is not None:
-                surf[i].append(M.surface_distance_stats(pred_idx[:, :s], lab_idx, num_classes, q=surf_q))
-            if les is not None:
-                les[i].append(M.lesion_stats(pred_idx[:, :s], lab_idx, num_classes, connectivity=les_conn, overlaps=les_overlaps))
-            if match is not None:
-                match[i].append(M.lesion_match_stats(pred_idx[:, :s], lab_idx, num_classes, connectivity=match_conn,
-                                                     thresholds=match_thresholds, min_size=match_min_size))
-            if detect is not None:
-                detect[i].append(M.sample_findings(pred_idx[:, :s], lab_idx, num_classes, n_min=max(1, M._ceil_fraction(detect_freq, s)),
-                                                   m_min=detect_m_min, connectivity=detect_conn, max_candidates=detect_cap))
-            if modes is not None:
-                modes[i].append(mode_summary_scores(pred_idx[:, :s], lab_idx, num_classes, modes_count, modes_swaps))
-            if consensus is not None:
-                consensus[i].append(consensus_scores(pred_idx[:, :s], lab_idx, num_classes, cons_metric))
+            for option, settings, parts in scores:
+                parts[i].append(option.collect(settings, pred_idx[:, :s], lab_idx, s))
         # log-mean vote exactly as the reference takes it (:125): log(0) = -inf stays -inf (one-hot "majority" predictions:
         # a class any sample rejects is out; where every class is rejected by someone argmax falls to class 0)
         mean_pred = torch.log(prediction).mean(dim=1).argmax(dim=1)
@@ -548,109 +634,16 @@ def eval_lidc_uncertainty(params: dict, dataset=None, device=None, init_t: Optio
         res["sampling"] = dict(sampling)
     for i, s in enumerate(evaluations):
         LOGGER.info("GED (%d): %.4g  diversity samples: %.4g  HM IoU: %.4g", s, res["GED"][i], res["diversity_samples"][i], res["HM_IoU"][i])
-    if soft is not None:
-        kw = {"bins": int(section.get("soft_label_bins", 10))}
-        if section.get("soft_label_thresholds") is not None:
-            kw["thresholds"] = [float(t) for t in section["soft_label_thresholds"]]
-        res["soft_labels"] = [M.soft_label_scores_from_counts(np.concatenate(j), np.concatenate(m), **kw) for j, m in soft]
-        for s, r in zip(evaluations, res["soft_labels"]):
-            LOGGER.info("soft labels (%d): ECE %.4g  Brier %.4g  Dice %.4g  NCC %s", s, r["ece_soft"], r["brier_soft"], r["dice_soft"], r["ncc"])
-        if params.get("output_path") and rank == 0:
-            import json
-            out_dir = expanduservars(params["output_path"])
-            os.makedirs(out_dir, exist_ok=True)
-            with open(os.path.join(out_dir, "lidc_soft_labels.json"), "w") as f:
-                json.dump(res["soft_labels"], f, indent=1)
-    if surf is not None:
-        res["surface_distances"] = [M.surface_scores_from_stats(M.concat_surface_stats(parts)) for parts in surf]
-        for s, r in zip(evaluations, res["surface_distances"]):
-            LOGGER.info("surface distances (%d): HD%g %s  ASSD %s  HD %s  (%d of %d cells defined)", s, r["percentile"], r["hd_percentile"],
-                        r["assd"], r["hd"], r["cells_defined"], r["cells_defined"] + r["cells_undefined"])
-        if params.get("output_path") and rank == 0:
-            import json
-            out_dir = expanduservars(params["output_path"])
-            os.makedirs(out_dir, exist_ok=True)
-            with open(os.path.join(out_dir, "lidc_surface_distances.json"), "w") as f:
-                json.dump(res["surface_distances"], f, indent=1)
-    if les is not None:
-        res["lesions"] = [M.lesion_scores_from_stats(M.concat_lesion_stats(parts)) for parts in les]
-        for s, r in zip(evaluations, res["lesions"]):
-            LOGGER.info("lesions (%d): recall %s  precision %s  F1 %s at overlaps %s  count error %.4g  (%d of %d cells without a lesion)", s,
-                        r["recall"], r["precision"], r["f1"], r["thresholds"], r["count_error"], r["cells_both_empty"], r["cells"])
-        if params.get("output_path") and rank == 0:
-            import json
-            out_dir = expanduservars(params["output_path"])
-            os.makedirs(out_dir, exist_ok=True)
-            with open(os.path.join(out_dir, "lidc_lesions.json"), "w") as f:
-                json.dump(res["lesions"], f, indent=1)
-    if match is not None:
-        res["lesion_matching"] = [M.lesion_match_scores_from_stats(M.concat_lesion_match_stats(parts)) for parts in match]
-        for s, r in zip(evaluations, res["lesion_matching"]):
-            LOGGER.info("lesion matching (%d): PQ %s  SQ %s  RQ %s at IoU > %s  pooled PQ %s  (%d of %d cells without a lesion)", s,
-                        r["pq"], r["sq"], r["rq"], r["ious"], r["pq_pooled"], r["cells_both_empty"], r["cells"])
-        if params.get("output_path") and rank == 0:
-            import json
-            out_dir = expanduservars(params["output_path"])
-            os.makedirs(out_dir, exist_ok=True)
-            with open(os.path.join(out_dir, "lidc_lesion_matching.json"), "w") as f:
-                json.dump(res["lesion_matching"], f, indent=1)
-    if detect is not None:
-        res["detection"] = [M.detection_scores_from_findings(M.concat_findings(parts), score=detect_score, fp_rates=detect_rates)
-                            for parts in detect]
-        for s, r in zip(evaluations, res["detection"]):
-            LOGGER.info("detection (%d): CPM %s  AP %s by %s, candidates from %d of %d samples  (%d candidates, %d reference lesions)", s,
-                        r["cpm"], r["average_precision"], r["score"], r["n_min"], s, sum(c["candidates"] for c in r["per_class"]),
-                        sum(c["reference_lesions"] for c in r["per_class"]))
-        if params.get("output_path") and rank == 0:
-            import json
-            out_dir = expanduservars(params["output_path"])
-            os.makedirs(out_dir, exist_ok=True)
-            with open(os.path.join(out_dir, "lidc_detection.json"), "w") as f:
-                json.dump(res["detection"], f, indent=1)
-    if modes is not None:
-        res["modes"] = []
-        for s, parts in zip(evaluations, modes):
-            per_image = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
-            res["modes"].append({"samples": int(s), "images": int(per_image["found"].size), "mode_count": modes_count, "max_swaps": modes_swaps,
-                                 "modes_found": float(per_image["found"].mean()), "largest_share": float(per_image["largest_share"].mean()),
-                                 "ged_summary": float(per_image["ged_summary"].sum() / n_img), "coverage": float(per_image["coverage"].mean()),
-                                 "converged": float(per_image["converged"].mean())})
-            r = res["modes"][-1]
-            LOGGER.info("modes (%d): %.3g of %d found  largest share %.3g  GED of the summary %.4g  coverage %.4g", s, r["modes_found"],
-                        modes_count, r["largest_share"], r["ged_summary"], r["coverage"])
-        if params.get("output_path") and rank == 0:
-            import json
-            out_dir = expanduservars(params["output_path"])
-            os.makedirs(out_dir, exist_ok=True)
-            with open(os.path.join(out_dir, "lidc_modes.json"), "w") as f:
-                json.dump(res["modes"], f, indent=1)
-    if consensus is not None:
-        res["consensus"] = []
-        for s, parts in zip(evaluations, consensus):
-            per_image = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
-            res["consensus"].append({"samples": int(s), "images": int(per_image["expected"].size), "metric": cons_metric,
-                                     **{k: float(v.mean()) for k, v in per_image.items()}})
-            r = res["consensus"][-1]
-            LOGGER.info("consensus (%d, %s): IoU %.4g  Dice %.4g  (majority vote: %.4g, %.4g)  expected %.4g (%.4g)  threshold %.3g of the samples",
-                        s, cons_metric, r["iou_consensus"], r["dice_consensus"], r["iou_majority"], r["dice_majority"], r["expected"],
-                        r["expected_majority"], r["threshold_share"])
-        if params.get("output_path") and rank == 0:
-            import json
-            out_dir = expanduservars(params["output_path"])
-            os.makedirs(out_dir, exist_ok=True)
-            with open(os.path.join(out_dir, "lidc_consensus.json"), "w") as f:
-                json.dump(res["consensus"], f, indent=1)
+    for option, settings, parts in scores:
+        res[option.key] = [option.finish(settings, p, s, ctx) for s, p in zip(evaluations, parts)]
+        for s, r in zip(evaluations, res[option.key]):
+            option.log(s, r)
+        _write_result(params, rank, option.key, res[option.key])
     if bound is not None:
-        res["label_bound"] = label_bound_summary(bound, bound_draws)
-        r = res["label_bound"]
+        res["label_bound"] = r = label_bound_summary(bound, bound_draws)
         LOGGER.info("label bound: %.6g nats per map, %.4g bits per pixel over %d images (%d timesteps, %d draw(s)%s)", r["bound"],
                     r["bits_per_pixel"], r["images"], len(r["timestep_curve"]), r["draws"], "" if r["complete"] else ", partial sum")
-        if params.get("output_path") and rank == 0:
-            import json
-            out_dir = expanduservars(params["output_path"])
-            os.makedirs(out_dir, exist_ok=True)
-            with open(os.path.join(out_dir, "lidc_label_bound.json"), "w") as f:
-                json.dump(res["label_bound"], f, indent=1)
+        _write_result(params, rank, "label_bound", r)
     return res
 
 

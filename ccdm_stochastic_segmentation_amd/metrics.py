@@ -45,17 +45,86 @@ import torch
 from . import hip
 
 
+# ------------------------------------------------------------------------------------------------ shared launch prologue and host checks
+def _class_map_stacks(name: str, a_idx: torch.Tensor, b_idx: Optional[torch.Tensor], flat: bool = False,
+                      expected: str = "[B,S,H,W] and [B,L,H,W]"):
+    """What every launch over a sample stack a_idx [B,S,...] and a rater stack b_idx [B,L,...] (None: no raters, L = 0) starts with: both
+    on the GPU, of one image count and one map size -> (a8, b8, dims), the stacks as contiguous uint8 on a_idx's device.  dims is
+    (B, S, L, H, W) of the [B,S,H,W] / [B,L,H,W] maps, or with `flat` (B, S, L, HW) of trailing dimensions of any rank, flattened."""
+    if a_idx.device.type != "cuda" or (b_idx is not None and b_idx.device.type != "cuda"):
+        raise hip.CcdmHipError(f"{name} needs GPU tensors (no CPU path)")
+    if flat:
+        B, S = a_idx.shape[:2]
+        a8 = a_idx.reshape(B, S, -1).to(torch.uint8).contiguous()
+        b8 = b_idx.reshape(B, b_idx.shape[1], -1).to(device=a8.device, dtype=torch.uint8).contiguous()
+        assert b8.shape[2] == a8.shape[2] and b8.shape[0] == B
+        return a8, b8, (B, S, b8.shape[1], a8.shape[2])
+    if a_idx.dim() != 4 or (b_idx is not None and (b_idx.dim() != 4 or b_idx.shape[0] != a_idx.shape[0] or b_idx.shape[2:] != a_idx.shape[2:])):
+        raise ValueError(f"{name}: {tuple(a_idx.shape)} / {None if b_idx is None else tuple(b_idx.shape)} (expected {expected})")
+    a8 = a_idx.to(torch.uint8).contiguous()
+    b8 = None if b_idx is None else b_idx.to(device=a8.device, dtype=torch.uint8).contiguous()
+    B, S, H, W = (int(v) for v in a_idx.shape)
+    return a8, b8, (B, S, 0 if b8 is None else int(b8.shape[1]), H, W)
+
+
+def _sample_stack(samples_idx, max_samples: int) -> Tuple[int, int, int, int]:
+    """(B, S, H, W) of samples_idx, which has to be integer class maps [B,S,H,W] with 1 <= S <= max_samples and a pixel to score."""
+    if not isinstance(samples_idx, torch.Tensor) or samples_idx.dim() != 4 or samples_idx.dtype.is_floating_point or samples_idx.dtype.is_complex \
+            or samples_idx.dtype == torch.bool:
+        raise ValueError(f"samples_idx: expected integer class maps [B,S,H,W], got {getattr(samples_idx, 'dtype', type(samples_idx).__name__)} "
+                         f"{tuple(getattr(samples_idx, 'shape', ()))}")
+    B, S, H, W = (int(v) for v in samples_idx.shape)
+    if not 1 <= S <= max_samples:
+        raise ValueError(f"samples_idx: S={S} samples per image (expected 1 to {max_samples})")
+    if H * W < 1:
+        raise ValueError(f"samples_idx: empty maps {H}x{W}")
+    return B, S, H, W
+
+
+def _scored_classes(num_classes: int) -> List[int]:
+    """The classes a score is taken over: 1..K-1 (the reference's distance drops class 0), class 0 when K == 1."""
+    return list(range(1, num_classes)) if num_classes > 1 else [0]
+
+
+def _workspace(nbytes: int, device) -> torch.Tensor:
+    """A kernel's workspace of at least `nbytes` bytes (and never empty), as int32."""
+    return torch.empty((max(nbytes, 4) + 3) // 4, dtype=torch.int32, device=device)
+
+
+def _mean_of_image_means(values, mask):
+    """The mean over the images of the mean over an image's cells under `mask`; an image without one is left out, None: every image is."""
+    per_image = [float(values[b][mask[b]].mean()) for b in range(len(values)) if mask[b].any()]
+    return float(np.mean(per_image)) if per_image else None
+
+
+def _check_cells(stats: Dict[str, object], first: str, second: str, class_names, need_image: Optional[str] = None):
+    """The per-cell arrays stats[first], stats[second] as int64 [B,S,L,C] and the scored classes, C of them like `class_names` if given;
+    need_image: the name of a caller that scores at least one image."""
+    a, b = np.asarray(stats[first]).astype(np.int64), np.asarray(stats[second]).astype(np.int64)
+    if a.ndim != 4 or b.shape != a.shape:
+        raise ValueError(f"{first} {a.shape} / {second} {b.shape}: expected [B,S,L,C]")
+    classes = [int(c) for c in stats["classes"]]
+    if len(classes) != a.shape[3]:
+        raise ValueError(f"classes: {len(classes)} entries for {a.shape[3]} scored classes")
+    if class_names is not None and len(class_names) != a.shape[3]:
+        raise ValueError(f"class_names: {len(class_names)} names for {a.shape[3]} scored classes")
+    if need_image is not None and a.shape[0] < 1:
+        raise ValueError(f"{need_image}: the stats hold no image")
+    return a, b, classes
+
+
+def _concat_stats(parts: Sequence[Dict[str, object]], fields: Sequence[str], settings: Sequence[str]) -> Dict[str, object]:
+    """The stats of several batches as one: `fields` concatenated along the images, `settings` as the first part has them."""
+    plain = lambda v: [plain(x) for x in v] if isinstance(v, (list, tuple)) else v
+    out: Dict[str, object] = {k: np.concatenate([np.asarray(p[k]) for p in parts]) for k in fields}
+    out.update({k: plain(parts[0][k]) for k in settings})
+    return out
+
+
 def pairwise_class_counts(a_idx: torch.Tensor, b_idx: torch.Tensor, num_classes: int) -> np.ndarray:
     """a_idx [B,S,...] / b_idx [B,L,...] integer class maps on the GPU -> int32 [B,S,L,K,2] (intersection, union)."""
     lib = hip.load()
-    if a_idx.device.type != "cuda":
-        raise hip.CcdmHipError("pairwise_class_counts needs GPU tensors (no CPU path)")
-    B, S = a_idx.shape[:2]
-    L = b_idx.shape[1]
-    a8 = a_idx.reshape(B, S, -1).to(torch.uint8).contiguous()
-    b8 = b_idx.reshape(B, L, -1).to(device=a8.device, dtype=torch.uint8).contiguous()
-    HW = a8.shape[2]
-    assert b8.shape[2] == HW and b8.shape[0] == B
+    a8, b8, (B, S, L, HW) = _class_map_stacks("pairwise_class_counts", a_idx, b_idx, flat=True)
     out = torch.empty((B, S, L, num_classes, 2), dtype=torch.int32, device=a8.device)
     hip.check(lib.ccdm_pairwise_class_counts(a8.data_ptr(), b8.data_ptr(), B, S, L, HW, num_classes, out.data_ptr(),
                                              torch.cuda.current_stream(a8.device).cuda_stream), "pairwise_class_counts")
@@ -98,14 +167,7 @@ def vote_joint_counts(samples_idx: torch.Tensor, raters_idx: torch.Tensor, num_c
     joint[b,k,n,m] = the pixels of image b where n samples and m raters say class k; moments[b] = {sum u, sum v, sum u^2, sum v^2,
     sum u*v} of the integer Gini impurities u = S^2 - sum_k n_k^2, v = L^2 - sum_k m_k^2 (include/ccdm_hip.h, ccdm_lidcscore)."""
     lib = hip.load()
-    if samples_idx.device.type != "cuda" or raters_idx.device.type != "cuda":
-        raise hip.CcdmHipError("vote_joint_counts needs GPU tensors (no CPU path)")
-    B, S = samples_idx.shape[:2]
-    L = raters_idx.shape[1]
-    s8 = samples_idx.reshape(B, S, -1).to(torch.uint8).contiguous()
-    r8 = raters_idx.reshape(B, L, -1).to(device=s8.device, dtype=torch.uint8).contiguous()
-    HW = s8.shape[2]
-    assert r8.shape[2] == HW and r8.shape[0] == B
+    s8, r8, (B, S, L, HW) = _class_map_stacks("vote_joint_counts", samples_idx, raters_idx, flat=True)
     joint = torch.zeros((B, num_classes, S + 1, L + 1), dtype=torch.int32, device=s8.device)
     moments = torch.zeros((B, 5), dtype=torch.int64, device=s8.device)
     hip.check(lib.ccdm_lidcscore(s8.data_ptr(), r8.data_ptr(), B, S, L, HW, num_classes, joint.data_ptr(), moments.data_ptr(),
@@ -158,7 +220,7 @@ def soft_label_scores_from_counts(joint, moments, *, bins: int = 10, thresholds:
     p = (np.arange(S + 1, dtype=np.float64) / S)[:, None]            # [S+1,1]
     q = (np.arange(L + 1, dtype=np.float64) / L)[None, :]            # [1,L+1]
     total = joint.sum(axis=0).astype(np.float64)                     # [K,S+1,L+1]
-    scored = list(range(1, K)) if K > 1 else [0]
+    scored = _scored_classes(K)
 
     level_bin = np.minimum(np.arange(S + 1) * bins // S, bins - 1)
     reliability, ece_k = [], []
@@ -220,21 +282,14 @@ def surface_distance_stats(a_idx: torch.Tensor, b_idx: torch.Tensor, num_classes
     floor(pos), ceil(pos), pos = q[0]*(n-1)/q[1], of the pooled squared surface distances; 0 in an undefined cell) and float64
     sum_ar, sum_ra (the sums of the distances of each direction); plus "q": [q[0], q[1]] and "classes": the scored classes."""
     lib = hip.load()
-    if a_idx.device.type != "cuda" or b_idx.device.type != "cuda":
-        raise hip.CcdmHipError("surface_distance_stats needs GPU tensors (no CPU path)")
-    if a_idx.dim() != 4 or b_idx.dim() != 4 or a_idx.shape[0] != b_idx.shape[0] or a_idx.shape[2:] != b_idx.shape[2:]:
-        raise ValueError(f"surface_distance_stats: {tuple(a_idx.shape)} / {tuple(b_idx.shape)} (expected [B,S,H,W] and [B,L,H,W])")
-    B, S, H, W = a_idx.shape
-    L = b_idx.shape[1]
+    a8, b8, (B, S, L, H, W) = _class_map_stacks("surface_distance_stats", a_idx, b_idx)
     q_num, q_den = int(q[0]), int(q[1])
-    a8 = a_idx.to(torch.uint8).contiguous()
-    b8 = b_idx.to(device=a8.device, dtype=torch.uint8).contiguous()
-    classes = list(range(1, num_classes)) if num_classes > 1 else [0]
+    classes = _scored_classes(num_classes)
     Cn = len(classes)
     stats = torch.zeros((B, S, L, Cn, 5), dtype=torch.int32, device=a8.device)
     sums = torch.zeros((B, S, L, Cn, 2), dtype=torch.float64, device=a8.device)
     need = int(lib.ccdm_surfdist_workspace_bytes(B, S, L, H, W, num_classes))
-    ws = torch.empty((max(need, 4) + 3) // 4, dtype=torch.int32, device=a8.device)
+    ws = _workspace(need, a8.device)
     hip.check(lib.ccdm_surfdist(a8.data_ptr(), b8.data_ptr(), B, S, L, H, W, num_classes, q_num, q_den, stats.data_ptr(), sums.data_ptr(),
                                 ws.data_ptr(), need, torch.cuda.current_stream(a8.device).cuda_stream), "surfdist")
     st, sm = stats.cpu().numpy().astype(np.int64), sums.cpu().numpy()
@@ -245,9 +300,7 @@ def surface_distance_stats(a_idx: torch.Tensor, b_idx: torch.Tensor, num_classes
 
 def concat_surface_stats(parts: Sequence[Dict[str, object]]) -> Dict[str, object]:
     """The stats of several batches as one (concatenated along the images)."""
-    out = {k: np.concatenate([p[k] for p in parts]) for k in SURFACE_STAT_FIELDS + ("sum_ar", "sum_ra")}
-    out.update(q=list(parts[0]["q"]), classes=list(parts[0]["classes"]))
-    return out
+    return _concat_stats(parts, SURFACE_STAT_FIELDS + ("sum_ar", "sum_ra"), ("q", "classes"))
 
 
 def surface_scores_from_stats(stats: Dict[str, object], *, class_names: Optional[Sequence[str]] = None) -> Dict[str, object]:
@@ -261,18 +314,11 @@ def surface_scores_from_stats(stats: Dict[str, object], *, class_names: Optional
     without a defined cell is left out; `*_per_class`: the same over one class's cells.  Undefined cells are counted
     (cells_undefined, of which cells_both_empty have neither surface) and never folded into a mean; a score with no defined
     cell is None.  The result holds lists, numbers and None only: it survives a JSON round trip."""
-    n_ar, n_ra = np.asarray(stats["n_ar"]).astype(np.int64), np.asarray(stats["n_ra"]).astype(np.int64)
-    if n_ar.ndim != 4 or n_ra.shape != n_ar.shape:
-        raise ValueError(f"n_ar {n_ar.shape} / n_ra {n_ra.shape}: expected [B,S,L,C]")
+    n_ar, n_ra, classes = _check_cells(stats, "n_ar", "n_ra", class_names)
     B, S, L, Cn = n_ar.shape
     q_num, q_den = (int(x) for x in stats["q"])
     if not 0 < q_num <= q_den:
         raise ValueError(f"q: {q_num}/{q_den} (expected 0 < q_num <= q_den)")
-    classes = [int(c) for c in stats["classes"]]
-    if len(classes) != Cn:
-        raise ValueError(f"classes: {len(classes)} entries for {Cn} scored classes")
-    if class_names is not None and len(class_names) != Cn:
-        raise ValueError(f"class_names: {len(class_names)} names for {Cn} scored classes")
     defined = (n_ar > 0) & (n_ra > 0)
     safe_ar, safe_ra = np.where(defined, n_ar, 1), np.where(defined, n_ra, 1)
     t = q_num * (n_ar + n_ra - 1)                                    # pos = t / q_den, exact
@@ -281,17 +327,13 @@ def surface_scores_from_stats(stats: Dict[str, object], *, class_names: Optional
     cell = {"hd": np.sqrt(np.asarray(stats["d2_max"], dtype=np.float64)), "hd_percentile": lo + frac * (hi - lo),
             "assd": (np.asarray(stats["sum_ar"], dtype=np.float64) / safe_ar + np.asarray(stats["sum_ra"], dtype=np.float64) / safe_ra) / 2.0}
 
-    def mean_of_image_means(values, mask):
-        per_image = [float(values[b][mask[b]].mean()) for b in range(B) if mask[b].any()]
-        return float(np.mean(per_image)) if per_image else None
-
     res: Dict[str, object] = {"images": int(B), "samples": int(S), "raters": int(L), "classes": classes, "q": [q_num, q_den],
                               "percentile": 100.0 * q_num / q_den, "cells_defined": int(defined.sum()),
                               "cells_undefined": int((~defined).sum()), "cells_both_empty": int(((n_ar == 0) & (n_ra == 0)).sum()),
                               "images_scored": int(defined.reshape(B, -1).any(axis=1).sum())}
     for key, values in cell.items():
-        res[key] = mean_of_image_means(values, defined)
-        res[key + "_per_class"] = [mean_of_image_means(values[..., c], defined[..., c]) for c in range(Cn)]
+        res[key] = _mean_of_image_means(values, defined)
+        res[key + "_per_class"] = [_mean_of_image_means(values[..., c], defined[..., c]) for c in range(Cn)]
     res["cells_defined_per_class"] = [int(defined[..., c].sum()) for c in range(Cn)]
     if class_names is not None:
         res["class_names"] = [str(c) for c in class_names]
@@ -311,21 +353,14 @@ def lesion_stats(a_idx: torch.Tensor, b_idx: torch.Tensor, num_classes: int, con
     mask covers to overlaps[t] = (num, den): cov >= 1 and cov*den >= num*size); plus "overlaps": [[num, den], ...],
     "connectivity" and "classes": the scored classes."""
     lib = hip.load()
-    if a_idx.device.type != "cuda" or b_idx.device.type != "cuda":
-        raise hip.CcdmHipError("lesion_stats needs GPU tensors (no CPU path)")
-    if a_idx.dim() != 4 or b_idx.dim() != 4 or a_idx.shape[0] != b_idx.shape[0] or a_idx.shape[2:] != b_idx.shape[2:]:
-        raise ValueError(f"lesion_stats: {tuple(a_idx.shape)} / {tuple(b_idx.shape)} (expected [B,S,H,W] and [B,L,H,W])")
-    B, S, H, W = a_idx.shape
-    L = b_idx.shape[1]
+    a8, b8, (B, S, L, H, W) = _class_map_stacks("lesion_stats", a_idx, b_idx)
     ov = np.ascontiguousarray([[int(n), int(d)] for n, d in overlaps], dtype=np.int32).reshape(-1, 2)
     T = int(ov.shape[0])
-    a8 = a_idx.to(torch.uint8).contiguous()
-    b8 = b_idx.to(device=a8.device, dtype=torch.uint8).contiguous()
-    classes = list(range(1, num_classes)) if num_classes > 1 else [0]
+    classes = _scored_classes(num_classes)
     Cn = len(classes)
     stats = torch.zeros((B, S, L, Cn, 2 + 2 * T), dtype=torch.int32, device=a8.device)
     need = int(lib.ccdm_lesions_workspace_bytes(B, S, L, H, W, num_classes))
-    ws = torch.empty((max(need, 4) + 3) // 4, dtype=torch.int32, device=a8.device)
+    ws = _workspace(need, a8.device)
     hip.check(lib.ccdm_lesions(a8.data_ptr(), b8.data_ptr(), B, S, L, H, W, num_classes, int(connectivity), ov.ctypes.data, T,
                                stats.data_ptr(), ws.data_ptr(), need, torch.cuda.current_stream(a8.device).cuda_stream), "lesions")
     st = stats.cpu().numpy().astype(np.int64)
@@ -335,9 +370,7 @@ def lesion_stats(a_idx: torch.Tensor, b_idx: torch.Tensor, num_classes: int, con
 
 def concat_lesion_stats(parts: Sequence[Dict[str, object]]) -> Dict[str, object]:
     """The stats of several batches as one (concatenated along the images)."""
-    out = {k: np.concatenate([p[k] for p in parts]) for k in LESION_STAT_FIELDS}
-    out.update(overlaps=[list(o) for o in parts[0]["overlaps"]], connectivity=int(parts[0]["connectivity"]), classes=list(parts[0]["classes"]))
-    return out
+    return _concat_stats(parts, LESION_STAT_FIELDS, ("overlaps", "connectivity", "classes"))
 
 
 def lesion_scores_from_stats(stats: Dict[str, object], *, class_names: Optional[Sequence[str]] = None) -> Dict[str, object]:
@@ -353,9 +386,7 @@ def lesion_scores_from_stats(stats: Dict[str, object], *, class_names: Optional[
     images_scored (images with a cell that has a lesion).  Over all cells: count_error = mean |n_a - n_r|, count_exact = the share
     with n_a == n_r, lesions_per_sample_map / lesions_per_rater_map = mean n_a / mean n_r.  The result holds lists, numbers and None
     only: it survives a JSON round trip."""
-    n_a, n_r = np.asarray(stats["n_a"]).astype(np.int64), np.asarray(stats["n_r"]).astype(np.int64)
-    if n_a.ndim != 4 or n_r.shape != n_a.shape:
-        raise ValueError(f"n_a {n_a.shape} / n_r {n_r.shape}: expected [B,S,L,C]")
+    n_a, n_r, classes = _check_cells(stats, "n_a", "n_r", class_names, need_image="lesion_scores_from_stats")
     B, S, L, Cn = n_a.shape
     overlaps = [[int(n), int(d)] for n, d in stats["overlaps"]]
     T = len(overlaps)
@@ -367,19 +398,8 @@ def lesion_scores_from_stats(stats: Dict[str, object], *, class_names: Optional[
     connectivity = int(stats["connectivity"])
     if connectivity not in (4, 8):
         raise ValueError(f"connectivity: {connectivity} (expected 4 or 8)")
-    classes = [int(c) for c in stats["classes"]]
-    if len(classes) != Cn:
-        raise ValueError(f"classes: {len(classes)} entries for {Cn} scored classes")
-    if class_names is not None and len(class_names) != Cn:
-        raise ValueError(f"class_names: {len(class_names)} names for {Cn} scored classes")
-    if B < 1:
-        raise ValueError("lesion_scores_from_stats: the stats hold no image")
     cell = {"recall": (hit_r, n_r[..., None], n_r > 0), "precision": (hit_a, n_a[..., None], n_a > 0),
             "f1": (hit_a + hit_r, (n_a + n_r)[..., None], (n_a + n_r) > 0)}
-
-    def mean_of_image_means(values, mask):
-        per_image = [float(values[b][mask[b]].mean()) for b in range(B) if mask[b].any()]
-        return float(np.mean(per_image)) if per_image else None
 
     res: Dict[str, object] = {
         "images": int(B), "samples": int(S), "raters": int(L), "classes": classes, "connectivity": connectivity, "overlaps": overlaps,
@@ -388,8 +408,8 @@ def lesion_scores_from_stats(stats: Dict[str, object], *, class_names: Optional[
         "images_scored": int(((n_a + n_r) > 0).reshape(B, -1).any(axis=1).sum())}
     for key, (num, den, defined) in cell.items():
         values = num.astype(np.float64) / np.where(defined[..., None], den, 1).astype(np.float64)          # [B,S,L,C,T]
-        res[key] = [mean_of_image_means(values[..., t], defined) for t in range(T)]
-        res[key + "_per_class"] = [[mean_of_image_means(values[..., c, t], defined[..., c]) for t in range(T)] for c in range(Cn)]
+        res[key] = [_mean_of_image_means(values[..., t], defined) for t in range(T)]
+        res[key + "_per_class"] = [[_mean_of_image_means(values[..., c, t], defined[..., c]) for t in range(T)] for c in range(Cn)]
     res.update(count_error=float(np.abs(n_a - n_r).mean()), count_exact=float((n_a == n_r).mean()),
                lesions_per_sample_map=float(n_a.mean()), lesions_per_rater_map=float(n_r.mean()))
     if class_names is not None:
@@ -412,24 +432,17 @@ def lesion_match_stats(a_idx: torch.Tensor, b_idx: torch.Tensor, num_classes: in
     floor(inter * 2^32 / union) over those pairs); plus "thresholds": [[num, den], ...], "connectivity", "min_size" and "classes".
     ccdm_lesions labels the maps, ccdm_lesion_match reads its workspace: one buffer, one stream."""
     lib = hip.load()
-    if a_idx.device.type != "cuda" or b_idx.device.type != "cuda":
-        raise hip.CcdmHipError("lesion_match_stats needs GPU tensors (no CPU path)")
-    if a_idx.dim() != 4 or b_idx.dim() != 4 or a_idx.shape[0] != b_idx.shape[0] or a_idx.shape[2:] != b_idx.shape[2:]:
-        raise ValueError(f"lesion_match_stats: {tuple(a_idx.shape)} / {tuple(b_idx.shape)} (expected [B,S,H,W] and [B,L,H,W])")
-    B, S, H, W = a_idx.shape
-    L = b_idx.shape[1]
+    a8, b8, (B, S, L, H, W) = _class_map_stacks("lesion_match_stats", a_idx, b_idx)
     th = np.ascontiguousarray([[int(n), int(d)] for n, d in thresholds], dtype=np.int32).reshape(-1, 2)
     T = int(th.shape[0])
-    a8 = a_idx.to(torch.uint8).contiguous()
-    b8 = b_idx.to(device=a8.device, dtype=torch.uint8).contiguous()
-    classes = list(range(1, num_classes)) if num_classes > 1 else [0]
+    classes = _scored_classes(num_classes)
     Cn = len(classes)
     any_overlap = np.array([[0, 1]], dtype=np.int32)              # ccdm_lesions' own counts are not used here
     hits = torch.zeros((B, S, L, Cn, 4), dtype=torch.int32, device=a8.device)
     stats = torch.zeros((B, S, L, Cn, 2 + T), dtype=torch.int32, device=a8.device)
     iou = torch.zeros((B, S, L, Cn, T), dtype=torch.int64, device=a8.device)
     need = int(lib.ccdm_lesion_match_workspace_bytes(B, S, L, H, W, num_classes))
-    ws = torch.empty((max(need, 4) + 3) // 4, dtype=torch.int32, device=a8.device)
+    ws = _workspace(need, a8.device)
     stream = torch.cuda.current_stream(a8.device).cuda_stream
     hip.check(lib.ccdm_lesions(a8.data_ptr(), b8.data_ptr(), B, S, L, H, W, num_classes, int(connectivity), any_overlap.ctypes.data, 1,
                                hits.data_ptr(), ws.data_ptr(), need, stream), "lesions")
@@ -442,10 +455,7 @@ def lesion_match_stats(a_idx: torch.Tensor, b_idx: torch.Tensor, num_classes: in
 
 def concat_lesion_match_stats(parts: Sequence[Dict[str, object]]) -> Dict[str, object]:
     """The stats of several batches as one (concatenated along the images)."""
-    out = {k: np.concatenate([p[k] for p in parts]) for k in LESION_MATCH_STAT_FIELDS}
-    out.update(thresholds=[list(t) for t in parts[0]["thresholds"]], connectivity=int(parts[0]["connectivity"]),
-               min_size=int(parts[0]["min_size"]), classes=list(parts[0]["classes"]))
-    return out
+    return _concat_stats(parts, LESION_MATCH_STAT_FIELDS, ("thresholds", "connectivity", "min_size", "classes"))
 
 
 def lesion_match_scores_from_stats(stats: Dict[str, object], *, class_names: Optional[Sequence[str]] = None) -> Dict[str, object]:
@@ -461,9 +471,7 @@ def lesion_match_scores_from_stats(stats: Dict[str, object], *, class_names: Opt
     sum tp, rq_pooled = sum tp / (sum tp + sum fp / 2 + sum fn / 2), with tp_total, fp_total, fn_total per threshold beside them.
     Never folded into a mean: cells, cells_both_empty (n_a == n_r == 0), cells_matched per threshold (tp > 0), images_scored
     (images with a cell that has a lesion).  The result holds lists, numbers and None only: it survives a JSON round trip."""
-    n_a, n_r = np.asarray(stats["n_a"]).astype(np.int64), np.asarray(stats["n_r"]).astype(np.int64)
-    if n_a.ndim != 4 or n_r.shape != n_a.shape:
-        raise ValueError(f"n_a {n_a.shape} / n_r {n_r.shape}: expected [B,S,L,C]")
+    n_a, n_r, classes = _check_cells(stats, "n_a", "n_r", class_names, need_image="lesion_match_scores_from_stats")
     B, S, L, Cn = n_a.shape
     thresholds = [[int(n), int(d)] for n, d in stats["thresholds"]]
     T = len(thresholds)
@@ -477,21 +485,10 @@ def lesion_match_scores_from_stats(stats: Dict[str, object], *, class_names: Opt
         raise ValueError(f"connectivity: {connectivity} (expected 4 or 8)")
     if min_size < 1:
         raise ValueError(f"min_size: {min_size} (expected at least 1)")
-    classes = [int(c) for c in stats["classes"]]
-    if len(classes) != Cn:
-        raise ValueError(f"classes: {len(classes)} entries for {Cn} scored classes")
-    if class_names is not None and len(class_names) != Cn:
-        raise ValueError(f"class_names: {len(class_names)} names for {Cn} scored classes")
-    if B < 1:
-        raise ValueError("lesion_match_scores_from_stats: the stats hold no image")
     q = iou_sum.astype(np.float64) / float(LESION_IOU_ONE)                                                # [B,S,L,C,T]
     both = (n_a + n_r)[..., None]
     some = np.broadcast_to(both > 0, tp.shape)
     cell = {"rq": (2.0 * tp, both, some), "sq": (q, tp, tp > 0), "pq": (2.0 * q, both, some)}
-
-    def mean_of_image_means(values, mask):
-        per_image = [float(values[b][mask[b]].mean()) for b in range(B) if mask[b].any()]
-        return float(np.mean(per_image)) if per_image else None
 
     res: Dict[str, object] = {
         "images": int(B), "samples": int(S), "raters": int(L), "classes": classes, "connectivity": connectivity, "min_size": min_size,
@@ -500,8 +497,8 @@ def lesion_match_scores_from_stats(stats: Dict[str, object], *, class_names: Opt
         "images_scored": int(((n_a + n_r) > 0).reshape(B, -1).any(axis=1).sum())}
     for key, (num, den, defined) in cell.items():
         values = np.asarray(num, dtype=np.float64) / np.where(defined, den, 1).astype(np.float64)          # [B,S,L,C,T]
-        res[key] = [mean_of_image_means(values[..., t], defined[..., t]) for t in range(T)]
-        res[key + "_per_class"] = [[mean_of_image_means(values[..., c, t], defined[..., c, t]) for t in range(T)] for c in range(Cn)]
+        res[key] = [_mean_of_image_means(values[..., t], defined[..., t]) for t in range(T)]
+        res[key + "_per_class"] = [[_mean_of_image_means(values[..., c, t], defined[..., c, t]) for t in range(T)] for c in range(Cn)]
     tp_total = [int(tp[..., t].sum()) for t in range(T)]
     fp_total = [int(n_a.sum()) - n for n in tp_total]
     fn_total = [int(n_r.sum()) - n for n in tp_total]
@@ -545,14 +542,7 @@ def sample_findings(samples_idx: torch.Tensor, raters_idx: Optional[torch.Tensor
     An (image, class) with more candidates or reference lesions than `max_candidates` (at most 1024) raises, naming the value needed."""
     if not isinstance(samples_idx, torch.Tensor) or (raters_idx is not None and not isinstance(raters_idx, torch.Tensor)):
         raise ValueError("sample_findings: expected tensors [B,S,H,W] and [B,L,H,W] (or None)")
-    if samples_idx.device.type != "cuda" or (raters_idx is not None and raters_idx.device.type != "cuda"):
-        raise hip.CcdmHipError("sample_findings needs GPU tensors (no CPU path)")
-    if samples_idx.dim() != 4 or (raters_idx is not None and (raters_idx.dim() != 4 or raters_idx.shape[0] != samples_idx.shape[0]
-                                                              or raters_idx.shape[2:] != samples_idx.shape[2:])):
-        raise ValueError(f"sample_findings: {tuple(samples_idx.shape)} / {None if raters_idx is None else tuple(raters_idx.shape)} "
-                         "(expected [B,S,H,W] and [B,L,H,W] or None)")
-    B, S, H, W = (int(v) for v in samples_idx.shape)
-    L = 0 if raters_idx is None else int(raters_idx.shape[1])
+    s8, r8, (B, S, L, H, W) = _class_map_stacks("sample_findings", samples_idx, raters_idx, expected="[B,S,H,W] and [B,L,H,W] or None")
     if raters_idx is not None and L == 0:
         raise ValueError("sample_findings: raters_idx holds no rater (pass None)")
     n_min = whole_number(n_min, "n_min", 1, None, "expected a whole number of samples, at least 1")
@@ -562,9 +552,7 @@ def sample_findings(samples_idx: torch.Tensor, raters_idx: Optional[torch.Tensor
         m_min = L // 2 + 1 if m_min is None else whole_number(m_min, "m_min", 1, None, "expected a whole number of raters, at least 1")
     cap = whole_number(max_candidates, "max_candidates", 1, None, "expected a whole number, at least 1")
     lib = hip.load()
-    s8 = samples_idx.to(torch.uint8).contiguous()
-    r8 = None if raters_idx is None else raters_idx.to(device=s8.device, dtype=torch.uint8).contiguous()
-    classes = list(range(1, num_classes)) if num_classes > 1 else [0]
+    classes = _scored_classes(num_classes)
     Cn = len(classes)
     dev = s8.device
     counts = torch.zeros((B, Cn, 2), dtype=torch.int32, device=dev)
@@ -572,7 +560,7 @@ def sample_findings(samples_idx: torch.Tensor, raters_idx: Optional[torch.Tensor
     ref = torch.zeros((B, Cn, cap, len(FINDING_REFERENCE_FIELDS)), dtype=torch.int32, device=dev)
     conf = torch.zeros((B, Cn, H, W), dtype=torch.uint8, device=dev) if return_map else None
     need = int(lib.ccdm_findings_workspace_bytes(B, S, L, H, W, num_classes, cap))
-    ws = torch.empty((max(need, 4) + 3) // 4, dtype=torch.int32, device=dev)
+    ws = _workspace(need, dev)
     hip.check(lib.ccdm_findings(s8.data_ptr(), None if r8 is None else r8.data_ptr(), B, S, L, H, W, num_classes, int(connectivity), n_min,
                                 0 if m_min is None else m_min, cap, counts.data_ptr(), cand.data_ptr(), ref.data_ptr(),
                                 None if conf is None else conf.data_ptr(), ws.data_ptr(), need, torch.cuda.current_stream(dev).cuda_stream),
@@ -599,9 +587,7 @@ def concat_findings(parts: Sequence[Dict[str, object]]) -> Dict[str, object]:
         differ = [k for k in FINDING_SETTINGS if p[k] != parts[0][k]]
         if differ:
             raise ValueError(f"concat_findings: the parts differ in {differ}")
-    out: Dict[str, object] = {k: np.concatenate([np.asarray(p[k]) for p in parts]) for k in FINDING_ARRAYS}
-    out.update({k: (list(parts[0][k]) if k == "classes" else parts[0][k]) for k in FINDING_SETTINGS})
-    return out
+    return _concat_stats(parts, FINDING_ARRAYS, FINDING_SETTINGS)
 
 
 def detection_scores_from_findings(findings: Dict[str, object], *, score: str = "support", fp_rates: Sequence[float] = DETECTION_FP_RATES,
@@ -726,18 +712,10 @@ def sample_modes(samples_idx: torch.Tensor, num_classes: int, modes: int, max_sw
       mode_entropy fp32 [B,M,H,W]  ("entropy") the entropy in nats of the members' class frequencies: where the mode is unsure; 0: unused
       mode_counts int32 [B,M,H,W,K]  ("counts") the members saying each class
       distance   int32 [B,S,S]     (return_distance) Q; Q / ((K-1) * 2^20) is within 2^-21 of `batched_distance`."""
-    if not isinstance(samples_idx, torch.Tensor) or samples_idx.dim() != 4 or samples_idx.dtype.is_floating_point or samples_idx.dtype.is_complex \
-            or samples_idx.dtype == torch.bool:
-        raise ValueError(f"samples_idx: expected integer class maps [B,S,H,W], got {getattr(samples_idx, 'dtype', type(samples_idx).__name__)} "
-                         f"{tuple(getattr(samples_idx, 'shape', ()))}")
+    B, S, H, W = _sample_stack(samples_idx, MODES_MAX_SAMPLES)
     K = whole_number(num_classes, "num_classes", 2, MODES_MAX_CLASSES, f"expected a whole number in [2, {MODES_MAX_CLASSES}]")
     M = whole_number(modes, "modes", 1, MODES_MAX_MODES, f"expected a whole number in [1, {MODES_MAX_MODES}]")
     max_swaps = whole_number(max_swaps, "max_swaps", 0, 2 ** 31 - 1, "expected a whole number, at least 0")
-    B, S, H, W = (int(v) for v in samples_idx.shape)
-    if not 1 <= S <= MODES_MAX_SAMPLES:
-        raise ValueError(f"samples_idx: S={S} samples per image (expected 1 to {MODES_MAX_SAMPLES})")
-    if H * W < 1:
-        raise ValueError(f"samples_idx: empty maps {H}x{W}")
     maps = tuple(maps)
     bad = [m for m in maps if m not in MODE_MAPS]
     if bad:
@@ -836,18 +814,10 @@ def sample_consensus(samples_idx: torch.Tensor, num_classes: int, metric: str = 
       label       uint8 [B,H,W]      ("label" in maps) the consensus map: the class whose mask holds the pixel, by the largest n and then
                                      the lowest class where several do, class 0 where none does
       mask        uint8 [B,C,H,W]    ("mask") n >= threshold, 0 / 1."""
-    if not isinstance(samples_idx, torch.Tensor) or samples_idx.dim() != 4 or samples_idx.dtype.is_floating_point or samples_idx.dtype.is_complex \
-            or samples_idx.dtype == torch.bool:
-        raise ValueError(f"samples_idx: expected integer class maps [B,S,H,W], got {getattr(samples_idx, 'dtype', type(samples_idx).__name__)} "
-                         f"{tuple(getattr(samples_idx, 'shape', ()))}")
+    B, S, H, W = _sample_stack(samples_idx, CONSENSUS_MAX_SAMPLES)
     K = whole_number(num_classes, "num_classes", 2, MODES_MAX_CLASSES, f"expected a whole number in [2, {MODES_MAX_CLASSES}]")
     if metric not in CONSENSUS_METRICS:
         raise ValueError(f"metric: {metric!r} (choose from {CONSENSUS_METRICS})")
-    B, S, H, W = (int(v) for v in samples_idx.shape)
-    if not 1 <= S <= CONSENSUS_MAX_SAMPLES:
-        raise ValueError(f"samples_idx: S={S} samples per image (expected 1 to {CONSENSUS_MAX_SAMPLES})")
-    if H * W < 1:
-        raise ValueError(f"samples_idx: empty maps {H}x{W}")
     maps = tuple(maps)
     bad = [m for m in maps if m not in CONSENSUS_MAPS]
     if bad:
@@ -861,7 +831,7 @@ def sample_consensus(samples_idx: torch.Tensor, num_classes: int, metric: str = 
     curve = torch.empty((B, C, 2, S + 1), dtype=torch.int64, device=dev)
     best = torch.empty((B, C, 2), dtype=torch.int32, device=dev)
     nbytes = int(lib.ccdm_consensus_workspace_bytes(B, S, HW, K))
-    ws = torch.empty((max(nbytes, 4) // 4,), dtype=torch.int32, device=dev)
+    ws = _workspace(nbytes, dev)
     hip.check(lib.ccdm_consensus(a8.data_ptr(), B, S, HW, K, freq.data_ptr(), curve.data_ptr(), best.data_ptr(), ws.data_ptr(), nbytes,
                                  torch.cuda.current_stream(dev).cuda_stream), "consensus")
     # (divided by a device tensor: by a host scalar the device multiplies by the reciprocal, which is not the rounded quotient)

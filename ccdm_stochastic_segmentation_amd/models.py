@@ -352,6 +352,13 @@ def auto_substreams(N: int, H: int, W: int) -> int:
     return 2 if (N >= 2 and N * H * W >= 32 * 128 * 128) else 1
 
 
+def _num_evaluations(value, hi: Optional[int] = None) -> int:
+    """`num_evaluations` of the predict_* methods: a whole number of samples from 1, up to `hi` where the summary has a cap."""
+    if isinstance(value, bool) or int(value) != value or int(value) < 1 or (hi is not None and int(value) > hi):
+        raise ValueError(f"num_evaluations: {value!r} (expected an integer " + (">= 1)" if hi is None else f"in [1, {hi}])"))
+    return int(value)
+
+
 class DenoisingModel(nn.Module):
     """The sampler.  `rng` selects where the Exp(1) noise of the categorical draws comes from:
     "philox" (default) — Philox4x32-10 inside the epilogue kernel, keyed by (pixel, global sample index, step) under a 64-bit key
@@ -720,9 +727,7 @@ class DenoisingModel(nn.Module):
         voting = self.step_T_sample if voting is None else voting
         if voting not in ("confidence", "majority"):
             raise ValueError(f"voting: {voting!r} (expected 'confidence' or 'majority')")
-        if isinstance(num_evaluations, bool) or int(num_evaluations) != num_evaluations or int(num_evaluations) < 1:
-            raise ValueError(f"num_evaluations: {num_evaluations!r} (expected an integer >= 1)")
-        S = int(num_evaluations)
+        S = _num_evaluations(num_evaluations)
         maps = tuple(maps)
         bad = [m for m in maps if m not in self.MULTI_MAPS or (m == "counts" and voting != "majority")]
         if bad:
@@ -877,9 +882,7 @@ class DenoisingModel(nn.Module):
         255 where unused), mode_vote / mode_entropy / mode_counts as asked for — and `samples` [B,S,H,W] uint8, the class maps."""
         from . import metrics as MT
         G.known_keywords("DenoisingModel.predict_modes", guidance)
-        if isinstance(num_evaluations, bool) or int(num_evaluations) != num_evaluations or not 1 <= int(num_evaluations) <= MT.MODES_MAX_SAMPLES:
-            raise ValueError(f"num_evaluations: {num_evaluations!r} (expected an integer in [1, {MT.MODES_MAX_SAMPLES}])")
-        S = int(num_evaluations)
+        S = _num_evaluations(num_evaluations, MT.MODES_MAX_SAMPLES)
         K = self.diffusion.num_classes
         MT.whole_number(K, "num_classes", 2, MT.MODES_MAX_CLASSES, f"predict_modes: expected a model of 2 to {MT.MODES_MAX_CLASSES} classes")
         MT.whole_number(modes, "modes", 1, MT.MODES_MAX_MODES, f"expected a whole number in [1, {MT.MODES_MAX_MODES}]")
@@ -912,9 +915,7 @@ class DenoisingModel(nn.Module):
         expected_majority, frequency, label [B,H,W] / mask [B,K-1,H,W] as asked for — and `samples` [B,S,H,W] uint8, the class maps."""
         from . import metrics as MT
         G.known_keywords("DenoisingModel.predict_consensus", guidance)
-        if isinstance(num_evaluations, bool) or int(num_evaluations) != num_evaluations or not 1 <= int(num_evaluations) <= MT.CONSENSUS_MAX_SAMPLES:
-            raise ValueError(f"num_evaluations: {num_evaluations!r} (expected an integer in [1, {MT.CONSENSUS_MAX_SAMPLES}])")
-        S = int(num_evaluations)
+        S = _num_evaluations(num_evaluations, MT.CONSENSUS_MAX_SAMPLES)
         K = self.diffusion.num_classes
         MT.whole_number(K, "num_classes", 2, MT.MODES_MAX_CLASSES, f"predict_consensus: expected a model of 2 to {MT.MODES_MAX_CLASSES} classes")
         if metric not in MT.CONSENSUS_METRICS:
@@ -949,9 +950,7 @@ class DenoisingModel(nn.Module):
         that holds the pixel, 0 outside) and `samples` uint8 [B,S,H,W] on the model's device, and `n_min`, `classes`."""
         from . import metrics as MT
         G.known_keywords("DenoisingModel.predict_findings", guidance)
-        if isinstance(num_evaluations, bool) or int(num_evaluations) != num_evaluations or not 1 <= int(num_evaluations) <= 255:
-            raise ValueError(f"num_evaluations: {num_evaluations!r} (expected an integer in [1, 255])")
-        S = int(num_evaluations)
+        S = _num_evaluations(num_evaluations, 255)
         K = self.diffusion.num_classes
         if isinstance(min_frequency, bool) or not isinstance(min_frequency, (int, float)) or not 0 <= min_frequency <= 1:
             raise ValueError(f"min_frequency: {min_frequency!r} (expected a share of the samples in [0, 1])")
