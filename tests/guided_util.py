@@ -7,13 +7,18 @@ import torch
 
 from oracle import ccdm_oracle as O
 from ccdm_stochastic_segmentation_amd import hip
+from tests import ladder_util
 from tests.sampler_util import DEV, H, SEED, W, onehot_np
 
-SHAPES = [(3, 63, 2), (2, 300, 5), (2, 64, 20), (1, 64, 255)]       # a partial block; a block boundary inside a sample; staged; the largest K
+# a partial block; a block boundary inside a sample; staged; the largest K; then one shape per class count at the ends of every rung of
+# the kernels' class-count ladder (ladder_util)
+SHAPES = [(3, 63, 2), (2, 300, 5), (2, 64, 20), (1, 64, 255)] + ladder_util.SHAPES
 # test_tempered_kernel_against_float64: the kernel's largest relative error against the float64 definition on that test's inputs, measured
 # on an MI355X, and what the test allows the device's power for it (four times that: the ROCm installation states no ulp bound for exp2f
-# and log2f)
-POWER_ERROR_MEASURED = 1.851e-6
+# and log2f).  The largest per rung of the class-count ladder, over SHAPES: 2.085e-6 (rung 2: K = 2), 1.600e-6 (4: K = 4), 1.717e-6 (8:
+# K = 5), 1.968e-6 (16: K = 9), 1.307e-6 (20: K = 20), 1.279e-6 (24: K = 21), 2.095e-6 (32: K = 32), 1.323e-6 (64: K = 64), 2.284e-6
+# (128: K = 128), 2.849e-6 (256: K = 255 at (2, 75); 1.851e-6 at (1, 64), the largest of the four shapes the constant was first taken on)
+POWER_ERROR_MEASURED = 2.849e-6
 POWER_ERROR_ALLOWED = 4 * POWER_ERROR_MEASURED
 
 
@@ -140,6 +145,33 @@ def mixed_inputs(rng, N, HW, K):
     p = (p / p.sum(-1, keepdims=True, dtype=np.float32)).astype(np.float32)
     x0[:, 1::2] = p[:, 1::2]
     return x0, ev, xt
+
+
+TEMPERED_TAUS, TEMPERED_RS, TEMPERED_TS = (0.7, 1.5), (1.0, 0.9), (200, 2)
+TEMPERED_ROW, TEMPERED_OFF = 1, 3
+
+
+def tempered_reference(x0, ev, xt, tau, r, t, row=TEMPERED_ROW, off=TEMPERED_OFF, seed=SEED):
+    """The float64 side of test_tempered_kernel_against_float64 for one (tau, r, evidence, t), from the definition and the oracle alone:
+    float64 shaping of the fp32 v with the fp32 inv_temperature and top_r, float64 Bayes posterior.  Returns inv_temperature, (a, c),
+    `want` [N,HW,K], `big` (the entries the probabilities are compared at: > 1e-9, of pixels not within 1e-5 of a truncation threshold)
+    and `skip` (the pixels the draws are not compared at: near a threshold, or a float64 race margin <= 1e-4)."""
+    N, HW, K = x0.shape
+    inv = float(np.float32(1.0 / tau))
+    v = weighted(x0, ev)
+    q64 = shape_rows(v, inv, float(np.float32(r)), np.float64)
+    near = threshold_margin64(shape_rows(v, inv, 1.0, np.float64), r) <= 1e-5 if r != 1.0 else np.zeros((N, HW), dtype=bool)
+    a, c = coefficients(t)
+    want = posterior64(q64, xt, a, c)
+    big = (want > 1e-9) & ~near[..., None]
+    score = np.sort(want / O.philox_exponential(seed, row, off, N, HW, K).astype(np.float64), axis=-1)
+    skip = near | ((score[..., -1] - score[..., -2]) / score[..., -1] <= 1e-4)
+    return inv, (a, c), want, big, skip
+
+
+def tempered_cases(ev_all):
+    """Every (tau, r, evidence, t) of the tempered test, in its order"""
+    return [(tau, r, ev, t) for tau in TEMPERED_TAUS for r in TEMPERED_RS for ev in (None, ev_all) for t in TEMPERED_TS]
 
 
 def run_shaped_kernel(lib, x0, ev, xt, inv_tau, r, a, c, mode, *, step_row=0, seed=SEED, sample_offset=0, xin=None, probs=None, onehot=None,

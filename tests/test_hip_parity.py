@@ -871,7 +871,9 @@ def test_sampler_bit_exact_on_reference_golden(U, golden, K, parity_log):
         assert mis <= 2.0 / idx.numel()
 
 
-@pytest.mark.parametrize("K,N,HW,xs", [(20, 3, 1000, 23), (20, 2, 512, 24), (5, 3, 333, 8), (7, 2, 700, 7), (9, 1, 257, 12), (21, 2, 300, 24), (32, 2, 513, 35)])
+@pytest.mark.parametrize("K,N,HW,xs", [(20, 3, 1000, 23), (20, 2, 512, 24), (5, 3, 333, 8), (7, 2, 700, 7), (9, 1, 257, 12), (21, 2, 300, 24), (32, 2, 513, 35),
+                                       (4, 2, 300, 7), (8, 2, 300, 11), (16, 2, 300, 19), (24, 2, 300, 28)])          # the last four: K equal to a rung
+                                                                                                                 # (K = 4: one thread per pixel on both sides)
 def test_epilogue_many_classes_moves_whole_pixel_runs(U, K, N, HW, xs):
     """K > 4: the epilogue stages the block's 256 * K head values and writes the 256 * xin_stride stem-input floats as contiguous 16-byte
     runs through LDS (k_posterior_staged).  Same bits as the one-thread-per-pixel kernel (reached here by giving the head a row pitch the
@@ -901,7 +903,8 @@ def test_epilogue_many_classes_moves_whole_pixel_runs(U, K, N, HW, xs):
         check_epilogue_against_oracle(s_, logits, xt, a, c, noise, mode, K)
 
 
-@pytest.mark.parametrize("K,N,HW,xs", [(2, 2, 300, 4), (5, 3, 333, 8), (20, 2, 512, 24), (32, 2, 513, 35)])
+@pytest.mark.parametrize("K,N,HW,xs", [(2, 2, 300, 4), (5, 3, 333, 8), (20, 2, 512, 24), (32, 2, 513, 35),
+                                       (4, 2, 300, 7), (8, 2, 300, 11), (16, 2, 300, 19), (24, 2, 300, 28)])          # the last four: K equal to a rung
 def test_epilogue_lds_rows_equal_the_register_kernels(U, K, N, HW, xs):
     """k_posterior_many (the kernel more than 32 classes run: a pixel's classes in an LDS row, run-time loops) against the register
     kernels at class counts both can take: every output identical, bit for bit, in every step mode, with the device Philox stream and
@@ -922,7 +925,7 @@ def test_epilogue_lds_rows_equal_the_register_kernels(U, K, N, HW, xs):
                     assert torch.equal(r_[key], m_[key]), (mode, sm, key)
 
 
-@pytest.mark.parametrize("K", [33, 40, 100, 255])
+@pytest.mark.parametrize("K", [33, 40, 64, 100, 128, 255])
 def test_epilogue_more_than_32_classes_against_the_oracle(U, K):
     """K > 32 (k_posterior_many): posterior, clamp, normalisation and the Exp(1) race against the oracle's restatement of the reference's
     forms, every step mode; ragged block counts; the stem input's image channels untouched."""

@@ -23,6 +23,7 @@ import torch
 
 from oracle import ccdm_oracle as O
 from tests import sampler_util as U
+from tests.ladder_util import RUNG_KS, rung_of
 from ccdm_stochastic_segmentation_amd import hip
 from ccdm_stochastic_segmentation_amd import models as MD
 
@@ -382,6 +383,13 @@ def run_terms(lib, x0, xt, labels, tab, K, weights=None, want_map=True, guard=8)
     return rs[:N].cpu(), rw[:N].cpu(), mp[:N * HW].reshape(N, HW).cpu()
 
 
+# k_bound_terms is built per rung of the class-count ladder (256 pixels per block up to K = 32, 64 above): both ends of every rung.  Above
+# K = 33 the short map alone (77 = 64 + 13 pixels): 1024 pixels of up to 255 classes add time and no other path.
+TERMS_KS = sorted({2, 5, 20, 33} | set(RUNG_KS))
+TERMS_HW_K = [(HW, K) for HW in (77, 1024) for K in TERMS_KS if HW == 77 or K <= 33]
+TERMS_MAXIMA = {}          # (K, HW) -> the largest error against float64 seen in this session (parity_log: ladder_bound_terms)
+
+
 def row_inputs(tab, labels, K):
     """per engine row: the label map it scores (idle rows: all 255, so the restatement gives 0) and its coefficients"""
     y = np.stack([labels[r["label_row"]] if r["t"] >= 1 else np.full(labels.shape[1], 255, np.uint8) for r in tab]).astype(np.int64)
@@ -389,10 +397,9 @@ def row_inputs(tab, labels, K):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("K", (2, 5, 20, 33))
-@pytest.mark.parametrize("HW", (77, 1024))
+@pytest.mark.parametrize("HW,K", TERMS_HW_K)
 @pytest.mark.parametrize("N", (1, 3))
-def test_terms_kernel_against_float64(lib, N, HW, K):
+def test_terms_kernel_against_float64(lib, parity_log, N, HW, K):
     dm = diffusion(K)
     rng = np.random.default_rng(2000 * N + HW + K)
     labels = random_labels(rng, 2, HW, K)
@@ -405,6 +412,8 @@ def test_terms_kernel_against_float64(lib, N, HW, K):
     err = np.abs(mp.numpy().astype(np.float64) - want)
     print(f"bound_terms N={N} HW={HW} K={K}: max |l - float64| = {err.max():.3e} = {err.max() / 2.0 ** -24:.1f} * 2^-24 (bound {K + 256}), "
           f"largest term {want.max():.3f}")
+    TERMS_MAXIMA[(K, HW)] = max(TERMS_MAXIMA.get((K, HW), 0.0), float(err.max()))
+    parity_log("ladder_bound_terms", **{f"rung{rung_of(K)}_K{K}_HW{HW}_max_abs_err_vs_float64": TERMS_MAXIMA[(K, HW)], f"K{K}_bound": tol(K)})
     assert err.max() <= tol(K)
     counted = y < K
     assert (mp.numpy()[~counted] == 0).all() and np.array_equal(rw.numpy(), counted.sum(1).astype(np.float64))
@@ -430,7 +439,7 @@ def test_terms_kernel_against_float64(lib, N, HW, K):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("K", (2, 5, 20, 33))
+@pytest.mark.parametrize("K", TERMS_KS)
 def test_terms_kernel_exact_cases(lib, K):
     """x0 = onehot(y): every term within the tolerance of 0, so the bound of a label under the perfect denoiser is the prior alone;
     class weights with a zero entry: those pixels are out, row_weight is the exact sum of the weights"""

@@ -13,8 +13,10 @@ import pytest
 import torch
 
 from ccdm_stochastic_segmentation_amd import SamplingQueue, hip, serving, step_values
-from tests.guided_util import bits, coefficients, evidence_restatement, random_inputs
-from tests.sampler_util import DEV, H, ROOT, T_SMALL, T_STRIDED, W, assert_symbol_declared_bound_and_built, load_lib, make_sampler, small_model
+from tests.guided_util import bits, coefficients, evidence_restatement, random_inputs, shaped_restatement
+from tests.ladder_util import RUNG_KS
+from tests.sampler_util import (DEV, H, ROOT, T_SMALL, T_STRIDED, W, assert_symbol_declared_bound_and_built, load_lib, make_sampler, onehot_np,
+                                small_model)
 
 SYMBOL = "ccdm_slots_step"
 # the four requests of the scheduler test and of the end-to-end test: (name, n, t, vote, the tick before which it arrives)
@@ -220,12 +222,16 @@ def run_shaped_per_slot(lib, d, table, with_xin, alias):
     return g
 
 
+SLOT_HW_K = [(195, K) for K in RUNG_KS] + [(256, 2), (256, 5)]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("HW,K", [(195, 2), (195, 3), (195, 4), (195, 5), (195, 20), (195, 33), (256, 2), (256, 5)])
+@pytest.mark.parametrize("HW,K", SLOT_HW_K)
 def test_slots_kernel_equals_the_shaped_step_slot_by_slot(lib, HW, K):
     """Five slots with different coefficients, step rows, keys and sample indices: the four real modes and an idle slot.  HW = 195: blocks
-    straddle slot boundaries (K <= 4: 256 threads; K <= 32: 256 staged pixels; K = 33: 64 staged pixels) and the runs are unaligned, with
-    an odd xin stride; HW = 256: the aligned vector paths, xin stride a multiple of 4.  With xin and without, with out_probs a buffer of
+    straddle slot boundaries (K <= 4: 256 threads; K <= 32: 256 staged pixels; K >= 33: 64 staged pixels) and the runs are unaligned, with
+    an odd xin stride, at both ends of every rung of the class-count ladder; HW = 256: the aligned vector paths, xin stride a multiple of
+    4.  With xin and without, with out_probs a buffer of
     its own and aliased to x0 as in the engine: every buffer is torch.equal to what five ccdm_shaped_step calls at (1.0, 1.0) leave, the
     idle slot's bytes are the fill they started with, the image channels of xin are untouched."""
     stride = (K + 4) // 4 * 4 + 1 if HW == 195 else (K + 3) // 4 * 4
@@ -277,6 +283,43 @@ def test_slots_kernel_against_the_cpu_restatement(lib, K):
         if mode == hip.STEP_LAST_MAJORITY:
             assert np.array_equal(got["onehot"][n].argmax(-1), idx[0])
     assert bits(got["x0"]).tobytes() == bits(x0).tobytes()
+
+
+ANCHOR_KS = RUNG_KS          # the slot-by-slot definition above is another kernel, held at most of these by the shaped tests' new cases alone
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("K", ANCHOR_KS)
+def test_slots_kernel_equals_the_cpu_restatement_bit_for_bit(lib, K):
+    """HW = 195, one running slot of each step mode, against the shaped tests' numpy restatement at (1, 1) with the slot's coefficients,
+    key, sample and row, directly (the slot-by-slot test compares two kernels): the drawn classes and their one-hot in xin, the
+    confidence probabilities bit for bit, the majority class and its one-hot; what a mode does not write, the keeping slot and the idle
+    slot are the bytes they started with."""
+    HW = 195
+    d = slot_buffers(K, HW, K + 1)
+    table = slot_table()
+    got = {k: v.cpu().numpy() for k, v in run_slots(lib, d, table, True, False).items()}
+    was = {k: v.cpu().numpy() for k, v in d.items()}
+    for n, mode in enumerate(MODES):
+        r = table[n]
+        sl = slice(n, n + 1)
+        wrote = set()
+        if mode not in (hip.SLOT_IDLE, hip.STEP_LAST_KEEP):
+            probs, idx = shaped_restatement(was["x0"][sl], None, was["xt"][sl], 1.0, 1.0, float(r["alpha_t"]), float(r["cumalpha_tm1"]), mode,
+                                            int(r["step_row"]), SLOT_KEY[n], SLOT_SAMPLE[n])
+            if mode == hip.STEP_LAST_CONFIDENCE:
+                assert np.array_equal(bits(got["probs"][n]), bits(probs[0])), f"slot {n}: {int((bits(got['probs'][n]) != bits(probs[0])).sum())} probabilities differ"
+                wrote = {"probs"}
+            else:
+                assert np.array_equal(got["xt"][n].astype(np.int64), idx[0]), f"slot {n}: {int((got['xt'][n] != idx[0]).sum())} of {HW} classes differ"
+                wrote = {"xt", "xin"} if mode == hip.STEP_SAMPLE else {"xt", "onehot"}
+            if mode == hip.STEP_SAMPLE:
+                assert np.array_equal(got["xin"][n, :, :K], onehot_np(idx, K)[0].astype(np.float32)), n
+                assert np.array_equal(bits(got["xin"][n, :, K:]), bits(was["xin"][n, :, K:])), n
+            if mode == hip.STEP_LAST_MAJORITY:
+                assert np.array_equal(got["onehot"][n], onehot_np(idx, K)[0].astype(np.int64)), n
+        for k in set(d) - wrote:
+            assert got[k][n].tobytes() == was[k][n].tobytes(), f"slot {n} (mode {mode}): {k} changed"
 
 
 # ------------------------------------------------------------------------------------------------ GPU: the queue

@@ -14,6 +14,7 @@ from oracle import ccdm_oracle as O
 from ccdm_stochastic_segmentation_amd import guidance, hip
 from ccdm_stochastic_segmentation_amd.models import Guidance, tile_origins
 from tests.guided_util import bits, coefficients, mixed_inputs, nhwk, run_shaped_kernel, shaped_restatement
+from tests.ladder_util import RUNG_KS
 from tests.sampler_util import (DEV, H, SEED, SMALL_CFG, T_SMALL, T_STRIDED, W, assert_symbol_declared_bound_and_built, load_lib, make_sampler,
                                 onehot_np, sample_sharded_keywords, settings, small_model)
 
@@ -284,7 +285,7 @@ def run_kernel(lib, x0t, ev, cxt, txt, N, geom, inv_tau, r, a, c, mode, *, step_
 # N = 3: 360 canvas pixels, so blocks straddle samples and the last block is partial; the last tiles are shifted in the second (c up to 4)
 # and in the fourth, where three tiles overlap along x (origins 8, 12, 14: c = 3 at x = 14, 15); the third is a row of five whole tiles
 KERNEL_GEOMS = [(12, 10, 8, 8, 4, 2), (12, 10, 8, 8, 3, 5), (8, 24, 8, 8, 8, 4), (8, 22, 8, 8, 8, 4)]
-KERNEL_KS = [2, 3, 4, 5, 20, 40]
+KERNEL_KS = sorted({2, 3, 4, 5, 20, 40} | set(RUNG_KS))          # both ends of every rung of the kernels' class-count ladder
 
 
 @pytest.mark.gpu

@@ -15,6 +15,7 @@ from ccdm_stochastic_segmentation_amd import guidance, hip
 from ccdm_stochastic_segmentation_amd.models import DenoisingModel, Guidance
 from tests.guided_util import (POWER_ERROR_ALLOWED, bits, coefficients, mixed_inputs, nhwk, posterior64, run_shaped_kernel, sampler_evidence, shape_rows,
                                shaped_restatement, threshold_margin64, weighted)
+from tests.ladder_util import RUNG_KS, rung_of
 from tests.sampler_util import (DEV, H, SEED, SMALL_CFG, T_SMALL, T_STRIDED, W, assert_symbol_declared_bound_and_built, load_lib, make_sampler,
                                 onehot_np, sample_sharded_keywords, settings, small_model)
 
@@ -280,7 +281,9 @@ def run_kernel(lib, x0v, ev, xtv, N, Hh, Ww, flips, inv_tau, r, a, c, mode, *, s
 
 
 KERNEL_SHAPES = [(2, 3, 5), (2, 9, 37)]          # odd both ways, one partial block; 666 pixels: block edges at 256 and at 64
-KERNEL_KS = [2, 3, 4, 5, 20, 40]
+KERNEL_KS = sorted({2, 3, 4, 5, 20, 40} | set(RUNG_KS))          # both ends of every rung of the kernels' class-count ladder
+TEMPERED_KS = [2, 5, 16, 24, 32, 40, 128]
+MIRRORED_KS = [2, 16, 20, 32, 255]
 
 
 @pytest.mark.gpu
@@ -347,21 +350,17 @@ def test_views_kernel_equals_the_restatement(lib, N, Hh, Ww, K):
         assert np.array_equal(full[keep], tail)
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("K", [2, 5, 40])
-def test_tempered_views_kernel_against_float64(lib, K):
-    """tau = 0.7 and r in {1, 0.9} at V = 3: the device's power is not numpy's, so the confidence-mode probabilities are held against
-    the float64 form of the shaping and of the posterior on the fp32 view mean (and its fp32 product with the evidence), to the shaped
-    test's bound: its 5 K + 31 counted roundings, the clamp's 2 K 1e-12 and POWER_ERROR_ALLOWED.  Entries > 1e-9 of pixels that are not
-    within 1e-5 of a truncation threshold."""
+def tempered_views_reference(K):
+    """The float64 side of test_tempered_views_kernel_against_float64, from the definition and the oracle alone: the geometry and
+    inv_temperature, the seeded inputs, and per (r, evidence, t) the coefficients, the float64 probabilities and the entries they are
+    compared at."""
     N, Hh, Ww = 2, 9, 37
     flips = (VFLIP, HFLIP)
     rng = np.random.default_rng(9500 + K)
     x0v, ev_all, xtv = mixed_inputs(rng, 3 * N, Hh * Ww, K)
-    n = 5 * K + 31
-    bound = n * 2.0 ** -24 / (1 - n * 2.0 ** -24) + 2 * K * 1e-12 + POWER_ERROR_ALLOWED
     inv = float(np.float32(1.0 / 0.7))
     m = view_mean(x0v, N, Hh, Ww, flips)
+    cases = []
     for r in (1.0, 0.9):
         for ev in (None, ev_all[:N]):
             v = weighted(m, ev)
@@ -370,15 +369,32 @@ def test_tempered_views_kernel_against_float64(lib, K):
             for t in (200, 2):
                 a, c = coefficients(t)
                 want = posterior64(q64, xtv[:N], a, c)
-                got = run_kernel(lib, x0v, ev, xtv, N, Hh, Ww, flips, inv, r, a, c, hip.STEP_LAST_CONFIDENCE, alias=True)["x0"][:N].astype(np.float64)
-                big = (want > 1e-9) & ~near[..., None]
-                rel = float((np.abs(got - want)[big] / want[big]).max())
-                print(f"tempered views K={K} r={r} ev={ev is not None} t={t}: max relative error {rel:.3e} (bound {bound:.3e})")
-                assert big.mean() > 0.5 and rel <= bound, (r, ev is not None, t, rel, bound)
+                cases.append((r, ev, t, (a, c), want, (want > 1e-9) & ~near[..., None]))
+    return (N, Hh, Ww, flips, inv), (x0v, xtv), cases
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("K", [2, 20])
+@pytest.mark.parametrize("K", TEMPERED_KS)
+def test_tempered_views_kernel_against_float64(lib, parity_log, K):
+    """tau = 0.7 and r in {1, 0.9} at V = 3: the device's power is not numpy's, so the confidence-mode probabilities are held against
+    the float64 form of the shaping and of the posterior on the fp32 view mean (and its fp32 product with the evidence), to the shaped
+    test's bound: its 5 K + 31 counted roundings, the clamp's 2 K 1e-12 and POWER_ERROR_ALLOWED.  Entries > 1e-9 of pixels that are not
+    within 1e-5 of a truncation threshold."""
+    (N, Hh, Ww, flips, inv), (x0v, xtv), cases = tempered_views_reference(K)
+    n = 5 * K + 31
+    bound = n * 2.0 ** -24 / (1 - n * 2.0 ** -24) + 2 * K * 1e-12 + POWER_ERROR_ALLOWED
+    worst = 0.0
+    for r, ev, t, (a, c), want, big in cases:
+        got = run_kernel(lib, x0v, ev, xtv, N, Hh, Ww, flips, inv, r, a, c, hip.STEP_LAST_CONFIDENCE, alias=True)["x0"][:N].astype(np.float64)
+        rel = float((np.abs(got - want)[big] / want[big]).max())
+        worst = max(worst, rel)
+        print(f"tempered views K={K} r={r} ev={ev is not None} t={t}: max relative error {rel:.3e} (bound {bound:.3e})")
+        parity_log("ladder_views_step", **{f"rung{rung_of(K)}_K{K}_max_rel_err_vs_float64": worst, f"K{K}_bound": bound})
+        assert big.mean() > 0.5 and rel <= bound, (r, ev is not None, t, rel, bound)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("K", MIRRORED_KS)
 def test_one_view_and_mirrored_views_are_the_shaped_step(lib, K):
     """Against ccdm_shaped_step itself on the device, bit for bit: V = 1 is that step; V = 2 and V = 4 on views whose x0 are exact
     mirror images of view 0 are that step on view 0 (xt in sample mode with tau = 0.7 and r = 0.8 — the same device power on the same
