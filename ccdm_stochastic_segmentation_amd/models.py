@@ -71,14 +71,19 @@ def step_values(time_steps: int, init_t: Optional[int]) -> List[int]:
     return list(range(init_t, 0, -1))
 
 
+PASS_STRIDE = 0xD1342543DE82EF95         # pass_key's Weyl increment: odd, and not the call counter's 0x9E3779B97F4A7C15
+
+
 def pass_key(key: int, p: int) -> int:
     """Philox key of pass `p` of a table row (p = the number of earlier visits of the row in a resampled walk): the call's key itself
-    for p = 0, else the splitmix64 finaliser of key + 0x9E3779B97F4A7C15 * p — the mixing DenoisingModel._philox_key applies to
-    (philox_seed, philox_call).  A revisit must not replay the first visit's noise: the epilogue keys its draws by the table row."""
+    for p = 0, else the splitmix64 finaliser of key + PASS_STRIDE * p.  A revisit must not replay the first visit's noise: the epilogue
+    keys its draws by the table row.  The increment is NOT the one DenoisingModel._philox_key steps (philox_seed, philox_call) by: call 0
+    uses the seed itself as its key, so with one increment for both, pass p of call 0 would run under the key of call p and replay that
+    call's first visit of the row, pixel for pixel (tests/test_host_logic.py holds calls and passes apart)."""
     key = int(key) & 0xFFFFFFFFFFFFFFFF
     if int(p) == 0:
         return key
-    z = (key + 0x9E3779B97F4A7C15 * int(p)) & 0xFFFFFFFFFFFFFFFF
+    z = (key + PASS_STRIDE * int(p)) & 0xFFFFFFFFFFFFFFFF
     z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & 0xFFFFFFFFFFFFFFFF
     z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & 0xFFFFFFFFFFFFFFFF
     return z ^ (z >> 31)

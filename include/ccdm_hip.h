@@ -368,8 +368,9 @@ int ccdm_known_labels_step(const uint8_t* known /*dev [N,HW]: class < K = known,
  * image, untouched).  A byte xt[i] >= K on entry is a caller's error the host never makes; it is treated as class K - 1.
  * Keying of a revisit: the epilogue keys its noise by the table row, so a row that is walked again must not see the same key.  Every
  * launch of pass p of a row (the denoise step, its clamp, and the renoise that precedes it) runs under pass_key(key, p): the call's key
- * itself for p = 0, and for p >= 1 the splitmix64 finaliser of key + 0x9E3779B97F4A7C15 * p (mod 2^64) — the mixing that derives a
- * call's key from (philox_seed, philox_call).
+ * itself for p = 0, and for p >= 1 the splitmix64 finaliser of key + 0xD1342543DE82EF95 * p (mod 2^64) — the finaliser that derives a
+ * call's key from (philox_seed, philox_call), on another increment: call 0's key is the seed itself, so under the call counter's
+ * increment 0x9E3779B97F4A7C15 pass p of call 0 would run under call p's key.
  * One thread per pixel; without xin one thread per 4 consecutive pixels of the flat map (one 32-bit load and store, where xt is 4-byte
  * aligned; the last N*HW % 4 bytes one by one).  K in [1, CCDM_MAX_CLASSES]; xin_stride >= K where xin is given.  Results depend on
  * (pixel, global sample index, step row, key) only.

@@ -814,3 +814,26 @@ def test_conv_plan_depends_on_the_batch_only_through_the_block_partition(plan_ut
             assert not p["skip_wide"] or p["ntiles_per_block"] == 1, (name, N, p)
             seen_ni.add((p["kernel"], p["ntiles_per_block"]))
     assert {(hip.CONV_KERNEL_GENERAL, 1), (hip.CONV_KERNEL_GENERAL, 2), (hip.CONV_KERNEL_UPCONV, 2), (hip.CONV_KERNEL_1X1_MULTI, 5)} <= seen_ni
+
+
+def test_philox_keys_passes_and_tag_ranges_never_meet():
+    """The host's part of keeping the sampler's noise streams apart: `_philox_key` over calls 0 .. 4095 of three seeds (label_bound takes
+    its keys from the same function of its own counter) and `pass_key` over p = 0 .. 63 of each of them are pairwise distinct, none of them
+    is the key of another seed's call 0, and the fourth counter words of the epilogue (k / 4 < 64), the clamp (0x80000000 | k / 4), the
+    renoise (0x40000000 | k / 4) and the bound's noising (0x20000000 | k / 4) are pairwise disjoint for every k / 4 < 64."""
+    seeds = (0, 99, 0xFEEDFACE12345678)
+    stub = type("M", (), {"philox_seed": 0, "philox_call": 0})()
+    keys = {}
+    for seed in seeds:
+        stub.philox_seed = seed
+        keys[seed] = [models.DenoisingModel._philox_key(stub, call) for call in range(4096)]
+        assert keys[seed][0] == seed and all(0 <= k < 2 ** 64 for k in keys[seed])
+    every = [models.pass_key(k, p) for seed in seeds for k in keys[seed] for p in range(64)]
+    assert len(every) == 3 * 4096 * 64 and len(set(every)) == len(every)
+    assert [models.pass_key(k, 0) for k in keys[99][:8]] == keys[99][:8]
+    # a seed's call 0 uses the seed itself as its key: no other (seed, call, pass) may land on it
+    for seed in seeds:
+        assert every.count(seed) == 1 and every.index(seed) == seeds.index(seed) * 4096 * 64
+    ranges = [{tag | kq for kq in range(64)} for tag in (0, 0x80000000, 0x40000000, 0x20000000)]
+    assert all(len(r) == 64 for r in ranges) and len(set().union(*ranges)) == 4 * 64
+    assert (hip.MAX_CLASSES + 3) // 4 <= 64          # every class count the kernels take keeps k / 4 below 64

@@ -55,10 +55,12 @@ def test_pass_key():
     for key in (0, 99, 0xFEEDFACE12345678, 2 ** 64 - 1):
         keys = [pass_key(key, p) for p in range(10)]
         assert keys[0] == key and len(set(keys)) == 10 and all(0 <= k < 2 ** 64 for k in keys)
-    # the mixing _philox_key applies to (seed, call)
+    # the finaliser _philox_key applies to (seed, call), on another increment: call 0's key is the seed itself, so pass p of call 0 must
+    # not run under the key of call p
     m, _ = small_model(2)
-    m.philox_seed, m.philox_call = 1234, 7
-    assert pass_key(1234, 7) == m._philox_key()
+    for p in range(1, 10):
+        m.philox_seed, m.philox_call = 1234, p
+        assert pass_key(1234, p) != m._philox_key() and pass_key(1234, p) not in [pass_key(m._philox_key(), q) for q in range(10)]
 
 
 def test_renoise_symbol_declared_bound_and_built():
