@@ -31,10 +31,11 @@ def gn_stats(x_nhwc: torch.Tensor, slices: int = 1) -> torch.Tensor:
 
 def conv2d(srcs, weight, bias, ksize, *, stats=None, gamma=None, beta=None, act=hip.ACT_NONE, stride=1, up=False,
            emb=None, emb_rows=None, film=None, resid=None, want_stats=True, prec=hip.PREC_F32, skip=None, bench=None, fine=False, diag=0,
-           plan=None):
+           plan=None, launched=None):
     """srcs: list of 1-2 NHWC cuda tensors; weight OIHW numpy/torch cpu; stats: list of stats tensors or None.
     emb: [rows, E] cpu tensor added per output channel (row per sample via emb_rows) ; film: (table cpu [rows, 2C]).
     plan: a dict that receives the launch plan of this very call (ccdm_conv_plan of the argument struct that is launched).
+    launched: a list that receives that argument struct itself (its pointers are dead once the call returns: shapes and flags only).
     Returns (out NHWC cuda, out_stats or None)."""
     lib = hip.load()
     a = srcs[0]
@@ -109,6 +110,8 @@ def conv2d(srcs, weight, bias, ksize, *, stats=None, gamma=None, beta=None, act=
     if plan is not None:
         info = hip.conv_plan(args)
         plan.update({f: getattr(info, f) for f, _ in hip.ConvPlanInfo._fields_})
+    if launched is not None:
+        launched.append(args)
     hip.check(lib.ccdm_conv2d(C.byref(args), 0), "conv2d")
     sync()
     if bench is not None:       # tools/bench_conv.py: {"iters": n} in, {"ms": mean launch time} out
@@ -121,6 +124,35 @@ def conv2d(srcs, weight, bias, ksize, *, stats=None, gamma=None, beta=None, act=
         bench["ms"] = e0.elapsed_time(e1) / bench.get("iters", 20)
     del keep
     return out, ost
+
+
+def conv_float64(x, weight, bias, *, gamma=None, beta=None, film=None, silu=False, up=False, stride=1, emb=None, resid=None, skip=None):
+    """The operator ccdm_conv2d fuses, in float64 on the CPU, from BCHW cpu tensors of any float type:
+        GroupNorm(32, eps = 1e-5) over the (already concatenated) input x, where gamma is given  ->  FiLM h * (1 + scale) + shift with
+        film = [N, 2C] rows (scale | shift)  ->  SiLU  ->  nearest x2  ->  conv k x k (pad k // 2) + bias  ->  + emb [N, Cout]
+        ->  + resid  ->  + the 1x1 skip conv with its bias, skip = (xs [N, Cs, H, W], ws [Cout, Cs, 1, 1], bs [Cout]).
+    Returns float64 [N, Cout, Hout, Wout]."""
+    import torch.nn.functional as F
+    h = x.double()
+    cin = h.shape[1]
+    if gamma is not None:
+        h = F.group_norm(h, 32, gamma.double(), beta.double(), 1e-5)
+    if film is not None:
+        t = film.double()
+        h = h * (1 + t[:, :cin, None, None]) + t[:, cin:, None, None]
+    if silu:
+        h = F.silu(h)
+    if up:
+        h = F.interpolate(h, scale_factor=2, mode="nearest")
+    ref = F.conv2d(h, weight.double(), bias.double(), stride=stride, padding=weight.shape[-1] // 2)
+    if emb is not None:
+        ref = ref + emb.double()[:, :, None, None]
+    if resid is not None:
+        ref = ref + resid.double()
+    if skip is not None:
+        xs, ws, bs = skip
+        ref = ref + F.conv2d(xs.double(), ws.double(), bs.double())
+    return ref
 
 
 def resample(x_nhwc, mode, *, stats=None, gamma=None, beta=None, act=hip.ACT_NONE, want_act=True, want_raw=True):

@@ -816,6 +816,70 @@ def test_conv_plan_depends_on_the_batch_only_through_the_block_partition(plan_ut
     assert {(hip.CONV_KERNEL_GENERAL, 1), (hip.CONV_KERNEL_GENERAL, 2), (hip.CONV_KERNEL_UPCONV, 2), (hip.CONV_KERNEL_1X1_MULTI, 5)} <= seen_ni
 
 
+# ------------------------------------------------------------------------------------------------ the ledger of conv launch plans
+# Every signature (tests/plan_util.signature) a shipped network emits has a kernel-level float64 case in plan_util.PLAN_CASES, which
+# tests/test_conv_plan_coverage.py runs on the GPU.  Nothing is exempt: a signature without a case fails the first test below.
+@pytest.fixture(scope="module")
+def ledger(plan_util):
+    """(signature -> layers that have it over plan_util.shipped_conv_calls(), the signature of every case of the table)"""
+    shipped = {}
+    for tag, name, a in plan_util.shipped_conv_calls():
+        shipped.setdefault(plan_util.signature_of(a), []).append(tag + ":" + name)
+    return shipped, [c.signature() for c in plan_util.PLAN_CASES]
+
+
+def missing_signatures(shipped, case_signatures):
+    """the shipped signatures no case has, each with up to three layers that have it"""
+    have = set(case_signatures)
+    return ["%r: %s" % (s, ", ".join(layers[:3])) for s, layers in shipped.items() if s not in have]
+
+
+def test_every_shipped_conv_signature_has_a_kernel_case(plan_util, ledger):
+    """The signature set of shipped_conv_calls() — LIDC at every fine_slices the model can choose, C4 at both image sizes, the
+    resblock_updown and the use_scale_shift_norm networks, each in both precisions — is a subset of the signature set of PLAN_CASES."""
+    shipped, cases = ledger
+    assert len(shipped) > 100 and sum(map(len, shipped.values())) == len(plan_util.shipped_conv_calls())
+    missing = missing_signatures(shipped, cases)
+    assert not missing, "%d shipped conv signatures have no kernel-level case in plan_util.PLAN_CASES:\n%s" % (len(missing), "\n".join(missing))
+
+
+def test_signature_is_a_function_of_the_layer_never_of_the_batch(plan_util):
+    """a layer keeps its signature at every batch size (what lets a case run at N = 2 and its last sample alone)"""
+    for tag, name, a in plan_util.shipped_conv_calls()[::7]:
+        want = plan_util.signature_of(a)
+        for N in (1, 2, 3, 22, 64, 1024):
+            a.N = N
+            assert plan_util.signature_of(a) == want, (tag, name, N)
+
+
+def test_plan_case_table_has_one_case_per_signature_and_no_unexplained_case(plan_util, ledger):
+    """No two cases share a signature (or an id); a case either has a signature that ships or says with edge="..." why it is there, and an
+    edge case has a signature that does not ship.  A shrunk case runs a smaller image than its layer, with the layer's signature."""
+    shipped, cases = ledger
+    table = plan_util.PLAN_CASES
+    assert len(set(cases)) == len(cases) == len(table), [c.id for c, s in zip(table, cases) if cases.count(s) > 1]
+    assert len({c.id for c in table}) == len(table)
+    for c, s in zip(table, cases):
+        assert (s in shipped) == (c.edge is None), (c.id, s, c.edge)
+        assert c.refused is None or c.edge, c.id
+        if c.shrink:
+            h, w = c.shape()
+            assert h * w <= c.H * c.W and s == plan_util.signature_of(c.args(H=c.H, W=c.W)), (c.id, h, w)
+
+
+def test_plan_case_ledger_negative_control(plan_util, ledger):
+    """Each case that is no edge case is load-bearing: with it deleted from the table the ledger test fails, naming its signature; with an
+    edge case deleted it still passes."""
+    shipped, cases = ledger
+    assert not missing_signatures(shipped, cases)
+    for i, c in enumerate(plan_util.PLAN_CASES):
+        missing = missing_signatures(shipped, cases[:i] + cases[i + 1:])
+        if c.edge:
+            assert not missing, c.id
+        else:
+            assert len(missing) == 1 and missing[0].startswith(repr(cases[i])), (c.id, missing)
+
+
 def test_philox_keys_passes_and_tag_ranges_never_meet():
     """The host's part of keeping the sampler's noise streams apart: `_philox_key` over calls 0 .. 4095 of three seeds (label_bound takes
     its keys from the same function of its own counter) and `pass_key` over p = 0 .. 63 of each of them are pairwise distinct, none of them
